@@ -8,7 +8,9 @@ on the host in the reference and is outside the timed GPU path.  For N>1 every r
 an independent replica on its own batch (inference shards by image, no data-path
 collective): weak scaling.
 
-Contract: `python bench.py --gpus N --steps K --warmup W` prints ONE JSON line on rank 0.
+Contract: `python bench.py --gpus N --steps K --warmup W` prints ONE JSON line on rank 0; `ms_per_step` is the
+wall time of one of the K timed steps.  `--dump-outputs DIR` also writes what the last timed step computed (inputs are
+seeded: the same arguments give the same inputs) so that two builds can be compared output for output.
 """
 import argparse
 import json
@@ -751,6 +753,24 @@ def launch_ranks(args):
 
 
 TRAIN_LEG_FAILED_EXIT = 3   # exit status when the training leg hung (watchdog) or failed with other ranks possibly waiting in a collective
+DUMP_PIXELS = 1 << 18       # pixel records of the network output kept by --dump-outputs (36 floats each: 37.7 MB)
+
+
+def dump_outputs(dirname, out, kpts):
+    """`--dump-outputs DIR`: what the last timed step handed its caller, as float32 .npy files that two builds can be compared by.
+    keypoints.npy = the LS voter's keypoints [B, objects, 9, 2] (y, x), whole.  network_output.npy = records of the network output
+    [B, H, W, 36] (9 logits, 18 vector-field components, 9 confidences) as rows [n, 36]: every pixel in (b, y, x) order when there are at
+    most DUMP_PIXELS of them, otherwise DUMP_PIXELS pixels drawn without replacement by a fixed seed, in ascending (b, y, x) order."""
+    import numpy as np
+    import torch
+
+    os.makedirs(dirname, exist_ok=True)
+    rec = out.reshape(-1, out.shape[-1])
+    if rec.shape[0] > DUMP_PIXELS:
+        pick = np.sort(np.random.default_rng(20240).choice(rec.shape[0], DUMP_PIXELS, replace=False))
+        rec = rec[torch.from_numpy(pick).to(rec.device)]
+    np.save(os.path.join(dirname, "network_output.npy"), rec.float().cpu().numpy())
+    np.save(os.path.join(dirname, "keypoints.npy"), kpts.float().cpu().numpy())
 
 
 def main():
@@ -772,7 +792,13 @@ def main():
     ap.add_argument("--train-leg-timeout", type=int, default=300, help="seconds after which a hanging training leg is abandoned (the headline line is printed without it)")
     ap.add_argument("--no-train-leg", action="store_true", help="skip the 3-step training leg (BASELINE configs[2]) the default line reports under `training_leg`")
     ap.add_argument("--stamp", action="store_true", help="print the source / binary stamp (JSON) and exit; no GPU is touched")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed (keypoints, a fixed sample of the network output) as float32 DIR/<name>.npy")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    if args.dump_outputs and args.mode != "infer":
+        ap.error("--dump-outputs is implemented for --mode infer (the headline workload)")
     if args.stamp:
         print(json.dumps(binary_stamp()))
         return
@@ -830,7 +856,7 @@ def main():
     def step():  # the reference's own call sequence (test_casapose.py:299-312): model call, split, voting layer
         out = net([img], training=False)
         s, d, c = torch.split(out, [seg_dim, 2 * kp, kp], dim=3)
-        return voter([s, d, c])
+        return out, voter([s, d, c])
 
     if cpu_workers:
         cpu_workers = wait_cpu_workers(cpu_workers)   # all built and idle (blocked on stdin) before anything here is timed
@@ -846,12 +872,17 @@ def main():
     barrier()
     t0 = time.perf_counter()
     for _ in range(args.steps):
-        kpts = step()
+        out, kpts = step()
     barrier()
     dt = time.perf_counter() - t0
     dt = parallel.max_over_ranks(dt, dev)
     assert torch.isfinite(kpts).all()
     _log("timed region done: %.3f ms/step" % (1e3 * dt / args.steps))
+    if rank == 0 and args.dump_outputs:
+        # now, before any later call of the network reuses the plan's output buffer
+        dump_outputs(args.dump_outputs, out, kpts)
+        _log("outputs of the last timed step written to %s" % args.dump_outputs)
+    del out
 
     result = {
         "metric": "images/sec at 640x480, 8-object LMO (casapose_c_gcu5 forward + component filter + LS keypoint voting)",
