@@ -14,7 +14,7 @@ from __future__ import annotations
 import ctypes as C
 import math
 import os
-from typing import Dict, List, Optional, Sequence, Tuple
+from typing import Callable, Dict, List, Optional, Sequence, Tuple
 
 import numpy as np
 import torch
@@ -356,7 +356,6 @@ class FusedConv:
         return 2.0 * d.batch * d.out_h * d.out_w * self.kh * self.kw * cin * self.cout + head
 
 
-WINO_GROUPED_CONV = os.environ.get("CASAPOSE_WINO_GROUPED_CONV", "0") == "1"
 # The Winograd GEMM as exact 3-way bf16 splits on the bf16 matrix pipe (fp32-EQUIVALENT: every product exact, fp32 accumulation, measured
 # error <= the fp32 MFMA's; csrc/wino_gemm_split.hip).  Round 3: the DEFAULT of both plans -- the training plan since round 2, the
 # inference plan whenever its conv mode is "split" (its default, see CasaposeNet); CASAPOSE_WINO_GEMM=f32 restores the fp32 MFMA in both,
@@ -395,16 +394,7 @@ F16X2_MONITOR_SLACK = 2.0
 # depends on the box) -- not a gain one can rely on.  The training plan's heads, stand-alone streaming kernels, do write whole records by default.
 WHOLE_RECORDS = os.environ.get("CASAPOSE_INFER_HEAD_RECORDS", "0") == "1"
 BF16_DEEP = os.environ.get("CASAPOSE_BF16_DEEP", "1") != "0"   # bf16 conv mode: deep layers on csrc/conv_bf16d.hip (0: two-plane Winograd)
-# images per Winograd batch group (0 = the whole batch in one go)
-WINO_CHUNK = int(os.environ.get("CASAPOSE_WINO_CHUNK", "0"))
-MATERIALISE_BILINEAR = os.environ.get("CASAPOSE_MATERIALISE_BILINEAR", "0") == "1"
-WINO_FUSE_OUT_IN = os.environ.get("CASAPOSE_WINO_FUSE_OUT_IN", "1") != "0"
 STEM_SPLIT = os.environ.get("CASAPOSE_STEM_SPLIT", "1") != "0"   # A/B switch: conv0 on csrc/conv_stem_split.hip in the split / bf16 conv modes
-# two-stream forward (CasaposeNet._forward_two_streams): half-batches pipelined over a matrix-pipe stream and an HBM stream
-TWO_STREAM = os.environ.get("CASAPOSE_TWO_STREAM", "0") == "1"
-TWO_STREAM_BLOCKS = int(os.environ.get("CASAPOSE_TWO_STREAM_BLOCKS", "224"))   # blocks of the persistent kernels while both streams run
-TWO_STREAM_MODE = os.environ.get("CASAPOSE_TWO_STREAM_MODE", "half")   # "half": a stream per half-batch; "tag": a stream per kernel class
-TWO_STREAM_SKEW = float(os.environ.get("CASAPOSE_TWO_STREAM_SKEW", "0.4"))     # fraction of its steps the first half runs ahead   # A/B switch of the fused output -> input transform
 
 
 def split_wino_weights(U: torch.Tensor, groups: int, n: int, k: int, out: Optional[torch.Tensor] = None, stream: Optional[int] = None) -> torch.Tensor:
@@ -508,7 +498,7 @@ class WinoConv:
         __slots__ = ("ptr",)
 
         def __init__(self, ptr):
-            self.ptr = None if WINO_GROUPED_CONV else ptr   # (the grouped mode of the general kernel converts nothing to fp16)
+            self.ptr = ptr
 
         def __enter__(self):
             if self.ptr:
@@ -522,21 +512,21 @@ class WinoConv:
     def _armed(self, ptr: Optional[int]):
         return WinoConv._Armed(ptr)
 
-    def _input_transform(self, src_ptr: int, ld: int, cpad: int, nb: int, off: int, stream: int):
+    def _input_transform(self, src_ptr: int, ld: int, cpad: int, off: int, stream: int):
         """V[.., off : off + cpad] = B^T d B of one source; with v_scale != 1 through the transform's per-channel input affine (x * 2^e + 0: exact)"""
         with self._armed(self.mon_ptr if self.planes == _lib.PLANES_F16X2 else None):
-            self._input_transform_launch(src_ptr, ld, cpad, nb, off, stream)
+            self._input_transform_launch(src_ptr, ld, cpad, off, stream)
 
-    def _input_transform_launch(self, src_ptr: int, ld: int, cpad: int, nb: int, off: int, stream: int):
+    def _input_transform_launch(self, src_ptr: int, ld: int, cpad: int, off: int, stream: int):
         lib = _lib.load()
         if self.v_scale == 1.0:
-            check(lib.cp_wino_input_transform_f32(src_ptr, ld, cpad, nb, self.h, self.w, self.dil, self.V.data_ptr(), self.ktot, off, stream),
+            check(lib.cp_wino_input_transform_f32(src_ptr, ld, cpad, self.batch, self.h, self.w, self.dil, self.V.data_ptr(), self.ktot, off, stream),
                   "cp_wino_input_transform_f32(%s)" % self.name)
             return
         if self._vs_vec is None or self._vs_vec[0] != self.v_scale:
             n = max(c for c, _ in self.sources)
             self._vs_vec = (self.v_scale, torch.full((n,), self.v_scale, dtype=torch.float32, device=self.V.device), torch.zeros(n, dtype=torch.float32, device=self.V.device))
-        check(lib.cp_wino_input_transform_pre_f32(src_ptr, ld, cpad, nb, self.h, self.w, self.dil, self.V.data_ptr(), self.ktot, off,
+        check(lib.cp_wino_input_transform_pre_f32(src_ptr, ld, cpad, self.batch, self.h, self.w, self.dil, self.V.data_ptr(), self.ktot, off,
                                                   self._vs_vec[1].data_ptr(), self._vs_vec[2].data_ptr(), _lib.ACT_NONE, stream), "cp_wino_input_transform_pre_f32(%s)" % self.name)
 
     def _tables_for_next(self):
@@ -551,90 +541,45 @@ class WinoConv:
             self._next_tabs = (nxt.v_scale, e["scale"] * nxt.v_scale, e["shift"] * nxt.v_scale)
         return self._next_tabs[1].data_ptr(), self._next_tabs[2].data_ptr()
 
-    def chunks(self) -> List[Tuple[int, int, int]]:
-        """[(first image, images, padded tiles)]: the batch is processed in groups of WINO_CHUNK images so that the two scratch tensors
-        of a group (V: 36*Tp*K, M: 36*Tp*Cout floats -- 2.25x the layer's input and output) stay resident in the 256 MiB Infinity Cache
-        between the input transform, the GEMM and the output transform instead of making two round trips to HBM each."""
-        # the grouped mode of the general kernel reads desc.group_rows = the whole batch's Tp: chunking does not apply to it
-        n = WINO_CHUNK if 0 < WINO_CHUNK < self.batch and not WINO_GROUPED_CONV else self.batch
-        return [(b0, min(n, self.batch - b0), self.tiles(min(n, self.batch - b0), self.h, self.w, self.dil)[1]) for b0 in range(0, self.batch, n)]
+    def launches(self) -> List[Tuple[str, Callable[[int], None]]]:
+        """The launches of run() in order, as (part, fn(stream)): "in" = the input transform of every source (absent when the producer's fused
+        output -> input transform writes V), "gemm" = the grouped GEMM over the 36 planes, "out" = the output transform with the epilogue, or
+        the fused output -> input transform into the next layer's V.  (tools/debug/wino_parts.py times the parts one by one.)"""
+        parts = [] if self.skip_input else [("in", self._transform_inputs)]
+        return parts + [("gemm", self.run_gemm), ("out", self._transform_output)]
 
     def run(self, stream: int):
+        for _, launch in self.launches():
+            launch(stream)
+
+    def _transform_inputs(self, stream: int):
+        off = 0
+        for (cpad, _), s in zip(self.sources, self.srcs):
+            self._input_transform(s["data"].data_ptr(), s["ld"], cpad, off, stream)
+            off += cpad
+
+    def run_gemm(self, stream: int):
         lib = _lib.load()
-        e = self.epi
-        px = self.h * self.w
-        at = lambda t, b0, ld, size=4: (t.data_ptr() + b0 * px * ld * size) if t is not None else None  # noqa: E731
-        for b0, nb, tp in self.chunks():
-            off = 0
-            for (cpad, _), s in zip(self.sources, self.srcs):
-                if getattr(self, "skip_input", False):   # the producer's fused output -> input transform has written V already
-                    break
-                self._input_transform(at(s["data"], b0, s["ld"]), s["ld"], cpad, nb, off, stream)
-                off += cpad
-            self.run_gemm(stream, tp)
-            nxt = getattr(self, "fuse_next", None)
-            if nxt is not None:   # Y = A^T M A + epilogue, then straight into the next layer's V (the activated map stays on chip)
-                sc_, sh_ = self._tables_for_next()
-                with self._armed(nxt.mon_ptr if nxt.planes == _lib.PLANES_F16X2 else None):   # it writes the NEXT layer's V
-                    check(lib.cp_wino_output_input_transform_f32(self.M.data_ptr(), self.cout, nb, self.h, self.w, self.dil, at(e["residual"], b0, self.cout), self.cout,
-                                                                 sc_, sh_, e["act"], at(e["out_raw"], b0, self.cout), self.cout, None, self.cout,
-                                                                 self.V.data_ptr(), nxt.ktot, 0, stream), "cp_wino_output_input_transform_f32(%s)" % self.name)
-                continue
-            check(lib.cp_wino_output_transform_f32(self.M.data_ptr(), self.cout, nb, self.h, self.w, self.dil, at(e["residual"], b0, self.cout), self.cout,
-                                                   _ptr(e["scale"]), _ptr(e["shift"]), at(e["epi_label"], b0, 1, 1), e["act"], at(e["out_raw"], b0, self.cout),
-                                                   self.cout, at(e["out_act"], b0, self.cout), self.cout, stream), "cp_wino_output_transform_f32(%s)" % self.name)
-
-    def micro_steps(self):
-        """[(tag, fn(stream))] of one run(): "H" = HBM-bound transform passes, "M" = the matrix-pipe GEMM (the two-stream forward puts them on
-        different streams).  Only without batch chunking (one chunk)."""
-        lib = _lib.load()
-        e = self.epi
-        tp = self.tiles(self.batch, self.h, self.w, self.dil)[1]
-        out: List = []
-
-        def t_in(stream):
-            off = 0
-            for (cpad, _), s in zip(self.sources, self.srcs):
-                self._input_transform(s["data"].data_ptr(), s["ld"], cpad, self.batch, off, stream)
-                off += cpad
-
-        def t_gemm(stream):
-            self.run_gemm(stream, tp)
-
-        def t_out(stream):
-            nxt = getattr(self, "fuse_next", None)
-            if nxt is not None:
-                sc_, sh_ = self._tables_for_next()
-                with self._armed(nxt.mon_ptr if nxt.planes == _lib.PLANES_F16X2 else None):
-                    check(lib.cp_wino_output_input_transform_f32(self.M.data_ptr(), self.cout, self.batch, self.h, self.w, self.dil, _ptr(e["residual"]), self.cout,
-                                                                 sc_, sh_, e["act"], _ptr(e["out_raw"]), self.cout, None, self.cout,
-                                                                 self.V.data_ptr(), nxt.ktot, 0, stream), "cp_wino_output_input_transform_f32(%s)" % self.name)
-            else:
-                check(lib.cp_wino_output_transform_f32(self.M.data_ptr(), self.cout, self.batch, self.h, self.w, self.dil, _ptr(e["residual"]), self.cout,
-                                                       _ptr(e["scale"]), _ptr(e["shift"]), _ptr(e["epi_label"]), e["act"], _ptr(e["out_raw"]), self.cout,
-                                                       _ptr(e["out_act"]), self.cout, stream), "cp_wino_output_transform_f32(%s)" % self.name)
-
-        if not getattr(self, "skip_input", False):
-            out.append(("H", t_in))
-        out.append(("M", t_gemm))
-        out.append(("H", t_out))
-        return out
-
-    def run_gemm(self, stream: int, tp: Optional[int] = None):
-        lib = _lib.load()
-        if tp is None:  # stand-alone timing of the GEMM (bench.py): every chunk's GEMM back to back on the same scratch
-            for _, _, tpc in self.chunks():
-                self.run_gemm(stream, tpc)
-            return
-        if WINO_GROUPED_CONV:  # the grouped mode of the general conv kernel (kept for comparison; whole batch only)
-            check(lib.cp_conv2d_fwd_f32(C.byref(self.desc), stream), "cp_conv2d_fwd_f32(wino %s)" % self.name)
+        if self.Us is not None:
+            check(lib.cp_wino_gemm_split_scaled_f32(self.V.data_ptr(), self.Us.data_ptr(), self.M.data_ptr(), 36 * self.Tp, self.Tp, self.ktot, self.cout, self.planes,
+                                                    self.c_scale / self.v_scale, stream), "cp_wino_gemm_split_scaled_f32(%s)" % self.name)
         else:
-            if self.Us is not None:
-                check(lib.cp_wino_gemm_split_scaled_f32(self.V.data_ptr(), self.Us.data_ptr(), self.M.data_ptr(), 36 * tp, tp, self.ktot, self.cout, self.planes,
-                                                        self.c_scale / self.v_scale, stream), "cp_wino_gemm_split_scaled_f32(%s)" % self.name)
-            else:
-                check(lib.cp_wino_gemm_f32(self.V.data_ptr(), self.U.data_ptr(), self.M.data_ptr(), 36 * tp, tp, self.ktot, self.cout, stream),
-                      "cp_wino_gemm_f32(%s)" % self.name)
+            check(lib.cp_wino_gemm_f32(self.V.data_ptr(), self.U.data_ptr(), self.M.data_ptr(), 36 * self.Tp, self.Tp, self.ktot, self.cout, stream),
+                  "cp_wino_gemm_f32(%s)" % self.name)
+
+    def _transform_output(self, stream: int):
+        lib = _lib.load()
+        e, nxt = self.epi, self.fuse_next
+        if nxt is not None:   # Y = A^T M A + epilogue, then straight into the next layer's V (the activated map stays on chip)
+            sc_, sh_ = self._tables_for_next()
+            with self._armed(nxt.mon_ptr if nxt.planes == _lib.PLANES_F16X2 else None):   # it writes the NEXT layer's V
+                check(lib.cp_wino_output_input_transform_f32(self.M.data_ptr(), self.cout, self.batch, self.h, self.w, self.dil, _ptr(e["residual"]), self.cout,
+                                                             sc_, sh_, e["act"], _ptr(e["out_raw"]), self.cout, None, self.cout,
+                                                             self.V.data_ptr(), nxt.ktot, 0, stream), "cp_wino_output_input_transform_f32(%s)" % self.name)
+            return
+        check(lib.cp_wino_output_transform_f32(self.M.data_ptr(), self.cout, self.batch, self.h, self.w, self.dil, _ptr(e["residual"]), self.cout,
+                                               _ptr(e["scale"]), _ptr(e["shift"]), _ptr(e["epi_label"]), e["act"], _ptr(e["out_raw"]), self.cout,
+                                               _ptr(e["out_act"]), self.cout, stream), "cp_wino_output_transform_f32(%s)" % self.name)
 
     @property
     def flops(self) -> float:
@@ -644,8 +589,8 @@ class WinoConv:
 
     @property
     def gemm_flops(self) -> float:
-        """FLOPs the grouped GEMMs actually execute (36 planes x padded tiles, summed over the batch groups)."""
-        return sum(2.0 * 36 * tp * self.ktot * self.cout for _, _, tp in self.chunks())
+        """FLOPs the grouped GEMM actually executes (36 planes x padded tiles)."""
+        return 2.0 * 36 * self.Tp * self.ktot * self.cout
 
 
 WINO_DIRECT_UNDILATED_128 = os.environ.get("CASAPOSE_WINO_DIRECT_128", "")   # "" = by conv mode (f16x2: yes), "0" / "1" force (A/B)
@@ -838,11 +783,9 @@ class ForwardPlan:
                 src0 = prev
                 mode = _lib.SRC_DIRECT
                 if up:
-                    # round 3 materialised the x2 bilinear tensor for the 32-output-channel layers (blocks 4, 5) on the bf16 pipe: four taps per
-                    # halo pixel from global memory did not fit their loaders (0.77 / 1.29 ms fused against 0.46 / 0.63 ms direct).  The loaders
-                    # now stage the half-resolution tile in LDS and interpolate from there (csrc/conv_hsplit.hip), so the fused form is the
-                    # default everywhere; CASAPOSE_MATERIALISE_BILINEAR=1 restores the separate streaming pass (A/B measurements)
-                    if fuse_upsample and not (net.conv_planes and dims[i] <= 32 and MATERIALISE_BILINEAR):
+                    # the convolution's loaders interpolate the x2 bilinear source from the half-resolution tile (staged in LDS by
+                    # csrc/conv_hsplit.hip); fuse_upsample=False materialises it in a separate streaming pass (the unfused reference)
+                    if fuse_upsample:
                         mode = _lib.SRC_BILINEAR_X2
                     else:
                         big = new(B, hs[l], ws[l], prev_c)
@@ -971,7 +914,7 @@ class ForwardPlan:
         # consecutive Winograd layers A -> B of one geometry where B's only source is A's activated output and nothing else reads it: A's output
         # transform writes B's transformed input directly (cp_wino_output_input_transform_f32); the activated map is not stored
         for (a, ka, private), (b, kb, _) in zip(self._wino_pending, self._wino_pending[1:]):
-            if not (WINO_FUSE_OUT_IN and private and WINO_CHUNK == 0 and not WINO_GROUPED_CONV):
+            if not private:
                 continue
             ia, ib = self.steps.index(a.run), self.steps.index(b.run)
             same = all(ka[k] == kb[k] for k in ("batch", "in_h", "in_w", "dilation"))
@@ -993,11 +936,8 @@ class ForwardPlan:
         elif fresh:
             self._mon.zero_()
         base = self._mon.data_ptr()
-        only = os.environ.get("CASAPOSE_F16X2_MONITOR_ONLY", "")   # (measurement aid: arm one kernel family only -- "wino", "fused" or a layer-name prefix)
         for i, c in enumerate(self.convs):
             c.mon_ptr = base + 16 * i
-            if only and not ((only == "wino" and isinstance(c, WinoConv)) or (only == "fused" and isinstance(c, FusedConv)) or c.name.startswith(only)):
-                c.mon_ptr = None
         try:
             for step in self.steps:
                 step(stream)
@@ -1229,30 +1169,6 @@ class ForwardPlan:
         self._out_bound = [(l, o, f) for l, o, f in self._out_bound if not (l is b5 and f == "head_out") and not (l is b10 and f == "head_out")]
         self._out_bound.append((b10, 0, "head_out"))   # block 10 addresses the record itself
 
-    def micro_steps(self, img: torch.Tensor, out: torch.Tensor):
-        """The launches of run(img, out=out) with the estimated mask as a list of (tag, fn(stream)): "M" = matrix-pipe kernels (convolutions, the
-        Winograd GEMMs), "H" = HBM-bound passes (Winograd transforms, pooling, label pyramid, resampling, channel padding).  Binds `out`."""
-        lib = _lib.load()
-        B, h, w = self.batch, self.h, self.w
-        if tuple(img.shape) != (B, h, w, 3) or img.dtype != torch.float32 or not img.is_contiguous():
-            raise ValueError("image must be a contiguous float32 [%d,%d,%d,3] tensor" % (B, h, w))
-        if WINO_CHUNK or WINO_GROUPED_CONV:
-            raise ValueError("the two-stream forward does not combine with CASAPOSE_WINO_CHUNK / CASAPOSE_WINO_GROUPED_CONV")
-        self.out = out
-        for layer, off, field in self._out_bound:
-            setattr(layer.desc, field, out.data_ptr() + 4 * off)
-        self.seg_input_ptr = None
-        steps = [("H", lambda stream: check(lib.cp_pad_channels_3to4(img.data_ptr(), self.img4.data_ptr(), B * h * w, stream), "cp_pad_channels_3to4"))]
-        for st in self.steps:
-            owner = getattr(st, "__self__", None)
-            if isinstance(owner, WinoConv):
-                steps += owner.micro_steps()
-            elif isinstance(owner, FusedConv):
-                steps.append(("M", st))
-            else:
-                steps.append(("H", st))
-        return steps
-
     def run(self, img: torch.Tensor, seg_input: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
         lib = _lib.load()
         B, h, w = self.batch, self.h, self.w
@@ -1333,8 +1249,6 @@ class CasaposeNet:
         self.f16x2_fallback: Dict[str, str] = {}   # layer -> why it left f16x2 (ForwardPlan._calibrate); reset by set_params
         self._f16x2_warned = False
         self.plans: Dict[Tuple[int, int, int], ForwardPlan] = {}
-        self._twin: Optional["CasaposeNet"] = None   # the second half-batch's layer objects (two-stream forward)
-        self._streams = None
         self.set_params(params)
 
     def recalibrate(self):
@@ -1343,8 +1257,6 @@ class CasaposeNet:
         incremental form of this by itself when a later batch leaves the band."""
         self.f16x2_fallback, self._f16x2_warned = {}, False
         self.plans.clear()
-        if self._twin is not None:
-            self._twin.recalibrate()
 
     def planes_for(self, layer_name: str) -> int:
         """operand planes of one layer: the conv mode's, or 3 (exact split) once the f16x2 guard has demoted the layer"""
@@ -1353,8 +1265,6 @@ class CasaposeNet:
     def set_params(self, params: Dict[str, np.ndarray]):
         self.params = {k: np.asarray(v, dtype=np.float32) for k, v in params.items()}
         self.f16x2_fallback, self._f16x2_warned = {}, False   # new parameters: every plan calibrates again on its first forward
-        if getattr(self, "_twin", None) is not None:
-            self._twin.set_params(params)
         dev = self.device
         p = self.params
         tabs: Dict[str, Tuple[torch.Tensor, torch.Tensor]] = {}
@@ -1435,86 +1345,4 @@ class CasaposeNet:
 
     def forward(self, img: torch.Tensor, seg_input: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None):
         b, h, w, _ = img.shape
-        if TWO_STREAM and seg_input is None and not self.pvnet and b >= 2 and b % 2 == 0 and not (WINO_CHUNK or WINO_GROUPED_CONV):
-            return self._forward_two_streams(img, out)
         return self.plan(b, h, w).run(img, seg_input, out)
-
-    def _forward_two_streams(self, img: torch.Tensor, out: Optional[torch.Tensor]) -> torch.Tensor:
-        """The batch as two halves software-pipelined over TWO HIP streams (round 4): matrix-pipe kernels ("M": convolutions, Winograd GEMMs)
-        on one stream, HBM-bound passes ("H": Winograd transforms, pooling, label pyramid, resampling) on the other, events where a half's
-        chain changes stream.  The persistent "M" kernels are launched with TWO_STREAM_BLOCKS (224 of 256) blocks, so the "H" kernels of one
-        half find free CUs while the other half's convolution runs: measured on the stage-4 shapes GEMM 0.325 ms + transforms 0.121 ms alone,
-        0.364 ms together.  Each half has its own CasaposeNet (descriptors and buffers live in the layer objects; the weights
-        are duplicated: 59 MB); results are those of two independent half-batch forwards -- the network has no cross-image term."""
-        b, h, w, _ = img.shape
-        hb = b // 2
-        if self._twin is None:
-            self._twin = CasaposeNet(self.params, self.seg_dim, self.ver_dim, self.device, decoder_dims=self.decoder_dims, fuse_upsample=self.fuse_upsample,
-                                     fuse_heads=self.fuse_heads, partial=self.partial, guided=self.guided, use_winograd=self.use_winograd,
-                                     bilinear=self.bilinear, pvnet=False, shared=self.shared, reuse_first=self.reuse_first, skips2=self.skips2,
-                                     conv_mode=self.conv_mode, f16x2_guard=self.f16x2_guard)
-            self._streams = (torch.cuda.Stream(self.device), torch.cuda.Stream(self.device))
-        if out is None:
-            out = torch.empty(b, h, w, self.seg_dim + self.ver_dim, dtype=torch.float32, device=img.device)
-        plans = [self.plan(hb, h, w), self._twin.plan(hb, h, w)]
-        for i, pl in enumerate(plans):   # f16x2 range guard: a plan's first forward runs layer by layer on the current stream
-            if pl.needs_calibration:
-                pl.run(img[i * hb:(i + 1) * hb], out=out[i * hb:(i + 1) * hb])
-        seqs = [plans[0].micro_steps(img[:hb], out[:hb]), plans[1].micro_steps(img[hb:], out[hb:])]
-        lib = _lib.load()
-        cur = torch.cuda.current_stream(self.device)
-        streams = {"M": self._streams[0], "H": self._streams[1]}
-        for s_ in streams.values():
-            s_.wait_stream(cur)
-        old_blocks = lib.cp_get_persistent_blocks()
-        check(lib.cp_set_persistent_blocks(min(old_blocks, TWO_STREAM_BLOCKS)), "cp_set_persistent_blocks")
-        try:
-            pos, last = [0, 0], [None, None]   # next micro-step / (tag, event) of the last issued step per half
-            lead = int(TWO_STREAM_SKEW * len(seqs[0]))
-            if TWO_STREAM_MODE == "half":
-                # one in-order stream per HALF (no cross-stream waits inside a chain): the hardware runs whatever of the two queues fits;
-                # half 1 starts when half 0 has passed `lead` steps, so that its transform-heavy encoder meets half 0's convolution-only decoders
-                s0, s1 = self._streams
-                gate = None
-                for k_, (tag, fn) in enumerate(seqs[0]):
-                    fn(s0.cuda_stream)
-                    if k_ + 1 == lead:
-                        gate = torch.cuda.Event()
-                        gate.record(s0)
-                    if k_ + 1 >= lead and pos[1] < len(seqs[1]):     # keep both queues fed: one step of half 1 per step of half 0
-                        if pos[1] == 0 and gate is not None:
-                            s1.wait_event(gate)
-                        seqs[1][pos[1]][1](s1.cuda_stream)
-                        pos[1] += 1
-                while pos[1] < len(seqs[1]):
-                    seqs[1][pos[1]][1](s1.cuda_stream)
-                    pos[1] += 1
-                pos[0] = len(seqs[0])
-
-            def issue(k):
-                tag, fn = seqs[k][pos[k]]
-                st = streams[tag]
-                if last[k] is not None and last[k][0] != tag:
-                    st.wait_event(last[k][1])                   # this half's previous step ran on the other stream
-                fn(st.cuda_stream)
-                pos[k] += 1
-                ev = None
-                if pos[k] < len(seqs[k]) and seqs[k][pos[k]][0] != tag:   # the next step of this half changes stream: it will wait for this one
-                    ev = torch.cuda.Event()
-                    ev.record(st)
-                last[k] = (tag, ev)
-
-            # "tag" mode: matrix-pipe kernels on one stream, HBM-bound passes on the other, events where a half's chain changes stream; half 0
-            # runs ahead by `lead` steps, then the two lists are issued alternately -- the streams serialise equal tags in issue order
-            for _ in range(lead if pos[0] == 0 else 0):
-                issue(0)
-            while pos[0] < len(seqs[0]) or pos[1] < len(seqs[1]):
-                for k in (1, 0):
-                    if pos[k] < len(seqs[k]):
-                        issue(k)
-        finally:
-            check(lib.cp_set_persistent_blocks(old_blocks), "cp_set_persistent_blocks")
-        for s_ in streams.values():
-            cur.wait_stream(s_)
-        _remember_labels(out, torch.cat([plans[0].labels[0], plans[1].labels[0]]))
-        return out

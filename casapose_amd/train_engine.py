@@ -664,8 +664,8 @@ class ConvOp:
             w["ps"].fill_(2.0 ** e)
         self._refresh_winograd(stream)
 
-    def bind_winograd(self, V: torch.Tensor, M: torch.Tensor, M2: Optional[torch.Tensor] = None):
-        self._wV, self._wM, self._wM2 = V, M, (M2 if M2 is not None else M)
+    def bind_winograd(self, V: torch.Tensor, M: torch.Tensor):
+        self._wV, self._wM = V, M
         for w in ([self.wino_fwd] if self.wino_fwd is not None else []) + list(self.wino_dgrad.values()):
             d = w["desc"]
             d.batch, d.in_h, d.in_w, d.out_h, d.out_w = 36, 1, w["tp"], 1, w["tp"]
@@ -906,14 +906,12 @@ class ConvOp:
         assert self.out.has_grad, "gradient of %s not produced" % self.layer.name
         return self.out.grad.data_ptr(), self.out.c
 
-    def backward(self, stream: int, wgrad_stream: Optional[int] = None):
-        """weight gradient, then the data gradient of every source.  wgrad_stream (TrainPlan.backward with a side stream): the weight-gradient
-        launches go there -- they are off the critical path of the backward (nothing but Adam reads them) and MFMA-bound, so they can run under
-        the HBM-bound normalisation / resampling passes of the layers before; the caller orders the two streams with events."""
-        self.backward_wgrad(stream if wgrad_stream is None else wgrad_stream, side=wgrad_stream is not None)
+    def backward(self, stream: int):
+        """weight gradient, then the data gradient of every source"""
+        self.backward_wgrad(stream)
         self.backward_dgrad(stream)
 
-    def backward_wgrad(self, stream: int, side: bool = False):
+    def backward_wgrad(self, stream: int):
         lib = _lib.load()
         L = self.layer
         dy, dy_ld = self._dy()
@@ -943,13 +941,12 @@ class ConvOp:
             # weight gradient through the Winograd planes: a quarter of the MFMA work of the direct kernel (V kept from the forward)
             w = self.wino_fwd
             cin, cout = self._cin, L.cout
-            wM = self._wM2 if side else self._wM   # the side stream transforms dY into a scratch of its own (the data gradients use _wM)
             f = w.get("wg16") if self.wino_wgrad_split() else None
             arm = f is not None and not f["dead"] and f["mon"]
             if arm:
                 lib.cp_f16x2_monitor_set(f["mon"])   # the transform reports max |dM|
             try:
-                check(lib.cp_wino_dy_transform_f32(dy, dy_ld, cout, self.batch, self.in_h, self.in_w, self.dil, wM.data_ptr(), stream),
+                check(lib.cp_wino_dy_transform_f32(dy, dy_ld, cout, self.batch, self.in_h, self.in_w, self.dil, self._wM.data_ptr(), stream),
                       "cp_wino_dy_transform_f32(%s)" % L.name)
             finally:
                 if arm:
@@ -959,14 +956,14 @@ class ConvOp:
                 if f is not None and f["e"] is not None and L.fwd_f16x2:
                     # fp16 two-way split (train_bwd_f16x2): dM x 2^e from its monitor slot; V as it is -- the forward's monitor keeps it in the band
                     # (a forward that left the band is demoted: L.fwd_f16x2 turns False and this GEMM returns to the exact split with it)
-                    check(lib.cp_wino_wgrad_split_scaled_f32(wM.data_ptr(), w["V"].data_ptr(), w["dU"].data_ptr(), 36, w["tp"], cout, w["ktot"],
+                    check(lib.cp_wino_wgrad_split_scaled_f32(self._wM.data_ptr(), w["V"].data_ptr(), w["dU"].data_ptr(), 36, w["tp"], cout, w["ktot"],
                                                              _lib.PLANES_F16X2, 2.0 ** f["e"], 1.0, stream), "cp_wino_wgrad_split_scaled_f32(%s)" % L.name)
                 else:
-                    check(lib.cp_wino_wgrad_split_f32(wM.data_ptr(), w["V"].data_ptr(), w["dU"].data_ptr(), 36, w["tp"], cout, w["ktot"],
+                    check(lib.cp_wino_wgrad_split_f32(self._wM.data_ptr(), w["V"].data_ptr(), w["dU"].data_ptr(), 36, w["tp"], cout, w["ktot"],
                                                       1 if self.layer.mode_planes == 1 else 3, stream),
                           "cp_wino_wgrad_split_f32(%s)" % L.name)
             else:
-                check(lib.cp_conv2d_wgrad_f32(C.byref(w["wdesc"]), wM.data_ptr(), cout, w["dU"].data_ptr(), 0, stream), "cp_conv2d_wgrad_f32(wino %s)" % L.name)
+                check(lib.cp_conv2d_wgrad_f32(C.byref(w["wdesc"]), self._wM.data_ptr(), cout, w["dU"].data_ptr(), 0, stream), "cp_conv2d_wgrad_f32(wino %s)" % L.name)
             c0 = k0 = 0
             for cp_, cr in L.sources:
                 check(lib.cp_wino_weight_grad_f32(w["dU"].data_ptr(), cr, cout, w["ktot"], k0, 3 * cin * cout, cin * cout, cout, 1,
@@ -1438,15 +1435,12 @@ class TrainPlan:
                 seen.add(op.layer.key)
         self.tensors = [o for o in self._all_tensors()]
         # fused training normalisation (CASAPOSE_FUSE_NORM=0 restores the separate passes everywhere)
-        fuse = os.environ.get("CASAPOSE_FUSE_NORM", "1")   # 1 = all, 0 = none, heads / wino = one family only (bisection aid)
-        self.fuse_norm = fuse != "0"
-        self._fuse_wino_ok = fuse in ("1", "wino", "wino_stats", "wino_pre")
-        self._fuse_mode = fuse
-        if fuse in ("1", "heads"):
+        fuse = os.environ.get("CASAPOSE_FUSE_NORM", "1")
+        if fuse not in ("0", "1"):
+            raise ValueError("CASAPOSE_FUSE_NORM must be 1 (fused normalisation) or 0 (separate passes), got %r" % fuse)
+        self.fuse_norm = fuse == "1"
+        if self.fuse_norm:
             self._fuse_heads()
-        # weight gradients on a second stream (CASAPOSE_WGRAD_STREAM=1; see backward())
-        self.wgrad_on_side_stream = os.environ.get("CASAPOSE_WGRAD_STREAM", "0") == "1"
-        self._side = torch.cuda.Stream(device=dev) if self.wgrad_on_side_stream else None
         for op in self.ops:
             if isinstance(op, ConvOp):
                 op.setup_gemm()
@@ -1460,11 +1454,10 @@ class TrainPlan:
             if nv:
                 self.wino_V = torch.empty(nv, **f32)
                 self.wino_M = torch.empty(nm, **f32)
-                self.wino_M2 = torch.empty(nm, **f32) if self.wgrad_on_side_stream else None   # dY planes of the side stream's weight gradients
                 for op, sz in sizes:
                     if sz[0]:
-                        op.bind_winograd(self.wino_V, self.wino_M, self.wino_M2)
-                if self._fuse_wino_ok:
+                        op.bind_winograd(self.wino_V, self.wino_M)
+                if self.fuse_norm:
                     self._fuse_winograd()
         # gather map of conv0's packed weight-gradient entries that belong to the padding channel (c = 3)
         ramp = np.zeros((7, 7, 3, 64), np.int64)  # unused values; only the layout matters
@@ -1533,10 +1526,8 @@ class TrainPlan:
             if bn.head is not None or bn.pad_one:
                 continue
             prod = [c for c in convs if c.out is bn.x and getattr(c, "wino_fwd", None) is not None and c.stats_to is None]
-            if prod and bn.x.c == prod[0].layer.cout and self._fuse_mode != "wino_pre":
+            if prod and bn.x.c == prod[0].layer.cout:
                 prod[0].stats_to, bn.stats_from = bn, prod[0]
-            if self._fuse_mode == "wino_stats":
-                continue
             if bn.classes != 1 or bn.labels is not None or any(t is bn.y for t in self.taps.values()) or self._consumers(bn.y) != 1:
                 continue
             for c in convs:
@@ -1951,10 +1942,6 @@ class TrainPlan:
         log = self.comm_log
         if (multi or log is not None) and self._buckets is None:
             self._buckets = self._gradient_buckets()
-        side = self._side
-        main = torch.cuda.current_stream(self.out.device)
-        if side is not None:
-            side.wait_stream(main)   # the forward's activations and the loss gradient are ready
         # the direct data gradients' operand range: max |dY| by a reduction pass of its own, on the step before a reading of the slots only
         check_now = self._f16x2_mon is not None and (not self._bwd_calibrated or self._f16x2_steps >= F16X2_TRAIN_CHECK_EVERY - 1)
         for i in range(len(self.ops) - 1, -1, -1):
@@ -1962,13 +1949,7 @@ class TrainPlan:
             if check_now and isinstance(op, ConvOp) and getattr(op, "bw16", None) is not None and op.bw16["mon"] and not op.bw16["dead"]:
                 dy_, ld_ = op._dy()
                 check(_lib.load().cp_amax_f32(dy_, op.batch * op.out_h * op.out_w, ld_, op.layer.cout, op.bw16["mon"], stream), "cp_amax_f32(dY %s)" % op.layer.name)
-            if side is not None and isinstance(op, ConvOp):
-                ev = torch.cuda.Event()
-                ev.record(main)                 # dY of this layer is complete on the main stream
-                side.wait_event(ev)
-                op.backward(stream, wgrad_stream=side.cuda_stream)
-            else:
-                op.backward(stream)
+            op.backward(stream)
             if log is not None:
                 log.append(("op", i))
             if multi or log is not None:
@@ -1978,12 +1959,8 @@ class TrainPlan:
                             log.append(("grad_bucket", 4 * (e - a), "async", stream, first))
                         if not multi:
                             continue
-                        if side is not None:
-                            main.wait_stream(side)   # the bucket's weight gradients come from the side stream
                         self._unscale_grads(stream, a, e)   # (the loss factor is this replica's own: out before the sum over replicas)
                         self._pending.append(parallel.all_reduce_sum_async(self.store.grad[a:e], self.group))
-        if side is not None:
-            main.wait_stream(side)
         if not self._bwd_calibrated:
             self._calibrate_bwd(stream)
         # d beta of bn_data from the padding-channel entries of conv0's weight gradient (see __init__)

@@ -537,66 +537,3 @@ def test_gemm_route_does_not_survive_a_shape_change(device):
         rows8 = b * (h // 8) * (w // 8)   # the stage-3 / stage-4 shortcuts run at 1/8 resolution
         assert ("stage4_unit1_sc" in routed) == (rows8 % 128 == 0) and ("stage3_unit1_sc" in routed) == (rows8 % 128 == 0), (routed, rows8)
         assert rel_err(outs["split"][..., :k], outs["f32"][..., :k]) < 1e-4, (b, h, w)
-
-
-@pytest.mark.parametrize("mode", ["half", "tag"])
-def test_two_stream_forward_equals_the_single_stream_forward(device, monkeypatch, mode):
-    """CASAPOSE_TWO_STREAM=1 (round 4, opt-in -- measured no faster): the batch as two halves over two HIP streams, either a stream per
-    half or a stream per kernel class with events between them, persistent kernels launched with fewer blocks.  The network has no cross-image
-    term, so the output must equal the one-stream forward -- bit for bit where both batch sizes take the same kernel routes (bs 16 at 480 x 640:
-    `tools/debug/two_stream_bench.py`), to fp32 rounding in general (a 1x1 shortcut whose pixel count is not a multiple of 128 at the half
-    batch leaves the bf16-pipe GEMM for the fp32 kernel); the cached label map must serve the filtered voter, and the block count must be
-    restored afterwards."""
-    from casapose_amd import _lib, engine
-    from casapose_amd.pose_estimation.voting_layers_2d import CoordLSVotingWeighted
-    from casapose_amd.pose_models.tfkeras import Classifiers
-
-    k, v, b, h, w = 5, 27, 4, 64, 96
-    params = O.init_params(k, v, seed=3, dtype=np.float32)
-    net = Classifiers.get("casapose_c_gcu5")(ver_dim=v, seg_dim=k, input_shape=(h, w, 3), weights=None, device=device)
-    net.set_parameters(params)
-    img = torch.from_numpy(np.random.default_rng(4).uniform(-1, 1, (b, h, w, 3)).astype(np.float32)).to(device)
-    voter = CoordLSVotingWeighted(name="v", num_classes=k, num_points=9, filter_estimates=True)
-
-    def run():
-        out = net([img], training=False)
-        s, d, c = torch.split(out, [k, 18, 9], dim=3)
-        kp = voter([s, d, c])
-        torch.cuda.synchronize()
-        return out.clone(), kp.clone()
-
-    def same(a, b_):
-        # segmentation logits (decoder 1) everywhere; the vector fields are conditioned on the arg-max label map, so ONE pixel whose two top logits
-        # tie to the last bits changes them by O(1) inside that pixel's receptive field (seen: 1 of 24576 labels, |difference| 390): they are compared
-        # everywhere when the label maps agree, and on all but a small fraction of the pixels otherwise
-        lab_a, lab_b = a[..., :k].argmax(-1), b_[..., :k].argmax(-1)
-        flips = float((lab_a != lab_b).float().mean())
-        seg_ok = float((a[..., :k] - b_[..., :k]).abs().max()) <= 1e-4 * float(a[..., :k].abs().max())
-        dv = (a[..., k:] - b_[..., k:]).abs().amax(-1)
-        tol = 1e-4 * float(a[..., k:].abs().max())
-        vec_ok = float(dv.max()) <= tol if flips == 0.0 else float((dv > tol).float().mean()) <= 2e-2
-        return seg_ok and flips <= 1e-3 and vec_ok
-
-    one, kp_one = run()
-    lib = _lib.load()
-    before = lib.cp_get_persistent_blocks()
-    monkeypatch.setattr(engine, "TWO_STREAM", True)
-    monkeypatch.setattr(engine, "TWO_STREAM_MODE", mode)
-    for _ in range(2):
-        two, kp_two = run()
-        assert same(one, two)
-        assert torch.isfinite(kp_two).all()
-        # the label map the filtered voter reads is the two halves' head arg-max maps joined (keypoints themselves are not comparable between
-        # runs that differ in the last bits: an untrained network's 2x2 systems are ill-conditioned)
-        raw = net([img], training=False)
-        cached = engine.cached_labels(raw.untyped_storage().data_ptr(), (b, h, w))
-        torch.cuda.synchronize()
-        assert cached is not None and torch.equal(cached.long(), raw[..., :k].argmax(-1))
-    assert lib.cp_get_persistent_blocks() == before
-    # new parameters reach the second half's layer objects too
-    params2 = O.init_params(k, v, seed=8, dtype=np.float32)
-    net.set_parameters(params2)
-    two2, _ = run()
-    monkeypatch.setattr(engine, "TWO_STREAM", False)
-    one2, _ = run()
-    assert same(one2, two2) and not same(one2, one)

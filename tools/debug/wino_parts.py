@@ -24,11 +24,9 @@ print("%-22s %4s %5s %5s | %8s %8s %8s | %8s %8s %8s  (us; MB moved: V, M, layer
 tot = [0.0, 0.0, 0.0]
 for c in plan.convs:
     if not isinstance(c, engine.WinoConv): continue
-    ms = c.micro_steps()
     t = {"in": 0.0, "gemm": 0.0, "out": 0.0}
-    for i, (tag, fn) in enumerate(ms):
-        key = "gemm" if tag == "M" else ("in" if i == 0 and len(ms) == 3 else "out")
-        t[key] += timed(fn)
+    for part, fn in c.launches():
+        t[part] += timed(fn)
     vmb, mmb = 36 * c.Tp * c.ktot * 4 / 1e6, 36 * c.Tp * c.cout * 4 / 1e6
     io = (B * c.h * c.w * (sum(s[0] for s in c.sources) + c.cout) * 4) / 1e6
     note = "  (input written by the layer before: fused out -> in)" if c.skip_input else ("  (out -> in fused into the next layer)" if c.fuse_next is not None else "")
