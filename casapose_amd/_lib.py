@@ -88,6 +88,41 @@ class ConvDesc(C.Structure):
     ]
 
 
+AUG_MAX_OPS, AUG_MAX_LUTS, AUG_MAX_TAPS, AUG_NOISE_MAX, AUG_NOISE_FIELDS, AUG_FINISH_SLOT = 12, 6, 49, 16, 3, 15
+AUG_LUT, AUG_HUE_SAT, AUG_FREQ_BLEND, AUG_GAUSS_NOISE, AUG_LAPLACE_NOISE, AUG_POISSON_NOISE, AUG_DROPOUT, AUG_REPLACE = range(1, 9)
+AUG_BLUR_LINEAR, AUG_BLUR_MEDIAN, AUG_BLUR_BILATERAL = 9, 10, 11
+
+
+class AugOp(C.Structure):
+    """cp_aug_op of include/casapose_hip.h."""
+    _fields_ = [("kind", C.c_int32), ("per_channel", C.c_int32), ("slot", C.c_int32), ("k", C.c_int32), ("i0", C.c_int32), ("i1", C.c_int32),
+                ("f0", C.c_float), ("f1", C.c_float)]
+
+
+class AugImage(C.Structure):
+    """cp_aug_image of include/casapose_hip.h: one image's program for the input-pipeline kernels (csrc/augment.hip)."""
+    _fields_ = [
+        ("seed", C.c_uint64),
+        ("src_offset", C.c_int64),
+        ("src_h", C.c_int32), ("src_w", C.c_int32),
+        ("crop_x", C.c_int32), ("crop_y", C.c_int32),
+        ("warp", C.c_int32),
+        ("n_ops", C.c_int32),
+        ("affine", C.c_double * 6),
+        ("brightness", C.c_float), ("contrast", C.c_float), ("noise_sigma", C.c_float),
+        ("noise_fields", C.c_int32),
+        ("noise_h", C.c_int32 * AUG_NOISE_FIELDS), ("noise_w", C.c_int32 * AUG_NOISE_FIELDS), ("noise_up", C.c_int32 * AUG_NOISE_FIELDS),
+        ("noise_aggregate", C.c_int32),
+        ("noise_sigmoid", C.c_int32),
+        ("noise_threshold", C.c_float),
+        ("ops", AugOp * AUG_MAX_OPS),
+        ("taps", (C.c_float * AUG_MAX_TAPS) * 2),
+        ("noise", (C.c_float * (AUG_NOISE_MAX * AUG_NOISE_MAX)) * AUG_NOISE_FIELDS),
+        ("label_map", C.c_uint8 * 256),
+        ("lut", ((C.c_uint8 * 256) * 3) * AUG_MAX_LUTS),
+    ]
+
+
 ABI_VERSION = 302  # CP_ABI_VERSION of include/casapose_hip.h
 PLANES_F16X2 = 0x12  # CP_PLANES_F16X2: the fp16 two-way split (three products, fp32-level accuracy)
 
@@ -212,6 +247,13 @@ SYMBOLS = [
     ("cp_vector_field_f32", _i, [_vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _vp, _i, _vp]),
     ("cp_smooth_l1_f32", _i, [_vp, _i, _vp, _i, _vp, _i, _i, _i, _i, _ll, _vp, _vp, _vp]),
     ("cp_proxy_voting_f32", _i, [_vp, _i, _i, _vp, _vp, _i, _i, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
+    # ---- input pipeline (csrc/augment.hip) ----
+    ("cp_aug_image_size", C.c_size_t, []),
+    ("cp_aug_geometry", _i, [_vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp]),
+    ("cp_aug_photometric", _i, [_vp, _vp, _i, _i, _i, _i, _vp, _vp]),
+    ("cp_aug_resize", _i, [_vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp]),
+    ("cp_aug_channel_sums", _i, [_vp, _i, _ll, _vp, _vp]),
+    ("cp_aug_finish", _i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp]),
     ("cp_pose_loss_f32", _i, [_vp, _i, _i, _i, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _f, _f, _f, _vp, _vp, _i, _i, _vp, _vp, _vp]),
 ]
 
@@ -238,6 +280,9 @@ def load() -> C.CDLL:
         raise CasaposeHipError("%s has ABI %d with sizeof(cp_conv_desc) = %d, sizeof(cp_conv_source) = %d; this binding is ABI %d with %d / %d -- "
                                "rebuild the library (python __graft_entry__.py)" % (LIB_PATH, lib.cp_version(), lib.cp_conv_desc_size(),
                                                                                   lib.cp_conv_source_size(), ABI_VERSION, C.sizeof(ConvDesc), C.sizeof(ConvSource)))
+    if lib.cp_aug_image_size() != C.sizeof(AugImage):
+        raise CasaposeHipError("%s has sizeof(cp_aug_image) = %d; this binding declares %d -- rebuild the library (python __graft_entry__.py)"
+                               % (LIB_PATH, lib.cp_aug_image_size(), C.sizeof(AugImage)))
     _lib = lib
     return lib
 

@@ -18,8 +18,9 @@ Batches are dicts with the field names used by casapose_amd.training (img_batch 
 img[0] target_seg[1] target_vert[3] keypoints3d[4] cam_mat[5] diameters[6] offsets[7] filtered_seg[8] poses_gt[10]
 pixel_gt_count[11] image_id[12].
 
-Not carried over: imgaug pipelines and hue / saturation jitter (data augmentation is outside SURVEY 8); brightness / contrast
-jitter and the additive noise of image_augmentation (:259-272) are.  Only one instance per object is read, like the reference
+Not carried over: hue / saturation jitter of the non-imgaug branch; brightness / contrast jitter and the additive noise of
+image_augmentation (:259-272) are.  use_imgaug (the reference's imgaug `seq`, augmentation_model.py:43-110) runs on the device path of
+generate_dataset only (device_pipeline.py, augment.py); the host path refuses it.  Only one instance per object is read, like the reference
 (`max_count = 1`, :795).  Parity with the reference's loader is untested here (no dataset on this machine): the round trip
 against write_ndds_scene() below pins the conventions as read from the reference's code.
 """
@@ -166,14 +167,15 @@ class VectorfieldDataset:
                  data_size=None, random_translation=(25.0, 25.0), random_rotation=15.0, random_crop=True, contrast=0.2, brightness=0.2, hue=0.05,
                  saturation=0.2, use_train_split=False, use_validation_split=False, train_validation_split=0.9, output_folder="", use_imgaug=False,
                  visibility_filter=False, separated_vectorfields=False, wxyz_quaterion_input=False, path_filter_root=None, seed: int = 0):
-        if use_imgaug:
-            raise NotImplementedError("use_imgaug pipelines (augmentation_model.py) are not part of this build")
+        if use_imgaug and not color_input:
+            raise NotImplementedError("use_imgaug with color_input off (the reference's seq_grayscale) is not part of this build")
         if separated_vectorfields:
             raise NotImplementedError("separated vector fields (modelname pvnet) are not part of this build")
         self.path_meshes, self.no_points, self.color_input, self.normal = path_meshes, no_points, color_input, list(normal)
         self.objectsofinterest = list(objectsofinterest)
         self.noise, self.random_translation, self.random_rotation, self.random_crop = noise, random_translation, random_rotation, random_crop
         self.contrast, self.brightness = contrast, brightness
+        self.use_imgaug = bool(use_imgaug)
         self.use_train_split, self.use_validation_split, self.train_validation_split = use_train_split, use_validation_split, train_validation_split
         self.visibility_filter, self.wxyz_quaterion_input = visibility_filter, wxyz_quaterion_input
         if seed is None:
@@ -261,15 +263,8 @@ class VectorfieldDataset:
         return out
 
     # ---- one sample ----------------------------------------------------------------------------------
-    def apply_preprocessing(self, item, imagesize, cropratio) -> dict:
-        from PIL import Image
-
-        img_path, name, js, seg_path, path_raw = item
-        data = self.load_json_minimal(js)
-        img = Image.open(img_path)
-        img = img.convert("RGB") if self.color_input else img.convert("L")
-        seg = Image.open(seg_path).convert("L")
-        width, height = img.size
+    def draw_geometry(self, width, height, imagesize, cropratio) -> dict:
+        """The crop / translation / rotation draws of one image (in this order, from self.rng) and the maps they define."""
         crop_h = round(float(height) * cropratio)
         crop_w = crop_h * (float(imagesize[1]) / float(imagesize[0]))
         out_h, out_w = int(crop_h), int(crop_w)
@@ -290,15 +285,12 @@ class VectorfieldDataset:
         ar[:2] = get_rotation_matrix_2D((width / 2, height / 2), -angle)
         at[:2] = [[1, 0, -dx], [0, 1, -dy]]
         affine = (ar @ at).flatten()[:6]
-        if dx or dy or angle:
-            img = img.transform(img.size, Image.AFFINE, data=tuple(affine), resample=Image.BILINEAR)
-            seg = seg.transform(seg.size, Image.AFFINE, data=tuple(affine), resample=Image.NEAREST)
-        box = (w_crop, h_crop, w_crop + out_w, h_crop + out_h)
-        img = img.crop(box).resize((imagesize[1], imagesize[0]), Image.BILINEAR)
-        seg = seg.crop(box).resize((imagesize[1], imagesize[0]), Image.NEAREST)
-        img = np.asarray(img, np.float32)
-        img = img[..., None] if img.ndim == 2 else img
-        seg = np.asarray(seg, np.uint8)
+        return dict(out_h=out_h, out_w=out_w, scale=scale, w_crop=w_crop, h_crop=h_crop, dx=dx, dy=dy, angle=angle, offsets=offsets, tm=tm, rm=rm,
+                    affine=affine, width=width, height=height)
+
+    def annotations(self, data, path_raw, geo) -> Tuple[dict, Dict[int, int]]:
+        """Keypoints / poses / counts of one image under the drawn geometry, and the segmentation id -> label map (1..oc in the order of
+        objectsofinterest; later objects win, like the reference's successive masks)."""
         labels, fixed, cam = self.class_labels[path_raw], self.fixed_transformations[path_raw], self.camera_data[path_raw]
         oc, kp = len(self.objectsofinterest), self.no_points
         kp2 = np.full((oc, 1, kp, 2), -1000.0, np.float32)
@@ -307,7 +299,8 @@ class VectorfieldDataset:
         poses = np.zeros((oc, 1, 3, 4), np.float32)
         pxc = np.zeros((oc, 1, 1), np.float32)
         diam = np.full((oc, 1, 1), -1.0, np.float32)
-        new_seg = np.zeros_like(seg)
+        remap: Dict[int, int] = {}
+        rm, tm, scale, w_crop, h_crop = geo["rm"], geo["tm"], geo["scale"], geo["w_crop"], geo["h_crop"]
         for o, obj in enumerate(self.objectsofinterest):
             mesh = self.meshes[obj]
             if obj in fixed:
@@ -327,8 +320,46 @@ class VectorfieldDataset:
                     poses[o, 0] = quaternion_matrix(data["poses_quaternions"][i], data["poses_loc"][i], wxyz_input=self.wxyz_quaterion_input)
                     pxc[o, 0, 0] = int(float(data["px_count_all"][i]) * scale + 0.5)
                     diam[o, 0, 0] = mesh["diameter"] * (np.linalg.norm(fixed[obj][:, 0]) if obj in fixed else 1.0)
-                    new_seg[seg == labels[obj]] = o + 1
+                    remap[int(labels[obj])] = o + 1
                     break
+        p = os.path.normpath(path_raw.replace("\\", "/")).split(os.sep)
+        name = os.path.basename(data.get("_img_path", ""))
+        return dict(target_vert=kp2, keypoints3d=kp3, cam_mat=cam.astype(np.float32), diameters=diam, offsets=geo["offsets"], cuboid3d=cub,
+                    poses_gt=poses, pixel_gt_count=pxc, image_id=p[-2] + "_" + p[-1] + "_" + os.path.splitext(name)[0]), remap
+
+    def draw_photometric(self) -> Tuple[float, float, float]:
+        """(brightness offset, contrast factor, noise sigma) of image_augmentation (:259-272), drawn in this order; 0 / 1 / 0 when off."""
+        b = float(self.rng.uniform(-self.brightness, self.brightness)) if self.brightness else 0.0
+        f = float(self.rng.uniform(1 - self.contrast, 1 + self.contrast)) if self.contrast else 1.0
+        sigma = float(self.rng.uniform(0, self.noise)) if self.noise else 0.0
+        return b, f, sigma
+
+    # ---- one sample ----------------------------------------------------------------------------------
+    def apply_preprocessing(self, item, imagesize, cropratio) -> dict:
+        from PIL import Image
+
+        img_path, name, js, seg_path, path_raw = item
+        data = self.load_json_minimal(js)
+        data["_img_path"] = name
+        img = Image.open(img_path)
+        img = img.convert("RGB") if self.color_input else img.convert("L")
+        seg = Image.open(seg_path).convert("L")
+        width, height = img.size
+        geo = self.draw_geometry(width, height, imagesize, cropratio)
+        out_h, out_w, w_crop, h_crop, affine = geo["out_h"], geo["out_w"], geo["w_crop"], geo["h_crop"], geo["affine"]
+        if geo["dx"] or geo["dy"] or geo["angle"]:
+            img = img.transform(img.size, Image.AFFINE, data=tuple(affine), resample=Image.BILINEAR)
+            seg = seg.transform(seg.size, Image.AFFINE, data=tuple(affine), resample=Image.NEAREST)
+        box = (w_crop, h_crop, w_crop + out_w, h_crop + out_h)
+        img = img.crop(box).resize((imagesize[1], imagesize[0]), Image.BILINEAR)
+        seg = seg.crop(box).resize((imagesize[1], imagesize[0]), Image.NEAREST)
+        img = np.asarray(img, np.float32)
+        img = img[..., None] if img.ndim == 2 else img
+        seg = np.asarray(seg, np.uint8)
+        ann, remap = self.annotations(data, path_raw, geo)
+        new_seg = np.zeros_like(seg)
+        for sid, lab in remap.items():
+            new_seg[seg == sid] = lab
         # photometric part of image_augmentation (:259-272)
         if self.brightness:
             img = img + self.rng.uniform(-self.brightness, self.brightness)
@@ -342,17 +373,24 @@ class VectorfieldDataset:
         img = np.clip(img, -1, 1).astype(np.float32)
         if img.shape[2] == 1:
             img = np.repeat(img, 3, axis=2)
-        p = os.path.normpath(path_raw.replace("\\", "/")).split(os.sep)
-        return dict(img=img, label=new_seg, target_vert=kp2, keypoints3d=kp3, cam_mat=cam.astype(np.float32), diameters=diam, offsets=offsets,
-                    cuboid3d=cub, poses_gt=poses, pixel_gt_count=pxc, image_id=p[-2] + "_" + p[-1] + "_" + os.path.splitext(name)[0])
+        return dict(img=img, label=new_seg, **ann)
 
     # ---- batches ---------------------------------------------------------------------------------------
     def generate_dataset(self, batchsize, epochs, prefetch=0, imagesize=(448, 448), cropratio=1.0, worker=1, no_objects=None, shuffle=True,
-                         mirrored_strategy=None, shard: Tuple[int, int] = (0, 1)) -> Tuple[Iterator[Dict[str, torch.Tensor]], int]:
+                         mirrored_strategy=None, shard: Tuple[int, int] = (0, 1), device=None) -> Tuple[Iterator[Dict[str, torch.Tensor]], int]:
         """`batchsize` is the GLOBAL batch (vectorfield_dataset.py:923; `experimental_distribute_dataset` splits it, :1000-1002).  Here every
         replica owns a process: shard = (rank, world) makes it read, decode and augment only its contiguous slice of each global batch
-        (the epoch permutation comes from a generator of its own, seeded alike on all replicas, so the slices partition the batch)."""
+        (the epoch permutation comes from a generator of its own, seeded alike on all replicas, so the slices partition the batch).
+        device: None = this host path; a GPU = the device path (device_pipeline.py: decode on `worker` threads, every per-pixel step on the
+        GPU, up to max(prefetch, 1) batches in flight), the only path that runs use_imgaug."""
         from ..parallel import shard_range
+
+        if device is not None:
+            from .device_pipeline import device_batches
+
+            return device_batches(self, device, batchsize, epochs, prefetch, imagesize, cropratio, worker, shard, shuffle)
+        if self.use_imgaug:
+            raise ValueError("use_imgaug runs on the device input pipeline only: call generate_dataset(..., device=<GPU>)")
 
         data_size = len(self.imgs) - (len(self.imgs) % batchsize)
         epoch_batches = data_size // batchsize

@@ -676,6 +676,83 @@ int cp_kp_stats_f32(const float* field, int ld, int conf_off, const uint8_t* lab
 int cp_kp_reproj_loss_f32(const float* coords_yx, const float* gt_xy, const float* affine, const float* avail, int batch, int objects,
                           int kp, float max_pixel_error, float weight, float* g_yx, double* loss_out, void* stream);
 
+/* ---- input pipeline: training batches assembled on the device (csrc/augment.hip) -----------------------------------------------
+ * One cp_aug_image per image, filled by the host (casapose_amd/data_handler/augment.py) and copied to the device with the batch; every
+ * kernel below reads the program of image b from progs[b] and handles the whole batch in one launch, on the caller's stream, with no
+ * allocation, synchronous copy or synchronisation.  Added in ABI 302 without changing any earlier struct or entry point. */
+#define CP_AUG_MAX_OPS 12
+#define CP_AUG_MAX_LUTS 6
+#define CP_AUG_MAX_TAPS 49          /* 7 x 7: the widest linear blur of the imgaug sequence */
+#define CP_AUG_NOISE_MAX 16         /* side of the largest FrequencyNoise field */
+#define CP_AUG_NOISE_FIELDS 3       /* iterations of its IterativeNoiseAggregator */
+#define CP_AUG_FINISH_SLOT 15       /* Philox counter slot of the Gaussian noise of cp_aug_finish */
+
+/* op kinds of the photometric program (cp_aug_photometric); the Philox counter of a random op is (slot, pixel, channel, 0) */
+enum cp_aug_op_kind {
+    CP_AUG_LUT = 1,          /* out[c] = lut[c][in[c]]: Add, Multiply, Gamma / Sigmoid / Log / Linear contrast (host-built, already rounded) */
+    CP_AUG_HUE_SAT = 2,      /* RGB -> HSV (OpenCV 8-bit) ; h = (h + i0) mod 180 ; s = clip(s + i1) ; HSV -> RGB */
+    CP_AUG_FREQ_BLEND = 3,   /* a = noise mask ; out = round(a lut[i0](x) + (1 - a) lut[i1](x)) */
+    CP_AUG_GAUSS_NOISE = 4,  /* out = round(clip(x + N(0, f0))) */
+    CP_AUG_LAPLACE_NOISE = 5,/* out = round(clip(x + Laplace(0, f0))) */
+    CP_AUG_POISSON_NOISE = 6,/* out = clip(x +- Poisson(f0)), sign uniform */
+    CP_AUG_DROPOUT = 7,      /* out = 0 with probability f0 */
+    CP_AUG_REPLACE = 8,      /* with probability f0: out = round(255 r), r = Beta(.5,.5) folded by i0 (0 both, 1 salt, 2 pepper) */
+    CP_AUG_BLUR_LINEAR = 9,  /* correlation with the k x k taps[i0] (anchor k/2), reflect-101 border */
+    CP_AUG_BLUR_MEDIAN = 10, /* k x k median (k odd), replicate border */
+    CP_AUG_BLUR_BILATERAL = 11 /* OpenCV bilateral: radius k, f0 = sigma colour, f1 = sigma space, reflect-101 border */
+};
+
+typedef struct cp_aug_op {
+    int32_t kind;            /* cp_aug_op_kind */
+    int32_t per_channel;     /* random ops: 1 = one draw per channel, 0 = one per pixel shared by the channels */
+    int32_t slot;            /* Philox counter slot */
+    int32_t k;               /* blur window (linear / median: side; bilateral: radius) */
+    int32_t i0, i1;          /* integer parameters (see the kinds) */
+    float f0, f1;            /* real parameters (see the kinds) */
+} cp_aug_op;
+
+typedef struct cp_aug_image {
+    uint64_t seed;                   /* Philox key of the image */
+    int64_t src_offset;              /* pixel offset of the image in the source buffers: rgb at 3 * src_offset, segmentation at src_offset */
+    int32_t src_h, src_w;            /* decoded size */
+    int32_t crop_x, crop_y;          /* crop origin in the (warped) source */
+    int32_t warp;                    /* 0: plain crop; 1: affine warp first (PIL AFFINE, output -> input map `affine`, fill 0) */
+    int32_t n_ops;                   /* photometric ops in `ops` (blur kinds contiguous, at most two) */
+    double affine[6];                /* x_in = a0 x + a1 y + a2, y_in = a3 x + a4 y + a5 at output pixel centres (x + .5, y + .5) */
+    float brightness;                /* cp_aug_finish: added to the 0..255 image (0 = off) */
+    float contrast;                  /* cp_aug_finish: (v - mean) * contrast + mean per channel (1 = off; needs channel sums) */
+    float noise_sigma;               /* cp_aug_finish: Gaussian noise of the normalised image (0 = off) */
+    int32_t noise_fields;            /* CP_AUG_FREQ_BLEND: fields aggregated (1..3) */
+    int32_t noise_h[CP_AUG_NOISE_FIELDS], noise_w[CP_AUG_NOISE_FIELDS], noise_up[CP_AUG_NOISE_FIELDS];  /* size, upscale 0 nearest 1 linear 2 cubic */
+    int32_t noise_aggregate;         /* 0 max, 1 average */
+    int32_t noise_sigmoid;           /* 1: a = 1 / (1 + exp(-(20 a - 10 - noise_threshold))) */
+    float noise_threshold;
+    cp_aug_op ops[CP_AUG_MAX_OPS];
+    float taps[2][CP_AUG_MAX_TAPS];  /* linear blur weights, row-major k x k */
+    float noise[CP_AUG_NOISE_FIELDS][CP_AUG_NOISE_MAX * CP_AUG_NOISE_MAX];  /* FrequencyNoise fields in [0,1], row-major h x w */
+    uint8_t label_map[256];          /* segmentation id -> training label (0 = background) */
+    uint8_t lut[CP_AUG_MAX_LUTS][3][256];
+} cp_aug_image;
+
+size_t cp_aug_image_size(void);
+/* A: warp + crop.  src_rgb uint8 HWC, src_seg uint8 HW (all images of the batch, at progs[b].src_offset); crop_rgb [batch][crop_h][crop_w][3]
+ * (bilinear, PIL's rounding) and crop_lab [batch][crop_h][crop_w] (nearest, then label_map). */
+int cp_aug_geometry(const uint8_t* src_rgb, const uint8_t* src_seg, const cp_aug_image* progs, int batch, int crop_h, int crop_w,
+                    uint8_t* crop_rgb, uint8_t* crop_lab, void* stream);
+/* B: the photometric program of every image on uint8 [batch][h][w][3] (in != out).  Pointwise ops before the blurs run while a tile and its
+ * halo are loaded to LDS, then up to two blurs, then the remaining ops; uint8 rounding after every op.  tile_hint 0: 32 x 32 tiles, 1: 16 x 8
+ * (same result). */
+int cp_aug_photometric(const uint8_t* in, const cp_aug_image* progs, int batch, int h, int w, int tile_hint, uint8_t* out, void* stream);
+/* C1: PIL BILINEAR resize of uint8 rgb [batch][in_h][in_w][3] and NEAREST resize of labels to out_h x out_w (in != out). */
+int cp_aug_resize(const uint8_t* in_rgb, const uint8_t* in_lab, int batch, int in_h, int in_w, int out_h, int out_w, uint8_t* out_rgb,
+                  uint8_t* out_lab, void* stream);
+/* C2: sums[b][c] = sum of channel c of image b (uint32, zeroed by the call with an asynchronous memset on `stream`). */
+int cp_aug_channel_sums(const uint8_t* rgb, int batch, long long pixels, uint32_t* sums, void* stream);
+/* C3: img fp32 [batch][h][w][3] = clip(((brightness / contrast of rgb) / 255 - .5) / .5 + N(0, noise_sigma), -1, 1); filtered int32
+ * [batch][h][w] = labels; target fp32 [batch][h][w][classes] = one-hot of labels.  sums may be null when no image has contrast != 1. */
+int cp_aug_finish(const uint8_t* rgb, const uint8_t* lab, const cp_aug_image* progs, const uint32_t* sums, int batch, int h, int w,
+                  int classes, float* img, int32_t* filtered, float* target, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
