@@ -238,6 +238,7 @@ SYMBOLS = [
     ("cp_scatter_f32", _i, [_vp, _vp, _ll, _vp, _i, _vp]),
     ("cp_axpby_f32", _i, [_vp, _f, _vp, _f, _ll, _vp, _vp]),
     ("cp_adam_step_f32", _i, [_vp, _vp, _vp, _vp, _ll, _f, _f, _f, _f, _i, _f, _vp]),
+    ("cp_adam_step_masked_f32", _i, [_vp, _vp, _vp, _vp, _ll, _f, _f, _f, _f, _i, _f, _vp, _vp]),
     ("cp_pose_loss_workspace_bytes", C.c_size_t, [_i, _i, _i]),
     ("cp_ls_vote_bwd_f32", _i, [_vp, _i, _i, _i, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp]),
     ("cp_kp_stats_f32", _i, [_vp, _i, _i, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp]),

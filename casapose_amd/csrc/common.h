@@ -54,7 +54,9 @@ inline int persistent_blocks() { return persistent_blocks_ref(); }
 // ---- f16x2 range monitor (round 6) -------------------------------------------------------------------------------------------------
 // A monitor slot is four 32-bit words of device memory: [0] = bits of max |operand| over every fp32 value a launch converted to an fp16 pair
 // (atomic max on the bit pattern: monotone for non-negative floats, inf included), [1] = launches that reported, [2] = the same maximum for the
-// operand of a fused 1x1 head (the activated map that exists in registers only), [3] reserved.  cp_f16x2_monitor_set() arms the slot for the
+// operand of a fused 1x1 head (the activated map that exists in registers only), [3] the overflow guard: bits 0-30 hold a threshold the caller
+// sets (the bit pattern of a positive float; 0 = no guard), bit 31 is set by any report of word [0] above that threshold (monitor_flush, or
+// monitor_flag for an operand the slot's maximum does not cover).  cp_f16x2_monitor_set() arms the slot for the
 // CALLING THREAD's next launches; every kernel that converts activations (conv_hsplit, conv_stem_split, the split GEMMs) or writes the Winograd
 // planes another kernel converts (wino_in, wino_out_in) reads it at launch time.  A null slot costs one uniform branch per staged slice.
 uint32_t*& f16x2_monitor_ref();   // capi.hip (thread-local)
@@ -64,11 +66,27 @@ __device__ __forceinline__ float amax4(float acc, const float4 v) {
     return fmaxf(fmaxf(fmaxf(fabsf(v.x), fabsf(v.y)), acc), fmaxf(fabsf(v.z), fabsf(v.w)));   // (v_max3_f32 with |.| modifiers; NaN operands are skipped)
 }
 
-// every lane of the wave calls it (wave-uniform control flow); word 0 or 2 of the slot
-__device__ __forceinline__ void monitor_flush(uint32_t* word, float amax) {
+__device__ __forceinline__ float wave_amax(float amax) {
 #pragma unroll
     for (int m = 32; m >= 1; m >>= 1) amax = fmaxf(amax, __shfl_xor(amax, m));
+    return amax;
+}
+// lane 0 of a wave, amax = the wave's maximum: bit 31 of word [3] when amax is above the slot's threshold (inf included: it compares as the
+// largest bit pattern; NaN operands are skipped by the maxima and are not clamped by a conversion either)
+__device__ __forceinline__ void monitor_guard(uint32_t* slot, float amax) {
+    const uint32_t t = __hip_atomic_load(slot + 3, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    if ((t & 0x7fffffffu) != 0u && __builtin_bit_cast(uint32_t, amax) > (t & 0x7fffffffu) && !(t >> 31)) atomicOr(slot + 3, 0x80000000u);
+}
+// every lane of the wave calls it: the overflow guard alone, for a converted operand whose maximum goes to no word of the slot
+__device__ __forceinline__ void monitor_flag(uint32_t* slot, float amax) {
+    amax = wave_amax(amax);
+    if ((threadIdx.x & 63) == 0 && amax > 0.f) monitor_guard(slot, amax);
+}
+// every lane of the wave calls it (wave-uniform control flow); word 0 of the slot (with its overflow guard) or, guard = false, word 2
+__device__ __forceinline__ void monitor_flush(uint32_t* word, float amax, bool guard = true) {
+    amax = wave_amax(amax);
     if ((threadIdx.x & 63) == 0 && amax > 0.f) {
+        if (guard) monitor_guard(word, amax);
         // Look before the atomic: the slot is a sticky maximum, so after the first waves of the first armed launch almost no wave has anything to add --
         // and tens of thousands of same-address atomics at the end of every transform launch cost 0.28 ms of an 7.8 ms forward (measured, A/B in one
         // call: 2040 against 1970 images/s).  A stale (smaller) value read here only means an atomic that was not needed.

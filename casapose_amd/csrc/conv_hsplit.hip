@@ -433,7 +433,7 @@ __global__ __launch_bounds__(512, 2) void conv_hsplit_kernel(const HSplitK p) {
         if constexpr (NP == 2) {
             if (p.mon) {   // uniform
                 cp::monitor_flush(p.mon, l_amax);
-                cp::monitor_flush(p.mon + 2, e_amax);
+                cp::monitor_flush(p.mon + 2, e_amax, false);
                 cp::monitor_count_launch(p.mon, threadIdx.x == 0);
             }
         }

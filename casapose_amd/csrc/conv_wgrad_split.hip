@@ -66,6 +66,7 @@ struct WSplitK {
     int tiles_m, tiles_n;   // (ci, co) tiles
     int strips, chunks, rc; // column strips per image, row chunks per strip, rows per chunk
     int J, U;               // pixel jobs per tile, units = tiles * J
+    uint32_t* mon;          // NP = 2: f16x2 range monitor slot (common.h) or null: the overflow guard of word [3] over dY as converted
 };
 
 struct Unit {
@@ -223,6 +224,7 @@ __global__ __launch_bounds__(512, 2) void wgrad_split_kernel(const WSplitK p) {
         // ------------------------------------------------ loaders ---------------------------------------------------------------
         const int lw = wave - 4;
         const int oct = lane & 3;
+        float d_amax = 0.f;   // NP = 2 with p.mon: max |dY| over what this loader converted
         constexpr int XPR = 16 * (4 / MB), XR = (XC + XPR - 1) / XPR;   // pixels per round / rounds of an input row
         constexpr int DPR = 16 * (4 / NB), DR = SW / DPR;
         const int x_mb = lw % MB, x_px0 = (lane >> 2) + 16 * (lw / MB);
@@ -321,6 +323,12 @@ __global__ __launch_bounds__(512, 2) void wgrad_split_kernel(const WSplitK p) {
             unsigned char* db = Ds + (T & 1) * DSLOT + d_nb * DROWB + oct * 16;
 #pragma unroll
             for (int r = 0; r < DR; ++r) store_planes<NP>(db + (d_px0 + r * DPR) * 64, DPLANE, dr[d][r][0], dr[d][r][1]);
+            if constexpr (NP == 2) {
+                if (p.mon) {   // (uniform; out-of-range rows loaded zeros)
+#pragma unroll
+                    for (int r = 0; r < DR; ++r) d_amax = cp::amax4(cp::amax4(d_amax, dr[d][r][0]), dr[d][r][1]);
+                }
+            }
             if constexpr (IMG) {
                 if (lane < 17 && i_px < XC) {
                     unsigned char* ib = Is + (T & 3) * ISLOT + i_px * 8;
@@ -367,6 +375,9 @@ __global__ __launch_bounds__(512, 2) void wgrad_split_kernel(const WSplitK p) {
                 issue(d);
                 WS_BARRIER();
             }
+        }
+        if constexpr (NP == 2) {
+            if (p.mon) cp::monitor_flag(p.mon, d_amax);   // (uniform: every loader wave gets here)
         }
         return;
     }
@@ -675,6 +686,7 @@ extern "C" int cp_conv2d_wgrad_split(const cp_conv_desc* d, const float* dy, int
         k.img_bytes = (unsigned)((long long)d->batch * d->in_h * d->in_w * in.ld * 4);
     }
     int rc;
+    k.mon = planes == CP_PLANES_F16X2 ? cp::f16x2_monitor() : nullptr;
     if (planes == CP_PLANES_F16X2) rc = d->tap_label ? launch_shape<2, true>(k, st) : launch_shape<2, false>(k, st);
     else if (planes == 3) rc = d->tap_label ? launch_shape<3, true>(k, st) : launch_shape<3, false>(k, st);
     else rc = d->tap_label ? launch_shape<1, true>(k, st) : launch_shape<1, false>(k, st);

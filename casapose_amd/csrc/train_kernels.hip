@@ -563,6 +563,23 @@ __global__ void adam_kernel(float* __restrict__ p, const float* __restrict__ g, 
     }
 }
 
+// cp_adam_step_masked_f32: skip[0] with bit 31 set leaves everything as it is; otherwise the step counts as step - skip[1]
+__global__ void adam_masked_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m, float* __restrict__ v, long long n,
+                                   float lr, float b1, float b2, float eps, int step, float grad_scale, const uint32_t* __restrict__ skip) {
+    const uint32_t flag = __builtin_nontemporal_load(skip), before = __builtin_nontemporal_load(skip + 1);
+    if (flag >> 31) return;
+    const double t = (double)(step - (int)before);
+    const float lr_t = (float)(lr * sqrt(1.0 - pow((double)b2, t)) / (1.0 - pow((double)b1, t)));
+    for (long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x) {
+        const float gi = g[i] * grad_scale;
+        const float mi = b1 * m[i] + (1.f - b1) * gi;
+        const float vi = b2 * v[i] + (1.f - b2) * gi * gi;
+        m[i] = mi;
+        v[i] = vi;
+        p[i] -= lr_t * mi / (sqrtf(vi) + eps);
+    }
+}
+
 // batch statistics -> normalisation constants, folded affine tables and moving-average update, one launch
 __global__ void bn_finalize_kernel(const double* __restrict__ sums, double inv_n, int C, int real_c, int classes, const float* __restrict__ gamma,
                                    const float* __restrict__ beta, float eps, int pad_one, float momentum, float* __restrict__ moving_mean,
@@ -741,6 +758,14 @@ extern "C" int cp_scatter_f32(const float* src, const int32_t* idx, long long n,
     CP_REQUIRE(src && idx && dst && n > 0, "cp_scatter_f32: bad arguments");
     CP_LAUNCH(scatter_kernel, dim3(grid_for(n)), dim3(THREADS), 0, (hipStream_t)stream, src, idx, n, dst, accumulate);
     return cp::check_launch("cp_scatter_f32");
+}
+
+extern "C" int cp_adam_step_masked_f32(float* params, const float* grads, float* m, float* v, long long n, float lr, float beta1, float beta2,
+                                       float eps, int step, float grad_scale, const uint32_t* skip, void* stream) {
+    CP_REQUIRE(params && grads && m && v && skip && n > 0 && step >= 1, "cp_adam_step_masked_f32: bad arguments");
+    CP_LAUNCH(adam_masked_kernel, dim3(grid_for(n)), dim3(THREADS), 0, (hipStream_t)stream, params, grads, m, v, n, lr, beta1, beta2, eps, step,
+              grad_scale, skip);
+    return cp::check_launch("cp_adam_step_masked_f32");
 }
 
 extern "C" int cp_axpby_f32(const float* a, float alpha, const float* b, float beta, long long n, float* out, void* stream) {

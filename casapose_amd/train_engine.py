@@ -156,6 +156,11 @@ class ParamStore:
         self.m = torch.zeros_like(self.theta)
         self.v = torch.zeros_like(self.theta)
         self.step_count = 0
+        # device-side skip of the fp16-pair backward (TrainPlan): int32 [skip flag (bit 31), steps skipped so far]; None = plain Adam.  skip[1] is
+        # not part of export(): a store rebuilt from exported parameters counts its bias correction from step_count again.  step_count itself
+        # (and with it training.Adam.iterations, the learning-rate schedule's clock) still advances on a skipped step: a skip is rare, one per
+        # gradient spike, and the schedule stays tied to the batches seen
+        self.skip: Optional[torch.Tensor] = None
 
     # ---- packed-weight arena: every kernel layout of every layer lives in ONE buffer refreshed by ONE gather of the master parameters
     def pack_reset(self):
@@ -204,8 +209,16 @@ class ParamStore:
 
     def adam_step(self, lr: float, stream: int, beta1=0.9, beta2=0.999, eps=1e-7, grad_scale=1.0):
         self.step_count += 1
-        check(_lib.load().cp_adam_step_f32(self.theta.data_ptr(), self.grad.data_ptr(), self.m.data_ptr(), self.v.data_ptr(), self.size,
-                                           lr, beta1, beta2, eps, self.step_count, grad_scale, stream), "cp_adam_step_f32")
+        if self.skip is None:
+            check(_lib.load().cp_adam_step_f32(self.theta.data_ptr(), self.grad.data_ptr(), self.m.data_ptr(), self.v.data_ptr(), self.size,
+                                               lr, beta1, beta2, eps, self.step_count, grad_scale, stream), "cp_adam_step_f32")
+            return
+        # a step whose fp16-pair backward clamped an operand (TrainPlan.backward sets bit 31 of skip[0]) leaves theta, m and v as they are and
+        # does not count: the kernel's bias correction uses step_count - skip[1], and skip[1] counts the skipped step behind it
+        check(_lib.load().cp_adam_step_masked_f32(self.theta.data_ptr(), self.grad.data_ptr(), self.m.data_ptr(), self.v.data_ptr(), self.size,
+                                                  lr, beta1, beta2, eps, self.step_count, grad_scale, self.skip.data_ptr(), stream),
+              "cp_adam_step_masked_f32")
+        self.skip[1:].sub_(self.skip[:1] >> 31)   # (bit 31 set: the int32 is negative, >> 31 gives -1)
 
 
 class TT:
@@ -976,7 +989,8 @@ class ConvOp:
             if planes == 3 and self.wgrad_f16x2():
                 planes = _lib.PLANES_F16X2   # both operands inside fp16's band: X watched by the forward's monitor, dY carrying the loss factor
             if planes:   # bf16 matrix pipe (csrc/conv_wgrad_split.hip): same packed result
-                check(lib.cp_conv2d_wgrad_split(C.byref(d), dy, dy_ld, L.dwp.data_ptr(), 0, planes, stream), "cp_conv2d_wgrad_split(%s)" % L.name)
+                with _armed(self.bw16["mon"] if planes == _lib.PLANES_F16X2 else None):   # (the fp16 pair: dY's overflow guard, every step)
+                    check(lib.cp_conv2d_wgrad_split(C.byref(d), dy, dy_ld, L.dwp.data_ptr(), 0, planes, stream), "cp_conv2d_wgrad_split(%s)" % L.name)
             else:
                 check(lib.cp_conv2d_wgrad_f32(C.byref(d), dy, dy_ld, L.dwp.data_ptr(), 0, stream), "cp_conv2d_wgrad_f32(%s)" % L.name)
             check(lib.cp_scatter_f32(L.dwp.data_ptr(), L.idx_fwd.data_ptr(), L.idx_fwd.numel(), L.master_grad.data_ptr(), 1 if self.accumulate_master else 0,
@@ -1030,12 +1044,30 @@ class ConvOp:
             g.residual = t.grad.data_ptr() if t.has_grad else None
             sp = ent["split"]
             if sp is not None and lib.cp_conv_split_applicable(C.byref(g)):
-                check(lib.cp_conv2d_fwd_split_scaled(C.byref(g), sp["planes"].data_ptr(), None, sp["np"], sp["descale"], 1.0, stream), "dgrad split(%s)" % L.name)
+                # the fp16 pair runs armed on every step: max |dY| into the op's backward slot, and its overflow guard
+                b16 = getattr(self, "bw16", None)
+                with _armed(b16["mon"] if sp["np"] == _lib.PLANES_F16X2 and b16 is not None else None):
+                    check(lib.cp_conv2d_fwd_split_scaled(C.byref(g), sp["planes"].data_ptr(), None, sp["np"], sp["descale"], 1.0, stream), "dgrad split(%s)" % L.name)
             else:
                 check(lib.cp_conv2d_fwd_f32(C.byref(g), stream), "dgrad(%s)" % L.name)
             t.has_grad = True
         if self.residual is not None:
             add_grad(self.residual, dy, self.out.pixels * self.out.c, stream)
+
+
+class _armed:
+    """arm an f16x2 monitor slot for the calling thread's launches inside the block (None: nothing)"""
+
+    def __init__(self, slot):
+        self.slot = slot
+
+    def __enter__(self):
+        if self.slot:
+            _lib.load().cp_f16x2_monitor_set(self.slot)
+
+    def __exit__(self, *exc):
+        if self.slot:
+            _lib.load().cp_f16x2_monitor_set(None)
 
 
 def add_grad(t: TT, src_ptr: int, n: int, stream: int):
@@ -1188,6 +1220,7 @@ class TrainPlan:
         self._f16x2_steps, self.f16x2_checks, self.f16x2_demoted = 0, 0, []
         self._bwd_f16, self._bwd_calibrated, self.f16x2_bwd_moves = None, False, []   # backward GEMMs in f16x2 (train_bwd_f16x2)
         self.loss_exp, self._dout_scale = 0, 1.0                                       # power of two on the loss (direct data gradients in f16x2)
+        self.f16x2_skipped_steps = 0   # optimizer steps skipped because the fp16-pair backward clamped an operand (as of the last reading)
         self.comm_timing = None   # start_comm_timing()
         self.comm_log = None      # start_comm_log()
         self._buckets = None
@@ -1692,11 +1725,12 @@ class TrainPlan:
 
     def _judge_direct(self, vals, stream: int):
         """vals: {slot index j: max |dY| as measured, i.e. including the loss factor in force}.  Moves the loss exponent when the largest of them
-        has left [2^7, 2^13), then switches every direct data gradient on (inside [1, 2^13]) or off (outside [0.25, 2^14])."""
+        has left [2^7, 2^13), then switches every direct data gradient on (inside [1, 2^13]) or off (outside [0.25, 65504 / 4], the band's HI of
+        DESIGN.md 4.1f).  Returns True when the loss exponent moved."""
         bwd = self._bwd_slots()
         live = {j: v for j, v in vals.items() if np.isfinite(v) and v > 0.0}
         if not live:
-            return
+            return False
         top = max(live.values())
         shift = 0
         if not (2.0 ** 7 <= top < 2.0 ** 13):
@@ -1710,11 +1744,17 @@ class TrainPlan:
                 f["dead"] = True
                 op.set_direct_dgrad_f16x2(False, stream)
                 continue
-            v2 = v * 2.0 ** shift
-            if not f["on"] and 1.0 <= v2 <= 2.0 ** 13:
-                op.set_direct_dgrad_f16x2(True, stream)
-            elif f["on"] and not (0.25 <= v2 <= 2.0 ** 14):
-                op.set_direct_dgrad_f16x2(False, stream)
+            on = TrainPlan._direct_band(f["on"], v * 2.0 ** shift)
+            if on != f["on"]:
+                op.set_direct_dgrad_f16x2(on, stream)
+        return shift != 0
+
+    @staticmethod
+    def _direct_band(on: bool, v: float) -> bool:
+        """a direct data gradient with max |dY| = v (loss factor included): joins the fp16 pair inside [1, 2^13], stays inside [0.25, HI]"""
+        from .engine import F16X2_AMAX_HI
+
+        return (0.25 <= v <= F16X2_AMAX_HI) if on else (1.0 <= v <= 2.0 ** 13)
 
     def _arm_f16x2(self):
         """one monitor slot per convolution op whose forward runs in the fp16 two-way split (slot i <-> self.ops[i]), then one per Winograd data
@@ -1724,6 +1764,14 @@ class TrainPlan:
             dev = self.out.device
             self._f16x2_mon = torch.zeros(4 * (len(self.ops) + len(bwd)), dtype=torch.int32, device=dev)
             self._f16x2_host = torch.zeros(4 * (len(self.ops) + len(bwd)), dtype=torch.int32).pin_memory()
+        # the store outlives its plans (model.training_plan builds one per batch / size / group): every plan has its own host copy, and a flag
+        # the previous plan's last step left in skip[0] must not skip this plan's first step (backward() clears or rewrites it every step)
+        if self.store.skip is None:
+            self.store.skip = torch.zeros(2, dtype=torch.int32, device=self._f16x2_mon.device)
+        else:
+            self.store.skip[:1].zero_()
+        self._skip_host = torch.zeros(2, dtype=torch.int32).pin_memory()
+        self._skip_base = None   # skip[1] when this plan calibrated (read in _calibrate_bwd, which synchronises anyway)
         base = self._f16x2_mon.data_ptr()
         for i, op in enumerate(self.ops):
             if isinstance(op, ConvOp):
@@ -1734,6 +1782,8 @@ class TrainPlan:
     def _calibrate_bwd(self, stream: int):
         """after the plan's FIRST backward (exact split, slots armed): one synchronous reading gives every Winograd data gradient its exponent"""
         self._bwd_calibrated = True
+        if self.store.skip is not None and getattr(self, "_skip_base", 1) is None:
+            self._skip_base = int(self.store.skip[1])
         bwd = self._bwd_slots()
         if not bwd or self._f16x2_mon is None:
             return
@@ -1750,6 +1800,42 @@ class TrainPlan:
             elif np.isfinite(amax) and amax > 0.0:
                 self._set_bwd_exponent(op, f, entry, int(np.clip(10 - int(np.floor(np.log2(amax))), -100, 100)), stream)
         self._judge_direct(direct, stream)   # (moves the Winograd exponents just set by the loss exponent it chooses)
+        self._sync_guards()
+
+    def _guard_thresholds(self) -> np.ndarray:
+        """the overflow guard of every backward slot (word [3], include/casapose_hip.h): the largest value its reports may reach before a conversion
+        of the fp16-pair backward clamps -- 65504 on what a slot measures as converted (direct dY with the loss factor, Winograd V x 2^e), 65504 2^-e
+        on a weight gradient's dM (its GEMM applies 2^e); 0 (no guard) for a GEMM on the exact split"""
+        out = np.zeros(len(self._bwd_slots()), np.float32)
+        for j, (op, f, entry) in enumerate(self._bwd_slots()):
+            if f["dead"]:
+                continue
+            if entry == "direct":
+                out[j] = 65504.0 if f["on"] else 0.0
+            elif f["e"] is not None and (entry is not None or op.layer.fwd_f16x2):
+                out[j] = 65504.0 * 2.0 ** (-f["e"] if entry is None else 0)
+        return out
+
+    def _sync_guards(self):
+        """write the guards into the backward slots (word [3]; clears their overflow bits)"""
+        if self._f16x2_mon is None or not self._bwd_slots():
+            return
+        n0, nb = len(self.ops), len(self._bwd_slots())
+        self._guards = torch.from_numpy(self._guard_thresholds().view(np.int32).copy()).to(self._f16x2_mon.device)
+        self._f16x2_mon.view(-1, 4)[n0:n0 + nb, 3].copy_(self._guards)
+
+    def _collect_skip(self, multi: bool):
+        """after a backward in the fp16 pair: bit 31 of store.skip[0] when any backward slot's guard fired in it (an operand was clamped), then the
+        slots' overflow bits are cleared for the next step.  With replicas every rank takes the same decision (MIN over ranks: a set bit 31 is
+        negative).  No host synchronisation."""
+        n0, nb = len(self.ops), len(self._bwd_slots())
+        col = self._f16x2_mon.view(-1, 4)[n0:n0 + nb, 3]
+        torch.amin(col, dim=0, keepdim=True, out=self.store.skip[:1])
+        col.bitwise_and_(0x7FFFFFFF)
+        if multi:
+            import torch.distributed as dist
+
+            dist.all_reduce(self.store.skip[:1], op=dist.ReduceOp.MIN, group=self.group)
 
     def _read_f16x2(self, dev):
         """every F16X2_TRAIN_CHECK_EVERY-th step: the slots (sticky maxima over the steps since the last reading) travel to pinned host memory, are
@@ -1759,7 +1845,12 @@ class TrainPlan:
         self._f16x2_steps += 1
         if self._f16x2_steps >= F16X2_TRAIN_CHECK_EVERY and self._f16x2_event is None:
             self._f16x2_host.copy_(self._f16x2_mon, non_blocking=True)
+            if self.store.skip is not None:
+                self._skip_host.copy_(self.store.skip, non_blocking=True)
             self._f16x2_mon.zero_()
+            if getattr(self, "_guards", None) is not None:
+                n0 = len(self.ops)
+                self._f16x2_mon.view(-1, 4)[n0:n0 + len(self._guards), 3].copy_(self._guards)
             self._f16x2_event = torch.cuda.Event()
             self._f16x2_event.record(torch.cuda.current_stream(dev))
             self._f16x2_steps = 0
@@ -1787,7 +1878,29 @@ class TrainPlan:
                 op.demote_forward_to_exact_split(stream)
                 op.mon_ptr = None
                 out.append("%s (max %.3g)" % (op.layer.name, amax))
-        n0 = len(self.ops)
+        out += self._judge_bwd(w[len(self.ops):], stream)
+        self._sync_guards()   # (a forward demoted above takes its Winograd weight gradient to the exact split: no guard)
+        self.f16x2_checks += 1
+        skipped = int(self._skip_host[1]) - (getattr(self, "_skip_base", None) or 0) if self.store.skip is not None else 0
+        if skipped > self.f16x2_skipped_steps:
+            if self.f16x2_skipped_steps == 0:
+                import warnings
+                warnings.warn("training backward (fp16 two-way split): an operand left fp16's range and the optimizer step was skipped (%d step(s) "
+                              "so far); the exponents are lowered from this reading on (TrainPlan.f16x2_skipped_steps)" % skipped)
+            self.f16x2_skipped_steps = skipped
+        if out:
+            self.f16x2_demoted += out
+            import warnings
+            warnings.warn("training forward (fp16 two-way split): %d layer(s) converted operands outside [%g, %g] and run their forward on the exact bf16 split "
+                          "from now on: %s" % (len(out), lo, hi, "; ".join(out)))
+
+    def _judge_bwd(self, w: np.ndarray, stream: int) -> list:
+        """the backward slots of one reading (w: uint32 [slots][4]): moves the Winograd exponents and the loss exponent.  When anything moved, the
+        slots are reset (_reset_bwd_slots): what the steps between the copy and this judgement reported was measured with the old factors and
+        would move them a second time at the next reading.  Returns the GEMMs that left the fp16 pair for good."""
+        out = []
+        before = (self.loss_exp, [f["e"] for _, f, _ in self._bwd_slots()], [f.get("on") for _, f, _ in self._bwd_slots()])
+        n0 = 0
         direct = {}
         for j, (op, f, entry) in enumerate(self._bwd_slots()):
             # backward GEMMs: a data gradient's slot holds max |V 2^e| (the transform applies the factor), a weight gradient's max |dM| (the GEMM
@@ -1811,12 +1924,16 @@ class TrainPlan:
                 self.f16x2_bwd_moves.append((op.layer.name, f["e"], e))
                 self._set_bwd_exponent(op, f, entry, e, stream)
         self._judge_direct(direct, stream)
-        self.f16x2_checks += 1
-        if out:
-            self.f16x2_demoted += out
-            import warnings
-            warnings.warn("training forward (fp16 two-way split): %d layer(s) converted operands outside [%g, %g] and run their forward on the exact bf16 split "
-                          "from now on: %s" % (len(out), lo, hi, "; ".join(out)))
+        after = (self.loss_exp, [f["e"] for _, f, _ in self._bwd_slots()], [f.get("on") for _, f, _ in self._bwd_slots()])
+        if after != before:
+            self._reset_bwd_slots()
+        return out
+
+    def _reset_bwd_slots(self):
+        """zero the backward slots' maxima (stream-ordered after the backward that just reported with the old factors) and write their guards"""
+        n0, nb = len(self.ops), len(self._bwd_slots())
+        self._f16x2_mon.view(-1, 4)[n0:n0 + nb].zero_()
+        self._sync_guards()
 
     def loss_and_grad(self, labels_ce: torch.Tensor, labels_fg: torch.Tensor, keypoints_yx: torch.Tensor, mask_w=1.0, vertex_w=1.0, proxy_w=1.0,
                       filter_with_segmentation=True, kp: int = 9, filter_high_proxy_errors: bool = False) -> torch.Tensor:
@@ -1962,7 +2079,13 @@ class TrainPlan:
                         self._unscale_grads(stream, a, e)   # (the loss factor is this replica's own: out before the sum over replicas)
                         self._pending.append(parallel.all_reduce_sum_async(self.store.grad[a:e], self.group))
         if not self._bwd_calibrated:
-            self._calibrate_bwd(stream)
+            self._calibrate_bwd(stream)   # (this backward ran on the exact split)
+            if self.store.skip is not None:
+                self.store.skip[:1].zero_()
+        elif self._f16x2_mon is not None and self._bwd_slots() and getattr(self, "_skip_base", None) is not None:
+            self._collect_skip(multi)
+        elif self.store.skip is not None:
+            self.store.skip[:1].zero_()   # no fp16-pair backward in this step (calibrating, or a plan without one): nothing to skip
         # d beta of bn_data from the padding-channel entries of conv0's weight gradient (see __init__)
         G = self.conv0.dwp[self.g_idx.reshape(-1)].view(49, 64)            # [tap][cout]
         W0 = self.store.view("conv0.kernel").reshape(49, 3, 64)               # [tap][c][cout]

@@ -202,7 +202,13 @@ float cp_f16x2_weight_scale(float max_abs);   /* the power of two that brings ma
  * ([0.5, 65504 / 4]).  WEIGHTS are brought there by cp_f16x2_weight_scale; ACTIVATIONS are measured on the device:
  *   - a MONITOR SLOT is four 32-bit words of device memory, 16-byte aligned, zeroed by the caller:
  *       [0] bits of max |x| over every fp32 value the armed launches converted to an fp16 pair (atomic max of the bit pattern), [1] number of
- *       launches that reported, [2] the same maximum for the operand of a fused 1x1 head (exists in registers only), [3] reserved;
+ *       launches that reported, [2] the same maximum for the operand of a fused 1x1 head (exists in registers only), [3] the OVERFLOW GUARD:
+ *       bits 0-30 a threshold the caller writes (the bit pattern of a positive float, 0 = none), bit 31 set by the device when a report of
+ *       word [0] -- by a reporting launch below or cp_amax_f32 -- exceeds it, or when cp_conv2d_wgrad_split with CP_PLANES_F16X2 converts a
+ *       dY value above it (that launch reports into word [3] only).  A threshold of 65504 on the operand as converted catches every conversion
+ *       that MODE.FP16_OVFL clamps in the reporting launches (inf included; NaN passes a conversion as NaN and is not flagged) -- with one
+ *       exception: the OTHER operands of cp_conv2d_wgrad_split (the layer input X and the 4-channel image) are not guarded there; they are the
+ *       forward's converted operands, watched by the forward's own slot.  Bit 31 stays set until the caller clears it;
  *   - cp_f16x2_monitor_set(slot) arms `slot` for the CALLING THREAD's following launches (NULL disarms).  Reporting launches:
  *       cp_conv2d_fwd_split_scaled / cp_conv2d_fwd_stem_split_scaled with CP_PLANES_F16X2 (what their loaders convert: the sources through the
  *       stem's input affine; the low-resolution source of a bilinear x2 input, which bounds its interpolation; word [2]: the fused head's operand),
@@ -600,6 +606,11 @@ int cp_axpby_f32(const float* a, float alpha, const float* b, float beta, long l
  *   params -= lr*sqrt(1-b2^step)/(1-b1^step) * m/(sqrt(v)+eps)          (step counts from 1) */
 int cp_adam_step_f32(float* params, const float* grads, float* m, float* v, long long n, float lr, float beta1, float beta2,
                      float eps, int step, float grad_scale, void* stream);
+/* the same step under a device-side skip (dynamic loss scaling's skip, without a host synchronisation): skip[0] with bit 31 set -- an f16x2
+ * monitor slot's overflow bit (cp_f16x2_monitor_set, word [3]) or several combined -- leaves params, m and v unchanged; otherwise the step
+ * runs with the bias correction of step - skip[1] (skip[1] = steps skipped before this one, kept by the caller on the device). */
+int cp_adam_step_masked_f32(float* params, const float* grads, float* m, float* v, long long n, float lr, float beta1, float beta2,
+                            float eps, int step, float grad_scale, const uint32_t* skip, void* stream);
 
 /* compute_loss for the merged-output models (train_casapose.py:40-145), value AND gradient:
  *   loss_sums[0] mask   = mean softmax cross-entropy(labels_ce)                         (:59-60)

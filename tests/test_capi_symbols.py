@@ -186,6 +186,9 @@ def test_argument_validation_reports_errors_without_a_gpu(lib):
     assert b"inconsistent" in lib.cp_last_error()
     assert lib.cp_ls_vote_f32(None, 36, 0, 9, 27, None, 1, 8, 8, 8, 9, None, None, None) == -1
     assert lib.cp_argmax_labels(16, 4, 9, 10, 16, None) == -1  # ld < classes
+    # the masked Adam step needs its skip words (no silent fall-back to an unmasked step)
+    assert lib.cp_adam_step_masked_f32(16, 16, 16, 16, 4, 1e-3, 0.9, 0.999, 1e-7, 1, 1.0, None, None) == -1
+    assert b"cp_adam_step_masked_f32" in lib.cp_last_error()
     assert lib.cp_ls_vote_workspace_bytes(2, 8, 9) == 2 * 8 * 9 * 5 * 8
 
 

@@ -65,8 +65,23 @@ def _worker(rank, world, port, outdir):
     plan = TrainPlan(ParamStore(params, dev), K, 27, e - b, H, W, group=torch.distributed.group.WORLD, world_size=world)
     plan.refresh_weights(torch.cuda.current_stream(dev).cuda_stream)
     out, sums, grad = _run(plan, dev, img[b:e], lab[b:e], kpts[b:e])
-    np.savez(os.path.join(outdir, "rank%d.npz" % rank), out=out, sums=sums, grad=grad,
-             mm=plan.store.state["bn0.moving_mean"].cpu().numpy())
+    mm = plan.store.state["bn0.moving_mean"].cpu().numpy()
+    # a gradient spike on ONE rank (loss weights x 2^12: far beyond fp16's range in that rank's fp16-pair backward): its overflow guards fire,
+    # the flag is combined over the ranks before Adam, and BOTH replicas skip the step -- they must not diverge
+    labd, imgd, kd = (torch.from_numpy(a[b:e]).to(dev) for a in (lab, img, kpts))
+    wts = (1.0, 0.5, 0.015)
+
+    def step(w):
+        plan.train_step(imgd, labd, labd, kd, 1e-4, cond_labels=labd, weights=w)
+        torch.cuda.synchronize()
+
+    step(wts)
+    theta0 = plan.store.theta.clone()
+    step(tuple(x * 2.0 ** 12 for x in wts) if rank == 1 else wts)
+    skip_flag, spike_moved = int(plan.store.skip[0]), not torch.equal(theta0, plan.store.theta)
+    step(wts)
+    np.savez(os.path.join(outdir, "rank%d.npz" % rank), out=out, sums=sums, grad=grad, mm=mm, skip_flag=skip_flag, spike_moved=spike_moved,
+             theta=plan.store.theta.cpu().numpy(), skipped=int(plan.store.skip[1]))
     torch.distributed.destroy_process_group()
 
 
@@ -97,6 +112,11 @@ def test_two_rank_dp_equals_whole_batch(device, tmp_path):
     err = np.linalg.norm(g_dp - g_ref) / np.linalg.norm(g_ref)
     assert err < 2e-3, "summed replica gradients / world_size differ from the whole-batch gradient: %g" % err
     assert np.allclose(r0["mm"], plan.store.state["bn0.moving_mean"].cpu().numpy(), atol=1e-6)   # global statistics feed the moving averages
+    # the spike on rank 1 only: both ranks skipped that step, then stepped together again
+    assert int(r0["skip_flag"]) < 0 and int(r1["skip_flag"]) < 0, (int(r0["skip_flag"]), int(r1["skip_flag"]))
+    assert not bool(r0["spike_moved"]) and not bool(r1["spike_moved"])
+    assert int(r0["skipped"]) == int(r1["skipped"]) == 1
+    assert np.array_equal(r0["theta"], r1["theta"]), "the replicas' parameters diverged"
 
 
 @pytest.mark.parametrize("mode", ["infer", "train"])

@@ -541,6 +541,30 @@ def test_adam_matches_keras_formula(device, hip_lib):
     assert rel(pd.cpu().numpy(), pr) < 1e-6
 
 
+def test_masked_adam_skips_on_the_flag_and_corrects_by_the_steps_that_ran(device, hip_lib):
+    """cp_adam_step_masked_f32: bit 31 of skip[0] leaves params, m and v untouched; otherwise the step equals cp_adam_step_f32's at step - skip[1]"""
+    lib = hip_lib
+    from casapose_amd._lib import check
+
+    rng = np.random.default_rng(7)
+    n = 10007
+    st = torch.cuda.current_stream(device).cuda_stream
+    lr, b1, b2, eps = 1e-3, 0.9, 0.999, 1e-7
+    p0, m0, v0 = (torch.from_numpy(rng.standard_normal(n).astype(np.float32)).to(device) for _ in range(3))
+    v0 = v0.abs()
+    g = torch.from_numpy(rng.standard_normal(n).astype(np.float32)).to(device)
+    skip = torch.tensor([-2 ** 31, 0], dtype=torch.int32, device=device)
+    p, m, v = p0.clone(), m0.clone(), v0.clone()
+    check(lib.cp_adam_step_masked_f32(p.data_ptr(), g.data_ptr(), m.data_ptr(), v.data_ptr(), n, lr, b1, b2, eps, 5, 1.0, skip.data_ptr(), st))
+    assert torch.equal(p, p0) and torch.equal(m, m0) and torch.equal(v, v0)
+    skip[0], skip[1] = 0x7FFFFFFF, 2   # (bits 0-30 are a guard threshold, not a flag)
+    check(lib.cp_adam_step_masked_f32(p.data_ptr(), g.data_ptr(), m.data_ptr(), v.data_ptr(), n, lr, b1, b2, eps, 5, 1.0, skip.data_ptr(), st))
+    pr, mr, vr = p0.clone(), m0.clone(), v0.clone()
+    check(lib.cp_adam_step_f32(pr.data_ptr(), g.data_ptr(), mr.data_ptr(), vr.data_ptr(), n, lr, b1, b2, eps, 3, 1.0, st))
+    assert torch.equal(m, mr) and torch.equal(v, vr)
+    assert rel(p.cpu().numpy(), pr.cpu().numpy()) < 1e-7
+
+
 # --------------------------------------------------------------------------------------------------
 # whole network
 # --------------------------------------------------------------------------------------------------
@@ -1155,3 +1179,311 @@ def test_backward_in_the_fp16_two_way_split_matches_the_exact_split(device, monk
     assert plan.loss_exp >= e_before + 8, (e_before, plan.loss_exp)
     refs = grad_of(exact, small)
     assert rel(gs, refs) < 2e-5, rel(gs, refs)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("variant", ["casapose_c_gcu5", "casapose_c_gcu5_sw1", "casapose_c_gcu4_bilat"])
+def test_fp16_pair_second_backward_matches_fp64_autograd(device, monkeypatch, variant):
+    """The default training arithmetic from a plan's SECOND backward on (the fp16 two-way split: Winograd data / weight gradients with their own
+    powers of two, direct 3x3 data / weight gradients under the loss factor) against the fp64 oracle, every variable at 1e-3 relative L2 -- the gate
+    of the first backward (test_train_forward_backward_matches_autograd), at a size where every kind of slot exists."""
+    from casapose_amd import engine as E
+    from casapose_amd import train_engine as TE
+
+    if not E.TRAIN_WINO_GEMM_SPLIT:
+        pytest.skip("CASAPOSE_WINO_GEMM=f32: the Winograd GEMMs of this process run on the fp32 MFMA (read at import), there is no fp16-pair backward to test")
+    monkeypatch.setattr(TE, "F16X2_TRAIN_CHECK_EVERY", 1)
+    for v_ in ("CASAPOSE_TRAIN_FWD", "CASAPOSE_CONV_MODE", "CASAPOSE_TRAIN_BWD"):
+        monkeypatch.delenv(v_, raising=False)
+    b, h, w, k = 2, 96, 128, 4
+    part, guid = O.VARIANTS[variant]
+    bil = O.BILINEAR_GUIDED.get(variant, (False,) * 5)
+    sharing = O.SHARED.get(variant, {})
+    params, store, plan, img, lab, kpts = _setup(device, b, h, w, k, partial=part, guided=guid, bilinear=bil, sharing=sharing)
+    stream = torch.cuda.current_stream(device).cuda_stream
+    plan.refresh_weights(stream)
+    labd, imgd, kd = torch.from_numpy(lab).to(device), torch.from_numpy(img).to(device), torch.from_numpy(kpts).to(device)
+    wts = (1.0, 0.5, 0.015)
+    p64 = R.to_torch(params)
+
+    def reference(pattern):
+        ref = R.forward_train(p64, torch.from_numpy(img.astype(np.float64)), torch.from_numpy(lab.astype(np.int64)), None, partial=part, guided=guid,
+                              bilinear=bil, act_pattern=pattern, **sharing)
+        ml, vl, pl = R.losses(ref, torch.from_numpy(lab.astype(np.int64)), torch.from_numpy(kpts.astype(np.float64)), k, 9, False)
+        for t in p64.values():
+            t.grad = None
+        (wts[0] * ml + wts[1] * vl + wts[2] * pl).backward()
+        return {name: p64[name].grad.numpy().copy() for name in store.offsets}
+
+    errs = []
+    for phase in ("first (exact split, calibrating)", "second (fp16 pair)"):
+        plan.forward(imgd, cond_labels=labd)
+        plan.loss_and_grad(labd, labd, kd, *wts, filter_with_segmentation=False)
+        plan.backward()
+        torch.cuda.synchronize()
+        if phase.startswith("second"):
+            slots = plan._bwd_slots()
+            direct = [f for _, f, e in slots if e == "direct"]
+            wino = [(f, e) for _, f, e in slots if e != "direct"]
+            assert plan.loss_exp > 0
+            assert direct and sum(1 for f in direct if f["on"]) >= len(direct) // 2, [f["on"] for f in direct]
+            assert wino and all(f["e"] is not None for f, _ in wino)
+            assert any(e is None for _, e in wino), "no Winograd weight gradient (wg16) in the fp16 pair"
+            assert int(store.skip[0]) >= 0, "the fp16-pair backward of an unchanged step reported a clamped operand"
+        g = reference(plan.activation_pattern())   # (the device's own ReLU branches: see test_train_forward_backward_matches_autograd)
+        worst = {name: rel_l2(store.grad_view(name).cpu().numpy(), g[name]) for name in store.offsets}
+        top = sorted(worst.items(), key=lambda t: -t[1])
+        print("%s %s backward: worst gradient %s %.2e, median %.2e" % (variant, phase, top[0][0], top[0][1], np.median(list(worst.values()))))
+        errs.append({n: e for n, e in worst.items() if e > 1e-3})
+    assert not errs[0] and not errs[1], "gradient mismatch (relative L2): first %s, second %s" % (
+        sorted(errs[0].items(), key=lambda t: -t[1])[:10], sorted(errs[1].items(), key=lambda t: -t[1])[:10])
+
+
+@pytest.mark.gpu
+def test_a_clamped_fp16_pair_step_is_skipped_and_the_exponents_follow(device, monkeypatch):
+    """A gradient spike between two readings of the slots: the loss weights times 2^8 on a step that is not a check step.  The fp16-pair backward
+    converts operands far beyond 65504 (MODE.FP16_OVFL clamps them); the overflow guards see it on the device, the optimizer step leaves the
+    parameters, m and v as they were, the following steps train normally, and the next reading counts the skip, warns and lowers the exponents."""
+    import warnings
+
+    from casapose_amd import engine as E
+    from casapose_amd import train_engine as TE
+
+    if not E.TRAIN_WINO_GEMM_SPLIT:
+        pytest.skip("CASAPOSE_WINO_GEMM=f32: the Winograd GEMMs of this process run on the fp32 MFMA (read at import), there is no fp16-pair backward to test")
+    monkeypatch.setattr(TE, "F16X2_TRAIN_CHECK_EVERY", 16)
+    for v_ in ("CASAPOSE_TRAIN_FWD", "CASAPOSE_CONV_MODE", "CASAPOSE_TRAIN_BWD"):
+        monkeypatch.delenv(v_, raising=False)
+    k, v, b, h, w = 4, 27, 2, 96, 128
+    params = O.init_params(k, v, seed=5, dtype=np.float32)
+    rng = np.random.default_rng(3)
+    img = torch.from_numpy(rng.uniform(-1, 1, (b, h, w, 3)).astype(np.float32)).to(device)
+    lab = np.zeros((b, h, w), np.uint8)
+    lab[:, 10:60, 12:70] = 1
+    lab[:, 40:90, 60:120] = 2
+    lab[:, 5:30, 90:125] = 3
+    labd = torch.from_numpy(lab).to(device)
+    kpts = torch.from_numpy(rng.uniform(0, min(h, w), (b, k - 1, 9, 2)).astype(np.float32)).to(device)
+    stream = torch.cuda.current_stream(device).cuda_stream
+
+    def plan_for(bwd):
+        monkeypatch.setenv("CASAPOSE_TRAIN_BWD", bwd)
+        plan = TE.TrainPlan(TE.ParamStore(params, device), k, v, b, h, w)
+        plan.refresh_weights(stream)
+        return plan
+
+    def grad_of(plan, wts):
+        plan.forward(img, cond_labels=labd)
+        plan.loss_and_grad(labd, labd, kpts, *wts)
+        plan.backward()
+        torch.cuda.synchronize()
+        return plan.store.grad.double().cpu().numpy().copy()
+
+    def exact_grad(theta, wts):
+        exact.store.theta.copy_(theta)
+        exact.refresh_weights(stream)
+        return grad_of(exact, wts)
+
+    def rel_(a, b_):
+        return float(np.abs(a - b_).max() / np.abs(b_).max())
+
+    wts = (1.0, 0.5, 0.015)
+    spike = tuple(x * 2.0 ** 8 for x in wts)
+    exact = plan_for("split")
+    plan = plan_for("f16x2")
+    st = plan.store
+
+    def step(wts_):
+        return plan.train_step(img, labd, labd, kpts, 1e-4, cond_labels=labd, weights=wts_)
+
+    for _ in range(3):   # the first backward calibrates; two more in the fp16 pair
+        step(wts)
+    torch.cuda.synchronize()
+    e_before = plan.loss_exp
+    assert e_before > 0 and plan.f16x2_checks == 0
+    before = [t.clone() for t in (st.theta, st.m, st.v)]
+    step(spike)          # step 4 of 16: no check step
+    torch.cuda.synchronize()
+    g_spike = st.grad.double().cpu().numpy().copy()
+    ref_spike = exact_grad(before[0], spike)
+    err_spike = rel_(g_spike, ref_spike)
+    # (the conversion saturates gracefully up to 131008, so the damage of one such step is small -- measured 7.6e-6 of max |g| here -- but it
+    # is not fp32 arithmetic and nothing reported it before the guards existed)
+    print("gradient of the spike step against the exact split: %.2e (loss exponent %d)" % (err_spike, e_before))
+    assert err_spike > 0.0, "the spike step's gradient equals the exact split's: nothing was clamped, the guard is not exercised"
+    for name, t0, t1 in zip(("parameters", "m", "v"), before, (st.theta, st.m, st.v)):
+        assert torch.equal(t0, t1), "the clamped step changed the %s" % name
+    assert int(st.skip[0]) < 0 and int(st.skip[1]) == 1
+    for _ in range(3):
+        step(wts)
+    torch.cuda.synchronize()
+    assert int(st.skip[1]) == 1 and not torch.equal(st.theta, before[0])
+    theta = st.theta.clone()
+    g = grad_of(plan, wts)
+    ref = exact_grad(theta, wts)
+    assert rel_(g, ref) < 2e-5, rel_(g, ref)
+    # the reading after the spike: one skip counted, one warning, the exponents lowered
+    with warnings.catch_warnings(record=True) as caught:
+        warnings.simplefilter("always")
+        for _ in range(2 * 16):
+            step(wts)
+            if plan.f16x2_checks:
+                break
+    torch.cuda.synchronize()
+    assert plan.f16x2_checks == 1 and plan.f16x2_skipped_steps == 1
+    assert sum("optimizer step was skipped" in str(c.message) for c in caught) == 1
+    # (the top sat anywhere in [2^7, 2^13) before the spike: 2^8 on it leaves [2^15, 2^21) and the exponent moves down by 5 to 10; measured 6)
+    assert plan.loss_exp <= e_before - 5, (e_before, plan.loss_exp)
+
+
+def _dy_view(op):
+    """the op's dY buffer as a [pixels, cout] view (a column slice of a wider buffer where the plan shares one)"""
+    P, cout = op.batch * op.out_h * op.out_w, op.layer.cout
+    if op.dy_ptr_ld is not None:
+        st, off, ld = op.dy_ptr_ld
+        return st.view(-1)[off:off + (P - 1) * ld + cout].as_strided((P, cout), (ld, 1))
+    op.out.has_grad = True
+    return op.out.grad.view(P, op.out.c)[:, :cout]
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("amax", [2.0 ** 13, 2.0 ** 14, 60000.0, 2.0 ** 17], ids=["2^13", "2^14", "60000", "2^17-clamps"])
+def test_direct_fp16_pair_gradients_of_every_layer_match_fp64(device, monkeypatch, amax):
+    """Layer level, with the plan's own ConvOps and launch arguments: every direct 3x3 data gradient (conv_hsplit, weights x 2^k as two fp16
+    planes: set_direct_dgrad_f16x2) and weight gradient (conv_wgrad_split, planes 0x12) of the network, with max |dY x 2^E| set to the band's
+    edges 2^13 (admitted) and 2^14 (kept on) and to 60000 (inside fp16's range): fp32-level against fp64 (conv_transpose2d / the weight gradient of
+    conv2d), and the overflow guard silent.  Layers with per-tap label masks (partial convolutions) or another weight layout are held to the exact
+    bf16 split of the same op instead.  Beyond 65504 (2^17) the conversion clamps and the guard of the op's slot must have fired."""
+    from casapose_amd import train_engine as TE
+
+    for v_ in ("CASAPOSE_TRAIN_FWD", "CASAPOSE_CONV_MODE", "CASAPOSE_TRAIN_BWD"):
+        monkeypatch.delenv(v_, raising=False)
+    b, h, w, k = 1, 96, 128, 4
+    params, store, plan, img, lab, kpts = _setup(device, b, h, w, k)
+    stream = torch.cuda.current_stream(device).cuda_stream
+    plan.refresh_weights(stream)
+    labd = torch.from_numpy(lab).to(device)
+    plan.forward(torch.from_numpy(img).to(device), cond_labels=labd)
+    plan.loss_and_grad(labd, labd, torch.from_numpy(kpts).to(device), 1.0, 0.5, 0.015)
+    plan.backward()   # calibrates: the slots are armed
+    torch.cuda.synchronize()
+    ops = [op for op in plan.ops if isinstance(op, TE.ConvOp) and getattr(op, "bw16", None) is not None and op.direct_dgrad_split()]
+    assert len(ops) >= 5 and {32, 64, 128} <= {op.layer.cout for op in ops}, [(op.layer.name, op.layer.cout) for op in ops]
+    base = plan._f16x2_mon.data_ptr()
+    mon4 = plan._f16x2_mon.view(-1, 4)
+    gen = torch.Generator(device="cpu").manual_seed(11)
+    checked = {"fp64": 0, "exact": 0, "wgrad": 0}
+    worst = 0.0
+
+    def run_dgrad(op, on):
+        op.set_direct_dgrad_f16x2(on, stream)
+        plan._sync_guards()
+        for t, _ in op.srcs:
+            t.has_grad = False
+        op.backward_dgrad(stream)
+        torch.cuda.synchronize()
+
+    def run_wgrad(op, on):
+        op.set_direct_dgrad_f16x2(on, stream)
+        plan._sync_guards()
+        acc, op.accumulate_master = op.accumulate_master, False
+        op.backward_wgrad(stream)
+        op.accumulate_master = acc
+        torch.cuda.synchronize()
+        return op.layer.master_grad.double().cpu().clone()
+
+    for op in ops:
+        L = op.layer
+        assert op.stride == 1 and op.dil == 1 and op.pad == 1
+        cout = L.cout
+        cin = L.master.numel() // (9 * cout)
+        dy = torch.randn(op.batch * op.out_h * op.out_w, cout, generator=gen, dtype=torch.float64)
+        dy *= amax / dy.abs().max()
+        _dy_view(op).copy_(dy.float().to(device))
+        dy = _dy_view(op).double().cpu().reshape(op.batch, op.out_h, op.out_w, cout)
+        slot = (op.bw16["mon"] - base) // 16
+        run_dgrad(op, True)
+        flag = int(mon4[slot, 3]) < 0
+        if amax > 65504.0:
+            assert flag, "%s: a clamped conversion (max |dY| %g) left the overflow guard silent" % (L.name, amax)
+            mon4[slot, 3].bitwise_and_(0x7FFFFFFF)
+            continue
+        assert not flag, "%s: the overflow guard fired at max |dY| %g" % (L.name, amax)
+        got = [None if t.grad is None else t.grad.double().cpu().clone() for t, _ in op.srcs]
+        simple = op.tap_label is None and L.layout == 0
+        if simple:
+            W = L.master.double().cpu().reshape(3, 3, cin, cout)
+        else:
+            run_dgrad(op, False)
+            exact = [None if t.grad is None else t.grad.double().cpu().clone() for t, _ in op.srcs]
+        c0 = 0
+        for s, (ent, (cp_, cr)) in enumerate(zip(L.dgrad, L.sources)):
+            direct = ent is not None and ent["split"] is not None and not ent.get("deep") and s not in getattr(op, "wino_dgrad", {})
+            if direct:
+                g = got[s].reshape(op.batch, op.in_h, op.in_w, -1)[..., :cr]
+                if simple:
+                    wt = W[:, :, c0:c0 + cr, :].permute(3, 2, 0, 1).contiguous()   # [cout][cr][ky][kx]
+                    ref = F.conv_transpose2d(dy.permute(0, 3, 1, 2), wt, padding=1).permute(0, 2, 3, 1)
+                    checked["fp64"] += 1
+                else:
+                    ref = exact[s].reshape(op.batch, op.in_h, op.in_w, -1)[..., :cr]
+                    checked["exact"] += 1
+                e = float((g - ref).abs().max() / ref.abs().max())
+                worst = max(worst, e)
+                assert e < 1e-5, "%s source %d (cout %d): fp16-pair data gradient %.2e from the %s" % (L.name, s, cout, e, "fp64" if simple else "exact split")
+            c0 += cr
+        if op.layer.fwd_f16x2 and op.wgrad_planes() == 3 and getattr(op, "wino_fwd", None) is None and getattr(op, "gemm", None) is None:
+            gw = run_wgrad(op, True)
+            assert op.wgrad_f16x2() and int(mon4[slot, 3]) >= 0, L.name
+            gx = run_wgrad(op, False)   # the exact split of the same op
+            if simple and len(op.srcs) == 1 and L.sources[0][1] == cin:
+                t, ld = op.srcs[0]
+                x = t.data.double().cpu().reshape(op.batch, op.in_h, op.in_w, -1)[..., :cin]
+                ref = torch.nn.grad.conv2d_weight(x.permute(0, 3, 1, 2), (cout, cin, 3, 3), dy.permute(0, 3, 1, 2), padding=1)
+                ref = ref.permute(2, 3, 1, 0).reshape(-1)
+                e64 = float((gw.reshape(-1)[:ref.numel()] - ref).abs().max() / ref.abs().max())
+                assert e64 < 1e-5, "%s: fp16-pair weight gradient %.2e from fp64" % (L.name, e64)
+            e = float((gw - gx).abs().max() / gx.abs().max())
+            worst = max(worst, e)
+            assert e < 1e-5, "%s: fp16-pair weight gradient %.2e from the exact split" % (L.name, e)
+            checked["wgrad"] += 1
+    print("max |dY| %g: %s layers checked, worst %.2e" % (amax, checked, worst))
+    if amax <= 65504.0:
+        assert checked["fp64"] >= 3 and checked["wgrad"] >= 1, checked
+
+
+@pytest.mark.gpu
+def test_a_second_plan_on_the_same_store_runs_past_a_reading(device, monkeypatch):
+    """The store outlives its plans (model.training_plan builds one per batch size / image size / group): a second plan on the same store reads
+    its slots without the first plan's host buffers, and a skip flag the first plan's last step left behind does not skip its first step."""
+    from casapose_amd import train_engine as TE
+
+    monkeypatch.setattr(TE, "F16X2_TRAIN_CHECK_EVERY", 4)
+    for v_ in ("CASAPOSE_TRAIN_FWD", "CASAPOSE_CONV_MODE", "CASAPOSE_TRAIN_BWD"):
+        monkeypatch.delenv(v_, raising=False)
+    k = 4
+    params, store, plan, img, lab, kpts = _setup(device, 2, 64, 96, k)
+    stream = torch.cuda.current_stream(device).cuda_stream
+    plan.refresh_weights(stream)
+
+    def steps(p, n, b, h, w, seed):
+        rng = np.random.default_rng(seed)
+        im = torch.from_numpy(rng.uniform(-1, 1, (b, h, w, 3)).astype(np.float32)).to(device)
+        lb = torch.from_numpy(blob_labels(b, h, w, k, seed)).to(device)
+        kp = torch.from_numpy(rng.uniform(0, min(h, w), (b, k - 1, 9, 2)).astype(np.float32)).to(device)
+        for _ in range(n):
+            p.train_step(im, lb, lb, kp, 1e-4, cond_labels=lb, weights=(1.0, 0.5, 0.015))
+
+    steps(plan, 3, 2, 64, 96, 1)
+    torch.cuda.synchronize()
+    assert store.skip is not None
+    store.skip[0] = -2 ** 31   # as if the first plan's last step had clamped
+    plan2 = TE.TrainPlan(store, k, 27, 1, 96, 128, partial=(True,) * 5, guided=(False, True, True, True, False), bilinear=(False,) * 5)
+    plan2.refresh_weights(stream)
+    theta = store.theta.clone()
+    steps(plan2, 1, 1, 96, 128, 2)
+    torch.cuda.synchronize()
+    assert not torch.equal(theta, store.theta), "the second plan's first step was skipped by the first plan's flag"
+    steps(plan2, 10, 1, 96, 128, 2)
+    torch.cuda.synchronize()
+    assert plan2.f16x2_checks >= 1 and plan2.f16x2_skipped_steps == 0 and int(store.skip[1]) == 0

@@ -70,3 +70,73 @@ def test_all_zero_gradients_change_nothing():
     plan, ops, _ = _plan(["a"], [3])
     plan._judge_direct({0: 0.0}, 0)
     assert plan.loss_exp == 0 and not ops[0].bw16["on"]
+
+
+def _reading(vals):
+    """uint32 [slots][4] as a reading of the backward slots: [0] float bits of max |operand|, [1] launches that reported"""
+    w = np.zeros((len(vals), 4), np.uint32)
+    w[:, 0] = np.asarray(vals, np.float32).view(np.uint32)
+    w[:, 1] = [1 if v > 0 else 0 for v in vals]
+    return w
+
+
+def _judging_plan(direct_names, wino_exps):
+    plan, ops, slots = _plan(direct_names, wino_exps)
+    plan.device = np.zeros(len(slots), np.float32)   # the device slots' maxima, as the backward kernels leave them
+    plan.resets = 0
+
+    def reset():
+        plan.device[:] = 0.0
+        plan.resets += 1
+
+    plan._reset_bwd_slots = reset
+    plan._judge_bwd = types.MethodType(TE.TrainPlan._judge_bwd, plan)
+    return plan, ops, slots
+
+
+def test_a_move_is_not_repeated_by_the_stale_window_behind_its_reading():
+    """The slots are copied at the end of a check step's forward and judged at the start of a later step; the backward in between still reports
+    with the OLD factors.  Without a reset those maxima stay in the sticky slots, the next reading judges them as if measured with the NEW factors
+    and moves a second time (loss exponent down by another 4, a Winograd exponent down again).  The plan resets the backward slots when anything
+    moved, so the next reading holds only what the new factors produced."""
+    plan, ops, slots = _judging_plan(["a", "b"], [3])
+    plan.loss_exp = 20
+    for op in ops:
+        op.bw16["on"] = True
+    # the window of reading 1: the largest direct layer drifted to 2^14 (loss exponent 20), the Winograd data gradient to 2^14 (e = 3).  Without
+    # the reset the second reading would see 2^14 again and take the loss exponent to 12 (checked below through the reset count)
+    window = [2.0 ** 14, 2.0 ** 9, 2.0 ** 14]
+    plan.device[:] = window
+    copy = _reading(plan.device)
+    plan.device[:] = 0.0                 # zeroed behind the copy
+    plan.device[:] = window              # the backward between the copy and the judgement: old factors, same maxima
+    plan._judge_bwd(copy, 0)
+    # the Winograd slot: its own drift (-4), then the loss move gives the factor back (+4)
+    assert plan.loss_exp == 16 and slots[2][1]["e"] == 3 - 4 + 4 and plan.f16x2_bwd_moves == [("wino0", 3, -1)], (plan.loss_exp, slots[2][1]["e"])
+    assert plan.resets == 1
+    # the steps after the judgement, with the new factors: everything back at 2^10 / 2^5 / 2^10
+    plan.device[:] = np.maximum(plan.device, [2.0 ** 10, 2.0 ** 5, 2.0 ** 10])
+    moves = len(plan.f16x2_bwd_moves)
+    plan._judge_bwd(_reading(plan.device), 0)
+    assert plan.loss_exp == 16 and slots[2][1]["e"] == 3 and len(plan.f16x2_bwd_moves) == moves, (plan.loss_exp, slots[2][1]["e"])
+    assert plan.resets == 1   # nothing moved: no reset
+
+
+def test_an_unchanged_reading_does_not_reset_the_slots():
+    plan, ops, slots = _judging_plan(["a"], [0])
+    plan.loss_exp = 10
+    ops[0].bw16["on"] = True
+    plan._judge_bwd(_reading([2.0 ** 10, 2.0 ** 10]), 0)
+    assert plan.resets == 0 and plan.loss_exp == 10 and slots[1][1]["e"] == 0
+
+
+
+def test_keep_on_band_ends_at_hi():
+    """the switch of a direct layer: joins inside [1, 2^13], stays inside [0.25, HI] with HI = 65504 / 4 = 16376, no longer
+    2^14 = 16384.  (Inside _judge_direct no layer reaches the upper edge after a move -- the top lands in [2^10, 2^11) -- so the rule is pinned on
+    its own.)"""
+    band = TE.TrainPlan._direct_band
+    assert band(False, 1.0) and band(False, 2.0 ** 13) and not band(False, 0.99) and not band(False, 2.0 ** 13 * 1.01)
+    assert band(True, 0.25) and band(True, 16376.0) and not band(True, 0.24)
+    for v in (16376.5, 16380.0, 16384.0):
+        assert not band(True, v), v
