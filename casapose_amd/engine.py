@@ -14,6 +14,7 @@ from __future__ import annotations
 import ctypes as C
 import math
 import os
+import warnings
 from typing import Callable, Dict, List, Optional, Sequence, Tuple
 
 import numpy as np
@@ -21,6 +22,7 @@ import torch
 
 from . import _lib
 from ._lib import ConvDesc, check
+from .f16x2_range import SlotBuffer, armed, decode
 
 BN_EPS = 2e-5  # resnet.py:44; _normalization_layers.py:108
 
@@ -311,15 +313,8 @@ class FusedConv:
 
     def run(self, stream: int):
         """One launch; while the plan runs armed (mon_ptr set) an f16x2 binding reports max |x| of what it converts into its monitor slot."""
-        if self.mon_ptr and self.f16x2_active():
-            lib = _lib.load()
-            lib.cp_f16x2_monitor_set(self.mon_ptr)
-            try:
-                self._launch(stream)
-            finally:
-                lib.cp_f16x2_monitor_set(None)
-            return
-        self._launch(stream)
+        with armed(self.mon_ptr if self.mon_ptr and self.f16x2_active() else None):
+            self._launch(stream)
 
     def _launch(self, stream: int):
         lib = _lib.load()
@@ -493,28 +488,9 @@ class WinoConv:
         self._keep = [V, M, residual, scale, shift, epi_label, out_raw, out_act] + [s["data"] for s in srcs]
         return in_h, in_w
 
-    class _Armed:
-        """context: the transform launched inside reports max |V| of what it writes into the monitor slot at `ptr` (None: nothing armed)"""
-        __slots__ = ("ptr",)
-
-        def __init__(self, ptr):
-            self.ptr = ptr
-
-        def __enter__(self):
-            if self.ptr:
-                _lib.load().cp_f16x2_monitor_set(self.ptr)
-
-        def __exit__(self, *exc):
-            if self.ptr:
-                _lib.load().cp_f16x2_monitor_set(None)
-            return False
-
-    def _armed(self, ptr: Optional[int]):
-        return WinoConv._Armed(ptr)
-
     def _input_transform(self, src_ptr: int, ld: int, cpad: int, off: int, stream: int):
         """V[.., off : off + cpad] = B^T d B of one source; with v_scale != 1 through the transform's per-channel input affine (x * 2^e + 0: exact)"""
-        with self._armed(self.mon_ptr if self.planes == _lib.PLANES_F16X2 else None):
+        with armed(self.mon_ptr if self.planes == _lib.PLANES_F16X2 else None):
             self._input_transform_launch(src_ptr, ld, cpad, off, stream)
 
     def _input_transform_launch(self, src_ptr: int, ld: int, cpad: int, off: int, stream: int):
@@ -572,7 +548,7 @@ class WinoConv:
         e, nxt = self.epi, self.fuse_next
         if nxt is not None:   # Y = A^T M A + epilogue, then straight into the next layer's V (the activated map stays on chip)
             sc_, sh_ = self._tables_for_next()
-            with self._armed(nxt.mon_ptr if nxt.planes == _lib.PLANES_F16X2 else None):   # it writes the NEXT layer's V
+            with armed(nxt.mon_ptr if nxt.planes == _lib.PLANES_F16X2 else None):   # it writes the NEXT layer's V
                 check(lib.cp_wino_output_input_transform_f32(self.M.data_ptr(), self.cout, self.batch, self.h, self.w, self.dil, _ptr(e["residual"]), self.cout,
                                                              sc_, sh_, e["act"], _ptr(e["out_raw"]), self.cout, None, self.cout,
                                                              self.V.data_ptr(), nxt.ktot, 0, stream), "cp_wino_output_input_transform_f32(%s)" % self.name)
@@ -640,7 +616,7 @@ class ForwardPlan:
         self.needs_calibration = bool(net.conv_planes == _lib.PLANES_F16X2 and net.f16x2_guard)
         self.f16x2_report: Dict[str, Tuple[float, str]] = {}
         # ... and afterwards every forward runs armed; every F16X2_MONITOR_EVERY-th the slots are read back and judged without a synchronisation (_poll_monitor)
-        self._mon = self._mon_host = self._mon_event = None
+        self.monitor: Optional[SlotBuffer] = None   # slot i <-> self.convs[i] (_run_armed)
         self._since_monitor = 0
         self.monitor_checks = self.monitor_fired = 0   # armed forwards judged so far / how many of them re-armed the calibration
         lib = _lib.load()
@@ -925,19 +901,20 @@ class ForwardPlan:
         self._wino_pending = []
 
     # ---- f16x2 range guard (the C-ABI side: cp_f16x2_monitor_set / cp_f16x2_range_check / cp_amax_f32) -----------------------------
+    _mon = property(lambda self: self.monitor and self.monitor.dev)            # the slot words (int32 [4 * convs]) on the device ...
+    _mon_host = property(lambda self: self.monitor and self.monitor.host)      # ... and as the last reading left them in pinned memory
+
     def _run_armed(self, stream: int, fresh: bool = True):
         """One forward with every f16x2 layer reporting into its monitor slot (slot i <-> self.convs[i]; include/casapose_hip.h): the converting
         kernels fold max |x| of what they convert -- a direct layer's staged sources, the stem's image through its input affine, a 1x1 GEMM's rows,
         the planes V a Winograd transform writes, the activated map a fused head converts in registers -- into the slot with one atomic per wave.
         fresh = False keeps what earlier armed forwards left in the slots (the monitor's sticky maxima)."""
-        if self._mon is None:
-            self._mon = torch.zeros(4 * len(self.convs), dtype=torch.int32, device=self.net.device)
-            self._mon_host = torch.zeros(4 * len(self.convs), dtype=torch.int32).pin_memory()
+        if self.monitor is None:
+            self.monitor = SlotBuffer(len(self.convs), self.net.device)
         elif fresh:
-            self._mon.zero_()
-        base = self._mon.data_ptr()
+            self.monitor.zero()
         for i, c in enumerate(self.convs):
-            c.mon_ptr = base + 16 * i
+            c.mon_ptr = self.monitor.ptr(i)
         try:
             for step in self.steps:
                 step(stream)
@@ -949,15 +926,14 @@ class ForwardPlan:
         """[(layer, "in" | "head", max |x| as converted, status, power of two)] for every slot that reported; status as cp_f16x2_range_check:
         0 inside [lo, hi], 1 rescale by the power of two, 2 no power of two helps (or not finite)"""
         lib = _lib.load()
-        w = np.ascontiguousarray(words).view(np.uint32).reshape(-1, 4)
+        (ins, n), (heads, _) = decode(words), decode(words, 2)
         out = []
         for i, c in enumerate(self.convs):
-            if int(w[i, 1]) == 0:
+            if n[i] == 0:
                 continue
-            for kind, bits in (("in", w[i, 0]), ("head", w[i, 2])):
-                if kind == "head" and (bits == 0 or isinstance(c, WinoConv)):
+            for kind, amax in (("in", ins[i]), ("head", heads[i])):
+                if kind == "head" and (amax == 0.0 or isinstance(c, WinoConv)):
                     continue
-                amax = float(np.array([bits], np.uint32).view(np.float32)[0])
                 r = C.c_float(1.0)
                 st = lib.cp_f16x2_range_check(amax, lo, hi, C.byref(r))
                 out.append((c, kind, amax, st, float(r.value)))
@@ -995,7 +971,7 @@ class ForwardPlan:
         settled = False
         for _ in range(8):
             self._run_armed(stream)
-            words = self._mon.cpu().numpy()   # (synchronises: calibration only)
+            words = self.monitor.read()
             acted = False
             for c, kind, amax, st, r in self._judge(words, lo, hi):
                 if isinstance(c, WinoConv):
@@ -1035,9 +1011,8 @@ class ForwardPlan:
                 settled = True
                 break
         self.needs_calibration = False
-        self._since_monitor, self._mon_event = 0, None
-        self._mon.zero_()   # the monitor's window starts behind the calibration (a sticky maximum of the calibration batch would hide a later, smaller regime)
-        import warnings
+        self._since_monitor, self.monitor.event = 0, None
+        self.monitor.zero()   # the monitor's window starts behind the calibration (a sticky maximum of the calibration batch would hide a later, smaller regime)
         if not settled:
             warnings.warn("conv_mode f16x2: the range calibration did not settle in 8 passes; the plan keeps its last fit")
         if changed and not net._f16x2_warned:
@@ -1048,18 +1023,16 @@ class ForwardPlan:
     def _poll_monitor(self):
         """judge an armed forward whose slots have arrived in pinned host memory (never waits): a layer outside [LO / SLACK, HI * SLACK] -- a batch far
         from the one the plan was calibrated on -- re-arms the calibration, with a warning"""
-        ev = self._mon_event
-        if ev is None or not ev.query():
+        words = self.monitor.poll()
+        if words is None:
             return
-        self._mon_event = None
         lo, hi = F16X2_AMAX_LO / F16X2_MONITOR_SLACK, F16X2_AMAX_HI * F16X2_MONITOR_SLACK
-        out = [(c.name + (":head" if kind == "head" else ""), amax) for c, kind, amax, st, _ in self._judge(self._mon_host.numpy().copy(), lo, hi) if st != 0]
+        out = [(c.name + (":head" if kind == "head" else ""), amax) for c, kind, amax, st, _ in self._judge(words, lo, hi) if st != 0]
         self.monitor_checks += 1
         if out:
             self.monitor_fired += 1
             self.needs_calibration = True
             self.net._f16x2_warned = False
-            import warnings
             warnings.warn("conv_mode f16x2: the range monitor found %d layer(s) converting operands outside [%g, %g] (%s): this batch is far from the one the "
                           "plan was calibrated on; calibrating again" % (len(out), lo, hi, "; ".join("%s max %.3g" % o for o in out[:6])))
 
@@ -1195,11 +1168,8 @@ class ForwardPlan:
         elif guard and F16X2_MONITOR:
             self._run_armed(stream, fresh=False)   # sticky: the slots keep the maxima of every forward since they were last read
             self._since_monitor += 1
-            if self._since_monitor >= F16X2_MONITOR_EVERY and self._mon_event is None:
-                self._mon_host.copy_(self._mon, non_blocking=True)   # judged at the start of a later forward, when the copy has landed
-                self._mon.zero_()                                    # (stream-ordered behind the copy)
-                self._mon_event = torch.cuda.Event()
-                self._mon_event.record(torch.cuda.current_stream(img.device))
+            if self._since_monitor >= F16X2_MONITOR_EVERY and self.monitor.event is None:
+                self.monitor.read_async(torch.cuda.current_stream(img.device))   # judged at the start of a later forward, when the copy has landed
                 self._since_monitor = 0
         else:
             for step in self.steps:

@@ -26,14 +26,16 @@ from __future__ import annotations
 
 import ctypes as C
 import os
+import warnings
 from typing import Callable, Dict, List, Optional, Sequence, Tuple
 
 import numpy as np
 import torch
 
-from . import _lib, parallel
+from . import _lib, engine, parallel
 from ._lib import ConvDesc, check
 from .engine import BILINEAR_DEFAULT, BN_EPS, DECODER_DIMS_DEFAULT, GUIDED_DEFAULT, PARTIAL_DEFAULT, STAGE_DILATION, STAGE_FILTERS, STAGE_STRIDE
+from .f16x2_range import BackwardRange, BwdSlot, SlotBuffer, armed, decode
 
 BN_MOMENTUM = 0.99  # resnet.py:43 (Keras default elsewhere)
 
@@ -88,18 +90,12 @@ def train_fwd_f16x2() -> bool:
 
 
 def train_bwd_f16x2() -> bool:
-    """The Winograd DATA-GRADIENT GEMMs of the training plan in the fp16 two-way split as well (round 6; CASAPOSE_TRAIN_BWD=split keeps the exact
-    three-way bf16 split).  A gradient has no natural magnitude, so the operand gets one: the input transform of dY multiplies by 2^e (its
-    per-channel affine with a constant table: exact), the GEMM's accumulator factor takes 2^-e.  e comes from the monitor slot the transform
-    reports max |V| into: the FIRST backward of a plan runs on the exact split with the slots armed and is followed by one synchronous reading
-    (like the inference plan's calibration); from then on the slots are judged with the forward's, every F16X2_TRAIN_CHECK_EVERY steps without a
-    synchronisation, and e follows when the maximum has drifted out of [2^7, 2^13] (target [2^10, 2^11): 8x headroom to the band's end, 32x to
-    fp16's clamp).  A non-finite maximum returns the op to the exact split.
-    The DIRECT 3x3 layers' data gradients (csrc/conv_hsplit.hip converts its source as it is) get their magnitude from ONE power of two on the
-    loss instead (TrainPlan.loss_exp: the loss weights are multiplied by 2^E, every gradient of the backward carries the factor, the flat
-    gradient is multiplied by 2^-E before anything reads it -- all exact): E puts the LARGEST max |dY| of those layers at [2^10, 2^11), the
-    layers whose own maximum then sits inside [1, 2^13] run on the fp16 pair (measured spread between the layers of this network: 2^9 - 2^12.5,
-    tools/debug/grad_ranges.py), the others stay on the exact split.  max |dY| comes from cp_amax_f32 passes on the check steps only."""
+    """The backward GEMMs of the training plan in the fp16 two-way split as well (round 6; CASAPOSE_TRAIN_BWD=split keeps the exact three-way bf16
+    split).  A gradient has no natural magnitude, so the operand gets one, a power of two (exact): a Winograd GEMM's own 2^e (applied by the input
+    transform of dY or the weight-gradient GEMM's loaders, taken back by the accumulators), and ONE 2^E on the loss for the DIRECT 3x3 layers
+    (conv_hsplit converts its source as it is; TrainPlan.loss_exp: the flat gradient takes 2^-E before anything reads it).  The maxima come from
+    monitor slots (max |dY| from cp_amax_f32 on the check steps): the FIRST backward of a plan runs on the exact split and ends with one synchronous
+    reading, later ones are judged with the forward's without a synchronisation.  The rules: f16x2_range.BackwardRange (tools/debug/grad_ranges.py)."""
     return os.environ.get("CASAPOSE_TRAIN_BWD", "f16x2") == "f16x2"
 
 
@@ -470,6 +466,9 @@ class ConvOp:
         self.stats_to: Optional["BnActOp"] = None
         self.pre_norm: Dict[int, "BnActOp"] = {}
         self.pre_bn: Optional["BnActOp"] = None   # fused normalisation (TrainPlan._fuse_heads): this head reads the RAW tensor and applies pre_bn's tables itself
+        self.gemm, self.wino_fwd, self.wino_dgrad = None, None, {}   # 1x1 GEMM route (setup_gemm), Winograd forward / data gradients (setup_winograd)
+        self.mon_ptr: Optional[int] = None        # the f16x2 forward's monitor slot (TrainPlan._arm_f16x2)
+        self.bw16: Optional[BwdSlot] = None   # the direct data / weight gradients' backward slot record (TrainPlan._finish_plan)
         # data-gradient descriptors
         for s, ent in enumerate(layer.dgrad):
             if ent is None:
@@ -507,7 +506,6 @@ class ConvOp:
         transposed partner (csrc/wino_wgrad_split.hip) -- instead of the fp32-MFMA implicit-GEMM kernel (84 TFLOP/s on the 256 -> 512 shortcut).
         CASAPOSE_SC_GEMM=0 keeps the fp32 kernels."""
         L = self.layer
-        self.gemm = None
         planes = self.layer.mode_planes
         if not planes or os.environ.get("CASAPOSE_SC_GEMM", "1") == "0":
             return
@@ -556,8 +554,6 @@ class ConvOp:
         from .engine import TRAIN_WINO_GEMM_SPLIT, WinoConv, wino_eligible
 
         L = self.layer
-        self.wino_fwd = None
-        self.wino_dgrad: Dict[int, dict] = {}
         nv = nm = 0
         if L.k != 3 or self.stride != 1 or self.pad != self.dil or self.tap_label is not None or L.layout != 0:
             return 0, 0
@@ -582,13 +578,13 @@ class ConvOp:
                                  dU=torch.empty(36 * L.cout * ktot, dtype=torch.float32, device=dev), wdesc=ConvDesc())
             nv, nm = max(nv, 36 * tp * ktot), max(nm, 36 * tp * L.cout)
             if L.mode_planes == 3 and TRAIN_WINO_GEMM_SPLIT and train_bwd_f16x2():   # the weight-gradient GEMM in f16x2: transformed dY x 2^e
-                self.wino_fwd["wg16"] = dict(e=None, mon=None, dead=False)
+                self.wino_fwd["wg16"] = BwdSlot("wino_wgrad", self)
         c0 = 0
         for s, (ent, (cp, cr)) in enumerate(zip(L.dgrad, L.sources)):
             if ent is not None and L.cout % 32 == 0 and wino_eligible(3, 1, self.dil, self.dil, [(L.cout, L.cout)], cr, split_gemm=split_gemm):
                 self.wino_dgrad[s] = dict(U=torch.zeros(36 * cr * L.cout, dtype=torch.float32, device=dev), ktot=L.cout, cout=cr, tp=tp, desc=ConvDesc(), c0=c0)
                 if L.mode_planes == 3 and TRAIN_WINO_GEMM_SPLIT and train_bwd_f16x2():   # (e = None while the exact split runs and the slot measures)
-                    self.wino_dgrad[s]["f16"] = dict(e=None, mon=None, dead=False)
+                    self.wino_dgrad[s]["f16"] = BwdSlot("wino_dgrad", self, entry=self.wino_dgrad[s])
                 nv, nm = max(nv, 36 * tp * L.cout), max(nm, 36 * tp * cr)
             c0 += cr
         if self.wino_fwd is not None or self.wino_dgrad:
@@ -623,12 +619,12 @@ class ConvOp:
                     w["c_scale"] = 1.0 / scale
                     check(lib.cp_wino_split_weights_scaled_f32(w["U"].data_ptr(), 36, w["cout"], w["ktot"], _lib.PLANES_F16X2, scale, w["Us"].data_ptr(), stream),
                           "cp_wino_split_weights_scaled_f32(%s)" % L.name)
-                elif w.get("f16") is not None and w["f16"]["e"] is not None:   # a data gradient in the fp16 two-way split (train_bwd_f16x2)
+                elif w.get("f16") is not None and w["f16"].e is not None:   # a data gradient in the fp16 two-way split (train_bwd_f16x2)
                     if w.get("Us16") is None:
                         w["Us16"] = torch.empty(lib.cp_wino_split_weights_bytes(36, w["cout"], w["ktot"]), dtype=torch.uint8, device=w["U"].device)
                         w["cache"] = {}
                     scale = f16x2_scale(w["cache"], w["U"])
-                    w["c_scale"] = 2.0 ** (-w["f16"]["e"]) / scale
+                    w["c_scale"] = 2.0 ** (-w["f16"].e) / scale
                     check(lib.cp_wino_split_weights_scaled_f32(w["U"].data_ptr(), 36, w["cout"], w["ktot"], _lib.PLANES_F16X2, scale, w["Us16"].data_ptr(), stream),
                           "cp_wino_split_weights_scaled_f32(dgrad %s)" % L.name)
                     w["Us"] = w["Us16"]
@@ -638,17 +634,16 @@ class ConvOp:
 
     def wgrad_f16x2(self) -> bool:
         """the direct weight gradient on fp16 pairs: dY inside the band (the switch its data gradient uses) and X too (the forward still f16x2)"""
-        b = getattr(self, "bw16", None)
-        return b is not None and b["on"] and not b["dead"] and self.layer.fwd_f16x2
+        return self.bw16 is not None and self.bw16.on and not self.bw16.dead and self.layer.fwd_f16x2
 
     def direct_dgrad_split(self) -> bool:
         """True when this op has a data gradient that runs on conv_hsplit as an exact three-way split and may move to the fp16 pair
         (train_bwd_f16x2): 3x3 / stride 1 / no dilation, not a Winograd / deep-bf16 / 1x1-GEMM route"""
         L = self.layer
-        if not (train_bwd_f16x2() and L.mode_planes == 3 and L.k == 3 and self.stride == 1 and self.dil == 1) or getattr(self, "gemm", None) is not None:
+        if not (train_bwd_f16x2() and L.mode_planes == 3 and L.k == 3 and self.stride == 1 and self.dil == 1) or self.gemm is not None:
             return False
         for s, ent in enumerate(L.dgrad):
-            if ent is None or ent["split"] is None or ent.get("deep") or s in getattr(self, "wino_dgrad", {}):
+            if ent is None or ent["split"] is None or ent.get("deep") or s in self.wino_dgrad:
                 continue
             if ent["split"]["np"] in (3, _lib.PLANES_F16X2):
                 return True
@@ -657,9 +652,9 @@ class ConvOp:
     def set_direct_dgrad_f16x2(self, on: bool, stream: int):
         """the direct data gradients of this op on the fp16 two-way split (weights x 2^k re-packed as two fp16 planes) or back on the exact split"""
         L = self.layer
-        self.bw16["on"] = on
+        self.bw16.on = on
         for s, ent in enumerate(L.dgrad):
-            if ent is None or ent["split"] is None or ent.get("deep") or s in getattr(self, "wino_dgrad", {}):
+            if ent is None or ent["split"] is None or ent.get("deep") or s in self.wino_dgrad:
                 continue
             sp = ent["split"]
             if sp["np"] in (3, _lib.PLANES_F16X2):
@@ -668,12 +663,10 @@ class ConvOp:
 
     def set_dgrad_exponent(self, w: dict, e: Optional[int], stream: int):
         """the power of two the transformed dY of this Winograd data gradient is multiplied by (None: back to the exact split); re-packs the weights"""
-        f = w["f16"]
-        f["e"] = e
+        w["f16"].e = e
         if e is not None:
             if w.get("ps") is None:
-                dev = w["U"].device
-                w["ps"] = torch.empty(w["ktot"], dtype=torch.float32, device=dev)
+                w["ps"] = torch.empty(w["ktot"], dtype=torch.float32, device=w["U"].device)
             w["ps"].fill_(2.0 ** e)
         self._refresh_winograd(stream)
 
@@ -705,17 +698,12 @@ class ConvOp:
         lib = _lib.load()
         off = 0
         V = w["V"] if "V" in w else self._wV
-        if mon:
-            lib.cp_f16x2_monitor_set(mon)
-        try:
+        with armed(mon):
             for i, (ptr, ld, ch) in enumerate(srcs):
                 ps, pb, pa = (pre or {}).get(i, (None, None, 0))
                 check(lib.cp_wino_input_transform_pre_f32(ptr, ld, ch, self.batch, self.in_h, self.in_w, self.dil, V.data_ptr(), w["ktot"], off, ps, pb, pa, stream),
                       "cp_wino_input_transform_pre_f32(%s)" % self.layer.name)
                 off += ch
-        finally:
-            if mon:
-                lib.cp_f16x2_monitor_set(None)
         if w.get("Us") is not None:
             # CASAPOSE_CONV_MODE=bf16: hi + mid planes only (three products, not fp32-equivalent: that mode's gates are 3e-2); else the exact split
             f16x2 = "c_scale" in w
@@ -731,17 +719,8 @@ class ConvOp:
 
     def forward(self, stream: int):
         """The forward launch(es) of this layer; an f16x2 forward runs armed when the plan has given the op a monitor slot (mon_ptr)."""
-        mon = getattr(self, "mon_ptr", None) if self.layer.fwd_f16x2 else None
-        if getattr(self, "wino_fwd", None) is not None:
-            return self._forward(stream, mon)
-        if not mon:
-            return self._forward(stream, None)
-        lib = _lib.load()
-        lib.cp_f16x2_monitor_set(mon)
-        try:
-            self._forward(stream, None)
-        finally:
-            lib.cp_f16x2_monitor_set(None)
+        with armed(self.mon_ptr if self.layer.fwd_f16x2 and self.wino_fwd is None else None):   # (a Winograd forward arms its input transforms)
+            self._forward(stream)
 
     def demote_forward_to_exact_split(self, stream: int):
         """this op's forward on the exact three-way bf16 split from now on (its f16x2 operands left the fp16 range condition): re-packs the forward
@@ -755,22 +734,22 @@ class ConvOp:
             sp["np"], sp["descale"] = 3, 1.0
             sp["planes"] = torch.empty(sp["f32"].numel() // 512 * 3 * 1024, dtype=torch.uint8, device=sp["f32"].device)
             L._refresh_split(stream)
-        g = getattr(self, "gemm", None)
+        g = self.gemm
         if g is not None and g["fwd_planes"] == _lib.PLANES_F16X2:
             g["fwd_planes"], g["c_scale"] = g["planes"], 1.0
             self._refresh_gemm(stream)
-        w = getattr(self, "wino_fwd", None)
+        w = self.wino_fwd
         if w is not None and "c_scale" in w:
             del w["c_scale"]
             self._refresh_winograd(stream)
 
-    def _forward(self, stream: int, mon):
-        if getattr(self, "gemm", None) is not None:
+    def _forward(self, stream: int):
+        if self.gemm is not None:
             g, d = self.gemm, self.layer.desc
             check(_lib.load().cp_wino_gemm_split_scaled_f32(self.srcs[0][0].data.data_ptr(), g["Us_f"].data_ptr(), d.out_raw, g["rows"], g["rows"], g["cin"],
                                                             self.layer.cout, g["fwd_planes"], g["c_scale"], stream), "cp_wino_gemm_split_scaled_f32(%s)" % self.layer.name)
             return
-        if getattr(self, "wino_fwd", None) is not None:
+        if self.wino_fwd is not None:
             d = self.layer.desc
             srcs, pre = [], {}
             for i, ((t, ld), c) in enumerate(zip(self.srcs, self.layer.sources)):
@@ -781,7 +760,7 @@ class ConvOp:
                 else:
                     srcs.append((t.data.data_ptr(), ld, c[0]))
             self._wino_run(self.wino_fwd, srcs, self.residual.data.data_ptr() if self.residual is not None else None, d.out_raw, stream, pre=pre,
-                           stats=self.stats_to.sums.data_ptr() if self.stats_to is not None else None, mon=mon)
+                           stats=self.stats_to.sums.data_ptr() if self.stats_to is not None else None, mon=self.mon_ptr if self.layer.fwd_f16x2 else None)
             return
         lib = _lib.load()
         if self.head_fast and self.pre_bn is not None and self.record_prefix is not None:
@@ -841,7 +820,7 @@ class ConvOp:
         def split_pipe(sp):
             return ("bf16", {3: 6.0, _lib.PLANES_F16X2: 3.0}.get(sp["np"], 1.0))   # products per fp32 product: exact bf16 split, fp16 two-way split, bf16
 
-        if getattr(self, "gemm", None) is not None:
+        if self.gemm is not None:
             gm = self.gemm
             mult = 6.0 if gm["planes"] == 3 else 3.0
             out["bf16"] += (3.0 if gm["fwd_planes"] == _lib.PLANES_F16X2 else mult) * direct     # forward
@@ -852,12 +831,12 @@ class ConvOp:
             else:
                 out["f32"] += direct
             return out
-        if getattr(self, "wino_fwd", None) is not None:
+        if self.wino_fwd is not None:
             w = self.wino_fwd
             g = 2.0 * 36 * w["tp"] * w["ktot"] * w["cout"]
             out[wino_pipe] += (3.0 if (L.fwd_f16x2 and TRAIN_WINO_GEMM_SPLIT) else wino_mult) * g      # forward GEMM
             if self.wino_wgrad_split():          # weight gradient: grouped GEMM over the 36 planes, exact splits / f16x2 on the 2-byte pipe or fp32 MFMA
-                wg16 = w.get("wg16") is not None and w["wg16"]["e"] is not None and L.fwd_f16x2
+                wg16 = w.get("wg16") is not None and w["wg16"].e is not None and L.fwd_f16x2
                 out["bf16"] += (1.0 if self.layer.mode_planes == 1 else (3.0 if wg16 else 6.0)) * g
             else:
                 out["f32"] += g
@@ -880,9 +859,9 @@ class ConvOp:
                 continue
             if ent.get("deep") and ent["split"] is not None:
                 out["bf16"] += 2.0 * float(self.batch * self.in_h * self.in_w) * L.k * L.k * ent["cin"] * cr
-            elif s in getattr(self, "wino_dgrad", {}):
+            elif s in self.wino_dgrad:
                 w = self.wino_dgrad[s]
-                f16 = w.get("f16") is not None and w["f16"]["e"] is not None
+                f16 = w.get("f16") is not None and w["f16"].e is not None
                 out[wino_pipe] += (3.0 if f16 else wino_mult) * 2.0 * 36 * w["tp"] * w["ktot"] * w["cout"]
             else:
                 m_in = float(self.batch * self.in_h * self.in_w)
@@ -899,7 +878,7 @@ class ConvOp:
         (CASAPOSE_WINO_GEMM != f32) and the shape fits (cout, cin multiples of 128); CASAPOSE_WINO_WGRAD=f32 keeps the fp32 grouped GEMM."""
         from .engine import TRAIN_WINO_GEMM_SPLIT
 
-        w = getattr(self, "wino_fwd", None)
+        w = self.wino_fwd
         if w is None or not TRAIN_WINO_GEMM_SPLIT or os.environ.get("CASAPOSE_WINO_WGRAD", "split") == "f32":
             return False
         return bool(_lib.load().cp_wino_wgrad_split_applicable(36, w["tp"], self.layer.cout, w["ktot"]))
@@ -908,7 +887,7 @@ class ConvOp:
         """3 / 1 when this op's weight gradient runs on the bf16 matrix pipe (CASAPOSE_CONV_MODE split / bf16 and a descriptor that
         cp_conv2d_wgrad_split covers: 3x3 / stride 1 / pad 1, 32-multiple sources + optional image, cout % 32 == 0), else 0 = fp32 MFMA."""
         planes = self.layer.mode_planes
-        if not planes or getattr(self, "wino_fwd", None) is not None:
+        if not planes or self.wino_fwd is not None:
             return 0
         return planes if _lib.load().cp_conv_wgrad_split_applicable(C.byref(self.layer.desc)) else 0
 
@@ -942,7 +921,7 @@ class ConvOp:
             check(lib.cp_head1x1_wgrad_f32(t.data.data_ptr(), ld, dy, dy_ld, px, L.cout, L.master_grad.data_ptr(), 1 if self.accumulate_master else 0, stream),
                   "cp_head1x1_wgrad_f32(%s)" % L.name)
             return
-        if getattr(self, "gemm", None) is not None and self.gemm["wgrad"]:
+        if self.gemm is not None and self.gemm["wgrad"]:
             # dU[co][ci] = sum_rows dY[row][co] A[row][ci] on the bf16 pipe, then through the transpose map into the master gradient [ci][co]
             g = self.gemm
             check(lib.cp_wino_wgrad_split_f32(dy, self.srcs[0][0].data.data_ptr(), g["dU"].data_ptr(), 1, g["rows"], L.cout, g["cin"],
@@ -950,27 +929,21 @@ class ConvOp:
             check(lib.cp_scatter_f32(g["dU"].data_ptr(), g["idx_t"].data_ptr(), g["idx_t"].numel(), L.master_grad.data_ptr(), 1 if self.accumulate_master else 0,
                                      stream), "cp_scatter_f32(%s)" % L.name)
             return
-        if getattr(self, "wino_fwd", None) is not None:
+        if self.wino_fwd is not None:
             # weight gradient through the Winograd planes: a quarter of the MFMA work of the direct kernel (V kept from the forward)
             w = self.wino_fwd
             cin, cout = self._cin, L.cout
             f = w.get("wg16") if self.wino_wgrad_split() else None
-            arm = f is not None and not f["dead"] and f["mon"]
-            if arm:
-                lib.cp_f16x2_monitor_set(f["mon"])   # the transform reports max |dM|
-            try:
+            with armed(f.mon if f is not None and not f.dead else None):   # the transform reports max |dM|
                 check(lib.cp_wino_dy_transform_f32(dy, dy_ld, cout, self.batch, self.in_h, self.in_w, self.dil, self._wM.data_ptr(), stream),
                       "cp_wino_dy_transform_f32(%s)" % L.name)
-            finally:
-                if arm:
-                    lib.cp_f16x2_monitor_set(None)
             if self.wino_wgrad_split():   # the grouped GEMM dU[p] = dM[p]^T V[p] on the bf16 matrix pipe (exact splits; csrc/wino_wgrad_split.hip)
                 # exact splits (fp32-equivalent) by default; CASAPOSE_CONV_MODE=bf16 rounds the operands of this GEMM to bf16 like the other weight gradients
-                if f is not None and f["e"] is not None and L.fwd_f16x2:
+                if f is not None and f.e is not None and L.fwd_f16x2:
                     # fp16 two-way split (train_bwd_f16x2): dM x 2^e from its monitor slot; V as it is -- the forward's monitor keeps it in the band
                     # (a forward that left the band is demoted: L.fwd_f16x2 turns False and this GEMM returns to the exact split with it)
                     check(lib.cp_wino_wgrad_split_scaled_f32(self._wM.data_ptr(), w["V"].data_ptr(), w["dU"].data_ptr(), 36, w["tp"], cout, w["ktot"],
-                                                             _lib.PLANES_F16X2, 2.0 ** f["e"], 1.0, stream), "cp_wino_wgrad_split_scaled_f32(%s)" % L.name)
+                                                             _lib.PLANES_F16X2, 2.0 ** f.e, 1.0, stream), "cp_wino_wgrad_split_scaled_f32(%s)" % L.name)
                 else:
                     check(lib.cp_wino_wgrad_split_f32(self._wM.data_ptr(), w["V"].data_ptr(), w["dU"].data_ptr(), 36, w["tp"], cout, w["ktot"],
                                                       1 if self.layer.mode_planes == 1 else 3, stream),
@@ -989,7 +962,7 @@ class ConvOp:
             if planes == 3 and self.wgrad_f16x2():
                 planes = _lib.PLANES_F16X2   # both operands inside fp16's band: X watched by the forward's monitor, dY carrying the loss factor
             if planes:   # bf16 matrix pipe (csrc/conv_wgrad_split.hip): same packed result
-                with _armed(self.bw16["mon"] if planes == _lib.PLANES_F16X2 else None):   # (the fp16 pair: dY's overflow guard, every step)
+                with armed(self.bw16.mon if planes == _lib.PLANES_F16X2 else None):   # (the fp16 pair: dY's overflow guard, every step)
                     check(lib.cp_conv2d_wgrad_split(C.byref(d), dy, dy_ld, L.dwp.data_ptr(), 0, planes, stream), "cp_conv2d_wgrad_split(%s)" % L.name)
             else:
                 check(lib.cp_conv2d_wgrad_f32(C.byref(d), dy, dy_ld, L.dwp.data_ptr(), 0, stream), "cp_conv2d_wgrad_f32(%s)" % L.name)
@@ -1015,7 +988,7 @@ class ConvOp:
             if ent is None:
                 continue
             t, _ = self.srcs[s]
-            if getattr(self, "gemm", None) is not None and self.gemm["Us_d"] is not None and not t.has_grad:
+            if self.gemm is not None and self.gemm["Us_d"] is not None and not t.has_grad:
                 # dA[row][ci] = sum_co dY[row][co] W[ci][co]; the GEMM writes (no accumulation): the plan runs this op's backward BEFORE the
                 # other consumers of its input (TrainPlan puts the shortcut after conv1 in the tape), which then accumulate into it
                 g = self.gemm
@@ -1031,12 +1004,12 @@ class ConvOp:
                     check(lib.cp_conv2d_fwd_bf16_deep(C.byref(g), ent["split"]["planes"].data_ptr(), stream), "dgrad bf16 deep(%s)" % L.name)
                     t.has_grad = True
                     continue
-            if s in getattr(self, "wino_dgrad", {}):  # stride 1, so the data gradient lives on the forward's input grid
+            if s in self.wino_dgrad:  # stride 1, so the data gradient lives on the forward's input grid
                 w = self.wino_dgrad[s]
                 f = w.get("f16")
-                pre = {0: (w["ps"].data_ptr(), None, _lib.ACT_NONE)} if f is not None and f["e"] is not None else None   # (a factor only: no shift table)
+                pre = {0: (w["ps"].data_ptr(), None, _lib.ACT_NONE)} if f is not None and f.e is not None else None   # (a factor only: no shift table)
                 self._wino_run(w, [(dy, dy_ld, L.cout)], t.grad.data_ptr() if t.has_grad else None, t.grad.data_ptr(), stream, pre=pre,
-                               mon=f["mon"] if f is not None and not f["dead"] else None)
+                               mon=f.mon if f is not None and not f.dead else None)
                 t.has_grad = True
                 continue
             g = ent["desc"]
@@ -1045,29 +1018,13 @@ class ConvOp:
             sp = ent["split"]
             if sp is not None and lib.cp_conv_split_applicable(C.byref(g)):
                 # the fp16 pair runs armed on every step: max |dY| into the op's backward slot, and its overflow guard
-                b16 = getattr(self, "bw16", None)
-                with _armed(b16["mon"] if sp["np"] == _lib.PLANES_F16X2 and b16 is not None else None):
+                with armed(self.bw16.mon if sp["np"] == _lib.PLANES_F16X2 and self.bw16 is not None else None):
                     check(lib.cp_conv2d_fwd_split_scaled(C.byref(g), sp["planes"].data_ptr(), None, sp["np"], sp["descale"], 1.0, stream), "dgrad split(%s)" % L.name)
             else:
                 check(lib.cp_conv2d_fwd_f32(C.byref(g), stream), "dgrad(%s)" % L.name)
             t.has_grad = True
         if self.residual is not None:
             add_grad(self.residual, dy, self.out.pixels * self.out.c, stream)
-
-
-class _armed:
-    """arm an f16x2 monitor slot for the calling thread's launches inside the block (None: nothing)"""
-
-    def __init__(self, slot):
-        self.slot = slot
-
-    def __enter__(self):
-        if self.slot:
-            _lib.load().cp_f16x2_monitor_set(self.slot)
-
-    def __exit__(self, *exc):
-        if self.slot:
-            _lib.load().cp_f16x2_monitor_set(None)
 
 
 def add_grad(t: TT, src_ptr: int, n: int, stream: int):
@@ -1216,11 +1173,8 @@ class TrainPlan:
                 self.GRAD_LD = (seg_dim + ver_dim + 31) // 32 * 32
             self.VERT_OFF = seg_dim
         self.group, self.world_size = group, world_size
-        self._f16x2_mon = self._f16x2_host = self._f16x2_event = None   # range monitor of the f16x2 forward (_poll_f16x2)
-        self._f16x2_steps, self.f16x2_checks, self.f16x2_demoted = 0, 0, []
-        self._bwd_f16, self._bwd_calibrated, self.f16x2_bwd_moves = None, False, []   # backward GEMMs in f16x2 (train_bwd_f16x2)
-        self.loss_exp, self._dout_scale = 0, 1.0                                       # power of two on the loss (direct data gradients in f16x2)
-        self.f16x2_skipped_steps = 0   # optimizer steps skipped because the fp16-pair backward clamped an operand (as of the last reading)
+        self.monitor: Optional[SlotBuffer] = None   # range monitor (_arm_f16x2): slot i <-> self.ops[i], then the backward slots (self.bwd)
+        self._f16x2_steps, self.f16x2_checks, self.f16x2_demoted, self._bwd_calibrated, self._dout_scale = 0, 0, [], False, 1.0
         self.comm_timing = None   # start_comm_timing()
         self.comm_log = None      # start_comm_log()
         self._buckets = None
@@ -1499,6 +1453,21 @@ class TrainPlan:
             k0[:, t * 4 + 3] = np.arange(64) * c0.ktot + t * 4 + 3
         self.g_idx = torch.from_numpy(k0[:, [t * 4 + 3 for t in range(49)]].T.copy()).to(dev)  # [49 taps][64 cout] -> flat index into dwp
         del ramp
+        # the backward GEMMs on fp16 pairs (train_bwd_f16x2), one slot each behind the forward's: Winograd data / weight gradients, direct 3x3 layers
+        slots = []
+        for op in (op for op in self.ops if isinstance(op, ConvOp)):
+            slots += [r for r in [w.get("f16") for w in op.wino_dgrad.values()] + [(op.wino_fwd or {}).get("wg16")] if r is not None]
+            if op.direct_dgrad_split() or (train_bwd_f16x2() and op.wgrad_planes() == 3):
+                op.bw16 = BwdSlot("direct", op)
+                slots.append(op.bw16)
+        for j, r in enumerate(slots):
+            r.slot = len(self.ops) + j
+        self.bwd = BackwardRange(slots, torch.zeros(2, dtype=torch.int32).pin_memory())
+
+    loss_exp = property(lambda self: self.bwd.loss_exp)   # (f16x2_range.BackwardRange: the power of two on the loss, the drift moves, the skipped steps)
+    f16x2_bwd_moves = property(lambda self: self.bwd.moves)
+    f16x2_skipped_steps = property(lambda self: self.bwd.skipped_steps)
+    _f16x2_mon = property(lambda self: self.monitor and self.monitor.dev)   # the slot words (int32 [4 * slots]) on the device
 
     def _consumers(self, t: TT) -> int:
         """ops that READ tensor t (convolution sources / residuals, normalisation inputs, the pooling / resampling closures); taps are
@@ -1558,14 +1527,14 @@ class TrainPlan:
         for bn in [op for op in self.ops if isinstance(op, BnActOp)]:
             if bn.head is not None or bn.pad_one:
                 continue
-            prod = [c for c in convs if c.out is bn.x and getattr(c, "wino_fwd", None) is not None and c.stats_to is None]
+            prod = [c for c in convs if c.out is bn.x and c.wino_fwd is not None and c.stats_to is None]
             if prod and bn.x.c == prod[0].layer.cout:
                 prod[0].stats_to, bn.stats_from = bn, prod[0]
             if bn.classes != 1 or bn.labels is not None or any(t is bn.y for t in self.taps.values()) or self._consumers(bn.y) != 1:
                 continue
             for c in convs:
                 for i, (t, ld) in enumerate(c.srcs):
-                    if t is bn.y and getattr(c, "wino_fwd", None) is not None and ld == bn.y.c and c.layer.sources[i][0] == bn.y.c:
+                    if t is bn.y and c.wino_fwd is not None and ld == bn.y.c and c.layer.sources[i][0] == bn.y.c:
                         c.pre_norm[i], bn.consumer = bn, c
 
     def _all_tensors(self):
@@ -1687,149 +1656,46 @@ class TrainPlan:
         self._read_f16x2(img.device)
         return self.out_view
 
-    # ---- range monitor of the f16x2 forward (round 6) -------------------------------------------------------------------------------
+    # ---- range monitor of the fp16-pair forward and backward (round 6; the policy: f16x2_range.BackwardRange) -----------------------------
     def _bwd_slots(self):
-        """[(op, state, entry)] of the backward GEMMs that run (or will run) in the fp16 two-way split: Winograd data gradients (entry = the
-        wino_dgrad dict, its weights are re-packed when the exponent moves) and Winograd weight gradients (entry None)"""
-        if self._bwd_f16 is None:
-            self._bwd_f16 = []
-            for op in self.ops:
-                if not isinstance(op, ConvOp):
-                    continue
-                self._bwd_f16 += [(op, w["f16"], w) for w in getattr(op, "wino_dgrad", {}).values() if w.get("f16") is not None]
-                wf = getattr(op, "wino_fwd", None)
-                if wf is not None and wf.get("wg16") is not None:
-                    self._bwd_f16.append((op, wf["wg16"], None))
-                if op.direct_dgrad_split() or (train_bwd_f16x2() and op.wgrad_planes() == 3):
-                    # direct 3x3 data / weight gradients (conv_hsplit, conv_wgrad_split): entry "direct", state on / off instead of an exponent
-                    op.bw16 = dict(on=False, mon=None, dead=False, e=None)
-                    self._bwd_f16.append((op, op.bw16, "direct"))
-        return self._bwd_f16
-
-    @staticmethod
-    def _set_bwd_exponent(op, f, entry, e, stream):
-        if entry is not None:
-            op.set_dgrad_exponent(entry, e, stream)
-        else:
-            f["e"] = e
-
-    def _set_loss_exponent(self, e_new: int, stream: int):
-        """move the power of two on the loss; the Winograd GEMMs' own exponents move the other way at the same moment (their operands carry it)"""
-        d = e_new - self.loss_exp
-        if d == 0:
-            return
-        self.loss_exp = e_new
-        for op, f, entry in self._bwd_slots():
-            if entry != "direct" and f["e"] is not None and not f["dead"]:
-                self._set_bwd_exponent(op, f, entry, f["e"] - d, stream)
-
-    def _judge_direct(self, vals, stream: int):
-        """vals: {slot index j: max |dY| as measured, i.e. including the loss factor in force}.  Moves the loss exponent when the largest of them
-        has left [2^7, 2^13), then switches every direct data gradient on (inside [1, 2^13]) or off (outside [0.25, 65504 / 4], the band's HI of
-        DESIGN.md 4.1f).  Returns True when the loss exponent moved."""
-        bwd = self._bwd_slots()
-        live = {j: v for j, v in vals.items() if np.isfinite(v) and v > 0.0}
-        if not live:
-            return False
-        top = max(live.values())
-        shift = 0
-        if not (2.0 ** 7 <= top < 2.0 ** 13):
-            shift = 10 - int(np.floor(np.log2(top)))
-            self._set_loss_exponent(int(np.clip(self.loss_exp + shift, -100, 100)), stream)
-        for j, v in vals.items():
-            op, f, _ = bwd[j]
-            if f["dead"]:
-                continue
-            if not np.isfinite(v):
-                f["dead"] = True
-                op.set_direct_dgrad_f16x2(False, stream)
-                continue
-            on = TrainPlan._direct_band(f["on"], v * 2.0 ** shift)
-            if on != f["on"]:
-                op.set_direct_dgrad_f16x2(on, stream)
-        return shift != 0
-
-    @staticmethod
-    def _direct_band(on: bool, v: float) -> bool:
-        """a direct data gradient with max |dY| = v (loss factor included): joins the fp16 pair inside [1, 2^13], stays inside [0.25, HI]"""
-        from .engine import F16X2_AMAX_HI
-
-        return (0.25 <= v <= F16X2_AMAX_HI) if on else (1.0 <= v <= 2.0 ** 13)
+        """[(op, record, entry "direct" / the wino_dgrad record / None for a Winograd weight gradient)]: the view bench.py reads"""
+        return [(r.op, r, "direct" if r.kind == "direct" else r.entry) for r in self.bwd.slots]
 
     def _arm_f16x2(self):
-        """one monitor slot per convolution op whose forward runs in the fp16 two-way split (slot i <-> self.ops[i]), then one per Winograd data
-        gradient of train_bwd_f16x2()"""
-        bwd = self._bwd_slots()
-        if self._f16x2_mon is None:
-            dev = self.out.device
-            self._f16x2_mon = torch.zeros(4 * (len(self.ops) + len(bwd)), dtype=torch.int32, device=dev)
-            self._f16x2_host = torch.zeros(4 * (len(self.ops) + len(bwd)), dtype=torch.int32).pin_memory()
+        """one monitor slot per convolution op whose forward runs in the fp16 two-way split (slot i <-> self.ops[i]), then one per backward record"""
+        self.monitor = SlotBuffer(len(self.ops) + len(self.bwd.slots), self.out.device)
         # the store outlives its plans (model.training_plan builds one per batch / size / group): every plan has its own host copy, and a flag
         # the previous plan's last step left in skip[0] must not skip this plan's first step (backward() clears or rewrites it every step)
         if self.store.skip is None:
-            self.store.skip = torch.zeros(2, dtype=torch.int32, device=self._f16x2_mon.device)
+            self.store.skip = torch.zeros(2, dtype=torch.int32, device=self.monitor.dev.device)
         else:
             self.store.skip[:1].zero_()
-        self._skip_host = torch.zeros(2, dtype=torch.int32).pin_memory()
-        self._skip_base = None   # skip[1] when this plan calibrated (read in _calibrate_bwd, which synchronises anyway)
-        base = self._f16x2_mon.data_ptr()
         for i, op in enumerate(self.ops):
             if isinstance(op, ConvOp):
-                op.mon_ptr = base + 16 * i if op.layer.fwd_f16x2 else None
-        for j, (_, f, _e) in enumerate(bwd):
-            f["mon"] = base + 16 * (len(self.ops) + j)
+                op.mon_ptr = self.monitor.ptr(i) if op.layer.fwd_f16x2 else None
+        for r in self.bwd.slots:
+            r.mon = self.monitor.ptr(r.slot)
 
     def _calibrate_bwd(self, stream: int):
-        """after the plan's FIRST backward (exact split, slots armed): one synchronous reading gives every Winograd data gradient its exponent"""
+        """after the plan's FIRST backward (exact split, slots armed): one synchronous reading gives every backward GEMM its exponent"""
         self._bwd_calibrated = True
-        if self.store.skip is not None and getattr(self, "_skip_base", 1) is None:
-            self._skip_base = int(self.store.skip[1])
-        bwd = self._bwd_slots()
-        if not bwd or self._f16x2_mon is None:
+        if self.monitor is None:
             return
-        n0 = len(self.ops)
-        w32 = self._f16x2_mon[4 * n0:].cpu().numpy().view(np.uint32).reshape(-1, 4)
-        self._f16x2_mon[4 * n0:].zero_()
-        direct = {}
-        for j, (op, f, entry) in enumerate(bwd):
-            if int(w32[j, 1]) == 0 or f["e"] is not None:
-                continue
-            amax = float(w32[j, :1].view(np.float32)[0])
-            if entry == "direct":
-                direct[j] = amax
-            elif np.isfinite(amax) and amax > 0.0:
-                self._set_bwd_exponent(op, f, entry, int(np.clip(10 - int(np.floor(np.log2(amax))), -100, 100)), stream)
-        self._judge_direct(direct, stream)   # (moves the Winograd exponents just set by the loss exponent it chooses)
-        self._sync_guards()
-
-    def _guard_thresholds(self) -> np.ndarray:
-        """the overflow guard of every backward slot (word [3], include/casapose_hip.h): the largest value its reports may reach before a conversion
-        of the fp16-pair backward clamps -- 65504 on what a slot measures as converted (direct dY with the loss factor, Winograd V x 2^e), 65504 2^-e
-        on a weight gradient's dM (its GEMM applies 2^e); 0 (no guard) for a GEMM on the exact split"""
-        out = np.zeros(len(self._bwd_slots()), np.float32)
-        for j, (op, f, entry) in enumerate(self._bwd_slots()):
-            if f["dead"]:
-                continue
-            if entry == "direct":
-                out[j] = 65504.0 if f["on"] else 0.0
-            elif f["e"] is not None and (entry is not None or op.layer.fwd_f16x2):
-                out[j] = 65504.0 * 2.0 ** (-f["e"] if entry is None else 0)
-        return out
+        self.bwd.skip_base = int(self.store.skip[1])   # (synchronises anyway)
+        if self.bwd.slots:
+            words = self.monitor.read(len(self.ops))
+            self.monitor.zero(len(self.ops))
+            self.bwd.calibrate(words, stream)
+            self._sync_guards()
 
     def _sync_guards(self):
         """write the guards into the backward slots (word [3]; clears their overflow bits)"""
-        if self._f16x2_mon is None or not self._bwd_slots():
-            return
-        n0, nb = len(self.ops), len(self._bwd_slots())
-        self._guards = torch.from_numpy(self._guard_thresholds().view(np.int32).copy()).to(self._f16x2_mon.device)
-        self._f16x2_mon.view(-1, 4)[n0:n0 + nb, 3].copy_(self._guards)
+        if self.bwd.slots:
+            self.monitor.set_guards(self.bwd.guard_thresholds(), len(self.ops))
 
     def _collect_skip(self, multi: bool):
-        """after a backward in the fp16 pair: bit 31 of store.skip[0] when any backward slot's guard fired in it (an operand was clamped), then the
-        slots' overflow bits are cleared for the next step.  With replicas every rank takes the same decision (MIN over ranks: a set bit 31 is
-        negative).  No host synchronisation."""
-        n0, nb = len(self.ops), len(self._bwd_slots())
-        col = self._f16x2_mon.view(-1, 4)[n0:n0 + nb, 3]
+        """after an fp16-pair backward: store.skip[0] = MIN of the guard words over slots and ranks (a fired guard is negative), guards cleared"""
+        col = self.monitor.dev.view(-1, 4)[len(self.ops):, 3]   # (the backward slots)
         torch.amin(col, dim=0, keepdim=True, out=self.store.skip[:1])
         col.bitwise_and_(0x7FFFFFFF)
         if multi:
@@ -1838,102 +1704,45 @@ class TrainPlan:
             dist.all_reduce(self.store.skip[:1], op=dist.ReduceOp.MIN, group=self.group)
 
     def _read_f16x2(self, dev):
-        """every F16X2_TRAIN_CHECK_EVERY-th step: the slots (sticky maxima over the steps since the last reading) travel to pinned host memory, are
-        zeroed behind the copy and judged at the start of a later step -- no synchronisation in the step"""
-        if self._f16x2_mon is None:
-            return
-        self._f16x2_steps += 1
-        if self._f16x2_steps >= F16X2_TRAIN_CHECK_EVERY and self._f16x2_event is None:
-            self._f16x2_host.copy_(self._f16x2_mon, non_blocking=True)
-            if self.store.skip is not None:
-                self._skip_host.copy_(self.store.skip, non_blocking=True)
-            self._f16x2_mon.zero_()
-            if getattr(self, "_guards", None) is not None:
-                n0 = len(self.ops)
-                self._f16x2_mon.view(-1, 4)[n0:n0 + len(self._guards), 3].copy_(self._guards)
-            self._f16x2_event = torch.cuda.Event()
-            self._f16x2_event.record(torch.cuda.current_stream(dev))
-            self._f16x2_steps = 0
+        """every F16X2_TRAIN_CHECK_EVERY-th step the slots (sticky maxima) go to pinned memory, judged at the start of a later step (_poll_f16x2)"""
+        if self.monitor is not None:
+            self._f16x2_steps += 1
+            if self._f16x2_steps >= F16X2_TRAIN_CHECK_EVERY and self.monitor.event is None:
+                self.monitor.read_async(torch.cuda.current_stream(dev), extra=(self.bwd.skip_host, self.store.skip))
+                self._f16x2_steps = 0
 
     def _poll_f16x2(self, stream: int):
-        from . import engine
-
-        if self._f16x2_mon is None:
-            if any(isinstance(op, ConvOp) and op.layer.fwd_f16x2 for op in self.ops) or self._bwd_slots():
+        if self.monitor is None:
+            if any(isinstance(op, ConvOp) and op.layer.fwd_f16x2 for op in self.ops) or self.bwd.slots:
                 self._arm_f16x2()
             return
-        ev = self._f16x2_event
-        if ev is None or not ev.query():
+        w = self.monitor.poll()
+        if w is None:
             return
-        self._f16x2_event = None
-        lib = _lib.load()
         lo, hi = engine.F16X2_AMAX_LO / engine.F16X2_MONITOR_SLACK, engine.F16X2_AMAX_HI * engine.F16X2_MONITOR_SLACK
-        w = self._f16x2_host.numpy().copy().view(np.uint32).reshape(-1, 4)
+        amax, n = decode(w)
         out = []
         for i, op in enumerate(self.ops):
-            if not isinstance(op, ConvOp) or not op.layer.fwd_f16x2 or int(w[i, 1]) == 0:
+            if not isinstance(op, ConvOp) or not op.layer.fwd_f16x2 or n[i] == 0:
                 continue
-            amax = float(w[i, :1].view(np.float32)[0])
-            if lib.cp_f16x2_range_check(amax, lo, hi, None) != 0:
+            if _lib.load().cp_f16x2_range_check(amax[i], lo, hi, None) != 0:
                 op.demote_forward_to_exact_split(stream)
                 op.mon_ptr = None
-                out.append("%s (max %.3g)" % (op.layer.name, amax))
-        out += self._judge_bwd(w[len(self.ops):], stream)
+                out.append("%s (max %.3g)" % (op.layer.name, amax[i]))
+        demoted, moved = self.bwd.judge(w[len(self.ops):], stream)
+        if moved:   # zero the backward slots' maxima (stream-ordered after the backward that reported with the old factors), then their guards
+            self.monitor.zero(len(self.ops))
+            self._sync_guards()
+        out += demoted
         self._sync_guards()   # (a forward demoted above takes its Winograd weight gradient to the exact split: no guard)
         self.f16x2_checks += 1
-        skipped = int(self._skip_host[1]) - (getattr(self, "_skip_base", None) or 0) if self.store.skip is not None else 0
-        if skipped > self.f16x2_skipped_steps:
-            if self.f16x2_skipped_steps == 0:
-                import warnings
-                warnings.warn("training backward (fp16 two-way split): an operand left fp16's range and the optimizer step was skipped (%d step(s) "
-                              "so far); the exponents are lowered from this reading on (TrainPlan.f16x2_skipped_steps)" % skipped)
-            self.f16x2_skipped_steps = skipped
+        if self.bwd.count_skips(int(self.bwd.skip_host[1])):
+            warnings.warn("training backward (fp16 two-way split): an operand left fp16's range and the optimizer step was skipped (%d step(s) "
+                          "so far); the exponents are lowered from this reading on (TrainPlan.f16x2_skipped_steps)" % self.bwd.skipped_steps)
         if out:
             self.f16x2_demoted += out
-            import warnings
             warnings.warn("training forward (fp16 two-way split): %d layer(s) converted operands outside [%g, %g] and run their forward on the exact bf16 split "
                           "from now on: %s" % (len(out), lo, hi, "; ".join(out)))
-
-    def _judge_bwd(self, w: np.ndarray, stream: int) -> list:
-        """the backward slots of one reading (w: uint32 [slots][4]): moves the Winograd exponents and the loss exponent.  When anything moved, the
-        slots are reset (_reset_bwd_slots): what the steps between the copy and this judgement reported was measured with the old factors and
-        would move them a second time at the next reading.  Returns the GEMMs that left the fp16 pair for good."""
-        out = []
-        before = (self.loss_exp, [f["e"] for _, f, _ in self._bwd_slots()], [f.get("on") for _, f, _ in self._bwd_slots()])
-        n0 = 0
-        direct = {}
-        for j, (op, f, entry) in enumerate(self._bwd_slots()):
-            # backward GEMMs: a data gradient's slot holds max |V 2^e| (the transform applies the factor), a weight gradient's max |dM| (the GEMM
-            # applies it); e follows a drift out of [2^7, 2^13), a non-finite maximum ends the f16x2 run of that GEMM
-            if f["dead"] or int(w[n0 + j, 1]) == 0:
-                continue
-            amax = float(w[n0 + j, :1].view(np.float32)[0])
-            if entry == "direct":
-                direct[j] = amax
-                continue
-            scaled = amax * (2.0 ** f["e"] if (entry is None and f["e"] is not None) else 1.0)
-            if not np.isfinite(amax):
-                f["dead"] = True
-                self._set_bwd_exponent(op, f, entry, None, stream)
-                out.append("%s %s gradient (max %.3g)" % (op.layer.name, "data" if entry is not None else "weight", amax))
-            elif f["e"] is None:
-                if amax > 0.0:
-                    self._set_bwd_exponent(op, f, entry, int(np.clip(10 - int(np.floor(np.log2(amax))), -100, 100)), stream)
-            elif scaled > 0.0 and not (2.0 ** 7 <= scaled < 2.0 ** 13):
-                e = int(np.clip(f["e"] + 10 - int(np.floor(np.log2(scaled))), -100, 100))
-                self.f16x2_bwd_moves.append((op.layer.name, f["e"], e))
-                self._set_bwd_exponent(op, f, entry, e, stream)
-        self._judge_direct(direct, stream)
-        after = (self.loss_exp, [f["e"] for _, f, _ in self._bwd_slots()], [f.get("on") for _, f, _ in self._bwd_slots()])
-        if after != before:
-            self._reset_bwd_slots()
-        return out
-
-    def _reset_bwd_slots(self):
-        """zero the backward slots' maxima (stream-ordered after the backward that just reported with the old factors) and write their guards"""
-        n0, nb = len(self.ops), len(self._bwd_slots())
-        self._f16x2_mon.view(-1, 4)[n0:n0 + nb].zero_()
-        self._sync_guards()
 
     def loss_and_grad(self, labels_ce: torch.Tensor, labels_fg: torch.Tensor, keypoints_yx: torch.Tensor, mask_w=1.0, vertex_w=1.0, proxy_w=1.0,
                       filter_with_segmentation=True, kp: int = 9, filter_high_proxy_errors: bool = False) -> torch.Tensor:
@@ -2060,12 +1869,13 @@ class TrainPlan:
         if (multi or log is not None) and self._buckets is None:
             self._buckets = self._gradient_buckets()
         # the direct data gradients' operand range: max |dY| by a reduction pass of its own, on the step before a reading of the slots only
-        check_now = self._f16x2_mon is not None and (not self._bwd_calibrated or self._f16x2_steps >= F16X2_TRAIN_CHECK_EVERY - 1)
+        check_now = self.monitor is not None and (not self._bwd_calibrated or self._f16x2_steps >= F16X2_TRAIN_CHECK_EVERY - 1)
         for i in range(len(self.ops) - 1, -1, -1):
             op = self.ops[i]
-            if check_now and isinstance(op, ConvOp) and getattr(op, "bw16", None) is not None and op.bw16["mon"] and not op.bw16["dead"]:
+            b = op.bw16 if check_now and isinstance(op, ConvOp) else None
+            if b is not None and b.mon and not b.dead:
                 dy_, ld_ = op._dy()
-                check(_lib.load().cp_amax_f32(dy_, op.batch * op.out_h * op.out_w, ld_, op.layer.cout, op.bw16["mon"], stream), "cp_amax_f32(dY %s)" % op.layer.name)
+                check(_lib.load().cp_amax_f32(dy_, op.batch * op.out_h * op.out_w, ld_, op.layer.cout, b.mon, stream), "cp_amax_f32(dY %s)" % op.layer.name)
             op.backward(stream)
             if log is not None:
                 log.append(("op", i))
@@ -2082,7 +1892,7 @@ class TrainPlan:
             self._calibrate_bwd(stream)   # (this backward ran on the exact split)
             if self.store.skip is not None:
                 self.store.skip[:1].zero_()
-        elif self._f16x2_mon is not None and self._bwd_slots() and getattr(self, "_skip_base", None) is not None:
+        elif self.bwd.slots and self.bwd.skip_base is not None:   # (armed and calibrated)
             self._collect_skip(multi)
         elif self.store.skip is not None:
             self.store.skip[:1].zero_()   # no fp16-pair backward in this step (calibrating, or a plan without one): nothing to skip

@@ -221,3 +221,19 @@ def test_f16x2_monitor_slot_is_per_thread_state(lib):
     assert seen == [None]                      # another thread's launches are not armed
     assert lib.cp_f16x2_monitor_set(4100) == -1 and b"16-byte" in lib.cp_last_error()   # a slot is four words, 16-byte aligned
     assert lib.cp_f16x2_monitor_set(None) == 0 and lib.cp_f16x2_monitor_get() is None
+
+
+def test_armed_sets_the_slot_and_always_clears_it(lib):
+    """f16x2_range.armed: the one place that arms a monitor slot -- set inside the block, cleared on exit and on an exception; a falsy slot arms nothing"""
+    from casapose_amd.f16x2_range import armed
+
+    with armed(8192):
+        assert lib.cp_f16x2_monitor_get() == 8192
+    assert lib.cp_f16x2_monitor_get() is None
+    with pytest.raises(RuntimeError):
+        with armed(8192):
+            raise RuntimeError("a failed launch")
+    assert lib.cp_f16x2_monitor_get() is None
+    for slot in (None, 0):
+        with armed(slot):
+            assert lib.cp_f16x2_monitor_get() is None

@@ -32,10 +32,10 @@ if len(sys.argv) > 2:   # worker
             v = sums.cpu().numpy()
             hist.append((s, float(v[0] + 0.5 * v[1] + 0.015 * v[2])))
             exps.append(plan.loss_exp)
-    slots = plan._bwd_slots()
+    direct = [r for r in plan.bwd.slots if r.kind == "direct"]
+    wino = [r for r in plan.bwd.slots if r.kind != "direct"]
     print(json.dumps({"hist": hist, "loss_exp": exps, "moves": len(plan.f16x2_bwd_moves), "demoted": plan.f16x2_demoted, "readings": plan.f16x2_checks,
-                      "direct_on": sum(1 for _, f, e in slots if e == "direct" and f["on"]), "direct": sum(1 for _, f, e in slots if e == "direct"),
-                      "wino_on": sum(1 for _, f, e in slots if e != "direct" and f["e"] is not None), "wino": sum(1 for _, f, e in slots if e != "direct")}))
+                      "direct_on": sum(1 for r in direct if r.on), "direct": len(direct), "wino_on": sum(1 for r in wino if r.e is not None), "wino": len(wino)}))
     sys.exit(0)
 
 res = {}
