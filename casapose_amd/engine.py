@@ -22,6 +22,8 @@ import torch
 
 from . import _lib
 from ._lib import ConvDesc, check
+from .architecture import (BILINEAR_DEFAULT, DECODER_DIMS_DEFAULT, GUIDED_DEFAULT, PARTIAL_DEFAULT, SHARED_DEFAULT, STAGE_DILATION,  # noqa: F401
+                           STAGE_FILTERS, STAGE_STRIDE, Arch, graph)
 from .f16x2_range import SlotBuffer, armed, decode
 
 BN_EPS = 2e-5  # resnet.py:44; _normalization_layers.py:108
@@ -57,15 +59,6 @@ def cached_labels(storage_ptr: int, shape: Tuple[int, int, int], version: Option
         return None
     return labels
 
-STAGE_FILTERS = (64, 128, 256, 512)
-STAGE_STRIDE = (1, 2, 1, 1)  # resnet.py:262-290 (output_stride 8)
-STAGE_DILATION = (1, 1, 2, 4)
-DECODER_DIMS_DEFAULT = (256, 128, 64, 32, 32)
-# decoder-2 configuration of blocks 6..10: which use a partial convolution, which upsample their output with the
-# label-guided gather (else plain nearest x2).  CASAPoseConditional1-5 (pose_models.py:14-635) differ only in these.
-PARTIAL_DEFAULT = (True, True, True, True, True)
-GUIDED_DEFAULT = (False, True, True, True, False)
-BILINEAR_DEFAULT = (False, False, False, False, False)  # with guided: GuidedBilinearUpsampling (casapose_c_gcu4_bilat)
 
 
 def _ptr(t: Optional[torch.Tensor]) -> Optional[int]:
@@ -101,6 +94,21 @@ def fold_clade(params: Dict[str, np.ndarray], name: str):
     scale = gamma * rstd[None, :]
     shift = beta - gamma * (mean * rstd)[None, :]
     return scale.astype(np.float32), shift.astype(np.float32)
+
+
+def label_pyramid(labels: Sequence[torch.Tensor], pnorm: Sequence[torch.Tensor], sel: Sequence[torch.Tensor], gmask: Sequence[Optional[torch.Tensor]],
+                  batch: int, h: int, w: int, stream: int):
+    """From the hard label map labels[0]: the label pyramid labels[1..3], the partial convolutions' row scales pnorm[0..3], the guided
+    upsampling's neighbour maps sel[0..2] and -- where allocated -- the GuidedBilinearUpsampling match masks gmask[0..2] (pose_models.py:547-559)."""
+    lib = _lib.load()
+    lab = (C.c_void_p * 4)(*[t.data_ptr() for t in labels])
+    pn = (C.c_void_p * 4)(*[t.data_ptr() for t in pnorm])
+    sl = (C.c_void_p * 3)(*[t.data_ptr() for t in sel])
+    check(lib.cp_label_pyramid(labels[0].data_ptr(), batch, h, w, lab, pn, sl, stream), "cp_label_pyramid")
+    for l in range(3):
+        if gmask[l] is not None:
+            check(lib.cp_guided_match_mask(labels[l].data_ptr(), labels[l + 1].data_ptr(), batch, h >> l, w >> l, gmask[l].data_ptr(), stream),
+                  "cp_guided_match_mask")
 
 
 class FusedConv:
@@ -602,7 +610,7 @@ class ForwardPlan:
             raise ValueError("input height/width must be multiples of 8 (got %dx%d)" % (h, w))
         self.net, self.batch, self.h, self.w = net, batch, h, w
         self.fuse_upsample = fuse_upsample
-        self.fuse_heads = fuse_heads and net.decoder_dims[4] == 32 and not net.pvnet
+        self.fuse_heads = fuse_heads and net.arch.decoder_dims[4] == 32 and not net.arch.pvnet
         dev = net.device
         f32 = dict(dtype=torch.float32, device=dev)
         u8 = dict(dtype=torch.uint8, device=dev)
@@ -634,15 +642,19 @@ class ForwardPlan:
         self.pnorm = [new(B, hs[l], ws[l]) for l in range(4)]
         self.sel = [torch.empty(B, hs[l], ws[l], **u8) for l in range(3)]
         self.sel_zero = [torch.zeros(B, hs[l], ws[l], **u8) for l in range(3)]  # plain nearest x2 = "guided" with neighbour 0 everywhere
-        self.gmask = [torch.empty(B, hs[l], ws[l], **u8) if any(net.bilinear) else None for l in range(3)]  # GuidedBilinearUpsampling match masks
+        self.gmask = [torch.empty(B, hs[l], ws[l], **u8) if any(net.arch.bilinear) else None for l in range(3)]  # GuidedBilinearUpsampling match masks
         self._out_bound: List[Tuple[FusedConv, int, str]] = []  # (conv, channel offset, descriptor field) writing into the per-call output
         self._bufs: List[torch.Tensor] = []
 
         self.wino_V = self.wino_M = None
 
-        def conv(layer: FusedConv, act_private: bool = False, **kw):
-            """act_private: nothing but the NEXT convolution of the plan reads this layer's activated output (lets two consecutive Winograd
-            layers hand it over on chip: WinoConv.fuse_next)"""
+        L, g = net.layers_by_name, net.graph
+
+        def conv(rec, act_private: bool = False, **kw):
+            """rec: the architecture.Conv record (its layer, stride, dilation and padding); act_private: nothing but the NEXT convolution of the
+            plan reads this layer's activated output (lets two consecutive Winograd layers hand it over on chip: WinoConv.fuse_next)"""
+            layer = L[rec.name]
+            kw.update(stride=rec.stride, dilation=rec.dilation, pad=rec.pad)
             wl = net.wino_by_name.get(layer.name) if net.use_winograd else None
             plain = all(s.get("mode", _lib.SRC_DIRECT) == _lib.SRC_DIRECT and not s.get("pre") for s in kw["srcs"])
             # bf16 conv mode: the deep 3x3 layers (cout a multiple of 128, any of the dilations, no labels) on the direct bf16-operand kernel
@@ -687,14 +699,12 @@ class ForwardPlan:
 
         self._wino_pending: List = []  # bound at the end, when the shared scratch has its final size
 
-        L = net.layers_by_name
         # ---- encoder (resnet.py:246-305) ---------------------------------------------------
         x2s = new(B, hs[1], ws[1], 64)
-        conv(L["conv0"], in_h=h, in_w=w, stride=2, pad=3,
-             srcs=[dict(data=self.img4, ld=4, pre=P["bn_data"])],
-             scale=P["bn0"][0], shift=P["bn0"][1], act=_lib.ACT_RELU, out_act=x2s)
+        conv(g.conv0, in_h=h, in_w=w, srcs=[dict(data=self.img4, ld=4, pre=P[g.bn_data.name])],
+             scale=P[g.bn0.name][0], shift=P[g.bn0.name][1], act=_lib.ACT_RELU, out_act=x2s)
         a = new(B, hs[2], ws[2], 64)
-        s1, b1 = P["stage1_unit1_bn1"]
+        s1, b1 = P[g.units[0].bn1.name]
 
         def pool(stream, src=x2s, dst=a, s1=s1, b1=b1):
             check(lib.cp_maxpool3x3s2_f32(src.data_ptr(), B, hs[1], ws[1], 64, s1.data_ptr(), b1.data_ptr(), 1,
@@ -702,106 +712,95 @@ class ForwardPlan:
 
         self.steps.append(pool)
         self._bufs += [x2s, a]
-        cur_h, cur_w, cin = hs[2], ws[2], 64
+        cur_h, cur_w = hs[2], ws[2]
         x_raw = None
         taps: Dict[str, torch.Tensor] = {"x2s": x2s}
-        tap_names = ["x4s", "x8s", "x16s", "x32s"]
-        for s, f in enumerate(STAGE_FILTERS):
-            d = STAGE_DILATION[s]
-            for u in range(2):
-                base = "stage%d_unit%d_" % (s + 1, u + 1)
-                stride = STAGE_STRIDE[s] if u == 0 else 1
-                oh, ow = (cur_h - 1) // stride + 1, (cur_w - 1) // stride + 1
-                t = new(B, oh, ow, f)
-                bn2 = P[base + "bn2"]
-                if u == 0:
-                    sc = new(B, oh, ow, f)
-                    conv(L[base + "sc"], in_h=cur_h, in_w=cur_w, stride=stride, srcs=[dict(data=a, ld=cin)], out_raw=sc)
-                    shortcut = sc
-                else:
-                    shortcut = x_raw
-                conv(L[base + "conv1"], in_h=cur_h, in_w=cur_w, stride=stride, dilation=d, pad=d, act_private=True,   # t feeds conv2 only
-                     srcs=[dict(data=a, ld=cin)], scale=bn2[0], shift=bn2[1], act=_lib.ACT_RELU, out_act=t)
-                if u == 0:
-                    nxt = P["stage%d_unit2_bn1" % (s + 1)]
-                    x_raw = new(B, oh, ow, f)
-                else:
-                    nxt = P["stage%d_unit1_bn1" % (s + 2)] if s < 3 else P["bn1"]
-                    x_raw = None
-                a_next = new(B, oh, ow, f)
-                # unit 1's activated output feeds unit 2's conv1 only (its shortcut is the RAW sum); unit 2's also feeds the next stage's 1x1
-                # shortcut / the decoders / the backbone's taps
-                conv(L[base + "conv2"], in_h=oh, in_w=ow, dilation=d, pad=d, srcs=[dict(data=t, ld=f)], act_private=(u == 0),
-                     residual=shortcut, out_raw=x_raw, scale=nxt[0], shift=nxt[1], act=_lib.ACT_RELU, out_act=a_next)
-                self._bufs += [t, shortcut, a_next]
-                a, cur_h, cur_w, cin = a_next, oh, ow, f
-                if u == 1:
-                    taps[tap_names[s]] = a
+        for j, u in enumerate(g.units):
+            oh, ow = (cur_h - 1) // u.conv1.stride + 1, (cur_w - 1) // u.conv1.stride + 1
+            t = new(B, oh, ow, u.cout)
+            bn2 = P[u.bn2.name]
+            if u.sc is not None:
+                sc = new(B, oh, ow, u.cout)
+                conv(u.sc, in_h=cur_h, in_w=cur_w, srcs=[dict(data=a, ld=u.cin)], out_raw=sc)
+                shortcut = sc
+            else:
+                shortcut = x_raw
+            conv(u.conv1, in_h=cur_h, in_w=cur_w, act_private=True,   # t feeds conv2 only
+                 srcs=[dict(data=a, ld=u.cin)], scale=bn2[0], shift=bn2[1], act=_lib.ACT_RELU, out_act=t)
+            nxt = g.units[j + 1] if j + 1 < len(g.units) else None
+            # a unit followed by one without a shortcut conv keeps its RAW sum (the next unit's shortcut), and its activated output feeds that
+            # unit's conv1 only; the last unit of a stage also feeds the next stage's 1x1 shortcut / the decoders / the backbone's taps
+            private = nxt is not None and nxt.sc is None
+            x_raw = new(B, oh, ow, u.cout) if private else None
+            nbn = P[nxt.bn1.name if nxt is not None else g.bn1.name]
+            a_next = new(B, oh, ow, u.cout)
+            conv(u.conv2, in_h=oh, in_w=ow, srcs=[dict(data=t, ld=u.cout)], act_private=private,
+                 residual=shortcut, out_raw=x_raw, scale=nbn[0], shift=nbn[1], act=_lib.ACT_RELU, out_act=a_next)
+            self._bufs += [t, shortcut, a_next]
+            a, cur_h, cur_w = a_next, oh, ow
+            if u.tap:
+                taps[u.tap] = a
         self.taps = taps
         self.encoder_steps = len(self.steps)   # run_encoder() stops here: the bare ResNet-18 backbone (resnet.py:319: the model's five outputs)
-        x32s, x8s, x4s = taps["x32s"], taps["x8s"], taps["x4s"]
-        skips = [None, (x8s, 128), (x4s, 64), (x2s, 64), (self.img4, 4)]
-        dims = net.decoder_dims
-        lvl = [3, 3, 2, 1, 0]  # pyramid level each decoder block runs at
+        x32s, skips = taps["x32s"], dict(taps, img4=self.img4)
+
+        def sources(i, blk, prev):
+            """the block's input list: x32s for the first block, else the previous block's output as the record's upsample says (fused into
+            the convolution's loaders, or materialised by a streaming pass first) + the skip tap"""
+            if i == 0:
+                return [dict(data=x32s, ld=512)]
+            l, pc = blk.level, blk.conv.sources[0][0]
+            src0, mode, sel = prev, _lib.SRC_DIRECT, None
+            # bilinear: the convolution's loaders interpolate the x2 source from the half-resolution tile (staged in LDS by csrc/conv_hsplit.hip);
+            # guided / nearest: they gather it by the label-guided neighbour map (nearest x2 = "guided" with neighbour 0 everywhere).
+            # fuse_upsample=False materialises both in a separate streaming pass (the unfused reference), and GuidedBilinearUpsampling, a
+            # 4-tap blend, is always materialised
+            if fuse_upsample and blk.upsample == "bilinear":
+                mode = _lib.SRC_BILINEAR_X2
+            elif fuse_upsample and blk.upsample in ("guided", "nearest"):
+                mode, sel = _lib.SRC_NEAREST_SEL, self.sel[l] if blk.upsample == "guided" else self.sel_zero[l]
+            elif blk.upsample != "none":
+                src0 = new(B, hs[l], ws[l], pc)
+                self.steps.append(self._upsample_step(blk.upsample, prev, src0, l, pc))
+                self._bufs.append(src0)
+            srcs = [dict(data=src0, ld=pc, mode=mode, sel=sel)]
+            if blk.skip:
+                srcs.append(dict(data=skips[blk.skip], ld=blk.conv.sources[1][0]))
+            return srcs
 
         # ---- decoder 1 (pose_models.py:541-546) -------------------------------------------
         self.out = None  # bound per call
-        prev, prev_c = None, 0
-        for i in range(5):
-            name = "pv_block_%d_conv2d" % (i + 1)
-            bn = P["pv_block_%d_bn" % (i + 1)]
-            l = lvl[i]
-            o = new(B, hs[l], ws[l], dims[i])
-            if i == 0:
-                srcs = [dict(data=x32s, ld=512)]
-            else:
-                up = i >= 2  # blocks 2,3,4 upsample their OUTPUT (casapose.py:109-140): consumed by block i+1
-                src0 = prev
-                mode = _lib.SRC_DIRECT
-                if up:
-                    # the convolution's loaders interpolate the x2 bilinear source from the half-resolution tile (staged in LDS by
-                    # csrc/conv_hsplit.hip); fuse_upsample=False materialises it in a separate streaming pass (the unfused reference)
-                    if fuse_upsample:
-                        mode = _lib.SRC_BILINEAR_X2
-                    else:
-                        big = new(B, hs[l], ws[l], prev_c)
-                        self.steps.append(self._bilinear_step(prev, big, hs[l] // 2, ws[l] // 2, prev_c))
-                        self._bufs.append(big)
-                        src0 = big
-                srcs = [dict(data=src0, ld=prev_c, mode=mode), dict(data=skips[i][0], ld=skips[i][1])]
-            fused = self.fuse_heads and i == 4
-            if fused:  # blocks 5 + pv_final_conv_segmentation in one launch; the 32-channel tensor is never stored
-                L[name].attach_head(net.params["pv_final_conv_segmentation.kernel"])
+        prev = None
+        for i, blk in enumerate(g.decoder1):
+            c, l = blk.conv, blk.level
+            bn = P[blk.norm.name]
+            o = new(B, hs[l], ws[l], c.cout)
+            srcs = sources(i, blk, prev)
+            if self.fuse_heads and i == 4:  # blocks 5 + pv_final_conv_segmentation in one launch; the 32-channel tensor is never stored
+                L[c.name].attach_head(net.params[g.seg_head.key])
                 # ... and the hard label map (arg-max of the K logits) straight from the head's registers: no pass over the strided records
-                conv(L[name], in_h=hs[l], in_w=ws[l], pad=1, srcs=srcs, scale=bn[0], shift=bn[1], act=_lib.ACT_LEAKY01,
+                conv(c, in_h=hs[l], in_w=ws[l], srcs=srcs, scale=bn[0], shift=bn[1], act=blk.act,
                      head_out=self.img4, head_out_ld=self.out_ld, head_label_out=self.labels[0], head_label_classes=K)
-                self._out_bound.append((L[name], 0, "head_out"))
+                self._out_bound.append((L[c.name], 0, "head_out"))
                 self.labels_from_head = True
             else:
                 extra = {}
-                if i == 0 and net.reuse_first:
-                    self.y_raw = new(B, hs[l], ws[l], dims[0])
+                if i == 0 and net.arch.reuse_first:
+                    self.y_raw = new(B, hs[l], ws[l], c.cout)
                     extra = dict(out_raw=self.y_raw)
-                conv(L[name], in_h=hs[l], in_w=ws[l], pad=1, srcs=srcs, scale=bn[0], shift=bn[1],
-                     act=_lib.ACT_RELU if i == 0 else _lib.ACT_LEAKY01, out_act=o, **extra)
+                conv(c, in_h=hs[l], in_w=ws[l], srcs=srcs, scale=bn[0], shift=bn[1], act=blk.act, out_act=o, **extra)
             self._bufs.append(o)
-            prev, prev_c = o, dims[i]
+            prev = o
         self.fuse_head2 = False
-        if net.pvnet:  # one head for all K + ver_dim channels; no conditioning, no second decoder
-            head = L["pv_final_conv"]
-            conv(head, in_h=h, in_w=w, srcs=[dict(data=prev, ld=prev_c)], out_raw=self.img4, out_raw_ld=self.out_ld)
-            self._out_bound.append((head, 0, "out_raw"))
-            self.seg_input_ptr = None
+        if not self.fuse_heads:   # (PVNet: one head for all K + ver_dim channels; no conditioning, no second decoder)
+            conv(g.seg_head, in_h=h, in_w=w, srcs=[dict(data=prev, ld=g.seg_head.sources[0][0])], out_raw=self.img4, out_raw_ld=self.out_ld)
+            self._out_bound.append((L[g.seg_head.name], 0, "out_raw"))
+        self.seg_input_ptr = None  # set per call when the model has a data_segmentation input
+        if net.arch.pvnet:
             self._bind_winograd()
             return
-        if not self.fuse_heads:
-            seg_head = L["pv_final_conv_segmentation"]
-            conv(seg_head, in_h=h, in_w=w, srcs=[dict(data=prev, ld=prev_c)], out_raw=self.img4, out_raw_ld=self.out_ld)
-            self._out_bound.append((seg_head, 0, "out_raw"))
 
         # ---- hard label map + pyramid (pose_models.py:547-559) -----------------------------
-        self.seg_input_ptr = None  # set per call when the model has a data_segmentation input
-
         def label_step(stream):
             if self.seg_input_ptr is not None:
                 src, ld = self.seg_input_ptr, K
@@ -809,76 +808,43 @@ class ForwardPlan:
                 src, ld = self.out.data_ptr(), self.out_ld
             if self.seg_input_ptr is not None or not self.labels_from_head:   # else block 5's fused head has written labels[0] already
                 check(lib.cp_argmax_labels(src, ld, K, B * h * w, self.labels[0].data_ptr(), stream), "cp_argmax_labels")
-            lab = (C.c_void_p * 4)(*[t.data_ptr() for t in self.labels])
-            pn = (C.c_void_p * 4)(*[t.data_ptr() for t in self.pnorm])
-            sl = (C.c_void_p * 3)(*[t.data_ptr() for t in self.sel])
-            check(lib.cp_label_pyramid(self.labels[0].data_ptr(), B, h, w, lab, pn, sl, stream), "cp_label_pyramid")
-            for l_ in range(3):
-                if self.gmask[l_] is not None:
-                    check(lib.cp_guided_match_mask(self.labels[l_].data_ptr(), self.labels[l_ + 1].data_ptr(), B, hs[l_], ws[l_], self.gmask[l_].data_ptr(), stream),
-                          "cp_guided_match_mask")
+            label_pyramid(self.labels, self.pnorm, self.sel, self.gmask, B, h, w, stream)
 
         self.steps.append(label_step)
 
         # ---- decoder 2 (pose_models.py:561-616) -------------------------------------------
-        prev, prev_c = None, 0
-        for i in range(5):
-            partial = net.partial[i]
-            name = ("pv_block_%d_prepare_conv2d" if partial else "pv_block_%d_conv2d") % (i + 6)
-            tab = P["pv_block_%d_clade" % (i + 6)]
-            l = lvl[i]
-            o = new(B, hs[l], ws[l], dims[i])
-            if i == 0 and net.reuse_first:  # casa_layer(y, "6", skip_conv=True): CLADE + ReLU on block 1's raw convolution output
-                def clade_step(stream, src=self.y_raw, dst=o, tab=tab, lab=self.labels[l], n=B * hs[l] * ws[l], c=dims[0]):
-                    check(lib.cp_affine_act_f32(src.data_ptr(), n, c, c, tab[0].data_ptr(), tab[1].data_ptr(), lab.data_ptr(), _lib.ACT_RELU,
+        prev = None
+        for i, blk in enumerate(g.decoder2):
+            c, l = blk.conv, blk.level
+            tab = P[blk.norm.name]
+            o = new(B, hs[l], ws[l], blk.norm.channels)
+            if c is None:  # casa_layer(y, "6", skip_conv=True): CLADE + ReLU on block 1's raw convolution output
+                def clade_step(stream, src=self.y_raw, dst=o, tab=tab, lab=self.labels[l], n=B * hs[l] * ws[l], c=blk.norm.channels, act=blk.act):
+                    check(lib.cp_affine_act_f32(src.data_ptr(), n, c, c, tab[0].data_ptr(), tab[1].data_ptr(), lab.data_ptr(), act,
                                                 dst.data_ptr(), c, stream), "cp_affine_act_f32(pv_block_6_clade)")
 
                 self.steps.append(clade_step)
                 self._bufs.append(o)
-                prev, prev_c = o, dims[i]
+                prev = o
                 continue
-            if i == 0:
-                srcs = [dict(data=x32s, ld=512)]
-            else:
-                up = i >= 2
-                src0, mode, sel = prev, _lib.SRC_DIRECT, None
-                if up and net.bilinear[i - 1]:
-                    if not net.guided[i - 1]:
-                        raise NotImplementedError("bilinear_upsampling without guided_upsampling in decoder 2 is not built")
-                    big = new(B, hs[l], ws[l], prev_c)  # GuidedBilinearUpsampling: a 4-tap blend, materialised
-                    self.steps.append(self._guided_bilinear_step(prev, self.gmask[l], big, hs[l] // 2, ws[l] // 2, prev_c))
-                    self._bufs.append(big)
-                    src0 = big
-                elif up:
-                    selmap = self.sel[l] if net.guided[i - 1] else self.sel_zero[l]  # block i-1 upsampled its output (casapose.py:109-131)
-                    if fuse_upsample:
-                        mode, sel = _lib.SRC_NEAREST_SEL, selmap
-                    else:
-                        big = new(B, hs[l], ws[l], prev_c)
-                        self.steps.append(self._guided_step(prev, selmap, big, hs[l] // 2, ws[l] // 2, prev_c))
-                        self._bufs.append(big)
-                        src0 = big
-                srcs = [dict(data=src0, ld=prev_c, mode=mode, sel=sel), dict(data=skips[i][0], ld=skips[i][1])]
-                if not net.skips2:
-                    srcs = srcs[:1]
-            pk = dict(tap_label=self.labels[l], row_scale=self.pnorm[l]) if partial else {}
+            srcs = sources(i, blk, prev)
+            pk = dict(tap_label=self.labels[l], row_scale=self.pnorm[l]) if c.partial else {}
             # the fused head lives in the halo kernel, which gathers a guided/nearest x2 source only together with the tap mask
-            fused = self.fuse_heads and i == 4 and (partial or not fuse_upsample or net.bilinear[3])
+            fused = self.fuse_heads and i == 4 and (c.partial or not fuse_upsample or blk.upsample == "guided_bilinear")
             self.fuse_head2 = fused if i == 4 else False
             if fused:  # block 10 + pv_final_conv_vertex in one launch
-                L[name].attach_head(net.params["pv_final_conv_vertex.kernel"])
-                conv(L[name], in_h=hs[l], in_w=ws[l], pad=1, srcs=srcs, scale=tab[0], shift=tab[1], epi_label=self.labels[l],
-                     act=_lib.ACT_LEAKY01, head_out=self.img4, head_out_ld=self.out_ld, **pk)
-                self._out_bound.append((L[name], K, "head_out"))
+                L[c.name].attach_head(net.params[g.ver_head.key])
+                conv(c, in_h=hs[l], in_w=ws[l], srcs=srcs, scale=tab[0], shift=tab[1], epi_label=self.labels[l],
+                     act=blk.act, head_out=self.img4, head_out_ld=self.out_ld, **pk)
+                self._out_bound.append((L[c.name], K, "head_out"))
             else:
-                conv(L[name], in_h=hs[l], in_w=ws[l], pad=1, srcs=srcs, scale=tab[0], shift=tab[1], epi_label=self.labels[l],
-                     act=_lib.ACT_RELU if i == 0 else _lib.ACT_LEAKY01, out_act=o, **pk)
+                conv(c, in_h=hs[l], in_w=ws[l], srcs=srcs, scale=tab[0], shift=tab[1], epi_label=self.labels[l],
+                     act=blk.act, out_act=o, **pk)
             self._bufs.append(o)
-            prev, prev_c = o, dims[i]
+            prev = o
         if not self.fuse_head2:
-            ver_head = L["pv_final_conv_vertex"]
-            conv(ver_head, in_h=h, in_w=w, srcs=[dict(data=prev, ld=prev_c)], out_raw=self.img4, out_raw_ld=self.out_ld)
-            self._out_bound.append((ver_head, K, "out_raw"))
+            conv(g.ver_head, in_h=h, in_w=w, srcs=[dict(data=prev, ld=g.ver_head.sources[0][0])], out_raw=self.img4, out_raw_ld=self.out_ld)
+            self._out_bound.append((L[g.ver_head.name], K, "out_raw"))
         self._whole_records(L, K, B * h * w, new)
         self._bind_winograd()
 
@@ -1077,31 +1043,24 @@ class ForwardPlan:
             out[conv.name] = (amax, amax)
         return out
 
-    def _bilinear_step(self, src, dst, sh, sw, c):
+    def _upsample_step(self, kind: str, src: torch.Tensor, dst: torch.Tensor, l: int, c: int):
+        """a materialised x2 upsampling of src into dst (level l) -- kind as architecture.Block.upsample"""
         lib = _lib.load()
-        B = self.batch
+        B, sh, sw = self.batch, self.h >> (l + 1), self.w >> (l + 1)
+        if kind == "bilinear":
+            def step(stream):
+                check(lib.cp_upsample_bilinear_x2_f32(src.data_ptr(), B, sh, sw, c, dst.data_ptr(), stream), "cp_upsample_bilinear_x2_f32")
+        elif kind == "guided_bilinear":
+            mask = self.gmask[l]
 
-        def step(stream):
-            check(lib.cp_upsample_bilinear_x2_f32(src.data_ptr(), B, sh, sw, c, dst.data_ptr(), stream), "cp_upsample_bilinear_x2_f32")
+            def step(stream):
+                check(lib.cp_guided_bilinear_upsample_x2_f32(src.data_ptr(), mask.data_ptr(), B, sh, sw, c, dst.data_ptr(), stream),
+                      "cp_guided_bilinear_upsample_x2_f32")
+        else:
+            sel = self.sel[l] if kind == "guided" else self.sel_zero[l]
 
-        return step
-
-    def _guided_bilinear_step(self, src, mask, dst, sh, sw, c):
-        lib = _lib.load()
-        B = self.batch
-
-        def step(stream):
-            check(lib.cp_guided_bilinear_upsample_x2_f32(src.data_ptr(), mask.data_ptr(), B, sh, sw, c, dst.data_ptr(), stream), "cp_guided_bilinear_upsample_x2_f32")
-
-        return step
-
-    def _guided_step(self, src, sel, dst, sh, sw, c):
-        lib = _lib.load()
-        B = self.batch
-
-        def step(stream):
-            check(lib.cp_guided_upsample_x2_f32(src.data_ptr(), sel.data_ptr(), B, sh, sw, c, dst.data_ptr(), stream), "cp_guided_upsample_x2_f32")
-
+            def step(stream):
+                check(lib.cp_guided_upsample_x2_f32(src.data_ptr(), sel.data_ptr(), B, sh, sw, c, dst.data_ptr(), stream), "cp_guided_upsample_x2_f32")
         return step
 
     def conv_flops(self) -> float:
@@ -1175,7 +1134,7 @@ class ForwardPlan:
             for step in self.steps:
                 step(stream)
             self._since_monitor += 1
-        if self.net.pvnet:
+        if self.net.arch.pvnet:
             _LABEL_CACHE.pop(out.untyped_storage().data_ptr(), None)
             return out
         if seg_input is None:  # labels[0] is the arg-max of THIS output's logits
@@ -1191,22 +1150,16 @@ class CasaposeNet:
     def __init__(self, params: Dict[str, np.ndarray], seg_dim: int, ver_dim: int, device: torch.device,
                  decoder_dims: Sequence[int] = DECODER_DIMS_DEFAULT, fuse_upsample: bool = True, fuse_heads: bool = True,
                  partial: Sequence[bool] = PARTIAL_DEFAULT, guided: Sequence[bool] = GUIDED_DEFAULT, use_winograd: bool = True,
-                 bilinear: Sequence[bool] = BILINEAR_DEFAULT, pvnet: bool = False, shared: Sequence[bool] = (False,) * 5,
-                 reuse_first: bool = False, skips2: bool = True, conv_mode: Optional[str] = None, f16x2_guard: Optional[bool] = None):
+                 bilinear: Sequence[bool] = BILINEAR_DEFAULT, pvnet: bool = False, shared: Sequence[bool] = SHARED_DEFAULT,
+                 reuse_first: bool = False, skips2: bool = True, conv_mode: Optional[str] = None, f16x2_guard: Optional[bool] = None,
+                 arch: Optional[Arch] = None):
         _lib.load()  # fail loudly if the HIP library is missing
         if device.type != "cuda":
             raise _lib.CasaposeHipError("casapose_amd runs on a ROCm GPU only (got device %s); there is no CPU fallback" % device)
         self.device = device
-        self.seg_dim, self.ver_dim = seg_dim, ver_dim
-        self.decoder_dims = tuple(decoder_dims)
-        self.partial, self.guided = tuple(bool(v) for v in partial), tuple(bool(v) for v in guided)
-        self.bilinear = tuple(bool(v) for v in bilinear)
-        self.pvnet = bool(pvnet)  # PVNet (pose_models.py:645-696): decoder 1 only, ONE 1x1 head producing seg + vertex channels
-        # weight sharing between the decoders (pose_models.py:699-1362, the `_sw*` registry entries): shared[i] -- blocks i+1 and i+6
-        # use the PartialConvolution weights pv_block_{i+1}_{i+6}_conv2d; reuse_first -- block 6 normalises the raw output of block
-        # 1's convolution instead of convolving; skips2 False -- decoder 2 has no skip connections
-        self.shared = tuple(bool(v) for v in shared)
-        self.reuse_first, self.skips2 = bool(reuse_first), bool(skips2)
+        self.arch = arch or Arch(seg_dim, ver_dim, decoder_dims, partial, guided, bilinear, pvnet, shared, reuse_first, skips2)
+        self.graph = graph(self.arch)
+        self.seg_dim, self.ver_dim = self.arch.seg_dim, self.arch.ver_dim
         self.fuse_upsample = fuse_upsample
         self.fuse_heads = fuse_heads
         self.use_winograd = use_winograd and os.environ.get("CASAPOSE_NO_WINOGRAD", "0") != "1"
@@ -1242,65 +1195,24 @@ class CasaposeNet:
         def put(name, pair):
             tabs[name] = tuple(torch.from_numpy(np.ascontiguousarray(a)).to(dev) for a in pair)
 
-        put("bn_data", fold_bn(p, "bn_data", pad_to=4))
-        put("bn0", fold_bn(p, "bn0"))
-        put("bn1", fold_bn(p, "bn1"))
-        for s in range(4):
-            for u in range(2):
-                base = "stage%d_unit%d_" % (s + 1, u + 1)
-                put(base + "bn1", fold_bn(p, base + "bn1"))
-                put(base + "bn2", fold_bn(p, base + "bn2"))
-        for i in range(5):
-            put("pv_block_%d_bn" % (i + 1), fold_bn(p, "pv_block_%d_bn" % (i + 1)))
-            if not self.pvnet:
-                put("pv_block_%d_clade" % (i + 6), fold_clade(p, "pv_block_%d_clade" % (i + 6)))
+        g = self.graph
+        norms = [g.bn_data, g.bn0] + [n for u in g.units for n in (u.bn1, u.bn2)] + [g.bn1] + [b.norm for b in g.decoder1 + g.decoder2]
+        for n in norms:
+            put(n.name, fold_clade(p, n.name) if n.clade else fold_bn(p, n.name, pad_to=4 if n is g.bn_data else None))
         self.device_tables = tabs
 
         L: Dict[str, FusedConv] = {}
         Wn: Dict[str, WinoConv] = {}
-
-        def add(name, key, layout, k, cout, sources, stride=1, dil=1, pad=None, partial=False):
-            L[name] = FusedConv(name, p[key], layout, k, k, cout, sources, dev, want_split=bool(self.conv_planes))
-            pad = dil * (k // 2) if pad is None else pad
-            planes = 2 if self.conv_mode == "bf16" else (self.conv_planes if self.conv_mode in ("split", "f16x2") and not WINO_GEMM_F32 else None)
-            if self.use_winograd and not partial and wino_eligible(k, stride, dil, pad, sources, cout, split_gemm=bool(planes) or WINO_GEMM_SPLIT, f16x2=self.conv_mode == "f16x2"):
-                Wn[name] = WinoConv(name, p[key] if layout == 0 else np.transpose(p[key], (1, 2, 0, 3)), cout, sources, dev, split_planes=planes)
-
-        add("conv0", "conv0.kernel", 0, 7, 64, [(4, 3)])
-        cin = 64
-        for s, f in enumerate(STAGE_FILTERS):
-            for u in range(2):
-                base = "stage%d_unit%d_" % (s + 1, u + 1)
-                st_, dl_ = (STAGE_STRIDE[s] if u == 0 else 1), STAGE_DILATION[s]
-                if u == 0:
-                    add(base + "sc", base + "sc.kernel", 0, 1, f, [(cin, cin)], stride=st_)
-                add(base + "conv1", base + "conv1.kernel", 0, 3, f, [(cin, cin)], stride=st_, dil=dl_)
-                add(base + "conv2", base + "conv2.kernel", 0, 3, f, [(f, f)], dil=dl_)
-                cin = f
-        dims = self.decoder_dims
-        skip_c = [None, (128, 128), (64, 64), (64, 64), (4, 3)]
-        for i in range(5):
-            srcs = [(512, 512)] if i == 0 else [(dims[i - 1], dims[i - 1]), skip_c[i]]
-            shared_key = "pv_block_%d_%d_conv2d.weights" % (i + 1, i + 6)
-            if self.shared[i]:  # one-input PartialConvolution = ordinary SAME conv with [Cin,3,3,Cout] weights
-                add("pv_block_%d_conv2d" % (i + 1), shared_key, 1, 3, dims[i], srcs)
-            else:
-                add("pv_block_%d_conv2d" % (i + 1), "pv_block_%d_conv2d.kernel" % (i + 1), 0, 3, dims[i], srcs)
-            if self.pvnet or (i == 0 and self.reuse_first):
+        planes = 2 if self.conv_mode == "bf16" else (self.conv_planes if self.conv_mode in ("split", "f16x2") and not WINO_GEMM_F32 else None)
+        convs = [g.conv0] + [c for u in g.units for c in (u.sc, u.conv1, u.conv2)] + [b.conv for b in g.decoder1 + g.decoder2] + [g.seg_head, g.ver_head]
+        for c in convs:
+            if c is None:
                 continue
-            srcs2 = srcs if (self.skips2 or i == 0) else [(dims[i - 1], dims[i - 1])]
-            name2 = ("pv_block_%d_prepare_conv2d" if self.partial[i] else "pv_block_%d_conv2d") % (i + 6)
-            if self.shared[i]:
-                add(name2, shared_key, 1, 3, dims[i], srcs2, partial=self.partial[i])
-            elif self.partial[i]:
-                add(name2, "pv_block_%d_prepare_conv2d.weights" % (i + 6), 1, 3, dims[i], srcs2, partial=True)
-            else:
-                add(name2, "pv_block_%d_conv2d.kernel" % (i + 6), 0, 3, dims[i], srcs2)
-        if self.pvnet:
-            add("pv_final_conv", "pv_final_conv.kernel", 0, 1, self.seg_dim + self.ver_dim, [(dims[4], dims[4])])
-        else:
-            add("pv_final_conv_segmentation", "pv_final_conv_segmentation.kernel", 0, 1, self.seg_dim, [(dims[4], dims[4])])
-            add("pv_final_conv_vertex", "pv_final_conv_vertex.kernel", 0, 1, self.ver_dim, [(dims[4], dims[4])])
+            w = p[c.key]
+            L[c.name] = FusedConv(c.name, w, c.layout, c.k, c.k, c.cout, c.sources, dev, want_split=bool(self.conv_planes))
+            if self.use_winograd and not c.partial and wino_eligible(c.k, c.stride, c.dilation, c.pad, c.sources, c.cout, split_gemm=bool(planes) or WINO_GEMM_SPLIT,
+                                                                      f16x2=self.conv_mode == "f16x2"):
+                Wn[c.name] = WinoConv(c.name, w if c.layout == 0 else np.transpose(w, (1, 2, 0, 3)), c.cout, c.sources, dev, split_planes=planes)
         self.layers_by_name = L
         self.wino_by_name = Wn
         self.plans.clear()

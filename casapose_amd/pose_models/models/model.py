@@ -11,7 +11,7 @@ from typing import Dict, List, Optional, Sequence
 import numpy as np
 import torch
 
-from ... import engine
+from ... import architecture, engine
 from ... import train_engine
 from ...utils import h5_weights
 
@@ -22,62 +22,44 @@ def _he_uniform(rng, shape, fan_in):
 
 
 def initial_parameters(seg_dim: int, ver_dim: int, dims: Sequence[int], seed: Optional[int] = None,
-                       partial: Sequence[bool] = engine.PARTIAL_DEFAULT, pvnet: bool = False, shared: Sequence[bool] = (False,) * 5,
-                       reuse_first: bool = False, skips2: bool = True) -> Dict[str, np.ndarray]:
+                       partial: Sequence[bool] = architecture.PARTIAL_DEFAULT, pvnet: bool = False, shared: Sequence[bool] = architecture.SHARED_DEFAULT,
+                       reuse_first: bool = False, skips2: bool = True, arch: Optional[architecture.Arch] = None) -> Dict[str, np.ndarray]:
     """Keras-default initial state: he_uniform kernels (resnet.py:31; _normalization_layers.py:317),
     BN gamma 1 / beta 0 / moving mean 0 / moving variance 1, CLADE gamma 1 / beta 0
-    (_normalization_layers.py:96-107).  Keys are `<keras layer name>.<weight>`."""
+    (_normalization_layers.py:96-107).  Keys are `<keras layer name>.<weight>`, in the Keras layer order (model.layers and the HDF5
+    writer follow it): per unit the kernels before the normalisations, each decoder-1 block followed by its decoder-2 partner."""
+    if arch is None:
+        arch = architecture.Arch(seg_dim, ver_dim, dims, partial, pvnet=pvnet, shared=shared, reuse_first=reuse_first, skips2=skips2)
+    g = architecture.graph(arch)
     rng = np.random.default_rng(seed)
     p: Dict[str, np.ndarray] = {}
 
-    def bn(name, c, gamma=True, beta=True):
-        if gamma:
-            p[name + ".gamma"] = np.ones(c, np.float32)
-        if beta:
-            p[name + ".beta"] = np.zeros(c, np.float32)
-        p[name + ".moving_mean"] = np.zeros(c, np.float32)
-        p[name + ".moving_variance"] = np.ones(c, np.float32)
+    def conv(c: Optional[architecture.Conv]):
+        if c is not None and c.key not in p:   # (a shared weight set is drawn once, by decoder 1)
+            p[c.key] = _he_uniform(rng, c.shape, c.k * c.k * c.cin)
 
-    p["conv0.kernel"] = _he_uniform(rng, (7, 7, 3, 64), 147)
-    bn("bn_data", 3, gamma=False)
-    bn("bn0", 64)
-    cin = 64
-    for s, f in enumerate(engine.STAGE_FILTERS):
-        for u in range(2):
-            base = "stage%d_unit%d_" % (s + 1, u + 1)
-            if u == 0:
-                p[base + "sc.kernel"] = _he_uniform(rng, (1, 1, cin, f), cin)
-            p[base + "conv1.kernel"] = _he_uniform(rng, (3, 3, cin, f), 9 * cin)
-            p[base + "conv2.kernel"] = _he_uniform(rng, (3, 3, f, f), 9 * f)
-            bn(base + "bn1", cin)
-            bn(base + "bn2", f)
-            cin = f
-    bn("bn1", 512)
-    dec_in = (512, dims[0] + 128, dims[1] + 64, dims[2] + 64, dims[3] + 3)
-    for i in range(5):
-        ci, co = dec_in[i], dims[i]
-        if shared[i]:  # one PartialConvolution for blocks i+1 and i+6 (pose_models.py:727-731)
-            p["pv_block_%d_%d_conv2d.weights" % (i + 1, i + 6)] = _he_uniform(rng, (ci, 3, 3, co), 9 * ci)
-        else:
-            p["pv_block_%d_conv2d.kernel" % (i + 1)] = _he_uniform(rng, (3, 3, ci, co), 9 * ci)
-        bn("pv_block_%d_bn" % (i + 1), co)
-        if pvnet:
-            continue
-        ci2 = ci if (skips2 or i == 0) else dims[i - 1]
-        if shared[i] or (i == 0 and reuse_first):
-            pass  # no convolution weights of its own
-        elif partial[i]:
-            p["pv_block_%d_prepare_conv2d.weights" % (i + 6)] = _he_uniform(rng, (ci2, 3, 3, co), 9 * ci2)
-        else:  # ordinary pad + Conv2D in decoder 2 (casapose.py:69-74)
-            p["pv_block_%d_conv2d.kernel" % (i + 6)] = _he_uniform(rng, (3, 3, ci2, co), 9 * ci2)
-        bn("pv_block_%d_clade" % (i + 6), co, gamma=False, beta=False)
-        p["pv_block_%d_clade.gamma" % (i + 6)] = np.ones((seg_dim, co), np.float32)
-        p["pv_block_%d_clade.beta" % (i + 6)] = np.zeros((seg_dim, co), np.float32)
-    if pvnet:  # PVNet: one head for segmentation + vector field (pose_models.py:678)
-        p["pv_final_conv.kernel"] = _he_uniform(rng, (1, 1, dims[4], seg_dim + ver_dim), dims[4])
-        return p
-    p["pv_final_conv_segmentation.kernel"] = _he_uniform(rng, (1, 1, dims[4], seg_dim), dims[4])
-    p["pv_final_conv_vertex.kernel"] = _he_uniform(rng, (1, 1, dims[4], ver_dim), dims[4])
+    def norm(n: architecture.Norm):   # BN: gamma, beta, moving statistics; CLADE: moving statistics, then the [seg_dim, C] tables
+        tab = (arch.seg_dim, n.channels) if n.clade else n.channels
+        affine = dict(([("gamma", np.ones(tab))] if n.gamma else []) + ([("beta", np.zeros(tab))] if n.beta else []))
+        stats = dict(moving_mean=np.zeros(n.channels), moving_variance=np.ones(n.channels))
+        for k, v in (dict(stats, **affine) if n.clade else dict(affine, **stats)).items():
+            p[n.name + "." + k] = v.astype(np.float32)
+
+    conv(g.conv0)
+    norm(g.bn_data)
+    norm(g.bn0)
+    for u in g.units:
+        for c in (u.sc, u.conv1, u.conv2):
+            conv(c)
+        norm(u.bn1)
+        norm(u.bn2)
+    norm(g.bn1)
+    for i, b1 in enumerate(g.decoder1):
+        for b in (b1,) + g.decoder2[i:i + 1]:
+            conv(b.conv)
+            norm(b.norm)
+    conv(g.seg_head)
+    conv(g.ver_head)
     return p
 
 
@@ -109,9 +91,9 @@ class Layer:
 class CasaposeModel:
     def __init__(self, name: str, ver_dim: int, seg_dim: int, dims: Sequence[int], input_shape=None,
                  input_segmentation_shape=None, weights=None, output_lablemap: bool = False, device=None, seed=None,
-                 fuse_upsample: bool = True, fuse_heads: bool = True, partial: Sequence[bool] = engine.PARTIAL_DEFAULT,
-                 guided: Sequence[bool] = engine.GUIDED_DEFAULT, bilinear: Sequence[bool] = engine.BILINEAR_DEFAULT, pvnet: bool = False,
-                 shared: Sequence[bool] = (False,) * 5, reuse_first: bool = False, skips2: bool = True, conv_mode: Optional[str] = None,
+                 fuse_upsample: bool = True, fuse_heads: bool = True, partial: Sequence[bool] = architecture.PARTIAL_DEFAULT,
+                 guided: Sequence[bool] = architecture.GUIDED_DEFAULT, bilinear: Sequence[bool] = architecture.BILINEAR_DEFAULT, pvnet: bool = False,
+                 shared: Sequence[bool] = architecture.SHARED_DEFAULT, reuse_first: bool = False, skips2: bool = True, conv_mode: Optional[str] = None,
                  f16x2_guard: Optional[bool] = None):
         self.output_lablemap = bool(output_lablemap)
         self.name = name
@@ -122,20 +104,16 @@ class CasaposeModel:
         if device is None:
             device = torch.device("cuda", torch.cuda.current_device()) if torch.cuda.is_available() else torch.device("cpu")
         self.device = torch.device(device)
-        self._dims = tuple(dims)
         if isinstance(weights, str) and weights == "imagenet":
             warnings.warn("weights='imagenet': the reference downloads ImageNet ResNet-18 weights (weights.py:13-39); "
                           "no network here -- using he_uniform initialisation; call load_weights() for real weights")
             weights = None
-        self._partial, self._guided = tuple(bool(v) for v in partial), tuple(bool(v) for v in guided)
-        self._bilinear = tuple(bool(v) for v in bilinear)
-        self._pvnet = bool(pvnet)
-        if self._pvnet and self.input_segmentation_shape is not None:
+        self.arch = architecture.Arch(self.seg_dim, self.ver_dim, dims, partial, guided, bilinear, pvnet, shared, reuse_first, skips2)
+        if self.arch.pvnet and self.input_segmentation_shape is not None:
             raise ValueError("PVNet has no data_segmentation input")
-        self._sharing = dict(shared=tuple(bool(v) for v in shared), reuse_first=bool(reuse_first), skips2=bool(skips2))
-        self._params = initial_parameters(self.seg_dim, self.ver_dim, self._dims, seed, self._partial, self._pvnet, **self._sharing)
-        self._net = engine.CasaposeNet(self._params, self.seg_dim, self.ver_dim, self.device, self._dims, fuse_upsample, fuse_heads,
-                                       self._partial, self._guided, bilinear=self._bilinear, pvnet=self._pvnet, conv_mode=conv_mode, f16x2_guard=f16x2_guard, **self._sharing)
+        self._params = initial_parameters(self.seg_dim, self.ver_dim, dims, seed, arch=self.arch)
+        self._net = engine.CasaposeNet(self._params, self.seg_dim, self.ver_dim, self.device, fuse_upsample=fuse_upsample, fuse_heads=fuse_heads,
+                                       conv_mode=conv_mode, f16x2_guard=f16x2_guard, arch=self.arch)
         self._store: Optional[train_engine.ParamStore] = None   # training state (flat master weights + Adam moments)
         self._plan: Optional[train_engine.TrainPlan] = None
         self._params_stale = False                               # the store holds newer weights than self._params
@@ -151,8 +129,7 @@ class CasaposeModel:
             self._store = train_engine.ParamStore(self._params, self.device)
         p = self._plan
         if p is None or (p.batch, p.h, p.w) != (batch, h, w) or p.group is not group:
-            self._plan = train_engine.TrainPlan(self._store, self.seg_dim, self.ver_dim, batch, h, w, self._dims, group, world_size,
-                                                self._partial, self._guided, bilinear=self._bilinear, pvnet=self._pvnet, **self._sharing)
+            self._plan = train_engine.TrainPlan(self._store, self.seg_dim, self.ver_dim, batch, h, w, group=group, world_size=world_size, arch=self.arch)
             self._plan.refresh_weights(torch.cuda.current_stream(self.device).cuda_stream)
         return self._plan, self.device
 

@@ -34,7 +34,8 @@ import torch
 
 from . import _lib, engine, parallel
 from ._lib import ConvDesc, check
-from .engine import BILINEAR_DEFAULT, BN_EPS, DECODER_DIMS_DEFAULT, GUIDED_DEFAULT, PARTIAL_DEFAULT, STAGE_DILATION, STAGE_FILTERS, STAGE_STRIDE
+from .architecture import BILINEAR_DEFAULT, DECODER_DIMS_DEFAULT, GUIDED_DEFAULT, PARTIAL_DEFAULT, SHARED_DEFAULT, Arch, forward_order, graph  # noqa: F401
+from .engine import BN_EPS
 from .f16x2_range import BackwardRange, BwdSlot, SlotBuffer, armed, decode
 
 BN_MOMENTUM = 0.99  # resnet.py:43 (Keras default elsewhere)
@@ -47,24 +48,6 @@ def _ptr(t):
 # ------------------------------------------------------------------------------------------------
 # parameters
 # ------------------------------------------------------------------------------------------------
-def forward_order() -> List[str]:
-    """Layer names in the order the forward uses them (resnet.py:246-305; pose_models.py:541-616).  The flat parameter buffer follows
-    this order, so the backward completes it from the END towards the start and gradient buckets are contiguous tail slices."""
-    order = ["bn_data", "conv0", "bn0"]
-    for s in range(1, 5):
-        for u in range(1, 3):
-            base = "stage%d_unit%d_" % (s, u)
-            order += [base + "bn1", base + "sc", base + "conv1", base + "bn2", base + "conv2"]
-    order.append("bn1")
-    for i in range(1, 6):
-        order += ["pv_block_%d_conv2d" % i, "pv_block_%d_%d_conv2d" % (i, i + 5), "pv_block_%d_bn" % i]
-    order += ["pv_final_conv_segmentation", "pv_final_conv"]
-    for i in range(6, 11):
-        order += ["pv_block_%d_prepare_conv2d" % i, "pv_block_%d_conv2d" % i, "pv_block_%d_clade" % i]
-    order.append("pv_final_conv_vertex")
-    return order
-
-
 # gradient buckets = groups of consecutive layers whose all-reduce is launched as soon as the backward has passed them
 BUCKET_STARTS = ("bn_data", "stage4_unit1_bn1", "pv_block_1_conv2d", "pv_block_6_prepare_conv2d")
 
@@ -1157,7 +1140,9 @@ class TrainPlan:
     def __init__(self, store: ParamStore, seg_dim: int, ver_dim: int, batch: int, h: int, w: int,
                  decoder_dims: Sequence[int] = DECODER_DIMS_DEFAULT, group=None, world_size: int = 1,
                  partial: Sequence[bool] = PARTIAL_DEFAULT, guided: Sequence[bool] = GUIDED_DEFAULT, bilinear: Sequence[bool] = BILINEAR_DEFAULT,
-                 pvnet: bool = False, shared: Sequence[bool] = (False,) * 5, reuse_first: bool = False, skips2: bool = True):
+                 pvnet: bool = False, shared: Sequence[bool] = SHARED_DEFAULT, reuse_first: bool = False, skips2: bool = True, arch: Optional[Arch] = None):
+        arch = arch or Arch(seg_dim, ver_dim, decoder_dims, partial, guided, bilinear, pvnet, shared, reuse_first, skips2)
+        seg_dim, ver_dim, pvnet = arch.seg_dim, arch.ver_dim, arch.pvnet
         if h % 8 or w % 8:
             raise ValueError("input height/width must be multiples of 8 (got %dx%d)" % (h, w))
         if seg_dim > 32 or (ver_dim > 32 and not pvnet):
@@ -1165,7 +1150,7 @@ class TrainPlan:
         lib = _lib.load()
         self.store, self.seg_dim, self.ver_dim = store, seg_dim, ver_dim
         self.batch, self.h, self.w = batch, h, w
-        self.pvnet = bool(pvnet)
+        self.arch, self.pvnet = arch, pvnet
         if self.pvnet:  # one merged head: its gradient row is the contiguous [seg | vertex] record
             if seg_dim + ver_dim > self.GRAD_LD:
                 # `pvnet` with SEPARATED vector fields (one 2*kp slice per object, train_casapose.py:57,97-125): a wider gradient row; a multiple
@@ -1190,7 +1175,6 @@ class TrainPlan:
         self.ops: List = []
         self.convs: List[TrainConv] = []
         store.pack_reset()  # this plan's kernel layouts share one arena (one gather per weight refresh)
-        dims = tuple(decoder_dims)
 
         def new(hh, ww, c, grad=True, name=""):
             return TT(torch.empty(B, hh, ww, c, **f32), grad, name)
@@ -1204,11 +1188,7 @@ class TrainPlan:
         self.pnorm = [torch.empty(B, hs[l], ws[l], **f32) for l in range(4)]
         self.sel = [torch.empty(B, hs[l], ws[l], **u8) for l in range(3)]
         self.sel_zero = [torch.zeros(B, hs[l], ws[l], **u8) for l in range(3)]  # plain nearest x2
-        self.partial, self.guided = tuple(bool(v) for v in partial), tuple(bool(v) for v in guided)
-        self.bilinear = tuple(bool(v) for v in bilinear)
-        # weight sharing between the decoders (the `_sw*` registry entries; see engine.CasaposeNet)
-        self.shared, self.reuse_first, self.skips2 = tuple(bool(v) for v in shared), bool(reuse_first), bool(skips2)
-        self.gmask = [torch.empty(B, hs[l], ws[l], **u8) if any(self.bilinear) else None for l in range(3)]
+        self.gmask = [torch.empty(B, hs[l], ws[l], **u8) if any(arch.bilinear) else None for l in range(3)]
         self.loss_sums = torch.zeros(3, dtype=torch.float64, device=dev)
         self.loss_ws = torch.empty(max(lib.cp_pose_loss_workspace_bytes(B, h, w), lib.cp_pose_loss_sep_workspace_bytes(B, h, w, K)), **u8)
         self.object_loss_values = torch.zeros(B, K - 1, **f32)  # per-object proxy distances (proxy_voting_dist)
@@ -1223,33 +1203,34 @@ class TrainPlan:
         self.ls_g = torch.zeros(B, oc, kp, 2, **f32)
         self.kp_loss_val = torch.zeros(1, dtype=torch.float64, device=dev)
 
-        def layer(key, layout, k, cout, sources, grad_sources):
-            L = TrainConv(store, key, layout, k, cout, sources, grad_sources)
+        def layer(rec, grad_sources):
+            L = TrainConv(store, rec.key, rec.layout, rec.k, rec.cout, rec.sources, grad_sources)
             self.convs.append(L)
             return L
 
-        def conv(L, srcs, o: TT, in_h, in_w, **kw):
-            op = ConvOp(L, srcs, (o.data, 0, o.c), B, in_h, in_w, out=o, **kw)
+        def conv(L, rec, srcs, o: TT, in_h, in_w, **kw):
+            op = ConvOp(L, srcs, (o.data, 0, o.c), B, in_h, in_w, stride=rec.stride, dilation=rec.dilation, pad=rec.pad, out=o, **kw)
             self.ops.append(op)
             return op
 
-        def bn(name, x, y, act, gamma=True, labels=None, classes=1, row_scale=None, pad_one=False, clade=False):
-            gk = (name + ".gamma") if gamma else None
-            self.ops.append(BnActOp(self, name, x, y, act, gk, name + ".beta", labels, classes, row_scale, pad_one))
+        def bn(norm, x, y, act, labels=None, row_scale=None, pad_one=False):
+            gk = (norm.name + ".gamma") if norm.gamma else None
+            self.ops.append(BnActOp(self, norm.name, x, y, act, gk, norm.name + ".beta", labels, K if norm.clade else 1, row_scale, pad_one))
 
         RELU, LEAKY, NONE = _lib.ACT_RELU, _lib.ACT_LEAKY01, _lib.ACT_NONE
+        g = graph(arch)
         # ---- encoder --------------------------------------------------------------------------------
         # bn_data has no gamma; its padding channel is forced to the constant 1 so that conv0's weight gradient
         # for that (zero-weight) channel is G[t][o] = sum of dy over the positions where tap t is inside the image:
         # d beta_data[c] = sum_{t,o} W0[t,c,o] * G[t][o] without a 7x7 transposed convolution for three numbers.
-        bn("bn_data", self.img4, self.x0, NONE, gamma=False, pad_one=True)
+        bn(g.bn_data, self.img4, self.x0, NONE, pad_one=True)
         self.bn_data_op = self.ops[-1]
-        c0 = layer("conv0.kernel", 0, 7, 64, [(4, 3)], [False])
+        c0 = layer(g.conv0, [False])
         self.conv0 = c0
         x = new(hs[1], ws[1], 64)
-        conv(c0, [(self.x0, 4)], x, h, w, stride=2, pad=3)
+        conv(c0, g.conv0, [(self.x0, 4)], x, h, w)
         x2s = new(hs[1], ws[1], 64, name="x2s")
-        bn("bn0", x, x2s, RELU)
+        bn(g.bn0, x, x2s, RELU)
         pooled = new(hs[2], ws[2], 64, name="pool")
 
         pool_idx = torch.empty(B, hs[2], ws[2], 64, dtype=torch.uint8, device=dev)   # arg-max tap per pooled element: the adjoint routes by it
@@ -1264,130 +1245,104 @@ class TrainPlan:
             src.has_grad = True
 
         self.ops.append(FnOp(pool_f, pool_b, reads=[x2s]))
-        xr, cur_h, cur_w, cin = pooled, hs[2], ws[2], 64
+        xr, cur_h, cur_w = pooled, hs[2], ws[2]
         taps: Dict[str, TT] = {"x2s": x2s}
-        tap_names = ["x4s", "x8s", "x16s", "x32s"]
-        for s, f in enumerate(STAGE_FILTERS):
-            dl = STAGE_DILATION[s]
-            for u in range(2):
-                base = "stage%d_unit%d_" % (s + 1, u + 1)
-                stride = STAGE_STRIDE[s] if u == 0 else 1
-                oh, ow = (cur_h - 1) // stride + 1, (cur_w - 1) // stride + 1
-                a = new(cur_h, cur_w, cin, name=base + "a")
-                bn(base + "bn1", xr, a, RELU)
-                if u == 0:
-                    if s > 0:
-                        taps[tap_names[s - 1]] = a
-                    sc = new(oh, ow, f, name=base + "sc")
-                    sc_layer = layer(base + "sc.kernel", 0, 1, f, [(cin, cin)], [True])
-                    shortcut = sc
-                else:
-                    shortcut = xr
-                t = new(oh, ow, f)
-                conv(layer(base + "conv1.kernel", 0, 3, f, [(cin, cin)], [True]), [(a, cin)], t, cur_h, cur_w, stride=stride, dilation=dl, pad=dl)
-                if u == 0:
-                    # the shortcut comes AFTER conv1 in the tape (both read `a`): the backward then runs its data gradient first, which lets the
-                    # GEMM route write `a.grad` plainly while conv1's data gradient, running after it, accumulates through its residual input
-                    conv(sc_layer, [(a, cin)], sc, cur_h, cur_w, stride=stride)
-                t2 = new(oh, ow, f)
-                bn(base + "bn2", t, t2, RELU)
-                xn = new(oh, ow, f, name=base + "out")
-                conv(layer(base + "conv2.kernel", 0, 3, f, [(f, f)], [True]), [(t2, f)], xn, oh, ow, dilation=dl, pad=dl, residual=shortcut)
-                xr, cur_h, cur_w, cin = xn, oh, ow, f
+        tap = None   # the backbone output the next unit's bn1 materialises
+        for u in g.units:
+            oh, ow = (cur_h - 1) // u.conv1.stride + 1, (cur_w - 1) // u.conv1.stride + 1
+            a = new(cur_h, cur_w, u.cin, name=u.base + "a")
+            bn(u.bn1, xr, a, RELU)
+            if tap:
+                taps[tap] = a
+            if u.sc is not None:
+                sc = new(oh, ow, u.cout, name=u.base + "sc")
+                sc_layer = layer(u.sc, [True])
+                shortcut = sc
+            else:
+                shortcut = xr
+            t = new(oh, ow, u.cout)
+            conv(layer(u.conv1, [True]), u.conv1, [(a, u.cin)], t, cur_h, cur_w)
+            if u.sc is not None:
+                # the shortcut comes AFTER conv1 in the tape (both read `a`): the backward then runs its data gradient first, which lets the
+                # GEMM route write `a.grad` plainly while conv1's data gradient, running after it, accumulates through its residual input
+                conv(sc_layer, u.sc, [(a, u.cin)], sc, cur_h, cur_w)
+            t2 = new(oh, ow, u.cout)
+            bn(u.bn2, t, t2, RELU)
+            xn = new(oh, ow, u.cout, name=u.base + "out")
+            conv(layer(u.conv2, [True]), u.conv2, [(t2, u.cout)], xn, oh, ow, residual=shortcut)
+            xr, cur_h, cur_w, tap = xn, oh, ow, u.tap
         x32s = new(cur_h, cur_w, 512, name="x32s")
-        bn("bn1", xr, x32s, RELU)
-        taps["x32s"] = x32s
+        bn(g.bn1, xr, x32s, RELU)
+        taps[tap] = x32s
         self.taps = taps
-        skips = [None, taps["x8s"], taps["x4s"], taps["x2s"], self.img4]
-        skip_c = [None, (128, 128), (64, 64), (64, 64), (4, 3)]
-        lvl = [3, 3, 2, 1, 0]
+        skips = dict(taps, img4=self.img4)
 
-        def upsample(prev: TT, l: int, guided: bool, selmap: Optional[torch.Tensor] = None, blend: bool = False) -> TT:
+        def upsample(prev: TT, l: int, kind: str) -> TT:
+            """the previous block's output at level l as the record's upsample says (architecture.Block.upsample), materialised"""
             big = new(hs[l], ws[l], prev.c)
             sh, sw, c = hs[l] // 2, ws[l] // 2, prev.c
-            selmap = self.sel[l] if selmap is None else selmap
+            selmap = self.sel[l] if kind == "guided" else self.sel_zero[l]   # plain nearest x2 = "guided" with neighbour 0 everywhere
+            blend, guided = kind == "guided_bilinear", kind in ("guided", "nearest")
 
             def f(stream):
+                x, y = prev.data.data_ptr(), big.data.data_ptr()
                 if blend:
-                    check(lib.cp_guided_bilinear_upsample_x2_f32(prev.data.data_ptr(), self.gmask[l].data_ptr(), B, sh, sw, c, big.data.data_ptr(), stream),
-                          "cp_guided_bilinear_upsample_x2_f32")
+                    check(lib.cp_guided_bilinear_upsample_x2_f32(x, self.gmask[l].data_ptr(), B, sh, sw, c, y, stream), "cp_guided_bilinear_upsample_x2_f32")
                 elif guided:
-                    check(lib.cp_guided_upsample_x2_f32(prev.data.data_ptr(), selmap.data_ptr(), B, sh, sw, c, big.data.data_ptr(), stream), "cp_guided_upsample_x2_f32")
+                    check(lib.cp_guided_upsample_x2_f32(x, selmap.data_ptr(), B, sh, sw, c, y, stream), "cp_guided_upsample_x2_f32")
                 else:
-                    check(lib.cp_upsample_bilinear_x2_f32(prev.data.data_ptr(), B, sh, sw, c, big.data.data_ptr(), stream), "cp_upsample_bilinear_x2_f32")
+                    check(lib.cp_upsample_bilinear_x2_f32(x, B, sh, sw, c, y, stream), "cp_upsample_bilinear_x2_f32")
 
             def b(stream):
                 assert big.has_grad and not prev.has_grad
+                dy, dx = big.grad.data_ptr(), prev.grad.data_ptr()
                 if blend:
-                    check(lib.cp_guided_bilinear_upsample_x2_bwd_f32(big.grad.data_ptr(), c, self.gmask[l].data_ptr(), B, sh, sw, c, prev.grad.data_ptr(), stream),
-                          "cp_guided_bilinear_upsample_x2_bwd_f32")
+                    check(lib.cp_guided_bilinear_upsample_x2_bwd_f32(dy, c, self.gmask[l].data_ptr(), B, sh, sw, c, dx, stream), "cp_guided_bilinear_upsample_x2_bwd_f32")
                 elif guided:
-                    check(lib.cp_guided_upsample_x2_bwd_f32(big.grad.data_ptr(), c, selmap.data_ptr(), B, sh, sw, c, prev.grad.data_ptr(), stream), "cp_guided_upsample_x2_bwd_f32")
+                    check(lib.cp_guided_upsample_x2_bwd_f32(dy, c, selmap.data_ptr(), B, sh, sw, c, dx, stream), "cp_guided_upsample_x2_bwd_f32")
                 else:
-                    check(lib.cp_upsample_bilinear_x2_bwd_f32(big.grad.data_ptr(), c, B, sh, sw, c, prev.grad.data_ptr(), stream), "cp_upsample_bilinear_x2_bwd_f32")
+                    check(lib.cp_upsample_bilinear_x2_bwd_f32(dy, c, B, sh, sw, c, dx, stream), "cp_upsample_bilinear_x2_bwd_f32")
                 prev.has_grad = True
 
             self.ops.append(FnOp(f, b, reads=[prev]))
             return big
 
-        def decoder(first: int, second: bool):
+        def decoder(blocks):
             prev = None
-            for i in range(5):
-                l = lvl[i]
-                idx = first + i
-                partial = second and self.partial[i]
-                act_kind = RELU if i == 0 else LEAKY
-                if second and i == 0 and self.reuse_first:  # casa_layer(y, "6", skip_conv=True): CLADE on block 1's raw convolution output
-                    act = new(hs[l], ws[l], dims[i])
-                    bn("pv_block_%d_clade" % idx, self._y_raw, act, act_kind, labels=self.labels[l], classes=K)
-                    prev = act
+            for i, blk in enumerate(blocks):
+                c, l = blk.conv, blk.level
+                labels = self.labels[l] if blk.norm.clade else None
+                if c is None:  # casa_layer(y, "6", skip_conv=True): CLADE on block 1's raw convolution output
+                    prev = new(hs[l], ws[l], blk.norm.channels)
+                    bn(blk.norm, self._y_raw, prev, blk.act, labels)
                     continue
-                if self.shared[i]:  # one PartialConvolution weight set for blocks i+1 and i+6 ([Cin,3,3,Cout])
-                    key, layout = "pv_block_%d_%d_conv2d.weights" % (i + 1, i + 6), 1
-                elif partial:
-                    key, layout = "pv_block_%d_prepare_conv2d.weights" % idx, 1
-                else:
-                    key, layout = "pv_block_%d_conv2d.kernel" % idx, 0
                 if i == 0:
-                    srcs, tts, gs = [(512, 512)], [(x32s, 512)], [True]
-                else:
-                    if i >= 2:  # the previous block upsampled its output: bilinear (decoder 1), label-guided or plain nearest (decoder 2)
-                        src0 = upsample(prev, l, second, None if (not second or self.guided[i - 1]) else self.sel_zero[l],
-                                        blend=second and self.guided[i - 1] and self.bilinear[i - 1])
-                    else:
-                        src0 = prev
-                    srcs = [(dims[i - 1], dims[i - 1]), skip_c[i]]
-                    tts = [(src0, dims[i - 1]), (skips[i], skips[i].c)]
-                    gs = [True, skips[i].needs_grad]
-                    if second and not self.skips2:
-                        srcs, tts, gs = srcs[:1], tts[:1], gs[:1]
-                L = layer(key, layout, 3, dims[i], srcs, gs)
-                raw = new(hs[l], ws[l], dims[i])
-                act = new(hs[l], ws[l], dims[i])
-                if not second and i == 0:
+                    tts, gs = [(x32s, 512)], [True]
+                else:   # the previous block's output, upsampled: bilinear (decoder 1), label-guided or plain nearest (decoder 2)
+                    tts, gs = [(prev if blk.upsample == "none" else upsample(prev, l, blk.upsample), c.sources[0][0])], [True]
+                    if blk.skip:
+                        tts.append((skips[blk.skip], c.sources[1][0]))
+                        gs.append(skips[blk.skip].needs_grad)
+                L = layer(c, gs)
+                raw = new(hs[l], ws[l], c.cout)
+                act = new(hs[l], ws[l], c.cout)
+                if blk.number == 1:
                     self._y_raw = raw
-                if partial:
-                    conv(L, tts, raw, hs[l], ws[l], pad=1, tap_label=self.labels[l], row_scale=self.pnorm[l])
-                    bn("pv_block_%d_clade" % idx, raw, act, act_kind, labels=self.labels[l], classes=K, row_scale=self.pnorm[l])
-                elif second:
-                    conv(L, tts, raw, hs[l], ws[l], pad=1)
-                    bn("pv_block_%d_clade" % idx, raw, act, act_kind, labels=self.labels[l], classes=K)
-                else:
-                    conv(L, tts, raw, hs[l], ws[l], pad=1)
-                    bn("pv_block_%d_bn" % idx, raw, act, act_kind)
+                pk = dict(tap_label=self.labels[l], row_scale=self.pnorm[l]) if c.partial else {}
+                conv(L, c, tts, raw, hs[l], ws[l], **pk)
+                bn(blk.norm, raw, act, blk.act, labels, pk.get("row_scale"))
                 prev = act
             return prev
 
-        feat1 = decoder(1, False)
-        self.cond_labels = None
-        if self.pvnet:  # PVNet (pose_models.py:645-696)
-            head = layer("pv_final_conv.kernel", 0, 1, K + V, [(dims[4], dims[4])], [True])
-            self.ops.append(ConvOp(head, [(feat1, dims[4])], (self.out, 0, self.out_ld), B, h, w, out=None, dy_ptr_ld=(self.dout, 0, self.GRAD_LD)))
+        def head(rec, feat, off, dy_off):
+            self.ops.append(ConvOp(layer(rec, [True]), [(feat, rec.sources[0][0])], (self.out, off, self.out_ld), B, h, w, out=None,
+                                   dy_ptr_ld=(self.dout, dy_off, self.GRAD_LD)))
+
+        head(g.seg_head, decoder(g.decoder1), 0, 0)   # (PVNet: the one head, pose_models.py:645-696)
+        self.cond_labels: Optional[torch.Tensor] = None  # ground-truth conditioning (train_vectors_with_ground_truth)
+        if self.pvnet:
             self._finish_plan(f32)
             return
-        seg_head = layer("pv_final_conv_segmentation.kernel", 0, 1, K, [(dims[4], dims[4])], [True])
-        self.ops.append(ConvOp(seg_head, [(feat1, dims[4])], (self.out, 0, self.out_ld), B, h, w, out=None, dy_ptr_ld=(self.dout, 0, self.GRAD_LD)))
-        self.cond_labels: Optional[torch.Tensor] = None  # ground-truth conditioning (train_vectors_with_ground_truth)
 
         def label_f(stream):
             if self.cond_labels is not None:
@@ -1395,19 +1350,10 @@ class TrainPlan:
             else:
                 logits, ld_ = (self.seg_dense, K) if getattr(self, "seg_dense", None) is not None else (self.out, self.out_ld)
                 check(lib.cp_argmax_labels(logits.data_ptr(), ld_, K, B * h * w, self.labels[0].data_ptr(), stream), "cp_argmax_labels")
-            lab = (C.c_void_p * 4)(*[t.data_ptr() for t in self.labels])
-            pn = (C.c_void_p * 4)(*[t.data_ptr() for t in self.pnorm])
-            sl = (C.c_void_p * 3)(*[t.data_ptr() for t in self.sel])
-            check(lib.cp_label_pyramid(self.labels[0].data_ptr(), B, h, w, lab, pn, sl, stream), "cp_label_pyramid")
-            for l_ in range(3):
-                if self.gmask[l_] is not None:
-                    check(lib.cp_guided_match_mask(self.labels[l_].data_ptr(), self.labels[l_ + 1].data_ptr(), B, hs[l_], ws[l_], self.gmask[l_].data_ptr(), stream),
-                          "cp_guided_match_mask")
+            engine.label_pyramid(self.labels, self.pnorm, self.sel, self.gmask, B, h, w, stream)
 
         self.ops.append(FnOp(label_f, lambda stream: None))
-        feat2 = decoder(6, True)
-        ver_head = layer("pv_final_conv_vertex.kernel", 0, 1, V, [(dims[4], dims[4])], [True])
-        self.ops.append(ConvOp(ver_head, [(feat2, dims[4])], (self.out, K, self.out_ld), B, h, w, out=None, dy_ptr_ld=(self.dout, self.VERT_OFF, self.GRAD_LD)))
+        head(g.ver_head, decoder(g.decoder2), K, self.VERT_OFF)
         self._finish_plan(f32)
 
     def _finish_plan(self, f32):
