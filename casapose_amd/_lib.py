@@ -255,6 +255,7 @@ SYMBOLS = [
     ("cp_aug_resize", _i, [_vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp]),
     ("cp_aug_channel_sums", _i, [_vp, _i, _ll, _vp, _vp]),
     ("cp_aug_finish", _i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp]),
+    ("cp_frames_to_input_f32", _i, [_vp, _i, _i, _i, _i, _ll, _ll, _f, _f, _vp, _vp]),
     ("cp_pose_loss_f32", _i, [_vp, _i, _i, _i, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _f, _f, _f, _vp, _vp, _i, _i, _vp, _vp, _vp]),
 ]
 

@@ -764,6 +764,15 @@ int cp_aug_channel_sums(const uint8_t* rgb, int batch, long long pixels, uint32_
 int cp_aug_finish(const uint8_t* rgb, const uint8_t* lab, const cp_aug_image* progs, const uint32_t* sums, int batch, int h, int w,
                   int classes, float* img, int32_t* filtered, float* target, void* stream);
 
+/* ---- input pipeline: inference frames (csrc/frames.hip) ------------------------------------------------------------------------
+ * Network input from decoded uint8 frames, the per-pixel half of ImageOnlyDataset.load_images (image_only_dataset.py:36-49; host side in
+ * casapose_amd/data_handler/image_only_dataset.py).  src: [batch][h][w][channels] uint8 with channels 1, 3 or 4, rows `src_pitch` bytes
+ * apart (>= w * channels), images `src_stride` bytes apart (>= h * src_pitch).  out: fp32 [batch][h][w][3] (dense),
+ * out = ((float)v / 255.0f - norm0) / norm1 with IEEE fp32 divisions (bit-identical to NumPy's float32 formula); one channel is replicated
+ * to three, a fourth (alpha) is dropped.  At most 2^30 pixels per call.  Added in ABI 302 without changing any earlier entry point. */
+int cp_frames_to_input_f32(const uint8_t* src, int batch, int h, int w, int channels, long long src_pitch, long long src_stride,
+                           float norm0, float norm1, float* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
