@@ -11,6 +11,12 @@ collective): weak scaling.
 Contract: `python bench.py --gpus N --steps K --warmup W` prints ONE JSON line on rank 0; `ms_per_step` is the
 wall time of one of the K timed steps.  `--dump-outputs DIR` also writes what the last timed step computed (inputs are
 seeded: the same arguments give the same inputs) so that two builds can be compared output for output.
+
+A plain run does only what the headline needs: set up, warm up, time the K steps, dump, print.  `--full` adds what the
+line reports beside the headline, each part measured in this run after the timed steps: the convolution roofline tables
+(bs 16 and bs 32) with the sustained-MFMA probe, the same workload in the other fp32 arithmetics, the training legs, and
+the CPU baseline with its fp64 accuracy check.  `--no-roofline`, `--no-bs32`, `--no-optin`, `--no-train-leg` and
+`--no-cpu-baseline` leave single parts out of a `--full` run.
 """
 import argparse
 import json
@@ -503,7 +509,7 @@ def bench_train(args):
 
 def train_leg(B, H, W, steps, warmup, dev, rank, world):
     """`steps` timed training steps (after `warmup`) on this rank's synthetic batch; returns the result dict of `--mode train`.  Also run by
-    the DEFAULT bench line (3 steps at bs 32, 448x448, key `training_leg`) so that the driver's clock covers the training path too."""
+    the `--full` bench line (3 steps at bs 32, 448x448, key `training_leg`) so that one inference line covers the training path too."""
     import numpy as np
     import torch
     import torch.distributed as dist
@@ -783,6 +789,9 @@ def main():
     ap.add_argument("--batch", type=int, default=16, help="images per GPU per step")
     ap.add_argument("--height", type=int, default=480)
     ap.add_argument("--width", type=int, default=640)
+    ap.add_argument("--full", action="store_true",
+                    help="infer mode: after the headline, also measure the roofline tables, the other fp32 arithmetics, the training legs and the CPU "
+                         "baseline with its fp64 accuracy check (the --no-* options below leave parts of it out)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--cpu-worker", default=None, help="internal: run as CPU-baseline worker i/N (started by the parent before it touches the GPU)")
     ap.add_argument("--cpu-seconds", type=float, default=12.0, help="timed seconds of every CPU-baseline worker process")
@@ -790,7 +799,7 @@ def main():
     ap.add_argument("--no-bs32", action="store_true", help="skip the bs-32 roofline annotation (`roofline_bs32`: the north-star operating point beside the bs-16 headline)")
     ap.add_argument("--no-optin", action="store_true", help="skip the extra line on the fp32 MFMA (conv_mode f32) reported beside the headline")
     ap.add_argument("--train-leg-timeout", type=int, default=300, help="seconds after which a hanging training leg is abandoned (the headline line is printed without it)")
-    ap.add_argument("--no-train-leg", action="store_true", help="skip the 3-step training leg (BASELINE configs[2]) the default line reports under `training_leg`")
+    ap.add_argument("--no-train-leg", action="store_true", help="skip the 3-step training leg (BASELINE configs[2]) a --full line reports under `training_leg`")
     ap.add_argument("--stamp", action="store_true", help="print the source / binary stamp (JSON) and exit; no GPU is touched")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
                     help="after the timed steps, write what the last one computed (keypoints, a fixed sample of the network output) as float32 DIR/<name>.npy")
@@ -799,6 +808,8 @@ def main():
         ap.error("--steps must be >= 1 and --warmup >= 0")
     if args.dump_outputs and args.mode != "infer":
         ap.error("--dump-outputs is implemented for --mode infer (the headline workload)")
+    if args.full and args.mode != "infer":
+        ap.error("--full adds to --mode infer (the headline workload); --mode train and --mode vote measure their own workload only")
     if args.stamp:
         print(json.dumps(binary_stamp()))
         return
@@ -814,9 +825,9 @@ def main():
     if args.mode == "vote":
         return bench_vote(args)
 
-    # CPU-baseline workers: started now, before anything here initialises the GPU; they wait until the GPU legs are over (rank 0 at N = 1 only)
+    # CPU-baseline workers (--full): started now, before anything here initialises the GPU; they wait until the GPU legs are over (rank 0 at N = 1 only)
     cpu_workers = None
-    if int(os.environ.get("RANK", "0")) == 0 and int(os.environ.get("WORLD_SIZE", "1")) == 1 and not args.no_cpu_baseline:
+    if args.full and int(os.environ.get("RANK", "0")) == 0 and int(os.environ.get("WORLD_SIZE", "1")) == 1 and not args.no_cpu_baseline:
         try:
             cpu_workers = spawn_cpu_workers(args)
         except Exception as exc:
@@ -1022,7 +1033,7 @@ def main():
                          "transform_ms": round(transform_ms, 3), "replaced_direct_gflop": round(wino["replaced_flops"] / 1e9, 2)},
         }
 
-    if rank == 0 and not args.no_roofline:
+    if rank == 0 and args.full and not args.no_roofline:
         result["roofline"] = conv_roofline(net)
         try:
             sus = _sustained_mfma(dev)
@@ -1030,8 +1041,9 @@ def main():
                                                                "datasheet peaks above stay the denominators of `frac`")
         except Exception as exc:  # the probe is an annotation: never fail the bench line over it
             result["roofline"]["sustained_on_this_box"] = {"error": str(exc)}
-    _log("roofline section done")
-    accuracy = {"params": params, "image": img[:1].cpu().numpy(), "logits": {}, "vertex": {}, "labels": {}} if rank == 0 else None
+    if args.full:
+        _log("roofline section done")
+    accuracy = {"params": params, "image": img[:1].cpu().numpy(), "logits": {}, "vertex": {}, "labels": {}} if rank == 0 and args.full else None
 
     def one_image(net_, mode):   # image 0 alone: logits, vector field and the label map the device conditioned decoder 2 on
         o = net_([img[:1]], training=False)
@@ -1042,10 +1054,11 @@ def main():
     if rank == 0:
         # the f16x2 range guard's findings on the timed plan (engine.ForwardPlan._calibrate): layers rescaled or moved to the exact split
         rep = dict(net._net.plan(B, H, W).f16x2_report)
-        one_image(net, net._net.conv_mode)
+        if args.full:
+            one_image(net, net._net.conv_mode)
         result["config"]["f16x2_guard"] = {"enabled": bool(net._net.f16x2_guard), "layers_checked": len(rep),
                                            "not_plain_f16x2": {n: "%s (max %.3g)" % (r[1], r[0]) for n, r in rep.items() if r[1] != "f16x2"}}
-    if rank == 0 and world == 1 and not args.no_roofline and B < 32 and not args.no_bs32:
+    if rank == 0 and world == 1 and args.full and not args.no_roofline and B < 32 and not args.no_bs32:
         # BASELINE.json's north-star target is quoted at bs 32 (">= 70 % MFMA roofline on the encoder-decoder forward at bs = 32"): the same network and
         # the same roofline accounting at bs 32, timed in THIS run (round-5 verdict, item 7) -- a few steps of forward + component filter + LS voting
         # under the host clock, then the per-launch HIP-event table.  An annotation: `value` above stays the bs-16 workload of configs[1].
@@ -1080,7 +1093,7 @@ def main():
         except Exception as exc:   # an annotation: never fail the headline over it
             result["roofline_bs32"] = {"error": "%s: %s" % (type(exc).__name__, exc)}
         torch.cuda.empty_cache()
-    if rank == 0 and world == 1 and not args.no_optin and net._net.conv_mode in ("split", "f16x2"):
+    if rank == 0 and world == 1 and args.full and not args.no_optin and net._net.conv_mode in ("split", "f16x2"):
         # the same workload in the other fp32 arithmetics, measured in the same run and reported BESIDE the headline, each with its own roofline:
         # conv_mode="f32" (v_mfma_f32_32x32x2_f32 in every convolution, the round-1/2 headline) and -- when the headline is the fp16 two-way split --
         # conv_mode="split" (exact three-way bf16 splits, the round-3 / early round-4 headline).  Their logits for one image go to the CPU leg,
@@ -1121,10 +1134,10 @@ def main():
             net2 = None
             torch.cuda.empty_cache()
         del ref_logits
-    if not args.no_train_leg:
-        # BASELINE configs[2] / [3] beside the headline, under the driver's clock: 3 training steps (1 warm-up) at the --mode train defaults.
+    if args.full and not args.no_train_leg:
+        # --full: BASELINE configs[2] / [3] beside the headline: 3 training steps (1 warm-up) at the --mode train defaults.
         # With N > 1 ranks this is the DATA-PARALLEL step -- every rank trains on its own 32 images, SyncBN tables and the four gradient buckets
-        # go through RCCL -- so the driver's 1 / 2 / 4 / 8-GPU runs carry a training scaling figure next to the replica-parallel headline.
+        # go through RCCL -- so 1 / 2 / 4 / 8-GPU --full runs carry a training scaling figure next to the replica-parallel headline.
         # It annotates the headline and must never cost it: an exception is reported in place, and a watchdog ends a leg that hangs (a rank
         # that failed while the others wait in a collective) -- rank 0 then prints the line without it.
         import threading
@@ -1185,7 +1198,7 @@ def main():
                 os._exit(TRAIN_LEG_FAILED_EXIT)
         dog.cancel()
     result["binary"] = binary_stamp()
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if rank == 0 and world == 1 and args.full and not args.no_cpu_baseline:
         result["cpu_baseline"] = cpu_baseline(H, W, seg_dim, ver_dim, B, accuracy, workers=cpu_workers, worker_seconds=args.cpu_seconds)
     if rank == 0:
         print(json.dumps(result))

@@ -153,8 +153,8 @@ def test_bench_multi_rank_contract(mode, tmp_path):
         assert abs(d["comm_exposed_ms"] - (c["syncbn_ms"] + c["grad_wait_ms"])) < 1e-3 and d["comm_exposed_ms"] < d["ms_per_step"]
 
 
-def test_bench_default_line_carries_the_dp_training_leg(tmp_path):
-    """The DEFAULT line at WORLD_SIZE = 2 (what the driver's scaling runs parse): the replica-parallel inference headline plus a `training_leg`
+def test_bench_full_line_carries_the_dp_training_leg(tmp_path):
+    """The `--full` line at WORLD_SIZE = 2: the replica-parallel inference headline plus a `training_leg`
     measured data-parallel over both ranks (SyncBN tables + gradient buckets all-reduced; here over gloo on one shared GPU), n_gpus = 2; and
     the watchdog: a leg that does not finish in time is abandoned and the headline line is still printed, exactly once."""
     import json
@@ -167,7 +167,7 @@ def test_bench_default_line_carries_the_dp_training_leg(tmp_path):
         port = s.getsockname()[1]
     env = dict(os.environ, MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port), WORLD_SIZE="2", LOCAL_RANK="0", CASAPOSE_DIST_BACKEND="gloo")
     cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--no-cpu-baseline", "--no-roofline", "--no-optin",
-           "--batch", "2", "--height", "64", "--width", "96"]
+           "--batch", "2", "--height", "64", "--width", "96", "--full"]
     procs = [subprocess.Popen(cmd, env=dict(env, RANK=str(r)), stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True) for r in (1, 0)]
     outs = [p.communicate(timeout=900) for p in procs]
     assert all(p.returncode == 0 for p in procs), [o[1][-2000:] for o in outs]

@@ -1,10 +1,10 @@
 #!/bin/bash
-# the whole -m gpu suite + the default bench line of the current tree
+# the whole -m gpu suite + the --full bench line of the current tree
 cd $GRAFT_REPO_ROOT
 O=gpurun_out/full_suite; mkdir -p $O
 timeout 2400 python -m pytest tests -m gpu -q -x 2>&1 | tail -15 > $O/tests.txt
 cat $O/tests.txt
-timeout 900 python bench.py > $O/bench.json 2> $O/bench.err
+timeout 900 python bench.py --full > $O/bench.json 2> $O/bench.err
 python - <<'PY'
 import json
 d = json.loads(open("gpurun_out/full_suite/bench.json").read().strip().splitlines()[-1])

@@ -133,7 +133,7 @@ if _tile is not None:
 md = ["# Round %s profile summary (MI355X)\n" % tag[1:].lstrip("0")]
 md.append("Generated by `python tools/make_summary.py {0}` from ONE run of `tools/profile_round.sh {0}` on the GPU box (`gpurun_out/{0}/`); source stamp "
           "`{1}` (`python bench.py --stamp`; `profiles/{0}_STAMP.json` lists the files) -- the generator refuses a set whose stamp differs from the working "
-          "tree's.  Files: `bench.json` (default `python bench.py --steps 20 --warmup 5`, un-profiled), `bench_bs32.json`, `bench_infer_f32.json` / "
+          "tree's.  Files: `bench.json` (`python bench.py --steps 20 --warmup 5 --full`, un-profiled), `bench_bs32.json`, `bench_infer_f32.json` / "
           "`bench_infer_bf16.json` (the other conv modes), `bench_profiled.json` + `bench_kernel_stats.csv` (`rocprofv3 --kernel-trace --stats`), "
           "`layer_times*.txt` (`tools/layer_times.py`), `pmc_traffic.{{json,txt}}` (FETCH_SIZE and WRITE_SIZE in separate `--pmc` passes, FETCH doubled as the "
           "microarchitecture guide prescribes for gfx950), `pmc_mfma.txt` (SQ MFMA-busy counters, per-dispatch join), `bench_train*.json` + "
@@ -183,7 +183,7 @@ if alone:
 tl = b.get("training_leg")
 if tl and "value" in tl:
     tb = b.get("training_leg_bf16_convs") or {}
-    md.append("Training leg inside the default line (3 steps at bs 32, 448x448): %.1f images/s, %.1f ms/step%s.\n"
+    md.append("Training leg inside the --full line (3 steps at bs 32, 448x448): %.1f images/s, %.1f ms/step%s.\n"
               % (tl["value"], tl["ms_per_step"], ("; the same leg with bf16 convolution operands (BASELINE configs[2] as named): %.1f images/s, %.1f ms/step"
                                                   % (tb["value"], tb["ms_per_step"])) if "value" in tb else ""))
 c = b.get("cpu_baseline")

@@ -2,10 +2,10 @@
 # ONE GPU-box call that produces every artefact of a round's profile set from the SAME tree, stamped (python3 bench.py --stamp):
 #   gpurun --timeout 3600 -- 'bash tools/profile_round.sh r03 [suites]'   ->   gpurun_out/<tag>/...   ->   python tools/make_summary.py r03
 # Pieces (each its own process; the --pmc passes use --kernel-trace only, as the pool requires):
-#   bench.json                 default `python3 bench.py` (headline + roofline + fp32-MFMA line + training leg + CPU baseline)
+#   bench.json                 `python3 bench.py --full` (headline + roofline + fp32-MFMA line + training leg + CPU baseline)
 #   bench_bs32.json            the same at bs 32 (the batch the north star quotes its MFMA target on), no CPU baseline / training leg
 #   bench_f32.json             CASAPOSE_INFER_CONV_MODE=f32 (fp32 MFMA everywhere)      bench_split.json  =split (exact bf16 splits)      bench_bf16.json  =bf16
-#   trace/                     rocprofv3 --kernel-trace --stats of the default bench (kernel stats csv)
+#   trace/                     rocprofv3 --kernel-trace --stats of the --full bench (kernel stats csv)
 #   pmc_traffic/               FETCH_SIZE and WRITE_SIZE in two --pmc passes -> traffic.json / summary.txt
 #   pmc_mfma/                  SQ MFMA-busy counters -> summary.txt
 #   layer_times*.txt           per-layer table, default (f16x2), split and f32
@@ -19,12 +19,12 @@ tag=${1:-r03}
 O=$R/gpurun_out/$tag
 rm -rf $O && mkdir -p $O
 python3 $R/bench.py --stamp > $O/stamp.json
-python3 $R/bench.py --steps 20 --warmup 5 > $O/bench.json 2> $O/bench.err
-python3 $R/bench.py --steps 20 --warmup 5 --batch 32 --no-cpu-baseline --no-train-leg > $O/bench_bs32.json 2>> $O/bench.err
-CASAPOSE_INFER_CONV_MODE=f32 python3 $R/bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-train-leg --no-optin > $O/bench_f32.json 2>> $O/bench.err
-CASAPOSE_INFER_CONV_MODE=split python3 $R/bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-train-leg --no-optin > $O/bench_split.json 2>> $O/bench.err
-CASAPOSE_INFER_CONV_MODE=bf16 python3 $R/bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-train-leg --no-optin > $O/bench_bf16.json 2>> $O/bench.err
-rocprofv3 --kernel-trace --stats -d $O/trace -o bench --output-format csv -- python3 $R/bench.py --steps 10 --warmup 3 --no-cpu-baseline --no-train-leg --no-optin > $O/bench_profiled.json 2> $O/rocprof.err
+python3 $R/bench.py --steps 20 --warmup 5 --full > $O/bench.json 2> $O/bench.err
+python3 $R/bench.py --steps 20 --warmup 5 --batch 32 --full --no-cpu-baseline --no-train-leg > $O/bench_bs32.json 2>> $O/bench.err
+CASAPOSE_INFER_CONV_MODE=f32 python3 $R/bench.py --steps 20 --warmup 5 --full --no-cpu-baseline --no-train-leg --no-optin > $O/bench_f32.json 2>> $O/bench.err
+CASAPOSE_INFER_CONV_MODE=split python3 $R/bench.py --steps 20 --warmup 5 --full --no-cpu-baseline --no-train-leg --no-optin > $O/bench_split.json 2>> $O/bench.err
+CASAPOSE_INFER_CONV_MODE=bf16 python3 $R/bench.py --steps 20 --warmup 5 --full --no-cpu-baseline --no-train-leg --no-optin > $O/bench_bf16.json 2>> $O/bench.err
+rocprofv3 --kernel-trace --stats -d $O/trace -o bench --output-format csv -- python3 $R/bench.py --steps 10 --warmup 3 --full --no-cpu-baseline --no-train-leg --no-optin > $O/bench_profiled.json 2> $O/rocprof.err
 mkdir -p $O/pmc_traffic $O/pmc_mfma
 rocprofv3 --pmc FETCH_SIZE --kernel-trace -d $O/pmc_traffic/fetch -o fetch --output-format csv -- python3 $R/bench.py --steps 3 --warmup 1 --no-cpu-baseline --no-roofline --no-train-leg --no-optin > $O/pmc_traffic/fetch.log 2>&1
 rocprofv3 --pmc WRITE_SIZE --kernel-trace -d $O/pmc_traffic/write -o write --output-format csv -- python3 $R/bench.py --steps 3 --warmup 1 --no-cpu-baseline --no-roofline --no-train-leg --no-optin > $O/pmc_traffic/write.log 2>&1
