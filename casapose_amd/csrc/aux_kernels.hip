@@ -138,61 +138,115 @@ __global__ void argmax_vec_kernel(const float* __restrict__ x, int ld, int K, lo
     }
 }
 
-// level l+1 labels = level l labels [::2, ::2]  (HalfSize, _normalization_layers.py:294-299)
-__global__ void half_labels_kernel(const uint8_t* __restrict__ in, int B, int H, int W, int Ho, int Wo, uint8_t* __restrict__ out) {
-    const long long total = (long long)B * Ho * Wo;
-    for (long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x; i < total; i += (long long)gridDim.x * blockDim.x) {
-        int ox = (int)(i % Wo);
-        long long t = i / Wo;
-        int oy = (int)(t % Ho);
-        int n = (int)(t / Ho);
-        out[i] = in[((size_t)n * H + 2 * oy) * W + 2 * ox];
-    }
-}
+// The label-derived maps of decoder 2, all levels in one launch.  Level l + 1 is level l [::2, ::2] (HalfSize,
+// _normalization_layers.py:294-299), so pixel (y, x) of level l is pixel (y << l, x << l) of the level-0 map and every map of every level is
+// read from level 0 alone:
+//   labels[l]  the level-l label map (l >= 1)
+//   pnorm[l]   9 / #{in-bounds 3x3 neighbours with the centre label} (_normalization_layers.py:344-352)
+//   sel[l]     guided-upsampling neighbour selection (_normalization_layers.py:534-551): first of {(y,x),(y,x+1),(y+1,x),(y+1,x+1)} (zero padded
+//              bottom/right) in the level-(l+1) map whose label equals the level-l label, else 0
+// A thread owns a tile of 2 rows x 4 columns of one level (even row, column a multiple of 4).  Everything the tile needs lies in the 4 x 6
+// window of level-l pixels rows y-1 .. y+2, columns x-1 .. x+4: the 3x3 neighbourhoods, and the level-(l+1) pixels (ly + dy, lx + dx), which
+// are the level-l pixels (2 ly + 2 dy, 2 lx + 2 dx).  A window pixel outside the level reads as -1, which equals no label.
+struct PyramidLevel {
+    uint8_t* labels;  // null for level 0 (the input) and for a level without outputs
+    float* pnorm;     // may be null
+    uint8_t* sel;     // may be null
+    int level, h, w, tiles_x, tiles_per_img;
+    int first_block;  // blocks [first_block, next level's first_block) work on this level
+};
+struct PyramidArgs {
+    PyramidLevel lv[4];  // the levels with work, in order
+    int levels;
+};
 
-// pnorm = 9 / #{in-bounds 3x3 neighbours with the centre label} (_normalization_layers.py:344-352)
-__global__ void pnorm_kernel(const uint8_t* __restrict__ lab, int B, int H, int W, float* __restrict__ out) {
-    const long long total = (long long)B * H * W;
-    for (long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x; i < total; i += (long long)gridDim.x * blockDim.x) {
-        int x = (int)(i % W);
-        long long t = i / W;
-        int y = (int)(t % H);
-        int n = (int)(t / H);
-        const uint8_t* base = lab + (size_t)n * H * W;
-        int c = base[(size_t)y * W + x], cnt = 0;
+__global__ __launch_bounds__(256) void label_pyramid_kernel(const uint8_t* __restrict__ lab0, int B, int H0, int W0, PyramidArgs args) {
+    int slot = 0;
 #pragma unroll
-        for (int dy = -1; dy <= 1; ++dy)
+    for (int k = 1; k < 4; ++k)
+        if (k < args.levels && (int)blockIdx.x >= args.lv[k].first_block) slot = k;
+    const PyramidLevel L = args.lv[slot];
+    const int l = L.level;
+    const int t = ((int)blockIdx.x - L.first_block) * 256 + (int)threadIdx.x;
+    if (t >= B * L.tiles_per_img) return;
+    const int n = t / L.tiles_per_img;
+    const int r = t - n * L.tiles_per_img;
+    const int ty = r / L.tiles_x;
+    const int y = 2 * ty, x = 4 * (r - ty * L.tiles_x);
+    const int H = L.h, W = L.w;
+    const uint8_t* base = lab0 + (size_t)n * H0 * W0;
+
+    int a[4][6];
+    const bool words = l == 0 && (W0 & 3) == 0 && ((uintptr_t)lab0 & 3) == 0;  // x + 3 < W and the four labels are one aligned word
 #pragma unroll
-            for (int dx = -1; dx <= 1; ++dx) {
-                int yy = y + dy, xx = x + dx;
-                if ((unsigned)yy < (unsigned)H && (unsigned)xx < (unsigned)W) cnt += (base[(size_t)yy * W + xx] == c);
+    for (int i = 0; i < 4; ++i) {
+        const int yy = y - 1 + i;
+        const bool yin = (unsigned)yy < (unsigned)H;
+        const uint8_t* row = base + (yin ? (yy << l) * W0 : 0);
+        if (words) {
+            const unsigned wv = yin ? *reinterpret_cast<const unsigned*>(row + x) : 0xffffffffu;
+#pragma unroll
+            for (int j = 0; j < 4; ++j) a[i][1 + j] = yin ? (int)((wv >> (8 * j)) & 0xffu) : -1;
+            a[i][0] = (yin && x > 0) ? (int)row[x - 1] : -1;
+            a[i][5] = (yin && x + 4 < W) ? (int)row[x + 4] : -1;
+        } else {
+#pragma unroll
+            for (int j = 0; j < 6; ++j) {
+                const int xx = x - 1 + j;
+                a[i][j] = (yin && (unsigned)xx < (unsigned)W) ? (int)row[xx << l] : -1;
             }
-        out[i] = 9.0f / (float)cnt;  // the centre always matches, cnt >= 1
+        }
     }
-}
 
-// guided-upsampling neighbour selection (_normalization_layers.py:534-551): first of
-// {(y,x),(y,x+1),(y+1,x),(y+1,x+1)} (zero padded bottom/right) in the LOW map whose label equals
-// the HIGH label, else 0.
-__global__ void guided_sel_kernel(const uint8_t* __restrict__ hi, const uint8_t* __restrict__ lo, int B, int H, int W,
-                                  uint8_t* __restrict__ sel) {
-    const int Hl = H / 2, Wl = W / 2;
-    const long long total = (long long)B * H * W;
-    for (long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x; i < total; i += (long long)gridDim.x * blockDim.x) {
-        int x = (int)(i % W);
-        long long t = i / W;
-        int y = (int)(t % H);
-        int n = (int)(t / H);
-        int c = hi[i];
-        int ly = y >> 1, lx = x >> 1;
-        const uint8_t* lb = lo + (size_t)n * Hl * Wl;
-        int s = 0;
-        bool xr = (lx + 1) < Wl, yb = (ly + 1) < Hl;
-        if (lb[(size_t)ly * Wl + lx] == c) s = 0;
-        else if (xr && lb[(size_t)ly * Wl + lx + 1] == c) s = 1;
-        else if (yb && lb[(size_t)(ly + 1) * Wl + lx] == c) s = 2;
-        else if (xr && yb && lb[(size_t)(ly + 1) * Wl + lx + 1] == c) s = 3;
-        sel[i] = (uint8_t)s;
+#pragma unroll
+    for (int i = 0; i < 2; ++i) {
+        if (y + i >= H) break;
+        const int o = (n * H + y + i) * W + x;
+        if (L.labels) {
+#pragma unroll
+            for (int j = 0; j < 4; ++j)
+                if (x + j < W) L.labels[o + j] = (uint8_t)a[1 + i][1 + j];
+        }
+        if (L.pnorm) {
+            float pn[4];
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                const int c = a[1 + i][1 + j];
+                int cnt = 0;
+#pragma unroll
+                for (int dy = 0; dy < 3; ++dy)
+#pragma unroll
+                    for (int dx = 0; dx < 3; ++dx) cnt += (a[i + dy][j + dx] == c);
+                pn[j] = 9.0f / (float)cnt;  // the centre always matches, cnt >= 1
+            }
+            if (x + 3 < W && (W & 3) == 0 && ((uintptr_t)L.pnorm & 15) == 0) {
+                *reinterpret_cast<float4*>(L.pnorm + o) = make_float4(pn[0], pn[1], pn[2], pn[3]);
+            } else {
+#pragma unroll
+                for (int j = 0; j < 4; ++j)
+                    if (x + j < W) L.pnorm[o + j] = pn[j];
+            }
+        }
+        if (L.sel) {  // H and W are even here, and the window's odd rows / columns are the level-(l+1) pixels
+            unsigned sv = 0;
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                const int c = a[1 + i][1 + j], e = j & ~1;
+                int s = 0;
+                if (a[1][1 + e] == c) s = 0;
+                else if (a[1][3 + e] == c) s = 1;
+                else if (a[3][1 + e] == c) s = 2;
+                else if (a[3][3 + e] == c) s = 3;
+                sv |= (unsigned)s << (8 * j);
+            }
+            if (x + 3 < W && (W & 3) == 0 && ((uintptr_t)L.sel & 3) == 0) {
+                *reinterpret_cast<unsigned*>(L.sel + o) = sv;
+            } else {
+#pragma unroll
+                for (int j = 0; j < 4; ++j)
+                    if (x + j < W) L.sel[o + j] = (uint8_t)(sv >> (8 * j));
+            }
+        }
     }
 }
 
@@ -284,31 +338,44 @@ extern "C" int cp_label_pyramid(const uint8_t* labels0, int batch, int h, int w,
                                 float* const* pnorm, uint8_t* const* sel, void* stream) {
     CP_REQUIRE(labels0 && batch > 0 && h > 0 && w > 0, "cp_label_pyramid: bad arguments");
     CP_REQUIRE(labels, "cp_label_pyramid: labels[] array required (labels[1..3] receive the half-size maps)");
+    CP_REQUIRE((long long)batch * h * w < (1LL << 31), "cp_label_pyramid: batch * h * w must stay below 2^31");
     hipStream_t st = (hipStream_t)stream;
-    const uint8_t* lv[4] = {labels0, nullptr, nullptr, nullptr};
+    bool have[4] = {true, false, false, false};  // level l exists: the input, or labels[l] given (and every level before it)
     int hs[4], ws[4];
     hs[0] = h; ws[0] = w;
     for (int l = 1; l < 4; ++l) { hs[l] = hs[l - 1] / 2; ws[l] = ws[l - 1] / 2; }
     for (int l = 1; l < 4; ++l) {
         if (!labels[l]) break;
         CP_REQUIRE(hs[l] > 0 && ws[l] > 0, "cp_label_pyramid: level %d is empty", l);
-        long long total = (long long)batch * hs[l] * ws[l];
-        CP_LAUNCH(half_labels_kernel, dim3(grid_for(total)), dim3(THREADS), 0, st, lv[l - 1], batch, hs[l - 1],
-                           ws[l - 1], hs[l], ws[l], labels[l]);
-        lv[l] = labels[l];
+        have[l] = true;
     }
+    PyramidArgs args;
+    args.levels = 0;
+    int blocks = 0;
     for (int l = 0; l < 4; ++l) {
+        PyramidLevel lv;
+        lv.labels = (l > 0 && have[l]) ? labels[l] : nullptr;
+        lv.pnorm = nullptr;
+        lv.sel = nullptr;
         if (pnorm && pnorm[l]) {
-            CP_REQUIRE(lv[l], "cp_label_pyramid: pnorm[%d] requested without labels[%d]", l, l);
-            long long total = (long long)batch * hs[l] * ws[l];
-            CP_LAUNCH(pnorm_kernel, dim3(grid_for(total)), dim3(THREADS), 0, st, lv[l], batch, hs[l], ws[l], pnorm[l]);
+            CP_REQUIRE(have[l], "cp_label_pyramid: pnorm[%d] requested without labels[%d]", l, l);
+            lv.pnorm = pnorm[l];
         }
         if (l < 3 && sel && sel[l]) {
-            CP_REQUIRE(lv[l] && lv[l + 1], "cp_label_pyramid: sel[%d] needs labels[%d] and labels[%d]", l, l, l + 1);
+            CP_REQUIRE(have[l] && have[l + 1], "cp_label_pyramid: sel[%d] needs labels[%d] and labels[%d]", l, l, l + 1);
             CP_REQUIRE(hs[l] == 2 * hs[l + 1] && ws[l] == 2 * ws[l + 1], "cp_label_pyramid: level %d size must be even", l);
-            long long total = (long long)batch * hs[l] * ws[l];
-            CP_LAUNCH(guided_sel_kernel, dim3(grid_for(total)), dim3(THREADS), 0, st, lv[l], lv[l + 1], batch, hs[l], ws[l], sel[l]);
+            lv.sel = sel[l];
         }
+        if (!lv.labels && !lv.pnorm && !lv.sel) continue;
+        lv.h = hs[l]; lv.w = ws[l];
+        lv.level = l;
+        lv.tiles_x = (ws[l] + 3) / 4;
+        lv.tiles_per_img = lv.tiles_x * ((hs[l] + 1) / 2);
+        lv.first_block = blocks;
+        blocks += (int)(((long long)batch * lv.tiles_per_img + THREADS - 1) / THREADS);
+        args.lv[args.levels++] = lv;
     }
+    if (blocks == 0) return CP_OK;
+    CP_LAUNCH(label_pyramid_kernel, dim3(blocks), dim3(THREADS), 0, st, labels0, batch, h, w, args);
     return cp::check_launch("cp_label_pyramid");
 }

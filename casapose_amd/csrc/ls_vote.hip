@@ -85,17 +85,29 @@ __global__ __launch_bounds__(256) void ls_accumulate_kernel(const float* __restr
         };
 
         const int y_end = min(y0 + ROWS, H);
+        // with given labels a row segment without a non-zero label contributes nothing: its records are not read.  The strip's labels are
+        // fetched up front (independent loads, one round trip) so that no row waits for its own label before its records are requested.
+        unsigned rowmask = 0xffffu;
+        if (labels) {
+            rowmask = 0;
+#pragma unroll
+            for (int ry = 0; ry < ROWS; ++ry) {
+                const int l = (y0 + ry < y_end && lane < ncols) ? (int)labels[((size_t)img * H + y0 + ry) * W + x] : 0;
+                rowmask |= (__builtin_amdgcn_ballot_w64(l != 0) != 0ull ? 1u : 0u) << ry;
+            }
+        }
         for (int y = y0; y < y_end; ++y) {
+            const bool rd = (rowmask >> (y - y0)) & 1u;  // wave-uniform; a row that is not read has label 0 in every lane, as before
             // ---- stage this row segment: ncols*ld contiguous floats, 16 B per lane per step ----
             const float* g = field + (((size_t)img * H + y) * W + x0) * ld;
-            const int nvec = (ncols * ld) >> 2;  // ld % 4 == 0
+            const int nvec = rd ? (ncols * ld) >> 2 : 0;  // ld % 4 == 0
             for (int v = lane; v < nvec; v += 64)
                 reinterpret_cast<float4*>(wstage)[v] = reinterpret_cast<const float4*>(g)[v];
             __builtin_amdgcn_wave_barrier();
             __builtin_amdgcn_s_waitcnt(0xc07f);  // lgkmcnt(0): LDS writes landed before the reads below
             int lab = 0;
             const float* px = wstage + lane * ld;
-            if (lane < ncols) {
+            if (rd && lane < ncols) {
                 if (labels) {
                     lab = labels[((size_t)img * H + y) * W + x];
                 } else {
@@ -157,9 +169,14 @@ __global__ __launch_bounds__(256) void ls_accumulate_kernel(const float* __restr
 // decomposition and arithmetic as above, but
 //   * the next row segment (64 pixels = 9216 contiguous bytes = nine 16-byte loads per lane) is fetched into registers while the
 //     current one is processed -- the generic kernel waits for every row's memory latency (measured 3.1 TB/s with the arithmetic
-//     removed); and
+//     removed);
 //   * a lane reads its pixel back from the staging buffer as nine 16-byte LDS reads (144-byte pixel stride: conflict-free) with
-//     compile-time channel positions, instead of 27 scalar reads with 4-way bank conflicts.
+//     compile-time channel positions, instead of 27 scalar reads with 4-way bank conflicts; and
+//   * with given labels (LAB) the wave first reads the labels of its whole 64 x 16 strip (1 KB: four 4-byte loads per lane) and
+//     forms by ballot the 16-bit mask of the row segments that hold a non-zero label.  Only those rows are requested, staged and
+//     processed (a wave-uniform walk over the set bits, still one row ahead); a label-0 pixel never contributed, so the sums are the
+//     same sums.  The component-filtered label map of CoordLSVotingWeighted(filter_estimates=True) keeps a small share of the image.
+template <bool LAB>
 __global__ __launch_bounds__(256) void ls_accumulate36_kernel(const float* __restrict__ field, const uint8_t* __restrict__ labels, int B, int H,
                                                               int W, double* __restrict__ sums, int strips_x, int strips_y) {
     constexpr int KP = 9, LD = 36, OBJ = 8, NV = LD / 4;
@@ -185,7 +202,40 @@ __global__ __launch_bounds__(256) void ls_accumulate36_kernel(const float* __res
         const int x = x0 + lane;
         const int ncols = min(64, W - x0);
         const int nvec = ncols * NV;
+        const int nrows = min(ROWS, H - y0);
         const float cx = ((float)x + 0.5f) / (float)H;
+
+        // ---- the strip's labels and its row mask, before any record is requested ----
+        // lw[k] of lane l holds the four labels of row 4k + (l >> 4), columns 4 (l & 15) .. + 3 (a label outside the image reads as 0).
+        unsigned lw[4] = {0u, 0u, 0u, 0u};
+        unsigned rowmask = (1u << nrows) - 1u;
+        if (LAB) {
+            const uint8_t* lb = labels + ((size_t)img * H + y0) * W + x0;
+            const int lr = lane >> 4, lc = (lane & 15) * 4;
+            const bool words = ((W & 3) == 0) && (((uintptr_t)labels & 3) == 0);  // every row segment starts on a 4-byte boundary
+            rowmask = 0;
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+                const int ry = 4 * k + lr;
+                if (ry < nrows) {
+                    const uint8_t* p = lb + (size_t)ry * W + lc;
+                    if (words) {
+                        if (lc < ncols) lw[k] = *reinterpret_cast<const unsigned*>(p);  // ncols % 4 == 0 here: the word is inside the row
+                    } else {
+#pragma unroll
+                        for (int c = 0; c < 4; ++c)
+                            if (lc + c < ncols) lw[k] |= (unsigned)p[c] << (8 * c);
+                    }
+                }
+            }
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+                const unsigned long long bal = __builtin_amdgcn_ballot_w64(lw[k] != 0u);
+#pragma unroll
+                for (int j = 0; j < 4; ++j)
+                    if ((bal >> (16 * j)) & 0xffffull) rowmask |= 1u << (4 * k + j);
+            }
+        }
 
         double a[KP][5];
 #pragma unroll
@@ -207,23 +257,38 @@ __global__ __launch_bounds__(256) void ls_accumulate36_kernel(const float* __res
         };
 
         float4 pre[NV];
-        int lab_pre = 0;
-        auto issue = [&](int y) {
-            const float4* g = reinterpret_cast<const float4*>(field + (((size_t)img * H + y) * W + x0) * LD);
+        auto issue = [&](int ry) {
+            const float4* g = reinterpret_cast<const float4*>(field + (((size_t)img * H + y0 + ry) * W + x0) * LD);
 #pragma unroll
             for (int i = 0; i < NV; ++i) {
                 const int v = lane + 64 * i;
                 pre[i] = (v < nvec) ? g[v] : make_float4(0.f, 0.f, 0.f, 0.f);
             }
-            if (labels) lab_pre = (lane < ncols) ? (int)labels[((size_t)img * H + y) * W + x] : 0;
         };
-        const int y_end = min(y0 + ROWS, H);
-        issue(y0);
-        for (int y = y0; y < y_end; ++y) {
+        // this lane's label in row ry: byte (lane & 3) of the word that lane 16 (ry & 3) + (lane >> 2) holds in lw[ry >> 2]
+        auto label_of = [&](int ry) {
+            const int k = ry >> 2;
+            const unsigned wsel = (k == 0) ? lw[0] : (k == 1) ? lw[1] : (k == 2) ? lw[2] : lw[3];
+            const unsigned wv = (unsigned)__shfl((int)wsel, ((ry & 3) << 4) + (lane >> 2));
+            return (int)((wv >> (8 * (lane & 3))) & 0xffu);
+        };
+
+        unsigned todo = rowmask;  // wave-uniform
+        int ry = -1, prev = -1;
+        if (todo) {
+            ry = __builtin_ctz(todo);
+            todo &= todo - 1;
+            issue(ry);
+        }
+        while (ry >= 0) {
 #pragma unroll
             for (int i = 0; i < NV; ++i) wstage[lane + 64 * i] = pre[i];
-            int lab = lab_pre;
-            if (y + 1 < y_end) issue(y + 1);  // in flight while this row is processed
+            int nxt = -1;
+            if (todo) {
+                nxt = __builtin_ctz(todo);
+                todo &= todo - 1;
+                issue(nxt);  // in flight while this row is processed
+            }
             __builtin_amdgcn_wave_barrier();
             asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // this wave's LDS writes have landed (the prefetch stays in flight)
             float r[LD];
@@ -232,8 +297,14 @@ __global__ __launch_bounds__(256) void ls_accumulate36_kernel(const float* __res
                 const float4 q = wstage[lane * NV + i];
                 r[4 * i] = q.x; r[4 * i + 1] = q.y; r[4 * i + 2] = q.z; r[4 * i + 3] = q.w;
             }
-            if (!labels) {
-                lab = 0;
+            int lab = 0;
+            if (LAB) {
+                lab = label_of(ry);
+                if (ry != prev + 1) {  // rows in between were skipped: every lane's label was 0 there, which ends its run as before
+                    flush();
+                    cur = 0;
+                }
+            } else {
                 float best = r[0];
 #pragma unroll
                 for (int k = 1; k <= OBJ; ++k)
@@ -249,7 +320,7 @@ __global__ __launch_bounds__(256) void ls_accumulate36_kernel(const float* __res
 #else
             if (lab > 0) {
 #endif
-                const float cy = ((float)y + 0.5f) / (float)H;
+                const float cy = ((float)(y0 + ry) + 0.5f) / (float)H;
 #pragma unroll
                 for (int j = 0; j < KP; ++j) {
                     const float dy = r[9 + 2 * j], dx = r[9 + 2 * j + 1];
@@ -274,6 +345,8 @@ __global__ __launch_bounds__(256) void ls_accumulate36_kernel(const float* __res
                 }
             }
             __builtin_amdgcn_wave_barrier();  // all lanes done reading before the next row overwrites
+            prev = ry;
+            ry = nxt;
         }
         flush();
     }
@@ -607,7 +680,10 @@ extern "C" int cp_ls_vote_w_f32(const float* field, int ld, int seg_off, int dir
     int blocks_per_img = (strips_x * strips_y + WAVES - 1) / WAVES;
     size_t lds = sizeof(double) * objects * kp * 5 + sizeof(float) * WAVES * 64 * ld;
     if (!sigmoid_weights && ld == 36 && seg_off == 0 && dir_off == 9 && conf_off == 27 && objects == 8 && !getenv("CP_LS_GENERIC")) {  // the production record
-        CP_LAUNCH(ls_accumulate36_kernel, dim3(batch * blocks_per_img), dim3(256), lds, st, field, labels, batch, h, w, sums_ws, strips_x, strips_y);
+        if (labels)
+            CP_LAUNCH(ls_accumulate36_kernel<true>, dim3(batch * blocks_per_img), dim3(256), lds, st, field, labels, batch, h, w, sums_ws, strips_x, strips_y);
+        else
+            CP_LAUNCH(ls_accumulate36_kernel<false>, dim3(batch * blocks_per_img), dim3(256), lds, st, field, labels, batch, h, w, sums_ws, strips_x, strips_y);
     } else {
         CP_LAUNCH((ls_accumulate_kernel<MAXKP>), dim3(batch * blocks_per_img), dim3(256), lds, st, field, ld, seg_off,
                   dir_off, conf_off, labels, batch, h, w, objects, sums_ws, strips_x, strips_y, sigmoid_weights ? 1 : 0);
