@@ -1,5 +1,6 @@
 // Library-level entry points of include/casapose_hip.h: error reporting and probing.
 #include "common.h"
+#include "mfma_helpers.h"
 
 #include <algorithm>
 #include <cmath>
@@ -124,8 +125,8 @@ extern "C" int cp_device_count(void) {
 // its power limit, as opposed to the datasheet peak the roofline entries are priced against.  bench.py times it with HIP events and prints
 // the result beside the roofline fraction.  which = 0: v_mfma_f32_32x32x2_f32, 1: v_mfma_f32_32x32x16_bf16.
 namespace {
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
+using cp::bf16x8;
+using cp::f32x16;
 
 template <int WHICH>
 __global__ __launch_bounds__(256) void mfma_probe_kernel(float* out, int iters) {

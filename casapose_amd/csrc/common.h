@@ -110,6 +110,21 @@ __device__ __forceinline__ int xcd_remap(int bid, int nblocks) {
     return start + idx;
 }
 
+// The same runs for a persistent launch with fewer blocks than tiles (grid a multiple of 8): the blocks of an XCD walk its run in lock-step
+// strides, so this block's it-th tile is tile(it), it < count.
+struct TileRun {
+    int start, idx, stride, count;
+    __device__ __forceinline__ int tile(int it) const { return start + idx + it * stride; }
+};
+__device__ __forceinline__ TileRun xcd_tile_run(int ntiles) {
+    const int nx = 8;
+    const int xcd = blockIdx.x % nx, bidx = blockIdx.x / nx, nb = gridDim.x / nx;
+    const int q = ntiles / nx, r = ntiles % nx;
+    const int start = (xcd < r) ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q;
+    const int cnt = q + (xcd < r ? 1 : 0);
+    return {start, bidx, nb, (cnt > bidx) ? (cnt - bidx + nb - 1) / nb : 0};
+}
+
 // Arg-max over the first `classes` head channels of this lane's pixel from the fused head's accumulator (conv_halo.hip / conv_hsplit.hip):
 // register g4 * 4 + e of lane half `half` holds channel q = 8 g4 + 4 half + e, so a pixel's 32 channels sit in lanes l and l ^ 32.
 // First maximum wins (cp_argmax_labels); all lanes of the wave must call it.

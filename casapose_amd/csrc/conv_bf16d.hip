@@ -16,6 +16,7 @@
 // cp_conv_pack_weights_split_host + cp_conv_split_weights_f32(planes = 1)); a 128-channel pass here reads the streams of passes 2q, 2q + 1.
 // Accumulators are transposed (MFMA A = weights, B = pixels: lane = pixel, four consecutive channels in four consecutive registers).
 #include "common.h"
+#include "mfma_helpers.h"
 
 #include <algorithm>
 #include <type_traits>
@@ -29,11 +30,7 @@
 
 namespace {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
+using namespace cp;
 
 struct DSrc {
     const float* data;
@@ -58,24 +55,6 @@ struct DeepK {
     float* out_act;
     int act_ld;
 };
-
-#define CP_BARRIER() asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory")
-
-__device__ __forceinline__ unsigned pack_hi16(unsigned a_lo, unsigned b_hi) { return __builtin_amdgcn_perm(b_hi, a_lo, 0x07060302u); }
-
-// round to nearest even, two v_cvt_pk_bf16_f32 (gfx950)
-__device__ __forceinline__ uint2 round4(const float4 v) {
-    const f32x2 a = {v.x, v.y}, b = {v.z, v.w};
-    return make_uint2(__builtin_bit_cast(unsigned, __builtin_convertvector(a, bf16x2)), __builtin_bit_cast(unsigned, __builtin_convertvector(b, bf16x2)));
-}
-
-template <int I, int N, typename F>
-__device__ __forceinline__ void deep_static_for(F&& f) {
-    if constexpr (I < N) {
-        f(std::integral_constant<int, I>{});
-        deep_static_for<I + 1, N>(f);
-    }
-}
 
 template <int D, int TW>
 __global__ __launch_bounds__(256, 1) void conv_bf16d_kernel(const DeepK p) {
@@ -164,7 +143,7 @@ __global__ __launch_bounds__(256, 1) void conv_bf16d_kernel(const DeepK p) {
     };
     auto store_item = [&](auto ic, unsigned char* hst) {   // hst = stage base + this lane's part
         constexpr int hy = decltype(ic)::value;
-        *reinterpret_cast<uint2*>(hst + hy * HW * 16) = round4(lv[hy]);
+        *reinterpret_cast<uint2*>(hst + hy * HW * 16) = round4_cvt(lv[hy]);
     };
     auto weights_dma = [&](const StepPos& sp, int stage) {   // fragments wave, wave + 4, ... of the slice's 36: (tap, cout block) = (f >> 2, f & 3)
         const unsigned sbase = (unsigned)(2 * sp.pass) * pass_w_bytes + (unsigned)(sp.c * 18) * 1024u;
@@ -241,9 +220,9 @@ __global__ __launch_bounds__(256, 1) void conv_bf16d_kernel(const DeepK p) {
     {   // prologue: step 0 goes through the registers into stage 0 (its weights straight into stage 0), step 1 is left in flight
         const StepPos s0 = step_pos(0), s1 = step_pos(1);
         weights_dma(s0, 0);
-        deep_static_for<0, NITEM>([&](auto ic) { issue_item(ic, s0); });
+        static_for<0, NITEM>([&](auto ic) { issue_item(ic, s0); });
         unsigned char* hst = halo + lds_lane;
-        deep_static_for<0, NITEM>([&](auto ic) {
+        static_for<0, NITEM>([&](auto ic) {
             store_item(ic, hst);
             issue_item(ic, s1);
         });
@@ -276,11 +255,11 @@ __global__ __launch_bounds__(256, 1) void conv_bf16d_kernel(const DeepK p) {
                 for (int j = 0; j < 4; ++j) fw[slot_][j] = *reinterpret_cast<const bf16x8*>(wb + (t * 4 + j) * 1024);
             };
             read_tap(std::integral_constant<int, 0>{}, 0);
-            deep_static_for<0, 9>([&](auto tc) {
+            static_for<0, 9>([&](auto tc) {
                 constexpr int t = decltype(tc)::value;
                 if constexpr (t + 1 < 9) read_tap(std::integral_constant<int, t + 1>{}, (t + 1) & 1);
                 // this tap's share of the staging: rows of step + 1 into the other stage, their registers re-armed with step + 2
-                deep_static_for<t * IPT, (t * IPT + IPT < NITEM ? t * IPT + IPT : NITEM)>([&](auto ic) {
+                static_for<t * IPT, (t * IPT + IPT < NITEM ? t * IPT + IPT : NITEM)>([&](auto ic) {
                     store_item(ic, hst);
                     issue_item(ic, n2);
                 });

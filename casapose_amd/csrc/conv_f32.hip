@@ -32,7 +32,7 @@ int launch_stem_conv(const cp_conv_desc* d, hipStream_t st);
 
 namespace {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
+using namespace cp;
 
 constexpr int BK = 32;
 constexpr int LDS_STRIDE = 36;  // floats per tile row (32 + 4 pad)
@@ -349,7 +349,6 @@ __global__ __launch_bounds__(512, (TM * TN >= 4) ? 2 : 4) void conv_f32_kernel(c
 
     // raw barrier: LDS traffic must be complete, but the producers' global loads stay in
     // flight across it (a __syncthreads() would drain vmcnt and serialise the prefetch)
-#define CP_BARRIER() asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory")
 
     if (producer) {
         load_sel(0);
@@ -429,7 +428,6 @@ __global__ __launch_bounds__(512, (TM * TN >= 4) ? 2 : 4) void conv_f32_kernel(c
         CP_BARRIER();  // stage buf^1 now holds chunk q+1; stage buf may be overwritten
         if (q + 1 < p.nchunks) read_frags(buf ^ 1, 0, 0);
     }
-#undef CP_BARRIER
 
     // ---- epilogue (epilogue.h: batched, branch-free) ---------------------------------------
     const int hi4 = (lane >> 5) * 4;

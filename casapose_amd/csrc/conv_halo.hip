@@ -14,13 +14,11 @@
 // range-checked buffer loads, the same operand modes (bilinear x2, guided-nearest x2, partial-conv
 // tap mask -- applied by the consumers because it depends on (output pixel, tap)) and epilogue.
 #include "common.h"
+#include "mfma_helpers.h"
 
 namespace {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned u32x3 __attribute__((ext_vector_type(3)));
-typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
+using namespace cp;
 
 constexpr int HW_COLS = 34;  // 32 output columns + 2 halo columns
 #ifndef CP_HALO_RING1
@@ -63,8 +61,6 @@ struct HaloK {
     uint8_t* head_lab;   // optional arg-max of the first head_lab_classes head channels
     int head_lab_classes;
 };
-
-#define CP_BARRIER() asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory")
 
 // Structure (v3).  Per tile the consumers run, for every 32-channel slice ("wide chunk"), 9 taps x 4
 // k8-steps of 4*TMW*TN MFMAs straight out of the LDS-resident halo, then (if the layer has the image

@@ -1,7 +1,7 @@
 // 3x3 / stride 1 / pad 1 convolution for the shallow, high-resolution layers (cout <= 64) on the bf16 matrix pipe:
 //   NP = 3  fp32-EQUIVALENT: every fp32 operand is split exactly into three bf16 terms (hi, mid, lo: 8 + 8 + 8 significand bits) and the
-//           six products lo*hi, hi*lo, mid*mid, mid*hi, hi*mid, hi*hi are accumulated in fp32 by v_mfma_f32_32x32x16_bf16 (the scheme of
-//           wino_gemm_split.hip; the three dropped products are <= 2^-24 of the full product -- the rounding an fp32 multiply makes anyway);
+//           six products lo*hi, hi*lo, mid*mid, mid*hi, hi*mid, hi*hi are accumulated in fp32 by v_mfma_f32_32x32x16_bf16 (the contract of
+//           the split: mfma_helpers.h);
 //   NP = 2  fp32-LEVEL with half the MFMAs: the fp16 two-way split of split_f16.h (hi = rn_f16(x), lo = rn_f16(x - hi): the operand to one fp32 ulp;
 //           products lo*hi, hi*lo, hi*hi on v_mfma_f32_32x32x16_f16).  The weights arrive multiplied by a power of two (their low parts stay
 //           normal numbers); the epilogue multiplies the accumulators by its inverse (HSplitK::descale, exact).
@@ -21,7 +21,7 @@
 // Accumulators are transposed as in conv_halo.hip (MFMA A = weights, B = pixels): lane = pixel, so the partial-conv tap mask, 9/count,
 // the CLADE table row, residual and stores are per lane with four consecutive channels in four consecutive registers.
 #include "common.h"
-#include "split_f16.h"
+#include "mfma_helpers.h"
 
 #include <algorithm>
 #include <cmath>
@@ -30,11 +30,7 @@
 
 namespace {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned u32x3 __attribute__((ext_vector_type(3)));
-typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
+using namespace cp;
 
 constexpr int COLS = 34;             // 32 output columns + 2 halo columns
 constexpr int TH = 8;                // output rows per tile (2 per consumer wave)
@@ -98,10 +94,10 @@ struct HSplitK {
 // cp_hs_trace_read (exported by that variant only): the time line of the two roles, phase by phase.
 __device__ unsigned long long hs_trace[2][2048];
 #define HST(tag) do { asm volatile("; HST " #tag ::: "memory"); if (hst_on && hst_i < 2046) hs_trace[hst_role][hst_i++] = ((unsigned long long)(tag) << 56) | (__builtin_readcyclecounter() & 0xffffffffffffffull); } while (0)
-#define CP_BARRIER() do { HST(0); asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); HST(1); } while (0)
+#define HS_BARRIER() do { HST(0); CP_BARRIER(); HST(1); } while (0)
 #else
 #define HST(tag)
-#define CP_BARRIER() asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory")
+#define HS_BARRIER() CP_BARRIER()
 #endif
 #ifndef HS_EPI_AUX
 #define HS_EPI_AUX 0   // cache policy bits of the generic epilogue's stores (variant builds: 2 = nt, 1 = sc0, 16 = sc1)
@@ -120,37 +116,6 @@ __device__ unsigned long long hs_prof[16];
 #define HSP(i)
 #define HSP_FLUSH(base)
 #endif
-
-__device__ __forceinline__ unsigned pack_hi16(unsigned a_lo, unsigned b_hi) { return __builtin_amdgcn_perm(b_hi, a_lo, 0x07060302u); }
-
-// exact three-way split of four floats into packed bf16 pairs (see wino_gemm_split.hip)
-__device__ __forceinline__ void split4(const float4 v, uint2& hi, uint2& mid, uint2& lo) {
-    const float x[4] = {v.x, v.y, v.z, v.w};
-    unsigned h[4], m[4], l[4];
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-        h[e] = __builtin_bit_cast(unsigned, x[e]);
-        const float r1 = x[e] - __builtin_bit_cast(float, h[e] & 0xffff0000u);
-        m[e] = __builtin_bit_cast(unsigned, r1);
-        const float r2 = r1 - __builtin_bit_cast(float, m[e] & 0xffff0000u);
-        l[e] = __builtin_bit_cast(unsigned, r2);
-    }
-    hi = make_uint2(pack_hi16(h[0], h[1]), pack_hi16(h[2], h[3]));
-    mid = make_uint2(pack_hi16(m[0], m[1]), pack_hi16(m[2], m[3]));
-    lo = make_uint2(pack_hi16(l[0], l[1]), pack_hi16(l[2], l[3]));
-}
-
-// round-to-nearest-even bf16 of four floats (finite inputs; NaN payloads are not preserved bit for bit, which no caller needs)
-__device__ __forceinline__ uint2 round4(const float4 v) {
-    const float x[4] = {v.x, v.y, v.z, v.w};
-    unsigned r[4];
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-        const unsigned u = __builtin_bit_cast(unsigned, x[e]);
-        r[e] = u + 0x7fffu + ((u >> 16) & 1u);
-    }
-    return make_uint2(pack_hi16(r[0], r[1]), pack_hi16(r[2], r[3]));
-}
 
 // planes of one float4 at `dst`, `dst + stride`, ...: the exact bf16 split (3), the fp16 two-way split (2) or rounded bf16 (1)
 template <int NP>
@@ -216,14 +181,6 @@ __global__ void hsplit_weights_kernel(const float* __restrict__ src, long long n
 // relu(t) - relu(-0.1 t) (casa_layer's LeakyReLU, casapose.py:98-105) in two instructions: max(t, 0.1 t).  Same value for every finite t -- t > 0: t
 // either way; t < 0: -fl(-0.1f * t) = fl(0.1f * t), rounding to nearest is symmetric -- only the sign of a zero result can differ (-0 for t = -0).
 __device__ __forceinline__ float leaky01(float t) { return fmaxf(t, 0.1f * t); }
-
-template <int I, int N, typename F>
-__device__ __forceinline__ void hs_static_for(F&& f) {
-    if constexpr (I < N) {
-        f(std::integral_constant<int, I>{});
-        hs_static_for<I + 1, N>(f);
-    }
-}
 
 // Taps per weight group (= per barrier phase).  32 output channels: the whole slice.  64 channels: the whole slice too where the LDS holds two
 // 9-tap groups (one or two operand planes: 36 / 72 KB of weight stages) -- round 5: with three taps per group (round 2-4) a slice was one loader-heavy
@@ -656,9 +613,9 @@ __global__ __launch_bounds__(512, 2) void conv_hsplit_kernel(const HSplitK p) {
         // ------------------------------------------------------------------ loaders ------------------------------------------------------
 #ifdef HS_LOADER_IDLE
         if (p.B > 0) {   // timing experiment: the consumers alone (LDS holds whatever it held)
-            if constexpr (BILINEAR) CP_BARRIER();
-            CP_BARRIER();
-            for (int gg = 0; gg < total_groups; ++gg) CP_BARRIER();
+            if constexpr (BILINEAR) HS_BARRIER();
+            HS_BARRIER();
+            for (int gg = 0; gg < total_groups; ++gg) HS_BARRIER();
             return;
         }
 #endif
@@ -1020,7 +977,6 @@ __global__ __launch_bounds__(512, 2) void conv_hsplit_kernel(const HSplitK p) {
             // two rows; arithmetic on float pairs (v_pk_mul_f32 / v_pk_fma_f32: the loader waves carry no MFMAs for them to disturb).
             // 5 x 17 blocks x 4 quads = 340 tasks on 256 threads.
             constexpr int NBX = COLS / 2, NTASK = (HR / 2) * NBX * 4, NT = (NTASK + 255) / 256;
-            typedef float f32x2 __attribute__((ext_vector_type(2)));
             unsigned t_low[NT], t_out[NT][4];
             int t_by[NT], t_bx[NT];
 #pragma unroll
@@ -1104,7 +1060,7 @@ __global__ __launch_bounds__(512, 2) void conv_hsplit_kernel(const HSplitK p) {
             step(cb);               // slice 1
             step_c(cb);
             issue_w(0);
-            CP_BARRIER();           // (the consumers run the same extra barrier) low-resolution stage 0 is complete
+            HS_BARRIER();           // (the consumers run the same extra barrier) low-resolution stage 0 is complete
             step_a(ca);             // interpolate slice 0, store tile 0's image / label halo
             store_w(0);
             if (cb.s < total_slices) {   // slice 1: its B-step without the extras of slice 0's tile being issued twice
@@ -1119,7 +1075,7 @@ __global__ __launch_bounds__(512, 2) void conv_hsplit_kernel(const HSplitK p) {
             step(cc);               // slice 2
             step_c(cc);
             if (total_groups > 1) issue_w(1);
-            CP_BARRIER();
+            HS_BARRIER();
             // from here: ca = slice gs + 1, cb = gs + 2, cc = gs + 3 at the first group of slice gs
             ca = cb;
             cb = cc;
@@ -1169,7 +1125,7 @@ __global__ __launch_bounds__(512, 2) void conv_hsplit_kernel(const HSplitK p) {
                 if (++lg == ngroups_tile) lg = 0;
                 HSP(2);
                 HST(5);
-                CP_BARRIER();
+                HS_BARRIER();
                 HSP(1);
             }
             if (esplit) loader_epilogue(0, true);   // the last tile's
@@ -1192,7 +1148,7 @@ __global__ __launch_bounds__(512, 2) void conv_hsplit_kernel(const HSplitK p) {
             issued = 2;
         }
         if (total_groups > 1) issue_w(1);
-        CP_BARRIER();
+        HS_BARRIER();
         int gs = 0, lg = 0;   // global slice counter / group index within the tile of the group being multiplied
         // Order inside a phase (round 4): every STORE (registers -> LDS) first, every ISSUE (global -> registers) after them, so that a vmcnt wait
         // before a store can only meet loads that are a whole phase old (the loads sit behind uniform branches; if the compiler cannot count
@@ -1231,7 +1187,7 @@ __global__ __launch_bounds__(512, 2) void conv_hsplit_kernel(const HSplitK p) {
             HST(5);
             if (++lg == ngroups_tile) lg = 0;
             HSP(0);
-            CP_BARRIER();
+            HS_BARRIER();
             HSP(1);
         }
         if (esplit) loader_epilogue(0, true);   // the last tile's
@@ -1243,9 +1199,9 @@ __global__ __launch_bounds__(512, 2) void conv_hsplit_kernel(const HSplitK p) {
     // ------------------------------------------------------------------ consumers: 4 waves x 2 rows --------------------------------------
 #ifdef HS_CONSUMER_IDLE
     if (p.B > 0) {   // timing experiment: the loaders alone
-        if constexpr (BILINEAR) CP_BARRIER();
-        CP_BARRIER();
-        for (int gg = 0; gg < total_groups; ++gg) CP_BARRIER();
+        if constexpr (BILINEAR) HS_BARRIER();
+        HS_BARRIER();
+        for (int gg = 0; gg < total_groups; ++gg) HS_BARRIER();
         return;
     }
 #endif
@@ -1293,8 +1249,8 @@ __global__ __launch_bounds__(512, 2) void conv_hsplit_kernel(const HSplitK p) {
 
     // ------------------------------------------------------------------ pipeline ---------------------------------------------------------
     TilePos ctile = first;
-    if constexpr (BILINEAR) CP_BARRIER();   // the loaders' hand-over of the first low-resolution stage (their interpolation reads other threads' stores)
-    CP_BARRIER();   // slice 0, the first weight group (and the first tile's image / label halo) are in LDS
+    if constexpr (BILINEAR) HS_BARRIER();   // the loaders' hand-over of the first low-resolution stage (their interpolation reads other threads' stores)
+    HS_BARRIER();   // slice 0, the first weight group (and the first tile's image / label halo) are in LDS
     HSP_DECL;
     int gs = 0, gg = 0;   // global slice / group counters
     for (int k = 0; k < my_tiles; ++k) {
@@ -1329,10 +1285,10 @@ __global__ __launch_bounds__(512, 2) void conv_hsplit_kernel(const HSplitK p) {
                 const unsigned char* wg = wst + (wres ? (unsigned)(c * GPS + g3) : (unsigned)(gg & 1)) * GROUP_B;
                 read_a(g3 * GT, 0);
                 ldw(wg, 0, 0);
-                hs_static_for<0, GT>([&](auto stc) {
+                static_for<0, GT>([&](auto stc) {
                     constexpr int st = decltype(stc)::value;
                     if (FAS == 2 && st + 1 < GT) read_a(g3 * GT + st + 1, (st + 1) & 1);
-                    hs_static_for<0, TN>([&](auto jc) {
+                    static_for<0, TN>([&](auto jc) {
                         constexpr int j = decltype(jc)::value;
                         constexpr int sub = st * TN + j;
                         if (sub + 1 < GSUB) ldw(wg, sub + 1, (sub + 1) & 1);
@@ -1374,7 +1330,7 @@ __global__ __launch_bounds__(512, 2) void conv_hsplit_kernel(const HSplitK p) {
                 HST(2);
                 if (g3 == GPS - 1 && c + 1 == nslices && !has_img) { finish_tile(n, y0, x0, cbase); HSP(3); HST(4); }
 #endif
-                CP_BARRIER();
+                HS_BARRIER();
                 HSP(4);
             }
         }
@@ -1424,7 +1380,7 @@ __global__ __launch_bounds__(512, 2) void conv_hsplit_kernel(const HSplitK p) {
             HSP(3);
             HST(4);
             ++gg;
-            CP_BARRIER();
+            HS_BARRIER();
             HSP(4);
         }
     }

@@ -8,11 +8,11 @@
 // (half-wave 0 takes tap 2s, half-wave 1 tap 2s+1; tap 49 does not exist: zero weights); the weight fragments come straight from L1/L2
 // through a 4-step register ring; accumulators are transposed (lane = pixel) so the epilogue moves 16 bytes per access.
 #include "common.h"
+#include "mfma_helpers.h"
 
 namespace {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
+using namespace cp;
 
 constexpr int TH = 4, TW = 32;                 // output tile
 constexpr int HR = 2 * TH + 5, HC = 2 * TW + 5;  // input halo (13 x 69 pixels of 4 floats)
@@ -34,8 +34,6 @@ struct StemK {
     float* out_act; int act_ld;
     int B, H, Wd, Ho, Wo, tiles_y, tiles_x, ntiles;
 };
-
-#define CP_BARRIER() asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory")
 
 __global__ __launch_bounds__(512, 4) void conv_stem_kernel(const StemK p) {
     extern __shared__ __attribute__((aligned(16))) float smem[];  // [2][HP][4]

@@ -1,6 +1,6 @@
 // The ResNet stem (`conv0`, resnet.py:248-249: 7x7 / stride 2 / pad 3, 4-channel image -> 64 channels, input batch-norm as a per-channel affine on
 // the real pixels, bn0 + ReLU in the epilogue) on the bf16 matrix pipe -- the arithmetic modes of conv_hsplit.hip:
-//   NP = 3  fp32-EQUIVALENT: every fp32 operand split exactly into three bf16 terms, six products accumulated in fp32;
+//   NP = 3  fp32-EQUIVALENT: every fp32 operand split exactly into three bf16 terms, six products accumulated in fp32 (mfma_helpers.h);
 //   NP = 2  fp32-LEVEL: the fp16 two-way split of split_f16.h, three products on v_mfma_f32_32x32x16_f16 (weights pre-multiplied by a power of two,
 //           accumulators multiplied by StemSK::descale);
 //   NP = 1  bf16 operands (round to nearest even), fp32 accumulation.
@@ -13,16 +13,14 @@
 //     life of the block -- six 16-byte fragments per step and wave from L1 would need the full L1 rate of a CU;
 //   * accumulators transposed (MFMA A = weights, B = pixels): lane = pixel, 16-byte epilogue accesses (conv_stem.hip's epilogue).
 #include "common.h"
-#include <cmath>
-#include "split_f16.h"
+#include "mfma_helpers.h"
 
 #include <algorithm>
+#include <cmath>
 
 namespace {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
+using namespace cp;
 
 constexpr int TH = 4, TW = 32;                   // output tile
 constexpr int HR = 2 * TH + 5, HC = 2 * TW + 5;  // input halo: 13 x 69 pixels
@@ -48,38 +46,6 @@ struct StemSK {
     float descale;           // NP = 2: 1 / (the power of two the weights were multiplied by); 1 otherwise
     uint32_t* mon;           // f16x2 range monitor slot (common.h) or null
 };
-
-#define CP_BARRIER() asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory")
-
-__device__ __forceinline__ unsigned ss_pack_hi16(unsigned a_lo, unsigned b_hi) { return __builtin_amdgcn_perm(b_hi, a_lo, 0x07060302u); }
-
-// exact three-way split of four floats into packed bf16 pairs (wino_gemm_split.hip)
-__device__ __forceinline__ void ss_split4(const float4 v, uint2& hi, uint2& mid, uint2& lo) {
-    const float x[4] = {v.x, v.y, v.z, v.w};
-    unsigned h[4], m[4], l[4];
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-        h[e] = __builtin_bit_cast(unsigned, x[e]);
-        const float r1 = x[e] - __builtin_bit_cast(float, h[e] & 0xffff0000u);
-        m[e] = __builtin_bit_cast(unsigned, r1);
-        const float r2 = r1 - __builtin_bit_cast(float, m[e] & 0xffff0000u);
-        l[e] = __builtin_bit_cast(unsigned, r2);
-    }
-    hi = make_uint2(ss_pack_hi16(h[0], h[1]), ss_pack_hi16(h[2], h[3]));
-    mid = make_uint2(ss_pack_hi16(m[0], m[1]), ss_pack_hi16(m[2], m[3]));
-    lo = make_uint2(ss_pack_hi16(l[0], l[1]), ss_pack_hi16(l[2], l[3]));
-}
-
-__device__ __forceinline__ uint2 ss_round4(const float4 v) {
-    const float x[4] = {v.x, v.y, v.z, v.w};
-    unsigned r[4];
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-        const unsigned u = __builtin_bit_cast(unsigned, x[e]);
-        r[e] = u + 0x7fffu + ((u >> 16) & 1u);
-    }
-    return make_uint2(ss_pack_hi16(r[0], r[1]), ss_pack_hi16(r[2], r[3]));
-}
 
 template <int NP>
 __global__ __launch_bounds__(512, 2) void conv_stem_split_kernel(const StemSK p) {
@@ -148,7 +114,7 @@ __global__ __launch_bounds__(512, 2) void conv_stem_split_kernel(const StemSK p)
                 if (NP == 2 && p.mon) l_amax = cp::amax4(l_amax, r);   // (uniform) the image through the input affine, as converted
                 if constexpr (NP == 3) {
                     uint2 a, b, c;
-                    ss_split4(r, a, b, c);
+                    split4(r, a, b, c);
                     *reinterpret_cast<uint2*>(h + e_lds[i]) = a;
                     *reinterpret_cast<uint2*>(h + PLANE_B + e_lds[i]) = b;
                     *reinterpret_cast<uint2*>(h + 2 * PLANE_B + e_lds[i]) = c;
@@ -158,7 +124,7 @@ __global__ __launch_bounds__(512, 2) void conv_stem_split_kernel(const StemSK p)
                     *reinterpret_cast<uint2*>(h + e_lds[i]) = a;
                     *reinterpret_cast<uint2*>(h + PLANE_B + e_lds[i]) = b;
                 } else {
-                    *reinterpret_cast<uint2*>(h + e_lds[i]) = ss_round4(r);
+                    *reinterpret_cast<uint2*>(h + e_lds[i]) = round4(r);
                 }
             }
         };

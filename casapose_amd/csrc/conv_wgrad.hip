@@ -15,13 +15,14 @@
 // atomics at the end); 4 consumer waves each hold one 32x32 accumulator, 4 producer waves gather
 // dY and im2col rows for the step after next while the current 32-pixel step is multiplied.
 #include "common.h"
+#include "mfma_helpers.h"
 
 #include <algorithm>
 #include <cstdlib>
 
 namespace {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
+using namespace cp;
 
 constexpr int BK = 32;
 constexpr int MAX_TAPS = 64;
@@ -80,8 +81,6 @@ __global__ __launch_bounds__(512, 2) void conv_wgrad_kernel(const WgK p) {
     const int total_steps = (p.M + 31) >> 5;
     const int nsteps = min(p.steps_per_split, total_steps - step0);
     if (nsteps <= 0) return;
-
-#define CP_BARRIER() asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory")
 
     if (producer) {
         const int col4 = tid & 7;
@@ -212,7 +211,6 @@ __global__ __launch_bounds__(512, 2) void conv_wgrad_kernel(const WgK p) {
         for (int s = 0; s < 16; ++s) acc = __builtin_amdgcn_mfma_f32_32x32x2f32(fa[s], fb[s], acc, 0, 0, 0);
         CP_BARRIER();
     }
-#undef CP_BARRIER
 
     // ---- accumulate into dWp: row = co, column = k (consecutive lanes -> consecutive k) --------
     const int k = (q0 + wk) * BK + lrow;
@@ -254,7 +252,6 @@ __global__ __launch_bounds__(512, 2) void wgrad_gemm128_kernel(const GemmT p) {
     if (nsteps <= 0) return;
     const int ntiles = p.tiles_co * p.tiles_k;
     int tile0 = (int)(s0 / p.spt), st0 = (int)(s0 - (long long)tile0 * p.spt);
-#define CP_BARRIER() asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory")
     if (wave >= 4) {
         const __amdgpu_buffer_rsrc_t rsa = __builtin_amdgcn_make_buffer_rsrc((void*)p.a, 0, p.a_bytes, 0x00020000);
         const __amdgpu_buffer_rsrc_t rsd = __builtin_amdgcn_make_buffer_rsrc((void*)p.d, 0, p.d_bytes, 0x00020000);
@@ -346,7 +343,6 @@ __global__ __launch_bounds__(512, 2) void wgrad_gemm128_kernel(const GemmT p) {
             ++tile;
         }
     }
-#undef CP_BARRIER
     if (st != 0) flush(tile);
 }
 

@@ -5,7 +5,7 @@
 //
 // in the packed [cout][ktot] layout of cp_conv2d_wgrad_f32, which this replaces for those layers (the reference obtains the product from
 // tf.GradientTape, train_casapose.py:594-611 -> Conv2DBackpropFilter).
-//   NP = 3  fp32-EQUIVALENT: both operands are split exactly into three bf16 terms, six products per fp32 product, fp32 accumulation
+//   NP = 3  fp32-EQUIVALENT: both operands are split exactly into three bf16 terms, six products per fp32 product, fp32 accumulation (mfma_helpers.h)
 //   NP = 1  operands rounded to bf16 (BASELINE.json configs[2])
 //   NP = 2  (round 6, planes = CP_PLANES_F16X2) both operands as fp16 pairs (split_f16.h): three exact products per fp32 product.  Both operands
 //           must sit inside fp16's band as they are: X is what the forward converted (its monitor watches it), dY carries the power of two the
@@ -24,7 +24,7 @@
 // and issue 6 MFMAs per (tap, 16 pixels).  One barrier per row.  The tile is flushed with fp32 atomics when the block moves to another
 // (ci, co) tile (summation order not fixed, as in cp_conv2d_wgrad_f32).
 #include "common.h"
-#include "split_f16.h"
+#include "mfma_helpers.h"
 
 #include <algorithm>
 #include <cstdlib>
@@ -32,10 +32,7 @@
 
 namespace {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef short s16x4 __attribute__((ext_vector_type(4)));
-typedef short s16x8 __attribute__((ext_vector_type(8)));
+using namespace cp;
 
 constexpr int SW = 64;            // output columns per row step
 constexpr int XC = SW + 2;        // input columns staged per row (one halo column each side)
@@ -89,65 +86,7 @@ __device__ __forceinline__ Unit decode(const WSplitK& p, int u) {
     return r;
 }
 
-#define WS_BARRIER() asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory")
-
-__device__ __forceinline__ unsigned pack_hi16(unsigned a_lo, unsigned b_hi) { return __builtin_amdgcn_perm(b_hi, a_lo, 0x07060302u); }
-
-// exact three-way split of 8 floats into packed bf16 (see conv_hsplit.hip / wino_gemm_split.hip)
-__device__ __forceinline__ void split8(const float4 v0, const float4 v1, uint4& hi, uint4& mid, uint4& lo) {
-    const float x[8] = {v0.x, v0.y, v0.z, v0.w, v1.x, v1.y, v1.z, v1.w};
-    unsigned h[8], m[8], l[8];
-#pragma unroll
-    for (int e = 0; e < 8; ++e) {
-        h[e] = __builtin_bit_cast(unsigned, x[e]);
-        const float r1 = x[e] - __builtin_bit_cast(float, h[e] & 0xffff0000u);
-        m[e] = __builtin_bit_cast(unsigned, r1);
-        const float r2 = r1 - __builtin_bit_cast(float, m[e] & 0xffff0000u);
-        l[e] = __builtin_bit_cast(unsigned, r2);
-    }
-    hi = make_uint4(pack_hi16(h[0], h[1]), pack_hi16(h[2], h[3]), pack_hi16(h[4], h[5]), pack_hi16(h[6], h[7]));
-    mid = make_uint4(pack_hi16(m[0], m[1]), pack_hi16(m[2], m[3]), pack_hi16(m[4], m[5]), pack_hi16(m[6], m[7]));
-    lo = make_uint4(pack_hi16(l[0], l[1]), pack_hi16(l[2], l[3]), pack_hi16(l[4], l[5]), pack_hi16(l[6], l[7]));
-}
-
-__device__ __forceinline__ uint4 round8(const float4 v0, const float4 v1) {
-    const float x[8] = {v0.x, v0.y, v0.z, v0.w, v1.x, v1.y, v1.z, v1.w};
-    unsigned r[8];
-#pragma unroll
-    for (int e = 0; e < 8; ++e) {
-        const unsigned u = __builtin_bit_cast(unsigned, x[e]);
-        r[e] = u + 0x7fffu + ((u >> 16) & 1u);
-    }
-    return make_uint4(pack_hi16(r[0], r[1]), pack_hi16(r[2], r[3]), pack_hi16(r[4], r[5]), pack_hi16(r[6], r[7]));
-}
-
-__device__ __forceinline__ void split4(const float4 v, uint2& hi, uint2& mid, uint2& lo) {
-    const float x[4] = {v.x, v.y, v.z, v.w};
-    unsigned h[4], m[4], l[4];
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-        h[e] = __builtin_bit_cast(unsigned, x[e]);
-        const float r1 = x[e] - __builtin_bit_cast(float, h[e] & 0xffff0000u);
-        m[e] = __builtin_bit_cast(unsigned, r1);
-        const float r2 = r1 - __builtin_bit_cast(float, m[e] & 0xffff0000u);
-        l[e] = __builtin_bit_cast(unsigned, r2);
-    }
-    hi = make_uint2(pack_hi16(h[0], h[1]), pack_hi16(h[2], h[3]));
-    mid = make_uint2(pack_hi16(m[0], m[1]), pack_hi16(m[2], m[3]));
-    lo = make_uint2(pack_hi16(l[0], l[1]), pack_hi16(l[2], l[3]));
-}
-
-__device__ __forceinline__ uint2 round4(const float4 v) {
-    const float x[4] = {v.x, v.y, v.z, v.w};
-    unsigned r[4];
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-        const unsigned u = __builtin_bit_cast(unsigned, x[e]);
-        r[e] = u + 0x7fffu + ((u >> 16) & 1u);
-    }
-    return make_uint2(pack_hi16(r[0], r[1]), pack_hi16(r[2], r[3]));
-}
-
+// planes of 8 channels of a pixel at `dst`, `dst + plane_stride`, ...: the exact bf16 split (3), the fp16 pair (2) or rounded bf16 (1): mfma_helpers.h
 template <int NP>
 __device__ __forceinline__ void store_planes(unsigned char* dst, int plane_stride, const float4 v0, const float4 v1) {
     if constexpr (NP == 2) {   // fp16 pair: hi, lo
@@ -164,23 +103,6 @@ __device__ __forceinline__ void store_planes(unsigned char* dst, int plane_strid
         *reinterpret_cast<uint4*>(dst + 2 * plane_stride) = l;
     } else {
         *reinterpret_cast<uint4*>(dst) = round8(v0, v1);
-    }
-}
-
-// 8 consecutive pixels (k) of this lane's channel: two transpose reads of 4 pixels each
-__device__ __forceinline__ bf16x8 frag_tr(const unsigned char* a) {
-    typedef s16x4 __attribute__((address_space(3))) * lds_p;
-    const s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_p)(a));
-    const s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_p)(a + 4 * 64));
-    const s16x8 v = __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7);
-    return __builtin_bit_cast(bf16x8, v);
-}
-
-template <int I, int N, typename F>
-__device__ __forceinline__ void static_for(F&& f) {
-    if constexpr (I < N) {
-        f(std::integral_constant<int, I>{});
-        static_for<I + 1, N>(f);
     }
 }
 
@@ -373,7 +295,7 @@ __global__ __launch_bounds__(512, 2) void wgrad_split_kernel(const WSplitK p) {
             for (int d = 0; d < D; ++d) {
                 write(d, T + d);
                 issue(d);
-                WS_BARRIER();
+                CP_BARRIER();
             }
         }
         if constexpr (NP == 2) {
@@ -444,7 +366,7 @@ __global__ __launch_bounds__(512, 2) void wgrad_split_kernel(const WSplitK p) {
         if (nu.pair != un.pair) flush(un);
         un = nu;
         for (int y = un.ya - 2; y < un.yb; ++y, ++T) {
-            WS_BARRIER();
+            CP_BARRIER();
             if (y < un.ya) continue;
 #ifdef WS_NOMFMA
             if (p.ktot >= 0) continue;
@@ -567,7 +489,7 @@ __global__ __launch_bounds__(512, 2) void wgrad_split_kernel(const WSplitK p) {
             }
         }
     }
-    for (; T < NTP; ++T) WS_BARRIER();
+    for (; T < NTP; ++T) CP_BARRIER();
     flush(un);
 }
 

@@ -8,10 +8,9 @@
 // batch, then the arithmetic and the stores.
 #pragma once
 #include "common.h"
+#include "mfma_helpers.h"
 
 namespace cp {
-
-typedef float f32x16_t __attribute__((ext_vector_type(16)));
 
 struct EpiArgs {
     const float* row_scale;  // [pixels] or null
@@ -56,7 +55,7 @@ __device__ __forceinline__ EpiRsrc epi_make(const EpiArgs& e, const void* any_va
 // factor computed by the caller (partial-conv 9/count) -- pass nullptr when unused.  `keep` receives the
 // activated values [16 rows][TN] of this lane (0 for rows/channels outside the tensor).
 template <int TN, int RB, typename RowPix>
-__device__ __forceinline__ void epilogue_block(const f32x16_t (&acc)[TN], const int (&co)[TN], const EpiArgs& e, const EpiRsrc& rr,
+__device__ __forceinline__ void epilogue_block(const f32x16 (&acc)[TN], const int (&co)[TN], const EpiArgs& e, const EpiRsrc& rr,
                                                RowPix rowpix, const float* rs_pre, float (&keep)[16][TN]) {
     constexpr unsigned OOB = 0x80000000u;
     static_assert(16 % RB == 0, "rows per batch must divide 16");  // RB trades registers for memory round trips

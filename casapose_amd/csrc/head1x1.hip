@@ -9,10 +9,11 @@
 // Weights and their gradient are addressed in the Keras layout [cin][cout] directly (no packing, no scatter).  (In inference the heads are
 // fused into the epilogues of decoder blocks 5 / 10; in training batch normalisation sits between, so they are separate passes.)
 #include "common.h"
+#include "mfma_helpers.h"
 
 namespace {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
+using namespace cp;
 constexpr int CIN = 32;
 
 // k-pair of MFMA m: channels (m, 16 + m) -- lane half h supplies channel 16 h + m, i.e. each lane needs 16 CONSECUTIVE channels

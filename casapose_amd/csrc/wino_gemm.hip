@@ -10,11 +10,12 @@
 //     a row-tile side by side), so V is fetched from memory once per XCD and re-read from that XCD's L2;
 //   * no per-row coordinate arithmetic at all: a row is a contiguous K-vector.
 #include "common.h"
+#include "mfma_helpers.h"
 #include <cstdlib>
 
 namespace {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
+using namespace cp;
 
 constexpr int BK = 32;
 constexpr int LS = 36;   // LDS row stride (floats)
@@ -42,17 +43,9 @@ __global__ __launch_bounds__(512, 4) void wino_gemm_kernel(const GemmK p) {
 
     // ---- this block's tile sequence: XCD x owns a contiguous run of the (m-major, n-minor) tile list; the blocks of
     // that XCD walk it in lock-step strides so that at any time they cover adjacent n-tiles of the same row-tiles
-    const int ntiles = p.tiles_m * p.tiles_n;
-    const int nx = 8;
-    const int xcd = blockIdx.x % nx, bidx = blockIdx.x / nx, nb = gridDim.x / nx;
-    const int q_ = ntiles / nx, r_ = ntiles % nx;
-    const int start = (xcd < r_) ? xcd * (q_ + 1) : r_ * (q_ + 1) + (xcd - r_) * q_;
-    const int cnt = q_ + (xcd < r_ ? 1 : 0);
-    const int my_items = (cnt > bidx) ? (cnt - bidx + nb - 1) / nb : 0;
-    const int total_chunks = my_items * p.nchunks;
+    const cp::TileRun run = cp::xcd_tile_run(p.tiles_m * p.tiles_n);
+    const int total_chunks = run.count * p.nchunks;
     if (total_chunks == 0) return;
-
-#define CP_BARRIER() asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory")
 
     if (producer) {
         const int col4 = tid & 7, rbase = tid >> 3;  // 32 rows x 8 float4 per pass, two passes per operand
@@ -65,7 +58,7 @@ __global__ __launch_bounds__(512, 4) void wino_gemm_kernel(const GemmK p) {
             if (++q >= p.nchunks) {
                 q = 0;
                 ++it;
-                const int tile = start + bidx + it * nb;
+                const int tile = run.tile(it);
                 const int tm = tile / p.tiles_n, tn = tile - tm * p.tiles_n;
                 const int m0 = tm * BM, n0 = tn * BN;
                 const unsigned gofs = (unsigned)(m0 / p.group_rows) * p.b_group_stride_bytes;
@@ -140,7 +133,7 @@ __global__ __launch_bounds__(512, 4) void wino_gemm_kernel(const GemmK p) {
         CP_BARRIER();
         if (c + 1 < total_chunks) read_frags(buf ^ 1, 0, 0);
         if (++q == p.nchunks) {  // tile finished: store and restart the accumulator (the producers are already a tile ahead)
-            const int tile = start + bidx + it * nb;
+            const int tile = run.tile(it);
             const int tm = tile / p.tiles_n, tn = tile - tm * p.tiles_n;
             const int col = tn * BN + wn * 32 + lrow;
             float* dst = p.C + (size_t)(tm * BM + wm * 32 + (lane >> 5) * 4) * p.N + col;
@@ -154,7 +147,6 @@ __global__ __launch_bounds__(512, 4) void wino_gemm_kernel(const GemmK p) {
             ++it;
         }
     }
-#undef CP_BARRIER
 }
 
 }  // namespace

@@ -1,10 +1,8 @@
 // Grouped GEMM of the Winograd path on the bf16 matrix pipe with fp32-equivalent accuracy (OPT-IN):
 //     M[p][t][n] = sum_k V[p][t][k] * U[p][n][k]
-// Every fp32 operand is split EXACTLY into three bf16 terms (8 + 8 + 8 significand bits):
-//     hi = trunc_bf16(x),  mid = trunc_bf16(x - hi),  lo = x - hi - mid
-// and the six products  hi*hi, hi*mid, mid*hi, mid*mid, hi*lo, lo*hi  are accumulated in fp32 by v_mfma_f32_32x32x16_bf16.  Each
-// product of two bf16 numbers is exact in fp32; the three dropped products (mid*lo, lo*mid, lo*lo) are <= 2^-24 of the full product,
-// i.e. the rounding an fp32 multiply makes anyway.  Six bf16 MFMAs of K = 16 cost 6 x 32 cycles against 8 x 64 for the fp32 MFMA.
+// Every fp32 operand is split EXACTLY into three bf16 terms and six bf16 x bf16 products, each exact in fp32, are accumulated in fp32 by
+// v_mfma_f32_32x32x16_bf16: the contract and the product order are stated once, in mfma_helpers.h.  Six bf16 MFMAs of K = 16 cost 6 x 32
+// cycles against 8 x 64 for the fp32 MFMA.
 //
 // Sizing (why this is not wino_gemm.hip with another instruction): at this MFMA rate a 32x32 per-wave tile would need ~3x the LDS
 // bandwidth of a CU for its fragment reads, so a block is 128 x 128 with four consumer waves of 64 x 64.  The activations (A) stay fp32 in
@@ -14,7 +12,7 @@
 // chunk ahead (issued unconditionally: a branch around the loads makes the compiler's wait counts conservative).  One persistent block per
 // CU.  Measured 178-195 TFLOP/s-equivalent against 115-120 for the fp32 MFMA kernel = ~1.1 PFLOP/s of bf16 MFMA work.  Variants measured within 3 %: all six planes staged in LDS (182); fp32 in LDS, split in the consumers (149).
 #include "common.h"
-#include "split_f16.h"
+#include "mfma_helpers.h"
 
 #include <algorithm>
 #include <cmath>
@@ -23,8 +21,7 @@
 
 namespace {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
+using namespace cp;
 
 constexpr int BK = 32;          // k per chunk
 constexpr int BM = 128, BN = 128;
@@ -33,25 +30,6 @@ constexpr int SPLIT_BYTES = BM * ROWB;          // one split plane of a 128-row 
 constexpr int TILE_BYTES = 3 * SPLIT_BYTES;     // hi, mid, lo
 constexpr int STAGE_BYTES = TILE_BYTES;         // only A is staged; B fragments come pre-split straight from L2
 constexpr int NSTAGE = 3;
-
-// exact three-way split of four floats into packed bf16 pairs: hi = top 16 bits of x, mid = top 16 bits of x - hi, lo = top 16 bits of
-// x - hi - mid (that last remainder has at most 8 significant bits, so taking its top half is exact).  v_perm_b32 packs the high halves.
-__device__ __forceinline__ void split4(const float4 v, uint2& hi, uint2& mid, uint2& lo) {
-    const float x[4] = {v.x, v.y, v.z, v.w};
-    unsigned h[4], m[4], l[4];
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-        h[e] = __builtin_bit_cast(unsigned, x[e]);
-        const float r1 = x[e] - __builtin_bit_cast(float, h[e] & 0xffff0000u);
-        m[e] = __builtin_bit_cast(unsigned, r1);
-        const float r2 = r1 - __builtin_bit_cast(float, m[e] & 0xffff0000u);
-        l[e] = __builtin_bit_cast(unsigned, r2);
-    }
-    // perm(src0, src1, sel): byte k of the result = byte sel[k] of {src0 (bytes 4-7), src1 (bytes 0-3)}; 0x07060302 = [hi16(src1), hi16(src0)]
-    hi = make_uint2(__builtin_amdgcn_perm(h[1], h[0], 0x07060302u), __builtin_amdgcn_perm(h[3], h[2], 0x07060302u));
-    mid = make_uint2(__builtin_amdgcn_perm(m[1], m[0], 0x07060302u), __builtin_amdgcn_perm(m[3], m[2], 0x07060302u));
-    lo = make_uint2(__builtin_amdgcn_perm(l[1], l[0], 0x07060302u), __builtin_amdgcn_perm(l[3], l[2], 0x07060302u));
-}
 
 struct SplitK {
     const float* A;
@@ -113,21 +91,13 @@ __global__ __launch_bounds__(512, 1) void wino_gemm_split_kernel(const SplitK p)
 
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const bool producer = wave >= 4;
+
+    // tile sequence: XCD x owns a contiguous run of the (m-major, n-minor) tile list (common.h)
+    const cp::TileRun run = cp::xcd_tile_run(p.tiles_m * p.tiles_n);
+    const int total_chunks = run.count * p.nchunks;
+    if (total_chunks == 0) return;
     const int tid = threadIdx.x & 255;
     const int lane = tid & 63;
-
-    // tile sequence: XCD x owns a contiguous run of the (m-major, n-minor) tile list (same scheme as wino_gemm.hip)
-    const int ntiles = p.tiles_m * p.tiles_n;
-    const int nx = 8;
-    const int xcd = blockIdx.x % nx, bidx = blockIdx.x / nx, nb = gridDim.x / nx;
-    const int q_ = ntiles / nx, r_ = ntiles % nx;
-    const int start = (xcd < r_) ? xcd * (q_ + 1) : r_ * (q_ + 1) + (xcd - r_) * q_;
-    const int cnt = q_ + (xcd < r_ ? 1 : 0);
-    const int my_items = (cnt > bidx) ? (cnt - bidx + nb - 1) / nb : 0;
-    const int total_chunks = my_items * p.nchunks;
-    if (total_chunks == 0) return;
-
-#define CP_BARRIER() asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory")
 
     if (producer) {
         if constexpr (F16) cp::f16_overflow_clamps();
@@ -152,7 +122,7 @@ __global__ __launch_bounds__(512, 1) void wino_gemm_split_kernel(const SplitK p)
             if (++q >= p.nchunks) {
                 q = 0;
                 ++it;
-                const int tile = start + bidx + it * nb;
+                const int tile = run.tile(it);
                 const int tm = tile / p.tiles_n;
                 const int m0 = tm * BM;
 #pragma unroll
@@ -246,7 +216,7 @@ __global__ __launch_bounds__(512, 1) void wino_gemm_split_kernel(const SplitK p)
         if (++f_q >= p.nchunks) {
             f_q = 0;
             ++f_it;
-            const int tile = start + bidx + f_it * nb;
+            const int tile = run.tile(f_it);
             const int tm = tile / p.tiles_n, tn = tile - tm * p.tiles_n;
             const unsigned g = (unsigned)((tm * BM) / p.group_rows);
 #pragma unroll
@@ -295,7 +265,7 @@ __global__ __launch_bounds__(512, 1) void wino_gemm_split_kernel(const SplitK p)
         CP_BARRIER();
         buf = nbuf;
         if (++q == p.nchunks) {
-            const int tile = start + bidx + it * nb;
+            const int tile = run.tile(it);
             const int tm = tile / p.tiles_n, tn = tile - tm * p.tiles_n;
 #pragma unroll
             for (int i = 0; i < 2; ++i)
@@ -323,7 +293,6 @@ __global__ __launch_bounds__(512, 1) void wino_gemm_split_kernel(const SplitK p)
         chunk(c + 1, 1);
     }
     if (c < total_chunks) chunk(c, 0);
-#undef CP_BARRIER
 }
 
 }  // namespace

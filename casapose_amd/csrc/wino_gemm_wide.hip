@@ -10,7 +10,7 @@
 // Only the two-plane fp16 split fits (a third plane would need 220 KB); the exact bf16 split and every N that is not a multiple of 256 stay on
 // wino_gemm_split.hip.  Same arithmetic, same results (tests/test_gpu_f16x2.py compares the two kernels bit for bit).
 #include "common.h"
-#include "split_f16.h"
+#include "mfma_helpers.h"
 
 #include <algorithm>
 #include <cstdlib>
@@ -27,8 +27,7 @@
 
 namespace {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));   // (container type of a 16-byte fragment; the MFMA below reads it as 8 x fp16)
+using namespace cp;
 
 constexpr int BK = 32;
 constexpr int BM = 128, BN = 256;
@@ -51,8 +50,6 @@ struct WideK {
     uint32_t* mon;   // f16x2 range monitor slot (common.h) or null: max |A| over every row the producers convert
 };
 
-#define CP_BARRIER() asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory")
-
 // MON: the producers also fold max |A| into the f16x2 range monitor slot p.mon (a compile-time variant: a run-time branch inside store() would put
 // basic-block boundaries between the DMA pieces and the hand-counted waits that cover them, tests/test_asm_invariants.py)
 template <bool MON>
@@ -63,19 +60,13 @@ __global__ __launch_bounds__(512, 1) void wino_gemm_wide_kernel(const WideK p) {
 
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const bool producer = wave >= 4;
+
+    // tile sequence: XCD x owns a contiguous run of the (m-major, n-minor) tile list (common.h)
+    const cp::TileRun run = cp::xcd_tile_run(p.tiles_m * p.tiles_n);
+    const int total_chunks = run.count * p.nchunks;
+    if (total_chunks == 0) return;
     const int tid = threadIdx.x & 255;
     const int lane = tid & 63;
-
-    // tile sequence: XCD x owns a contiguous run of the (m-major, n-minor) tile list (as wino_gemm_split.hip)
-    const int ntiles = p.tiles_m * p.tiles_n;
-    const int nx = 8;
-    const int xcd = blockIdx.x % nx, bidx = blockIdx.x / nx, nb = gridDim.x / nx;
-    const int q_ = ntiles / nx, r_ = ntiles % nx;
-    const int start = (xcd < r_) ? xcd * (q_ + 1) : r_ * (q_ + 1) + (xcd - r_) * q_;
-    const int cnt = q_ + (xcd < r_ ? 1 : 0);
-    const int my_items = (cnt > bidx) ? (cnt - bidx + nb - 1) / nb : 0;
-    const int total_chunks = my_items * p.nchunks;
-    if (total_chunks == 0) return;
     const unsigned ks_total = (unsigned)(p.K / 16);
 
     if (producer) {
@@ -92,7 +83,7 @@ __global__ __launch_bounds__(512, 1) void wino_gemm_wide_kernel(const WideK p) {
             if (++q >= p.nchunks) {
                 q = 0;
                 ++it;
-                const int tile = start + bidx + it * nb;
+                const int tile = run.tile(it);
                 const int m0 = (tile / p.tiles_n) * BM;
 #pragma unroll
                 for (int i = 0; i < 4; ++i) aoff[i] = ((unsigned)(m0 + rbase + 32 * i) * (unsigned)p.K + col4 * 4) * 4u;
@@ -128,7 +119,7 @@ __global__ __launch_bounds__(512, 1) void wino_gemm_wide_kernel(const WideK p) {
             if (++d_q >= p.nchunks) {
                 d_q = 0;
                 ++d_it;
-                const int tile = start + bidx + d_it * nb;
+                const int tile = run.tile(d_it);
                 const int tm = tile / p.tiles_n, tn = tile - tm * p.tiles_n;
                 const unsigned g = (unsigned)((tm * BM) / p.group_rows);
                 d_base = (g * (unsigned)p.nb32 + (unsigned)(tn * 8)) * ks_total * 3u * 1024u;
@@ -244,7 +235,7 @@ __global__ __launch_bounds__(512, 1) void wino_gemm_wide_kernel(const WideK p) {
         asm volatile("s_barrier" ::: "memory");
         buf = nbuf;
         if (++q == p.nchunks) {
-            const int tile = start + bidx + it * nb;
+            const int tile = run.tile(it);
             const int tm = tile / p.tiles_n, tn = tile - tm * p.tiles_n;
 #pragma unroll
             for (int i = 0; i < 2; ++i)
@@ -261,7 +252,6 @@ __global__ __launch_bounds__(512, 1) void wino_gemm_wide_kernel(const WideK p) {
             ++it;
         }
     }
-#undef CP_BARRIER
 }
 
 }  // namespace

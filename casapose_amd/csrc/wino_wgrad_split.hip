@@ -4,7 +4,7 @@
 //
 // (dM = A dY A^T from cp_wino_dy_transform_f32, V = the forward's transformed input, kept per layer) that cp_conv2d_wgrad_f32 computes in its
 // grouped mode with fp32 MFMAs (wgrad_gemm128_kernel, 6.3 ms of a 62 ms training step).  Here every fp32 operand is split EXACTLY into three bf16
-// terms and six bf16 x bf16 products (each exact in fp32) are accumulated in fp32 -- the arithmetic of wino_gemm_split.hip / conv_wgrad_split.hip,
+// terms and six bf16 x bf16 products (each exact in fp32) are accumulated in fp32 -- the exact split of mfma_helpers.h,
 // fp32-equivalent -- or, with planes = 1, operands are rounded to bf16 (CASAPOSE_CONV_MODE=bf16).  The reference obtains this product from
 // tf.GradientTape (train_casapose.py:594-611 -> Conv2DBackpropFilter of the layers.Conv2D call sites of resnet.py:97-103, casapose.py:71-74).
 // Round 6, planes = CP_PLANES_F16X2: both operands as fp16 pairs (split_f16.h: hi = rn_f16(x s), lo = rn_f16(x s - hi), three exact products per
@@ -22,17 +22,14 @@
 // block a contiguous share of the (tile, slab) stream: concurrent blocks then sat in different tiles, nothing was shared and the kernel ran at
 // the 3.7 GB of a 4x re-read: 125 TF/s-equivalent, 177 with bf16 operands.)  An item ends with fp32 atomics into the zeroed dU.
 #include "common.h"
-#include "split_f16.h"
+#include "mfma_helpers.h"
 
 #include <algorithm>
 #include <cmath>
 
 namespace {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef short s16x4 __attribute__((ext_vector_type(4)));
-typedef short s16x8 __attribute__((ext_vector_type(8)));
+using namespace cp;
 
 constexpr int TS = 32;              // rows (tiles of the Winograd grid) per slab
 constexpr int BLK = 4;              // 32-channel blocks per operand and block tile: 128 columns
@@ -51,38 +48,7 @@ struct TnK {
     float sa, sb, descale;         // f16x2: powers of two on the operands, 1 / (sa sb) on the accumulators
 };
 
-#define TN_BARRIER() asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory")
-
-__device__ __forceinline__ unsigned pack_hi16(unsigned a_lo, unsigned b_hi) { return __builtin_amdgcn_perm(b_hi, a_lo, 0x07060302u); }
-
-// exact three-way split of 8 floats into packed bf16 planes: hi = top 16 bits, mid = top 16 bits of x - hi, lo = top 16 bits of the rest
-__device__ __forceinline__ void split8(const float4 v0, const float4 v1, uint4& hi, uint4& mid, uint4& lo) {
-    const float x[8] = {v0.x, v0.y, v0.z, v0.w, v1.x, v1.y, v1.z, v1.w};
-    unsigned h[8], m[8], l[8];
-#pragma unroll
-    for (int e = 0; e < 8; ++e) {
-        h[e] = __builtin_bit_cast(unsigned, x[e]);
-        const float r1 = x[e] - __builtin_bit_cast(float, h[e] & 0xffff0000u);
-        m[e] = __builtin_bit_cast(unsigned, r1);
-        const float r2 = r1 - __builtin_bit_cast(float, m[e] & 0xffff0000u);
-        l[e] = __builtin_bit_cast(unsigned, r2);
-    }
-    hi = make_uint4(pack_hi16(h[0], h[1]), pack_hi16(h[2], h[3]), pack_hi16(h[4], h[5]), pack_hi16(h[6], h[7]));
-    mid = make_uint4(pack_hi16(m[0], m[1]), pack_hi16(m[2], m[3]), pack_hi16(m[4], m[5]), pack_hi16(m[6], m[7]));
-    lo = make_uint4(pack_hi16(l[0], l[1]), pack_hi16(l[2], l[3]), pack_hi16(l[4], l[5]), pack_hi16(l[6], l[7]));
-}
-
-__device__ __forceinline__ uint4 round8(const float4 v0, const float4 v1) {   // round to nearest even
-    const float x[8] = {v0.x, v0.y, v0.z, v0.w, v1.x, v1.y, v1.z, v1.w};
-    unsigned r[8];
-#pragma unroll
-    for (int e = 0; e < 8; ++e) {
-        const unsigned u = __builtin_bit_cast(unsigned, x[e]);
-        r[e] = u + 0x7fffu + ((u >> 16) & 1u);
-    }
-    return make_uint4(pack_hi16(r[0], r[1]), pack_hi16(r[2], r[3]), pack_hi16(r[4], r[5]), pack_hi16(r[6], r[7]));
-}
-
+// planes of 8 channels of a row: the fp16 pair of `s` times the values, the exact bf16 split (3) or rounded bf16 (1): mfma_helpers.h
 template <int NP, bool F16>
 __device__ __forceinline__ void store_planes(unsigned char* dst, int plane_stride, const float4 v0, const float4 v1, float s) {
     if constexpr (F16) {
@@ -100,15 +66,6 @@ __device__ __forceinline__ void store_planes(unsigned char* dst, int plane_strid
     } else {
         *reinterpret_cast<uint4*>(dst) = round8(v0, v1);
     }
-}
-
-// 8 consecutive rows (the MFMA's k) of this lane's channel: two transpose reads of 4 rows each
-__device__ __forceinline__ bf16x8 frag_tr(const unsigned char* a) {
-    typedef s16x4 __attribute__((address_space(3))) * lds_p;
-    const s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_p)(a));
-    const s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_p)(a + 4 * 64));
-    const s16x8 v = __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7);
-    return __builtin_bit_cast(bf16x8, v);
 }
 
 struct Item {
@@ -197,7 +154,7 @@ __global__ __launch_bounds__(512, 1) void wino_wgrad_split_kernel(const TnK p) {
             for (int d = 0; d < D; ++d) {
                 write(d, T + d);
                 issue(d);
-                TN_BARRIER();
+                CP_BARRIER();
             }
         }
         return;
@@ -236,7 +193,7 @@ __global__ __launch_bounds__(512, 1) void wino_wgrad_split_kernel(const TnK p) {
     for (int q = bid; q < p.items; q += G) {
       const Item un = decode(p, q);
       for (int s = 0; s < un.len; ++s, ++T) {
-        TN_BARRIER();
+        CP_BARRIER();
         const unsigned char* abase = As + (T & 1) * SLOT + (2 * wn) * ROWB + lane_off;
         const unsigned char* bbase = Bs + (T & 1) * SLOT + (2 * wk) * ROWB + lane_off;
         bf16x8 a[2][2][NP], b[2][2][NP];   // [sub-step parity][block][plane]
@@ -281,7 +238,7 @@ __global__ __launch_bounds__(512, 1) void wino_wgrad_split_kernel(const TnK p) {
       }
       flush(un);
     }
-    for (; T < NTP; ++T) TN_BARRIER();
+    for (; T < NTP; ++T) CP_BARRIER();
 }
 
 template <int NP, bool F16>

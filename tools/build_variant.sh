@@ -6,14 +6,16 @@ R=${GRAFT_REPO_ROOT:-$(cd "$(dirname "$0")/.." && pwd)}; C=$R/casapose_amd/csrc;
 FILES=${FILES:-"conv_f32 conv_halo"}
 mkdir -p $R/variants
 make -C $C -s
+# the source list, the compiler and the flags are the Makefile's own
+srcs=$(make -C $C -s print-SRCS); hipcc=$(make -C $C -s print-HIPCC); flags=$(make -C $C -s print-FLAGS)
 objs=""
-for n in capi conv_f32 conv_halo conv_stem aux_kernels ls_vote ccl ransac_vote train_kernels conv_wgrad loss_kernels wino wino_gemm wino_gemm_split wino_gemm_wide guided_bilinear conv_hsplit conv_wgrad_split head1x1 loss_functional wino_wgrad_split conv_bf16d conv_stem_split; do
+for n in ${srcs//.hip/}; do
   if echo " $FILES " | grep -q " $n "; then
-    /opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC -I$R/include -munsafe-fp-atomics -fno-slp-vectorize "$@" -c $C/$n.hip -o /tmp/${n}_$name.o
+    $hipcc $flags "$@" -c $C/$n.hip -o /tmp/${n}_$name.o
     objs="$objs /tmp/${n}_$name.o"
   else
     objs="$objs $C/build/$n.o"
   fi
 done
-/opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -fPIC $objs -o $R/variants/lib_$name.so
+$hipcc --offload-arch=gfx950 -shared -fPIC $objs -o $R/variants/lib_$name.so
 echo built variants/lib_$name.so
