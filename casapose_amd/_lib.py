@@ -257,6 +257,10 @@ SYMBOLS = [
     ("cp_aug_finish", _i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp]),
     ("cp_frames_to_input_f32", _i, [_vp, _i, _i, _i, _i, _ll, _ll, _f, _f, _vp, _vp]),
     ("cp_pose_loss_f32", _i, [_vp, _i, _i, _i, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _f, _f, _f, _vp, _vp, _i, _i, _vp, _vp, _vp]),
+    # ---- pose statistics (csrc/pose_eval.hip) ----
+    ("cp_pose_eval_workspace_bytes", C.c_size_t, [_i, _i, _i]),
+    ("cp_pose_eval_est_tile", _i, []),
+    ("cp_pose_eval_f32", _i, [_vp, _vp, _vp, _i, _i, _vp, _i, _f, _vp, _vp, _vp, _vp, _vp]),
 ]
 
 _lib: Optional[C.CDLL] = None

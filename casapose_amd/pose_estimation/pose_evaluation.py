@@ -151,24 +151,28 @@ def _eval_points(object_points_3d, evaluation_points, object_points_3d_count, b,
 
 
 def evaluate_pose_estimates(points_estimated, poses, poses_gt, target_seg, object_points_3d, camera_data, diameters,
-                            evaluation_points=None, object_points_3d_count=None, min_num: int = 20):
+                            evaluation_points=None, object_points_3d_count=None, min_num: int = 20, evaluator=None):
     """pose_evaluation.py:100-160: statistics for poses that were already estimated (the estimate_coords path of
     test_casapose.py:336-348).  -> ([valid_2d, valid_3d, valid_pose_count, zeros, err_2d, err_3d, missing, false_pos], poses,
-    points_estimated)."""
+    points_estimated).  evaluator: a DevicePoseEvaluator (device_evaluation.py) computes the statistics on the GPU from the meshes it
+    holds instead of evaluate_poses on the host."""
     G = _np(poses_gt)
     b, oc, ic = G.shape[0], G.shape[1], G.shape[2]
     avail = _objects_available(target_seg, min_num)
-    pts, cnt = _eval_points(object_points_3d, evaluation_points, object_points_3d_count, b, oc, ic)
     P = _np(poses).reshape(b, oc, 3, 4)
-    e2, e3, v2, v3, miss, vcount, fp = evaluate_poses(P, G, points_estimated, pts, cnt, camera_data, diameters, avail, 5.0)
+    if evaluator is not None:
+        e2, e3, v2, v3, miss, vcount, fp = evaluator.evaluate(P, G, camera_data, diameters, avail, 5.0)
+    else:
+        pts, cnt = _eval_points(object_points_3d, evaluation_points, object_points_3d_count, b, oc, ic)
+        e2, e3, v2, v3, miss, vcount, fp = evaluate_poses(P, G, points_estimated, pts, cnt, camera_data, diameters, avail, 5.0)
     return [v2, v3, vcount, np.zeros_like(v2), e2, e3, miss, fp], poses, points_estimated
 
 
 def estimate_and_evaluate_poses(output_seg, target_seg, output_vertex, poses_gt, object_points_3d, camera_data, diameters, offsets,
                                 evaluation_points=None, object_points_3d_count=None, points_estimated=None, min_num: int = 20,
-                                draws=None):
+                                draws=None, evaluator=None):
     """pose_evaluation.py:11-97: RANSAC keypoint voting on the arg-max mask (unless points are given), host PnP, then
-    evaluate_poses.  output_seg [b,h,w,K], output_vertex [b,h,w,2*kp] device tensors."""
+    evaluate_poses (on the GPU with a DevicePoseEvaluator as `evaluator`).  output_seg [b,h,w,K], output_vertex [b,h,w,2*kp] device tensors."""
     import torch
 
     from .ransac_voting import ransac_voting_layer_all_masks
@@ -193,8 +197,11 @@ def estimate_and_evaluate_poses(output_seg, target_seg, output_vertex, poses_gt,
     else:
         points_estimated = _np(points_estimated) * np.array([[[[h, w]]]], np.float64)
     poses, false_positive_mask = estimate_poses(points_estimated, object_points_3d, camera_data, avail, offsets)
-    pts, cnt = _eval_points(object_points_3d, evaluation_points, object_points_3d_count, b, oc, ic)
-    e2, e3, v2, v3, miss, vcount, fp = evaluate_poses(poses, G, points_estimated, pts, cnt, camera_data, diameters, avail, 5.0)
+    if evaluator is not None:
+        e2, e3, v2, v3, miss, vcount, fp = evaluator.evaluate(poses, G, camera_data, diameters, avail, 5.0)
+    else:
+        pts, cnt = _eval_points(object_points_3d, evaluation_points, object_points_3d_count, b, oc, ic)
+        e2, e3, v2, v3, miss, vcount, fp = evaluate_poses(poses, G, points_estimated, pts, cnt, camera_data, diameters, avail, 5.0)
     return [v2, v3, vcount, false_positive_mask, e2, e3, miss, fp], poses, points_estimated
 
 

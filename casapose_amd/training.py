@@ -222,9 +222,10 @@ def poses_from_coords(coords_yx, objects_available, batch, rng=None) -> Tuple[np
     return poses, pts
 
 
-def test_step(net, batch, opt, loss_factors, evaluation_points=None, object_points_3d_count=None):
+def test_step(net, batch, opt, loss_factors, evaluation_points=None, object_points_3d_count=None, evaluator=None):
     """One evaluation step of test_casapose.py (:268-384): inference forward, (component-filtered) LS keypoint voting or
-    RANSAC voting, host PnP, losses and the eight per-object pose statistics.
+    RANSAC voting, host PnP, losses and the eight per-object pose statistics (computed on the GPU with a DevicePoseEvaluator as `evaluator`, or,
+    with CASAPOSE_DEVICE_EVAL=1 and evaluation meshes, with the one device_evaluation.evaluator_from_environment keeps for them).
     Returns (losses [5 floats], pose_stats [8 arrays of oc], poses [B,oc,3,4], points, seconds)."""
     import time
 
@@ -232,6 +233,10 @@ def test_step(net, batch, opt, loss_factors, evaluation_points=None, object_poin
     from .pose_estimation.voting_layers_2d import CoordLSVotingWeighted
 
     dev = net.device
+    if evaluator is None:
+        from .pose_estimation.device_evaluation import evaluator_from_environment
+
+        evaluator = evaluator_from_environment(evaluation_points, object_points_3d_count, dev)   # None unless CASAPOSE_DEVICE_EVAL=1
     img = batch["img"].to(device=dev, dtype=torch.float32).contiguous()
     seg = batch["target_seg"].to(device=dev, dtype=torch.float32)
     K, kp = net.seg_dim, int(getattr(opt, "no_points", 9))
@@ -255,12 +260,13 @@ def test_step(net, batch, opt, loss_factors, evaluation_points=None, object_poin
         plan, _ = net.training_plan(img.shape[0], img.shape[1], img.shape[2])
         poses, pts = poses_from_coords(coords, plan.objects_available, batch)
         stats, poses, pts = evaluate_pose_estimates(pts, poses, batch["poses_gt"], seg, batch["keypoints3d"], batch["cam_mat"], batch["diameters"],
-                                                    evaluation_points=evaluation_points, object_points_3d_count=object_points_3d_count, min_num=1)
+                                                    evaluation_points=evaluation_points, object_points_3d_count=object_points_3d_count, min_num=1,
+                                                    evaluator=evaluator)
         poses = np.asarray(poses).reshape(poses.shape[0], poses.shape[1], 3, 4)
     else:
         stats, poses, pts = estimate_and_evaluate_poses(o_seg, seg, o_dirs, batch["poses_gt"], batch["keypoints3d"], batch["cam_mat"], batch["diameters"],
                                                         batch["offsets"], evaluation_points=evaluation_points, object_points_3d_count=object_points_3d_count,
-                                                        min_num=1)
+                                                        min_num=1, evaluator=evaluator)
     torch.cuda.synchronize(dev)
     return losses, stats, poses, pts, time.perf_counter() - t0
 

@@ -773,6 +773,31 @@ int cp_aug_finish(const uint8_t* rgb, const uint8_t* lab, const cp_aug_image* pr
 int cp_frames_to_input_f32(const uint8_t* src, int batch, int h, int w, int channels, long long src_pitch, long long src_stride,
                            float norm0, float norm1, float* out, void* stream);
 
+/* ---- pose statistics (csrc/pose_eval.hip) ----------------------------------------------------------------------------------------
+ * The per-(image, object) record of map_estimates (ransac_voting.py:561-625); evaluate_poses (:627-687) is the sum of the records over the
+ * batch.  Everything is device memory and fp32 unless noted.
+ *   points     [objects][vmax][3]  evaluation meshes; rows counts[o] .. vmax-1 are never read
+ *   counts     int32 [objects]     vertices per mesh.  The library cannot see it: counts[o] > vmax is the caller's error and is clamped to vmax
+ *                                  in the kernel (negative values to 0); an empty mesh gives NaN means, like a mean of nothing
+ *   symmetric  int32 [objects]     non-zero selects ADD-S (nearest estimated point, brute force) instead of ADD
+ *   pairs      [batch*objects][36] one record per pair, pair = image * objects + object: estimated pose (12, row-major 3x4), ground-truth
+ *                                  pose (12), camera matrix K (9, row-major), diameter, valid flag (object is in the ground truth), one pad
+ *   records    [batch*objects][6]  (err_2d, err_3d, valid_3d, valid_2d, missing, false_positive):
+ *                                  valid == 0: zeros but false_positive = |sum of the pose| > 1e-4;  valid != 0 and |sum| < 1e-4:
+ *                                  (99.9, 999.9, 0, 0, 1, 0);  else the mean 2-D reprojection distance (pixel = 0 where the projective z is
+ *                                  exactly 0), the mean ADD or ADD-S distance (ADD-S per point: sqrt(|min_j d^2| + 1e-5)),
+ *                                  err_3d < 0.1 * diameter and err_2d < allowed_error_2d
+ *   point_err2, point_err3         optional [batch*objects][vmax] (NULL in production): the 2-D distance and the ADD / ADD-S distance of target
+ *                                  point i; 0 for skipped pairs and for i >= counts[o]
+ *   workspace                      cp_pose_eval_workspace_bytes(batch, objects, vmax) bytes, 8-byte aligned (0 for non-positive arguments)
+ * fp32 arithmetic on direct coordinate differences, fp64 sums in a fixed order without atomics: two calls on the same input give bit-identical
+ * records.  At most 65535 pairs per call, vmax <= 2^24.  cp_pose_eval_est_tile(): the number of estimated points one LDS tile of the ADD-S walk
+ * holds (tests place their sizes by it).  Added in ABI 302 without changing any earlier entry point. */
+size_t cp_pose_eval_workspace_bytes(int batch, int objects, int vmax);
+int cp_pose_eval_est_tile(void);
+int cp_pose_eval_f32(const float* points, const int32_t* counts, const int32_t* symmetric, int objects, int vmax, const float* pairs, int batch,
+                     float allowed_error_2d, void* workspace, float* records, float* point_err2, float* point_err3, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
