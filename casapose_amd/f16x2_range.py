@@ -1,12 +1,15 @@
 """The fp16-pair ("f16x2") range monitor of engine.ForwardPlan and train_engine.TrainPlan, and the training backward's policy (BackwardRange).  A slot
 is four words (include/casapose_hip.h): [0] max |x| converted, [1] launches that reported, [2] a fused head's operand, [3] a backward overflow guard."""
 from dataclasses import dataclass
-from typing import Dict, List, Optional, Tuple
+from typing import TYPE_CHECKING, Dict, List, Optional, Tuple
 
 import numpy as np
 import torch
 
 from . import _lib
+
+if TYPE_CHECKING:
+    from .train_engine import WinoGemm
 
 
 class armed:
@@ -87,7 +90,7 @@ class BwdSlot:
     """a backward GEMM on fp16 pairs and its slot: "direct" (a 3x3 layer under the loss factor, switched by `on`) or a Winograd GEMM with its e"""
     kind: str
     op: object
-    entry: Optional[dict] = None   # wino_dgrad: the op's wino_dgrad record (set_dgrad_exponent re-packs its weights)
+    entry: Optional["WinoGemm"] = None   # wino_dgrad: the op's wino_dgrad record (set_dgrad_exponent re-packs its weights)
     e: Optional[int] = None
     on: bool = False
     dead: bool = False             # a non-finite maximum ended its fp16-pair run for good

@@ -27,6 +27,7 @@ from __future__ import annotations
 import ctypes as C
 import os
 import warnings
+from dataclasses import dataclass
 from typing import Callable, Dict, List, Optional, Sequence, Tuple
 
 import numpy as np
@@ -230,6 +231,103 @@ def _index_map(pack: Callable[[np.ndarray, np.ndarray], None], ramp_hwio: np.nda
     return (dst.astype(np.int64) - 1).astype(np.int32)
 
 
+# bf16-pipe products per fp32 product of an arithmetic: exact three-way bf16 split, fp16 two-way split, hi + mid bf16 planes, operands rounded to bf16
+PRODUCTS = {3: 6.0, _lib.PLANES_F16X2: 3.0, 2: 3.0, 1: 1.0}
+
+
+class SplitWeights:
+    """One weight set split into 2-byte operand planes.  `src` is its fp32 image, `arith` the arithmetic in force (a key of PRODUCTS), `planes` the
+    buffer the consuming launch reads and `out_scale` the factor that launch multiplies its output by (1.0 unless arith is the fp16 pair: the weights
+    are split as src * 2^k, f16x2_scale; a Winograd data gradient also takes the 2^e of its transformed dY back, `e`).  `shape` is None for the
+    fragment stream of conv_hsplit / the stem (`idx`: its gather map from the master weights) and (groups, n, k) for a GEMM's [groups][n][k]."""
+
+    def __init__(self, src: torch.Tensor, arith: int, shape: Optional[Tuple[int, int, int]] = None, idx: Optional[torch.Tensor] = None,
+                 two_buffers: bool = False):
+        self.src, self.arith, self.shape, self.idx = src, arith, shape, idx
+        self.out_scale, self.e, self.cache = 1.0, None, {}   # (cache: f16x2_scale's counter, maximum and scale)
+        # two_buffers (a Winograd GEMM): one buffer for the fp16 pair and one for the bf16 planes, each allocated by the first repack() that needs it
+        self.two_buffers, self._other = two_buffers, None
+        self.planes = None if two_buffers else self._alloc()
+
+    products = property(lambda self: PRODUCTS[self.arith])
+
+    def _alloc(self) -> torch.Tensor:   # (a fragment stream: 1 KiB per plane and 512 floats)
+        n = self.src.numel() // 512 * (self.arith & 15) * 1024 if self.shape is None else _lib.load().cp_wino_split_weights_bytes(*self.shape)
+        return torch.empty(n, dtype=torch.uint8, device=self.src.device)
+
+    def set_arith(self, arith: int):
+        """change the arithmetic; repack() makes the planes follow"""
+        pair = _lib.PLANES_F16X2
+        if self.two_buffers and (arith == pair) != (self.arith == pair):
+            self.planes, self._other = self._other, self.planes
+        self.arith = arith
+        if self.shape is None and self.planes.numel() < self.src.numel() // 512 * (arith & 15) * 1024:   # (a demoted forward: two planes -> three)
+            self.planes = self._alloc()
+
+    def repack(self, stream: int):
+        """src (just refreshed from the master weights) -> planes, in the arithmetic in force"""
+        lib = _lib.load()
+        pair = self.arith == _lib.PLANES_F16X2
+        if self.planes is None:
+            self.planes = self._alloc()
+        scale = f16x2_scale(self.cache, self.src) if pair else 1.0
+        self.out_scale = (1.0 if self.e is None else 2.0 ** (-self.e)) / scale
+        if self.shape is None:
+            check(lib.cp_conv_split_weights_scaled_f32(self.src.data_ptr(), self.src.numel(), self.arith, scale, self.planes.data_ptr(), stream),
+                  "cp_conv_split_weights_scaled_f32")
+        elif pair:
+            check(lib.cp_wino_split_weights_scaled_f32(self.src.data_ptr(), *self.shape, self.arith, scale, self.planes.data_ptr(), stream),
+                  "cp_wino_split_weights_scaled_f32")
+        else:
+            check(lib.cp_wino_split_weights_f32(self.src.data_ptr(), *self.shape, self.planes.data_ptr(), stream), "cp_wino_split_weights_f32")
+
+
+@dataclass(eq=False)
+class DgradPack:
+    """the flipped / transposed kernel of one source's data gradient: gather maps and arena views (plain and halo order), descriptor, conv_hsplit planes"""
+    idx: torch.Tensor
+    w: torch.Tensor
+    cout: int
+    cin: int
+    desc: ConvDesc
+    idx_halo: Optional[torch.Tensor] = None
+    w_halo: Optional[torch.Tensor] = None
+    split: Optional[SplitWeights] = None
+    deep: bool = False          # CASAPOSE_CONV_MODE=bf16: the direct bf16-operand kernel (csrc/conv_bf16d.hip) reads split.planes
+
+
+@dataclass(eq=False)
+class GemmRoute:
+    """a 1x1 / stride-1 convolution as GEMMs rows x cin x cout on the bf16 matrix pipe (ConvOp.setup_gemm)"""
+    rows: int
+    cin: int
+    idx_t: torch.Tensor               # [co][ci] -> master [ci][co]
+    Uf: torch.Tensor                  # the transposed weights, fp32
+    fwd: SplitWeights                 # planes of Uf
+    dgrad: Optional[SplitWeights]     # planes of the master itself (None: the source needs no gradient)
+    wgrad: bool                       # weight gradient on the transposed GEMM (csrc/wino_wgrad_split.hip) into dU
+    dU: Optional[torch.Tensor] = None
+
+
+@dataclass(eq=False)
+class WinoGemm:
+    """one Winograd GEMM of an op (ConvOp.setup_winograd): the forward (V kept for the weight gradient: dU, wdesc) or the data gradient of the source
+    whose channels start at c0.  split: the planes of U (None: fp32 GEMM, CASAPOSE_WINO_GEMM=f32); slot: its backward GEMM on fp16 pairs -- the
+    forward record's weight gradient, a data gradient's own GEMM (ps: the 2^e table its input transform applies)"""
+    U: torch.Tensor
+    ktot: int
+    cout: int
+    tp: int
+    desc: ConvDesc
+    split: Optional[SplitWeights] = None
+    slot: Optional[BwdSlot] = None
+    V: Optional[torch.Tensor] = None
+    dU: Optional[torch.Tensor] = None
+    wdesc: Optional[ConvDesc] = None
+    c0: int = 0
+    ps: Optional[torch.Tensor] = None
+
+
 class TrainConv:
     """One convolution layer of the training plan: packs, descriptors, forward / wgrad / dgrad launches."""
 
@@ -251,35 +349,21 @@ class TrainConv:
         real = (C.c_int * 2)(*([s[1] for s in sources] + [0] * (2 - ns)))
         self.ktot = lib.cp_conv_ktot(k, k, ns, chans)
 
-        def pack_fwd(src, dst):
-            check(lib.cp_conv_pack_weights_host(src.ctypes.data, 0, k, k, cout, ns, chans, real, dst.ctypes.data), "pack " + key)
+        def packed(pack, view, n_out: int):
+            """one kernel layout: the host packer `pack(src, dst)` pushed over the master indices `view` -> (device gather map, arena view)"""
+            imap = _index_map(lambda src, dst: check(pack(src.ctypes.data, dst.ctypes.data), "pack " + key), view, n_out)
+            return torch.from_numpy(imap).to(dev), store.pack_alloc(imap, off)
 
-        self._off = off
-        imap = _index_map(pack_fwd, hwio, cout * self.ktot)
-        self.idx_fwd = torch.from_numpy(imap).to(dev)
-        self.wp = store.pack_alloc(imap, off)
+        self.idx_fwd, self.wp = packed(lambda s, d: lib.cp_conv_pack_weights_host(s, 0, k, k, cout, ns, chans, real, d), hwio, cout * self.ktot)
         self.dwp = torch.empty(cout * self.ktot, dtype=torch.float32, device=dev)
         self.idx_halo = self.wp_halo = None
         if k == 3 and cout <= 64 and sources[0][0] % 32 == 0 and (ns == 1 or sources[1][0] == 4 or sources[1][0] % 32 == 0):
-            nfl = lib.cp_conv_halo_weight_floats(cout, ns, chans)
-
-            def pack_halo(src, dst):
-                check(lib.cp_conv_pack_weights_halo_host(src.ctypes.data, 0, cout, ns, chans, real, dst.ctypes.data), "pack halo " + key)
-
-            imap = _index_map(pack_halo, hwio, nfl)
-            self.idx_halo = torch.from_numpy(imap).to(dev)
-            self.wp_halo = store.pack_alloc(imap, off)
+            self.idx_halo, self.wp_halo = packed(lambda s, d: lib.cp_conv_pack_weights_halo_host(s, 0, cout, ns, chans, real, d), hwio,
+                                                 lib.cp_conv_halo_weight_floats(cout, ns, chans))
         elif k == 7 and cout == 64 and ns == 1 and sources[0][0] == 4:  # the stem (csrc/conv_stem.hip): its packing travels in weights_halo
-            nfl = 25 * 2 * 64 * 4
-
-            def pack_stem(src, dst):
-                check(lib.cp_conv_pack_weights_stem_host(src.ctypes.data, 0, sources[0][1], dst.ctypes.data), "pack stem " + key)
-
-            imap = _index_map(pack_stem, hwio, nfl)
-            self.idx_halo = torch.from_numpy(imap).to(dev)
-            self.wp_halo = store.pack_alloc(imap, off)
+            self.idx_halo, self.wp_halo = packed(lambda s, d: lib.cp_conv_pack_weights_stem_host(s, 0, sources[0][1], d), hwio, 25 * 2 * 64 * 4)
         # bf16-pipe kernel (csrc/conv_hsplit.hip) for the shallow 3x3 layers: fp32 image of its fragment stream in the arena, bf16 planes beside it
-        self.split = None
+        self.split: Optional[SplitWeights] = None
         planes = self.mode_planes = conv_split_planes()   # read ONCE per layer: the backward and the accounting reuse it (bench.py changes the variable between plans)
         self.fwd_f16x2 = planes == 3 and train_fwd_f16x2()   # forward launches of this layer in the fp16 two-way split
         fwd_np = _lib.PLANES_F16X2 if self.fwd_f16x2 else planes
@@ -292,27 +376,16 @@ class TrainConv:
             planes = 0   # the deep ordinary 3x3 layers run as Winograd (engine.wino_eligible); partial convolutions (layout 1) of that size do not
         if planes and k == 3 and cout <= 512 and cout % 4 == 0 and sources[0][0] % 16 == 0 and sources[0][0] != 4 and (
                 ns == 1 or (sources[1][0] == 4 and cout <= 32) or sources[1][0] % 16 == 0):
-            nfl = lib.cp_conv_split_weight_floats(cout, ns, chans)
-
-            def pack_split(src, dst):
-                check(lib.cp_conv_pack_weights_split_host(src.ctypes.data, 0, cout, ns, chans, real, dst.ctypes.data), "pack split " + key)
-
-            imap = _index_map(pack_split, hwio, nfl)
-            self.split = dict(f32=store.pack_alloc(imap, off), planes=torch.empty(nfl // 512 * (fwd_np & 15) * 1024, dtype=torch.uint8, device=dev), np=fwd_np,
-                              idx=torch.from_numpy(imap).to(dev), descale=1.0, cache={})
+            idx, f32 = packed(lambda s, d: lib.cp_conv_pack_weights_split_host(s, 0, cout, ns, chans, real, d), hwio,
+                              lib.cp_conv_split_weight_floats(cout, ns, chans))
+            self.split = SplitWeights(f32, fwd_np, idx=idx)
         elif planes and k == 7 and cout == 64 and ns == 1 and sources[0][0] == 4 and os.environ.get("CASAPOSE_STEM_SPLIT", "1") != "0":
             # the stem on the bf16 matrix pipe (csrc/conv_stem_split.hip, round 4): same bookkeeping as the 3x3 layers -- fp32 image of the fragment
             # stream in the arena (re-gathered with every weight refresh), bf16 planes beside it; the weight gradient stays on the fp32 kernel
-            nfl = lib.cp_conv_stem_split_weight_floats()
-
-            def pack_stem_split(src, dst):
-                check(lib.cp_conv_pack_weights_stem_split_host(src.ctypes.data, 0, sources[0][1], dst.ctypes.data), "pack stem split " + key)
-
-            imap = _index_map(pack_stem_split, hwio, nfl)
-            self.split = dict(f32=store.pack_alloc(imap, off), planes=torch.empty(nfl // 512 * (fwd_np & 15) * 1024, dtype=torch.uint8, device=dev), np=fwd_np,
-                              idx=torch.from_numpy(imap).to(dev), stem=True, descale=1.0, cache={})
+            idx, f32 = packed(lambda s, d: lib.cp_conv_pack_weights_stem_split_host(s, 0, sources[0][1], d), hwio, lib.cp_conv_stem_split_weight_floats())
+            self.split = SplitWeights(f32, fwd_np, idx=idx)
         # data-gradient packs: per source that needs a gradient, the flipped / transposed kernel
-        self.dgrad: List[Optional[dict]] = []
+        self.dgrad: List[Optional[DgradPack]] = []
         cpad = (cout + 31) // 32 * 32
         c0 = 0
         for s, (cs, cr) in enumerate(sources):
@@ -320,81 +393,55 @@ class TrainConv:
                 self.dgrad.append(None)
                 c0 += cr
                 continue
-            sub = hwio[::-1, ::-1, c0:c0 + cr, :].transpose(0, 1, 3, 2)  # [kh,kw,cout,cr]: taps flipped, in/out swapped
+            sub = np.ascontiguousarray(hwio[::-1, ::-1, c0:c0 + cr, :].transpose(0, 1, 3, 2))  # [kh,kw,cout,cr]: taps flipped, in/out swapped
             dch = (C.c_int * 2)(cpad, 0)
             dre = (C.c_int * 2)(cout, 0)
-            kt = lib.cp_conv_ktot(k, k, 1, dch)
-
-            def pack_d(src, dst, dch=dch, dre=dre, cr=cr):
-                check(lib.cp_conv_pack_weights_host(src.ctypes.data, 0, k, k, cr, 1, dch, dre, dst.ctypes.data), "pack dgrad " + key)
-
-            imap = _index_map(pack_d, np.ascontiguousarray(sub), cr * kt)
-            ent = dict(idx=torch.from_numpy(imap).to(dev), w=store.pack_alloc(imap, off), cout=cr, cin=cpad, idx_halo=None, w_halo=None,
-                       desc=ConvDesc())
+            idx, w = packed(lambda s_, d, dch=dch, dre=dre, cr=cr: lib.cp_conv_pack_weights_host(s_, 0, k, k, cr, 1, dch, dre, d), sub,
+                            cr * lib.cp_conv_ktot(k, k, 1, dch))
+            ent = DgradPack(idx=idx, w=w, cout=cr, cin=cpad, desc=ConvDesc(), deep=deep_dgrad and cr % 128 == 0 and cr <= 512 and cpad % 16 == 0)
             if k == 3 and cr <= 64:
-                nfl = lib.cp_conv_halo_weight_floats(cr, 1, dch)
-
-                def pack_dh(src, dst, dch=dch, dre=dre, cr=cr):
-                    check(lib.cp_conv_pack_weights_halo_host(src.ctypes.data, 0, cr, 1, dch, dre, dst.ctypes.data), "pack dgrad halo " + key)
-
-                imap = _index_map(pack_dh, np.ascontiguousarray(sub), nfl)
-                ent["idx_halo"] = torch.from_numpy(imap).to(dev)
-                ent["w_halo"] = store.pack_alloc(imap, off)
-            ent["split"] = None
-            ent["deep"] = deep_dgrad and cr % 128 == 0 and cr <= 512 and cpad % 16 == 0
-            if (planes or ent["deep"]) and k == 3 and cr <= 512 and cr % 4 == 0:
-                planes_d = planes or 1
-                nfl = lib.cp_conv_split_weight_floats(cr, 1, dch)
-
-                def pack_ds(src, dst, dch=dch, dre=dre, cr=cr):
-                    check(lib.cp_conv_pack_weights_split_host(src.ctypes.data, 0, cr, 1, dch, dre, dst.ctypes.data), "pack dgrad split " + key)
-
-                imap = _index_map(pack_ds, np.ascontiguousarray(sub), nfl)
-                ent["split"] = dict(f32=store.pack_alloc(imap, off), planes=torch.empty(nfl // 512 * planes_d * 1024, dtype=torch.uint8, device=dev), np=planes_d,
-                                    idx=torch.from_numpy(imap).to(dev), descale=1.0, cache={})
+                ent.idx_halo, ent.w_halo = packed(lambda s_, d, dch=dch, dre=dre, cr=cr: lib.cp_conv_pack_weights_halo_host(s_, 0, cr, 1, dch, dre, d), sub,
+                                                  lib.cp_conv_halo_weight_floats(cr, 1, dch))
+            if (planes or ent.deep) and k == 3 and cr <= 512 and cr % 4 == 0:
+                idx, f32 = packed(lambda s_, d, dch=dch, dre=dre, cr=cr: lib.cp_conv_pack_weights_split_host(s_, 0, cr, 1, dch, dre, d), sub,
+                                  lib.cp_conv_split_weight_floats(cr, 1, dch))
+                ent.split = SplitWeights(f32, planes or 1, idx=idx)
             self.dgrad.append(ent)
             c0 += cr
         self.desc = ConvDesc()
-        self._keep: List = []
         self.layout = layout
-        self.master_shape = tuple(shape)
         self.refresh_hooks: List[Callable[[int], None]] = []  # extra weight layouts owned by the ops (Winograd planes)
-        if self.split is not None or any(e is not None and e["split"] is not None for e in self.dgrad):
+        if self._splits():
             self.refresh_hooks.append(self._refresh_split)
+
+    def _splits(self) -> List[SplitWeights]:
+        """the conv_hsplit / stem weight sets of this layer: the forward's, then every data gradient's"""
+        return [sp for sp in [self.split] + [e.split for e in self.dgrad if e is not None] if sp is not None]
 
     def _refresh_split(self, stream: int):
         """fp32 fragment images (just re-gathered from the master weights) -> bf16 planes of the bf16-pipe kernel"""
-        lib = _lib.load()
-        for sp in [self.split] + [e["split"] for e in self.dgrad if e is not None]:
-            if sp is not None:
-                scale = f16x2_scale(sp["cache"], sp["f32"]) if sp["np"] == _lib.PLANES_F16X2 else 1.0
-                sp["descale"] = 1.0 / scale
-                check(lib.cp_conv_split_weights_scaled_f32(sp["f32"].data_ptr(), sp["f32"].numel(), sp["np"], scale, sp["planes"].data_ptr(), stream),
-                      "cp_conv_split_weights_scaled_f32")
+        for sp in self._splits():
+            sp.repack(stream)
 
     def refresh(self, stream: int, hooks_only: bool = False):
         """Re-pack the kernel layouts from the master weights (after an optimizer step / at start).  hooks_only: the plan refreshes the
         gather-type layouts of all layers with one launch over the packed-weight arena (ParamStore.pack_refresh)."""
         lib = _lib.load()
         m = self.master.data_ptr()
-        if hooks_only:
-            for hook in self.refresh_hooks:
-                hook(stream)
-            return
-        for sp in [self.split] + [e["split"] for e in self.dgrad if e is not None]:   # fp32 fragment images of the bf16-pipe kernel, then their planes
-            if sp is not None:
-                check(lib.cp_gather_f32(m, sp["idx"].data_ptr(), sp["idx"].numel(), sp["f32"].data_ptr(), stream), "cp_gather_f32")
+        if not hooks_only:
+            for sp in self._splits():   # fp32 fragment images of the bf16-pipe kernel, then their planes
+                check(lib.cp_gather_f32(m, sp.idx.data_ptr(), sp.idx.numel(), sp.src.data_ptr(), stream), "cp_gather_f32")
         for hook in self.refresh_hooks:
             hook(stream)
-        check(lib.cp_gather_f32(m, self.idx_fwd.data_ptr(), self.idx_fwd.numel(), self.wp.data_ptr(), stream), "cp_gather_f32")
-        if self.idx_halo is not None:
-            check(lib.cp_gather_f32(m, self.idx_halo.data_ptr(), self.idx_halo.numel(), self.wp_halo.data_ptr(), stream), "cp_gather_f32")
+        if hooks_only:
+            return
+        packs = [(self.idx_fwd, self.wp), (self.idx_halo, self.wp_halo)]
         for ent in self.dgrad:
-            if ent is None:
-                continue
-            check(lib.cp_gather_f32(m, ent["idx"].data_ptr(), ent["idx"].numel(), ent["w"].data_ptr(), stream), "cp_gather_f32")
-            if ent["idx_halo"] is not None:
-                check(lib.cp_gather_f32(m, ent["idx_halo"].data_ptr(), ent["idx_halo"].numel(), ent["w_halo"].data_ptr(), stream), "cp_gather_f32")
+            if ent is not None:
+                packs += [(ent.idx, ent.w), (ent.idx_halo, ent.w_halo)]
+        for idx, w in packs:
+            if idx is not None:
+                check(lib.cp_gather_f32(m, idx.data_ptr(), idx.numel(), w.data_ptr(), stream), "cp_gather_f32")
 
 
 class ConvOp:
@@ -414,7 +461,7 @@ class ConvOp:
         eff = (k - 1) * dilation + 1
         self.out_h = (in_h + 2 * pad - eff) // stride + 1
         self.out_w = (in_w + 2 * pad - eff) // stride + 1
-        d = layer.desc
+        d = layer.desc   # (a fresh ConvDesc is all zeros: no epilogue, no fused head, automatic tile -- here and in the data gradients' below)
         d.batch, d.in_h, d.in_w, d.out_h, d.out_w = batch, in_h, in_w, self.out_h, self.out_w
         d.cout, d.kh, d.kw, d.stride, d.dilation, d.pad = layer.cout, k, k, stride, dilation, pad
         d.num_sources = len(srcs)
@@ -427,15 +474,9 @@ class ConvOp:
         d.tap_label, d.row_scale = _ptr(tap_label), _ptr(row_scale)
         d.residual = residual.data.data_ptr() if residual is not None else None
         d.residual_ld = layer.cout
-        d.scale = d.shift = d.epi_label = None
-        d.act = 0
         st, off, ld = out_ptr_ld
         d.out_raw, d.out_raw_ld = st.data_ptr() + 4 * off, ld
-        d.out_act, d.out_act_ld = None, layer.cout
-        d.tile_hint = 0
-        d.head_weights = d.head_out = None
-        d.head_cout = d.head_out_ld = 0
-        d.head_label_out, d.head_label_classes = None, 0
+        d.out_act_ld = layer.cout
         self.dy_ptr_ld = dy_ptr_ld
         # the full-resolution 1x1 heads (32 -> K / ver_dim): streaming kernels on the Keras kernel itself (csrc/head1x1.hip) unless CASAPOSE_HEAD_CONV=generic
         self.head_fast = (k == 1 and stride == 1 and pad == 0 and len(srcs) == 1 and layer.sources[0] == (32, 32) and layer.cout <= 32
@@ -449,7 +490,12 @@ class ConvOp:
         self.stats_to: Optional["BnActOp"] = None
         self.pre_norm: Dict[int, "BnActOp"] = {}
         self.pre_bn: Optional["BnActOp"] = None   # fused normalisation (TrainPlan._fuse_heads): this head reads the RAW tensor and applies pre_bn's tables itself
-        self.gemm, self.wino_fwd, self.wino_dgrad = None, None, {}   # 1x1 GEMM route (setup_gemm), Winograd forward / data gradients (setup_winograd)
+        self.gemm: Optional[GemmRoute] = None         # 1x1 GEMM route (setup_gemm)
+        self.wino_fwd: Optional[WinoGemm] = None      # Winograd forward and data gradients by source index (setup_winograd)
+        self.wino_dgrad: Dict[int, WinoGemm] = {}
+        self._wV = self._wM = None                    # the plan's shared Winograd scratch (bind_winograd)
+        self._cin = sum(s[1] for s in layer.sources)
+        self._stem_fwd = self._split_fwd = None       # the forward's applicability probes, asked once (forward_route)
         self.mon_ptr: Optional[int] = None        # the f16x2 forward's monitor slot (TrainPlan._arm_f16x2)
         self.bw16: Optional[BwdSlot] = None   # the direct data / weight gradients' backward slot record (TrainPlan._finish_plan)
         # data-gradient descriptors
@@ -458,28 +504,22 @@ class ConvOp:
                 continue
             t, ld = srcs[s]
             assert t.needs_grad and ld == t.c
-            g = ent["desc"]
+            g = ent.desc
             g.batch = batch
             g.in_h, g.in_w = (in_h + 2 * pad - (eff - 1), in_w + 2 * pad - (eff - 1)) if stride == 2 else (self.out_h, self.out_w)
             if stride == 2:
                 assert dilation == 1 and g.in_h == 2 * self.out_h and g.in_w == 2 * self.out_w, "stride-2 data gradient expects even geometry"
             g.out_h, g.out_w = in_h, in_w
-            g.cout, g.kh, g.kw, g.stride, g.dilation, g.pad = ent["cout"], k, k, 1, dilation, dilation * (k - 1) - pad
+            g.cout, g.kh, g.kw, g.stride, g.dilation, g.pad = ent.cout, k, k, 1, dilation, dilation * (k - 1) - pad
             g.num_sources = 1
-            g.src[0].channels = ent["cin"]
+            g.src[0].channels = ent.cin
             g.src[0].mode = _lib.SRC_ZERO_INSERT_X2 if stride == 2 else _lib.SRC_DIRECT
             g.src[0].sel = g.src[0].pre_scale = g.src[0].pre_shift = None
-            g.weights, g.weights_halo = ent["w"].data_ptr(), _ptr(ent["w_halo"])
+            g.weights, g.weights_halo = ent.w.data_ptr(), _ptr(ent.w_halo)
             g.tap_label, g.row_scale = _ptr(tap_label), None
-            g.residual_ld = ent["cout"]
-            g.scale = g.shift = g.epi_label = None
-            g.act = 0
+            g.residual_ld = ent.cout
             g.out_raw, g.out_raw_ld = t.grad.data_ptr(), t.c
-            g.out_act, g.out_act_ld = None, t.c
-            g.tile_hint = 0
-            g.head_weights = g.head_out = None
-            g.head_cout = g.head_out_ld = 0
-            g.head_label_out, g.head_label_classes = None, 0
+            g.out_act_ld = t.c
 
     # ---- 1x1 / stride-1 shortcuts as plain GEMMs on the bf16 matrix pipe -----------------------------------------------------------------
     def setup_gemm(self):
@@ -503,32 +543,23 @@ class ConvOp:
         lib = _lib.load()
         dev = L.master.device
         idx_t = (np.arange(cin, dtype=np.int32)[None, :] * L.cout + np.arange(L.cout, dtype=np.int32)[:, None]).reshape(-1)   # [co][ci] -> master [ci][co]
-        g = dict(rows=rows, cin=cin, planes=3 if planes == 3 else 2, fwd_planes=_lib.PLANES_F16X2 if L.fwd_f16x2 else (3 if planes == 3 else 2), c_scale=1.0, cache={},
-                 idx_t=torch.from_numpy(idx_t).to(dev),
-                 Uf=torch.empty(L.cout * cin, dtype=torch.float32, device=dev),
-                 Us_f=torch.empty(lib.cp_wino_split_weights_bytes(1, L.cout, cin), dtype=torch.uint8, device=dev),
-                 Us_d=torch.empty(lib.cp_wino_split_weights_bytes(1, cin, L.cout), dtype=torch.uint8, device=dev) if L.dgrad[0] is not None else None,
-                 wgrad=bool(lib.cp_wino_wgrad_split_applicable(1, rows, L.cout, cin)) and os.environ.get("CASAPOSE_WINO_WGRAD", "split") != "f32")
-        if g["wgrad"]:
-            g["dU"] = torch.empty(L.cout * cin, dtype=torch.float32, device=dev)
+        exact = 3 if planes == 3 else 2
+        Uf = torch.empty(L.cout * cin, dtype=torch.float32, device=dev)
+        g = GemmRoute(rows=rows, cin=cin, idx_t=torch.from_numpy(idx_t).to(dev), Uf=Uf,
+                      fwd=SplitWeights(Uf, _lib.PLANES_F16X2 if L.fwd_f16x2 else exact, (1, L.cout, cin)),   # U[co][ci] = W[ci][co]
+                      dgrad=SplitWeights(L.master, exact, (1, cin, L.cout)) if L.dgrad[0] is not None else None,   # U[ci][co]: the master itself
+                      wgrad=bool(lib.cp_wino_wgrad_split_applicable(1, rows, L.cout, cin)) and os.environ.get("CASAPOSE_WINO_WGRAD", "split") != "f32")
+        if g.wgrad:
+            g.dU = torch.empty(L.cout * cin, dtype=torch.float32, device=dev)
         self.gemm = g
         L.refresh_hooks.append(self._refresh_gemm)
 
     def _refresh_gemm(self, stream: int):
-        from .engine import split_wino_weights
-
-        lib = _lib.load()
         L, g = self.layer, self.gemm
-        check(lib.cp_gather_f32(L.master.data_ptr(), g["idx_t"].data_ptr(), g["idx_t"].numel(), g["Uf"].data_ptr(), stream), "cp_gather_f32(%s)" % L.name)
-        if g["fwd_planes"] == _lib.PLANES_F16X2:   # forward in the fp16 two-way split: U times a power of two, the GEMM undoes it
-            scale = f16x2_scale(g["cache"], g["Uf"])
-            g["c_scale"] = 1.0 / scale
-            check(lib.cp_wino_split_weights_scaled_f32(g["Uf"].data_ptr(), 1, L.cout, g["cin"], _lib.PLANES_F16X2, scale, g["Us_f"].data_ptr(), stream),
-                  "cp_wino_split_weights_scaled_f32(%s)" % L.name)
-        else:
-            split_wino_weights(g["Uf"], 1, L.cout, g["cin"], out=g["Us_f"], stream=stream)          # forward: U[co][ci] = W[ci][co]
-        if g["Us_d"] is not None:
-            split_wino_weights(L.master, 1, g["cin"], L.cout, out=g["Us_d"], stream=stream)     # data gradient: U[ci][co] = W[ci][co], the master itself
+        check(_lib.load().cp_gather_f32(L.master.data_ptr(), g.idx_t.data_ptr(), g.idx_t.numel(), g.Uf.data_ptr(), stream), "cp_gather_f32(%s)" % L.name)
+        for sw in (g.fwd, g.dgrad):
+            if sw is not None:
+                sw.repack(stream)
 
     # ---- Winograd F(4x4,3x3) for the deep layers (csrc/wino.hip): forward and data gradient ------------------------
     def setup_winograd(self):
@@ -542,7 +573,6 @@ class ConvOp:
             return 0, 0
         _, tp = WinoConv.tiles(self.batch, self.in_h, self.in_w, self.dil)
         dev = L.master.device
-        cin = sum(s[1] for s in L.sources)
         # The training plan keeps the K >= 256 threshold of the fp32 GEMM.  Measured in round 3 with the dilated 128 -> 256 layer
         # (stage3_unit1_conv1) on the Winograd path as in the inference plan: no gain on the step (510 vs 519 images/s: its weight gradient
         # falls back to the fp32 grouped GEMM), and the F(4x4,3x3) rounding of one more layer in the forward moved the config-13 gradient
@@ -552,28 +582,39 @@ class ConvOp:
         # Round 6: the fp32-LEVEL default (forward in the fp16 two-way split, the config-13 comparison gated at 1e-2 like the fp32 MFMA's) takes it too:
         # forward 0.59 -> Winograd GEMM on fp16 pairs, weight gradient through the Winograd planes instead of the fp32 MFMA kernel.
         split_gemm = self.dil > 1 and (self.layer.mode_planes == 1 or (self.layer.fwd_f16x2 and os.environ.get("CASAPOSE_TRAIN_WINO_DILATED_128", "1") == "1"))
+        # the GEMMs on the bf16 matrix pipe read pre-split planes of U: hi + mid in the bf16 conv mode (three products, not fp32-equivalent: that
+        # mode's gates are 3e-2), else the exact split; the forward's may be the fp16 pair.  bwd16: the backward GEMMs may move to the fp16 pair
+        # (e = None while the exact split runs and the slot measures)
+        exact = 2 if L.mode_planes == 1 else 3
+        bwd16 = L.mode_planes == 3 and TRAIN_WINO_GEMM_SPLIT and train_bwd_f16x2()
+
+        def record(cout, ktot, arith, **kw):
+            U = torch.zeros(36 * cout * ktot, dtype=torch.float32, device=dev)
+            return WinoGemm(U=U, ktot=ktot, cout=cout, tp=tp, desc=ConvDesc(),
+                            split=SplitWeights(U, arith, (36, cout, ktot), two_buffers=True) if TRAIN_WINO_GEMM_SPLIT else None, **kw)
 
         if all(s[0] == s[1] for s in L.sources) and wino_eligible(3, 1, self.dil, self.pad, L.sources, L.cout, split_gemm=split_gemm):
             ktot = sum(s[0] for s in L.sources)
             # the forward's transformed input is kept per layer (not in the shared scratch): the weight gradient multiplies it again
-            self.wino_fwd = dict(U=torch.zeros(36 * L.cout * ktot, dtype=torch.float32, device=dev), ktot=ktot, cout=L.cout, tp=tp, desc=ConvDesc(),
-                                 V=torch.zeros(36 * tp * ktot, dtype=torch.float32, device=dev),  # padding tiles stay zero
-                                 dU=torch.empty(36 * L.cout * ktot, dtype=torch.float32, device=dev), wdesc=ConvDesc())
+            self.wino_fwd = record(L.cout, ktot, _lib.PLANES_F16X2 if L.fwd_f16x2 else exact,
+                                   V=torch.zeros(36 * tp * ktot, dtype=torch.float32, device=dev),  # padding tiles stay zero
+                                   dU=torch.empty(36 * L.cout * ktot, dtype=torch.float32, device=dev), wdesc=ConvDesc(),
+                                   slot=BwdSlot("wino_wgrad", self) if bwd16 else None)   # the weight-gradient GEMM in f16x2: transformed dY x 2^e
             nv, nm = max(nv, 36 * tp * ktot), max(nm, 36 * tp * L.cout)
-            if L.mode_planes == 3 and TRAIN_WINO_GEMM_SPLIT and train_bwd_f16x2():   # the weight-gradient GEMM in f16x2: transformed dY x 2^e
-                self.wino_fwd["wg16"] = BwdSlot("wino_wgrad", self)
         c0 = 0
         for s, (ent, (cp, cr)) in enumerate(zip(L.dgrad, L.sources)):
             if ent is not None and L.cout % 32 == 0 and wino_eligible(3, 1, self.dil, self.dil, [(L.cout, L.cout)], cr, split_gemm=split_gemm):
-                self.wino_dgrad[s] = dict(U=torch.zeros(36 * cr * L.cout, dtype=torch.float32, device=dev), ktot=L.cout, cout=cr, tp=tp, desc=ConvDesc(), c0=c0)
-                if L.mode_planes == 3 and TRAIN_WINO_GEMM_SPLIT and train_bwd_f16x2():   # (e = None while the exact split runs and the slot measures)
-                    self.wino_dgrad[s]["f16"] = BwdSlot("wino_dgrad", self, entry=self.wino_dgrad[s])
+                w = self.wino_dgrad[s] = record(cr, L.cout, exact, c0=c0)
+                if bwd16:
+                    w.slot = BwdSlot("wino_dgrad", self, entry=w)
                 nv, nm = max(nv, 36 * tp * L.cout), max(nm, 36 * tp * cr)
             c0 += cr
-        if self.wino_fwd is not None or self.wino_dgrad:
+        if self._wino_gemms():
             L.refresh_hooks.append(self._refresh_winograd)
-        self._cin = cin
         return nv, nm
+
+    def _wino_gemms(self) -> List[WinoGemm]:
+        return ([self.wino_fwd] if self.wino_fwd is not None else []) + list(self.wino_dgrad.values())
 
     def _refresh_winograd(self, stream: int):
         lib = _lib.load()
@@ -583,41 +624,25 @@ class ConvOp:
         if self.wino_fwd is not None:
             c0 = k0 = 0
             for cp, cr in L.sources:  # master is HWIO [3][3][cin][cout]
-                check(lib.cp_wino_transform_weights_f32(m + 4 * c0 * cout, 3 * cin * cout, cin * cout, cout, 1, 0, cr, cout, self.wino_fwd["ktot"], k0,
-                                                        self.wino_fwd["U"].data_ptr(), stream), "cp_wino_transform_weights_f32")
+                check(lib.cp_wino_transform_weights_f32(m + 4 * c0 * cout, 3 * cin * cout, cin * cout, cout, 1, 0, cr, cout, self.wino_fwd.ktot, k0,
+                                                        self.wino_fwd.U.data_ptr(), stream), "cp_wino_transform_weights_f32")
                 c0 += cr
                 k0 += cp
         for s, w in self.wino_dgrad.items():  # flipped taps, K index = forward output channel, output = forward input channel
-            check(lib.cp_wino_transform_weights_f32(m + 4 * w["c0"] * cout, 3 * cin * cout, cin * cout, 1, cout, 1, cout, w["cout"], w["ktot"], 0,
-                                                    w["U"].data_ptr(), stream), "cp_wino_transform_weights_f32")
-        from .engine import TRAIN_WINO_GEMM_SPLIT, split_wino_weights
-
-        if TRAIN_WINO_GEMM_SPLIT:  # GEMM on the bf16 matrix pipe (exact 3-way splits, fp32-equivalent): its weights are the pre-split planes of U
-            for w in ([self.wino_fwd] if self.wino_fwd is not None else []) + list(self.wino_dgrad.values()):
-                if w is self.wino_fwd and L.fwd_f16x2:   # the forward GEMM in the fp16 two-way split (the data gradients keep the exact bf16 split)
-                    if w.get("Us") is None:
-                        w["Us"] = torch.empty(lib.cp_wino_split_weights_bytes(36, w["cout"], w["ktot"]), dtype=torch.uint8, device=w["U"].device)
-                        w["cache"] = {}
-                    scale = f16x2_scale(w["cache"], w["U"])
-                    w["c_scale"] = 1.0 / scale
-                    check(lib.cp_wino_split_weights_scaled_f32(w["U"].data_ptr(), 36, w["cout"], w["ktot"], _lib.PLANES_F16X2, scale, w["Us"].data_ptr(), stream),
-                          "cp_wino_split_weights_scaled_f32(%s)" % L.name)
-                elif w.get("f16") is not None and w["f16"].e is not None:   # a data gradient in the fp16 two-way split (train_bwd_f16x2)
-                    if w.get("Us16") is None:
-                        w["Us16"] = torch.empty(lib.cp_wino_split_weights_bytes(36, w["cout"], w["ktot"]), dtype=torch.uint8, device=w["U"].device)
-                        w["cache"] = {}
-                    scale = f16x2_scale(w["cache"], w["U"])
-                    w["c_scale"] = 2.0 ** (-w["f16"].e) / scale
-                    check(lib.cp_wino_split_weights_scaled_f32(w["U"].data_ptr(), 36, w["cout"], w["ktot"], _lib.PLANES_F16X2, scale, w["Us16"].data_ptr(), stream),
-                          "cp_wino_split_weights_scaled_f32(dgrad %s)" % L.name)
-                    w["Us"] = w["Us16"]
-                else:
-                    w.pop("c_scale", None)
-                    w["Us"] = w["Us3"] = split_wino_weights(w["U"], 36, w["cout"], w["ktot"], out=w.get("Us3"), stream=stream)
+            check(lib.cp_wino_transform_weights_f32(m + 4 * w.c0 * cout, 3 * cin * cout, cin * cout, 1, cout, 1, cout, w.cout, w.ktot, 0,
+                                                    w.U.data_ptr(), stream), "cp_wino_transform_weights_f32")
+        for w in self._wino_gemms():
+            if w.split is not None:
+                w.split.repack(stream)
 
     def wgrad_f16x2(self) -> bool:
         """the direct weight gradient on fp16 pairs: dY inside the band (the switch its data gradient uses) and X too (the forward still f16x2)"""
         return self.bw16 is not None and self.bw16.on and not self.bw16.dead and self.layer.fwd_f16x2
+
+    def _direct_dgrad_splits(self) -> List[SplitWeights]:
+        """the data gradients that run on conv_hsplit as an exact three-way split or as the fp16 pair (not a Winograd / deep-bf16 route)"""
+        return [ent.split for s, ent in enumerate(self.layer.dgrad) if ent is not None and ent.split is not None and not ent.deep
+                and s not in self.wino_dgrad and ent.split.arith in (3, _lib.PLANES_F16X2)]
 
     def direct_dgrad_split(self) -> bool:
         """True when this op has a data gradient that runs on conv_hsplit as an exact three-way split and may move to the fp16 pair
@@ -625,85 +650,24 @@ class ConvOp:
         L = self.layer
         if not (train_bwd_f16x2() and L.mode_planes == 3 and L.k == 3 and self.stride == 1 and self.dil == 1) or self.gemm is not None:
             return False
-        for s, ent in enumerate(L.dgrad):
-            if ent is None or ent["split"] is None or ent.get("deep") or s in self.wino_dgrad:
-                continue
-            if ent["split"]["np"] in (3, _lib.PLANES_F16X2):
-                return True
-        return False
+        return bool(self._direct_dgrad_splits())
 
     def set_direct_dgrad_f16x2(self, on: bool, stream: int):
         """the direct data gradients of this op on the fp16 two-way split (weights x 2^k re-packed as two fp16 planes) or back on the exact split"""
-        L = self.layer
         self.bw16.on = on
-        for s, ent in enumerate(L.dgrad):
-            if ent is None or ent["split"] is None or ent.get("deep") or s in self.wino_dgrad:
-                continue
-            sp = ent["split"]
-            if sp["np"] in (3, _lib.PLANES_F16X2):
-                sp["np"] = _lib.PLANES_F16X2 if on else 3
-        L._refresh_split(stream)
+        for sp in self._direct_dgrad_splits():
+            sp.set_arith(_lib.PLANES_F16X2 if on else 3)
+        self.layer._refresh_split(stream)
 
-    def set_dgrad_exponent(self, w: dict, e: Optional[int], stream: int):
+    def set_dgrad_exponent(self, w: WinoGemm, e: Optional[int], stream: int):
         """the power of two the transformed dY of this Winograd data gradient is multiplied by (None: back to the exact split); re-packs the weights"""
-        w["f16"].e = e
+        w.slot.e = w.split.e = e
+        w.split.set_arith(3 if e is None else _lib.PLANES_F16X2)
         if e is not None:
-            if w.get("ps") is None:
-                w["ps"] = torch.empty(w["ktot"], dtype=torch.float32, device=w["U"].device)
-            w["ps"].fill_(2.0 ** e)
+            if w.ps is None:
+                w.ps = torch.empty(w.ktot, dtype=torch.float32, device=w.U.device)
+            w.ps.fill_(2.0 ** e)
         self._refresh_winograd(stream)
-
-    def bind_winograd(self, V: torch.Tensor, M: torch.Tensor):
-        self._wV, self._wM = V, M
-        for w in ([self.wino_fwd] if self.wino_fwd is not None else []) + list(self.wino_dgrad.values()):
-            d = w["desc"]
-            d.batch, d.in_h, d.in_w, d.out_h, d.out_w = 36, 1, w["tp"], 1, w["tp"]
-            d.cout, d.kh, d.kw, d.stride, d.dilation, d.pad = w["cout"], 1, 1, 1, 1, 0
-            d.num_sources = 1
-            d.src[0].data, d.src[0].channels, d.src[0].ld, d.src[0].mode = V.data_ptr(), w["ktot"], w["ktot"], _lib.SRC_DIRECT
-            d.weights = w["U"].data_ptr()
-            d.out_raw, d.out_raw_ld, d.out_act_ld, d.residual_ld = M.data_ptr(), w["cout"], w["cout"], w["cout"]
-            d.group_rows, d.group_weight_stride = w["tp"], w["cout"] * w["ktot"]
-        if self.wino_fwd is not None:  # grouped 1x1 weight-gradient problem over the 36 planes: dU[p] = dM[p]^T V[p]
-            w = self.wino_fwd
-            g = w["wdesc"]
-            g.batch, g.in_h, g.in_w, g.out_h, g.out_w = 1, 1, 36 * w["tp"], 1, 36 * w["tp"]
-            g.cout, g.kh, g.kw, g.stride, g.dilation, g.pad = w["cout"], 1, 1, 1, 1, 0
-            g.num_sources = 1
-            g.src[0].data, g.src[0].channels, g.src[0].ld, g.src[0].mode = w["V"].data_ptr(), w["ktot"], w["ktot"], _lib.SRC_DIRECT
-            g.group_rows = w["tp"]
-
-    def _wino_run(self, w, srcs, residual_ptr, out_ptr, stream, pre=None, stats=None, mon=None):
-        """srcs: list of (ptr, ld, channels); writes out_ptr[pix][w.cout] = conv (+ residual).  pre: {source index: (scale ptr, shift ptr, act)}
-        applied by the input transform; stats: fp64 [2][cout] table the output transform fills with the output's batch statistics; mon: f16x2 range
-        monitor slot armed around the input transforms (they report max |V| of what the f16x2 GEMM will convert; the GEMM itself stays un-armed:
-        the padding rows of V hold stale data)."""
-        lib = _lib.load()
-        off = 0
-        V = w["V"] if "V" in w else self._wV
-        with armed(mon):
-            for i, (ptr, ld, ch) in enumerate(srcs):
-                ps, pb, pa = (pre or {}).get(i, (None, None, 0))
-                check(lib.cp_wino_input_transform_pre_f32(ptr, ld, ch, self.batch, self.in_h, self.in_w, self.dil, V.data_ptr(), w["ktot"], off, ps, pb, pa, stream),
-                      "cp_wino_input_transform_pre_f32(%s)" % self.layer.name)
-                off += ch
-        if w.get("Us") is not None:
-            # CASAPOSE_CONV_MODE=bf16: hi + mid planes only (three products, not fp32-equivalent: that mode's gates are 3e-2); else the exact split
-            f16x2 = "c_scale" in w
-            check(lib.cp_wino_gemm_split_scaled_f32(V.data_ptr(), w["Us"].data_ptr(), self._wM.data_ptr(), 36 * w["tp"], w["tp"], w["ktot"], w["cout"],
-                                                    _lib.PLANES_F16X2 if f16x2 else (2 if self.layer.mode_planes == 1 else 3), w["c_scale"] if f16x2 else 1.0, stream),
-                  "cp_wino_gemm_split_scaled_f32(%s)" % self.layer.name)
-        else:
-            check(lib.cp_wino_gemm_f32(V.data_ptr(), w["U"].data_ptr(), self._wM.data_ptr(), 36 * w["tp"], w["tp"], w["ktot"], w["cout"], stream),
-                  "cp_wino_gemm_f32(%s)" % self.layer.name)
-        check(lib.cp_wino_output_transform_stats_f32(self._wM.data_ptr(), w["cout"], self.batch, self.in_h, self.in_w, self.dil, residual_ptr, w["cout"], None, None,
-                                                     None, 0, out_ptr, w["cout"], None, w["cout"], stats, stream),
-              "cp_wino_output_transform_stats_f32(%s)" % self.layer.name)
-
-    def forward(self, stream: int):
-        """The forward launch(es) of this layer; an f16x2 forward runs armed when the plan has given the op a monitor slot (mon_ptr)."""
-        with armed(self.mon_ptr if self.layer.fwd_f16x2 and self.wino_fwd is None else None):   # (a Winograd forward arms its input transforms)
-            self._forward(stream)
 
     def demote_forward_to_exact_split(self, stream: int):
         """this op's forward on the exact three-way bf16 split from now on (its f16x2 operands left the fp16 range condition): re-packs the forward
@@ -712,30 +676,119 @@ class ConvOp:
         if not L.fwd_f16x2:
             return
         L.fwd_f16x2 = False
-        sp = L.split
-        if sp is not None and sp["np"] == _lib.PLANES_F16X2:
-            sp["np"], sp["descale"] = 3, 1.0
-            sp["planes"] = torch.empty(sp["f32"].numel() // 512 * 3 * 1024, dtype=torch.uint8, device=sp["f32"].device)
-            L._refresh_split(stream)
-        g = self.gemm
-        if g is not None and g["fwd_planes"] == _lib.PLANES_F16X2:
-            g["fwd_planes"], g["c_scale"] = g["planes"], 1.0
-            self._refresh_gemm(stream)
-        w = self.wino_fwd
-        if w is not None and "c_scale" in w:
-            del w["c_scale"]
-            self._refresh_winograd(stream)
+        for sw, refresh in ((L.split, L._refresh_split), (self.gemm and self.gemm.fwd, self._refresh_gemm),
+                            (self.wino_fwd and self.wino_fwd.split, self._refresh_winograd)):
+            if sw is not None and sw.arith == _lib.PLANES_F16X2:
+                sw.set_arith(3)
+                refresh(stream)
+
+    def bind_winograd(self, V: torch.Tensor, M: torch.Tensor):
+        self._wV, self._wM = V, M
+        for w in self._wino_gemms():
+            d = w.desc
+            d.batch, d.in_h, d.in_w, d.out_h, d.out_w = 36, 1, w.tp, 1, w.tp
+            d.cout, d.kh, d.kw, d.stride, d.dilation, d.pad = w.cout, 1, 1, 1, 1, 0
+            d.num_sources = 1
+            d.src[0].data, d.src[0].channels, d.src[0].ld, d.src[0].mode = V.data_ptr(), w.ktot, w.ktot, _lib.SRC_DIRECT
+            d.weights = w.U.data_ptr()
+            d.out_raw, d.out_raw_ld, d.out_act_ld, d.residual_ld = M.data_ptr(), w.cout, w.cout, w.cout
+            d.group_rows, d.group_weight_stride = w.tp, w.cout * w.ktot
+        if self.wino_fwd is not None:  # grouped 1x1 weight-gradient problem over the 36 planes: dU[p] = dM[p]^T V[p]
+            w = self.wino_fwd
+            g = w.wdesc
+            g.batch, g.in_h, g.in_w, g.out_h, g.out_w = 1, 1, 36 * w.tp, 1, 36 * w.tp
+            g.cout, g.kh, g.kw, g.stride, g.dilation, g.pad = w.cout, 1, 1, 1, 1, 0
+            g.num_sources = 1
+            g.src[0].data, g.src[0].channels, g.src[0].ld, g.src[0].mode = w.V.data_ptr(), w.ktot, w.ktot, _lib.SRC_DIRECT
+            g.group_rows = w.tp
+
+    def _wino_run(self, w: WinoGemm, srcs, residual_ptr, out_ptr, stream, pre=None, stats=None, mon=None):
+        """srcs: list of (ptr, ld, channels); writes out_ptr[pix][w.cout] = conv (+ residual).  pre: {source index: (scale ptr, shift ptr, act)}
+        applied by the input transform; stats: fp64 [2][cout] table the output transform fills with the output's batch statistics; mon: f16x2 range
+        monitor slot armed around the input transforms (they report max |V| of what the f16x2 GEMM will convert; the GEMM itself stays un-armed:
+        the padding rows of V hold stale data)."""
+        lib = _lib.load()
+        off = 0
+        V = w.V if w.V is not None else self._wV
+        with armed(mon):
+            for i, (ptr, ld, ch) in enumerate(srcs):
+                ps, pb, pa = (pre or {}).get(i, (None, None, 0))
+                check(lib.cp_wino_input_transform_pre_f32(ptr, ld, ch, self.batch, self.in_h, self.in_w, self.dil, V.data_ptr(), w.ktot, off, ps, pb, pa, stream),
+                      "cp_wino_input_transform_pre_f32(%s)" % self.layer.name)
+                off += ch
+        sw = w.split
+        if sw is not None:
+            check(lib.cp_wino_gemm_split_scaled_f32(V.data_ptr(), sw.planes.data_ptr(), self._wM.data_ptr(), 36 * w.tp, w.tp, w.ktot, w.cout, sw.arith, sw.out_scale,
+                                                    stream), "cp_wino_gemm_split_scaled_f32(%s)" % self.layer.name)
+        else:
+            check(lib.cp_wino_gemm_f32(V.data_ptr(), w.U.data_ptr(), self._wM.data_ptr(), 36 * w.tp, w.tp, w.ktot, w.cout, stream),
+                  "cp_wino_gemm_f32(%s)" % self.layer.name)
+        check(lib.cp_wino_output_transform_stats_f32(self._wM.data_ptr(), w.cout, self.batch, self.in_h, self.in_w, self.dil, residual_ptr, w.cout, None, None,
+                                                     None, 0, out_ptr, w.cout, None, w.cout, stats, stream),
+              "cp_wino_output_transform_stats_f32(%s)" % self.layer.name)
+
+    # ---- which kernel family a launch takes: asked by the launch and by the accounting alike ------------------------------------------------
+    def forward_route(self) -> str:
+        """gemm / wino / head_record / head_affine / head / stem_split / split / f32"""
+        if self.gemm is not None:
+            return "gemm"
+        if self.wino_fwd is not None:
+            return "wino"
+        if self.head_fast:
+            return "head" if self.pre_bn is None else ("head_affine" if self.record_prefix is None else "head_record")
+        L = self.layer
+        if L.split is not None and L.k == 7:
+            if self._stem_fwd is None:   # stride 2 / pad 3 / one 4-channel source: the range of the stem kernels
+                self._stem_fwd = _lib.load().cp_conv_selected_tile(C.byref(L.desc)) == _lib.TILE_STEM
+            return "stem_split" if self._stem_fwd else "f32"
+        if L.split is not None:
+            if self._split_fwd is None:
+                self._split_fwd = bool(_lib.load().cp_conv_split_applicable(C.byref(L.desc)))
+            return "split" if self._split_fwd else "f32"
+        return "f32"
+
+    def wgrad_route(self) -> str:
+        """head_affine / head / gemm_split / wino_split / wino_f32 / direct_split / f32"""
+        if self.head_fast:
+            return "head" if self.pre_bn is None else "head_affine"
+        if self.gemm is not None and self.gemm.wgrad:
+            return "gemm_split"
+        if self.wino_fwd is not None:
+            return "wino_split" if self.wino_wgrad_split() else "wino_f32"
+        return "direct_split" if self.wgrad_planes() else "f32"
+
+    def wgrad_arith(self, route: str) -> int:
+        """the arithmetic a weight gradient on `route` runs in NOW (a key of PRODUCTS; 0: the fp32 MFMA)"""
+        L = self.layer
+        if route == "gemm_split":
+            return 1 if L.mode_planes == 1 else 3   # CASAPOSE_CONV_MODE=bf16 rounds the operands of this GEMM to bf16 like the other weight gradients
+        if route == "wino_split":
+            # fp16 two-way split (train_bwd_f16x2): dM x 2^e from its monitor slot; V as it is -- the forward's monitor keeps it in the band
+            # (a forward that left the band is demoted: L.fwd_f16x2 turns False and this GEMM returns to the exact split with it)
+            f = self.wino_fwd.slot
+            return _lib.PLANES_F16X2 if f is not None and f.e is not None and L.fwd_f16x2 else (1 if L.mode_planes == 1 else 3)
+        if route == "direct_split":
+            # both operands inside fp16's band: X watched by the forward's monitor, dY carrying the loss factor
+            return _lib.PLANES_F16X2 if L.mode_planes == 3 and self.wgrad_f16x2() else L.mode_planes
+        return 0
+
+    def forward(self, stream: int):
+        """The forward launch(es) of this layer; an f16x2 forward runs armed when the plan has given the op a monitor slot (mon_ptr)."""
+        with armed(self.mon_ptr if self.layer.fwd_f16x2 and self.wino_fwd is None else None):   # (a Winograd forward arms its input transforms)
+            self._forward(stream)
 
     def _forward(self, stream: int):
-        if self.gemm is not None:
-            g, d = self.gemm, self.layer.desc
-            check(_lib.load().cp_wino_gemm_split_scaled_f32(self.srcs[0][0].data.data_ptr(), g["Us_f"].data_ptr(), d.out_raw, g["rows"], g["rows"], g["cin"],
-                                                            self.layer.cout, g["fwd_planes"], g["c_scale"], stream), "cp_wino_gemm_split_scaled_f32(%s)" % self.layer.name)
-            return
-        if self.wino_fwd is not None:
-            d = self.layer.desc
+        lib = _lib.load()
+        L, d, route = self.layer, self.layer.desc, self.forward_route()
+        px = self.batch * self.out_h * self.out_w
+        st_, off, old_ = self._out_ptr_ld
+        if route == "gemm":
+            g = self.gemm
+            check(lib.cp_wino_gemm_split_scaled_f32(self.srcs[0][0].data.data_ptr(), g.fwd.planes.data_ptr(), d.out_raw, g.rows, g.rows, g.cin, L.cout, g.fwd.arith,
+                                                    g.fwd.out_scale, stream), "cp_wino_gemm_split_scaled_f32(%s)" % L.name)
+        elif route == "wino":
             srcs, pre = [], {}
-            for i, ((t, ld), c) in enumerate(zip(self.srcs, self.layer.sources)):
+            for i, ((t, ld), c) in enumerate(zip(self.srcs, L.sources)):
                 bn = self.pre_norm.get(i)
                 if bn is not None:   # read the RAW tensor; normalise + activate while loading
                     srcs.append((bn.x.data.data_ptr(), bn.x.c, c[0]))
@@ -743,128 +796,82 @@ class ConvOp:
                 else:
                     srcs.append((t.data.data_ptr(), ld, c[0]))
             self._wino_run(self.wino_fwd, srcs, self.residual.data.data_ptr() if self.residual is not None else None, d.out_raw, stream, pre=pre,
-                           stats=self.stats_to.sums.data_ptr() if self.stats_to is not None else None, mon=self.mon_ptr if self.layer.fwd_f16x2 else None)
-            return
-        lib = _lib.load()
-        if self.head_fast and self.pre_bn is not None and self.record_prefix is not None:
+                           stats=self.stats_to.sums.data_ptr() if self.stats_to is not None else None, mon=self.mon_ptr if L.fwd_f16x2 else None)
+        elif route == "head_record":
             bn = self.pre_bn
-            st_, off, old_ = self._out_ptr_ld
             pre, pre_ld, pre_n = self.record_prefix
             assert off == pre_n
-            check(lib.cp_head1x1_fwd_affine_record_f32(bn.x.data.data_ptr(), bn.x.c, self.batch * self.out_h * self.out_w, bn.scale.data_ptr(), bn.shift.data_ptr(),
-                                                       _ptr(bn.labels), bn.classes, bn.act, self.layer.master.data_ptr(), self.layer.cout,
-                                                       pre.data_ptr(), pre_ld, pre_n, st_.data_ptr(), old_, stream),
-                  "cp_head1x1_fwd_affine_record_f32(%s)" % self.layer.name)
-            return
-        if self.head_fast and self.pre_bn is not None:
+            check(lib.cp_head1x1_fwd_affine_record_f32(bn.x.data.data_ptr(), bn.x.c, px, bn.scale.data_ptr(), bn.shift.data_ptr(), _ptr(bn.labels), bn.classes, bn.act,
+                                                       L.master.data_ptr(), L.cout, pre.data_ptr(), pre_ld, pre_n, st_.data_ptr(), old_, stream),
+                  "cp_head1x1_fwd_affine_record_f32(%s)" % L.name)
+        elif route == "head_affine":
             bn = self.pre_bn
-            st_, off, old_ = self._out_ptr_ld
-            check(lib.cp_head1x1_fwd_affine_f32(bn.x.data.data_ptr(), bn.x.c, self.batch * self.out_h * self.out_w, bn.scale.data_ptr(), bn.shift.data_ptr(),
-                                                _ptr(bn.labels), bn.classes, bn.act, self.layer.master.data_ptr(), self.layer.cout,
-                                                st_.data_ptr() + 4 * off, old_, stream), "cp_head1x1_fwd_affine_f32(%s)" % self.layer.name)
-            return
-        if self.head_fast:
+            check(lib.cp_head1x1_fwd_affine_f32(bn.x.data.data_ptr(), bn.x.c, px, bn.scale.data_ptr(), bn.shift.data_ptr(), _ptr(bn.labels), bn.classes, bn.act,
+                                                L.master.data_ptr(), L.cout, st_.data_ptr() + 4 * off, old_, stream), "cp_head1x1_fwd_affine_f32(%s)" % L.name)
+        elif route == "head":
             t, ld = self.srcs[0]
-            st_, off, old_ = self._out_ptr_ld
-            check(lib.cp_head1x1_fwd_f32(t.data.data_ptr(), ld, self.batch * self.out_h * self.out_w, self.layer.master.data_ptr(), self.layer.cout,
-                                         st_.data_ptr() + 4 * off, old_, stream), "cp_head1x1_fwd_f32(%s)" % self.layer.name)
-            return
-        sp = self.layer.split
-        if sp is not None and sp.get("stem"):
-            if getattr(self, "_stem_fwd", None) is None:   # stride 2 / pad 3 / one 4-channel source: the range of the stem kernels
-                self._stem_fwd = lib.cp_conv_selected_tile(C.byref(self.layer.desc)) == _lib.TILE_STEM
-            if self._stem_fwd:
-                check(lib.cp_conv2d_fwd_stem_split_scaled(C.byref(self.layer.desc), sp["planes"].data_ptr(), sp["np"], sp["descale"], stream),
-                      "cp_conv2d_fwd_stem_split(%s)" % self.layer.name)
-                return
-        elif sp is not None:
-            if getattr(self, "_split_fwd", None) is None:
-                self._split_fwd = bool(lib.cp_conv_split_applicable(C.byref(self.layer.desc)))
-            if self._split_fwd:
-                check(lib.cp_conv2d_fwd_split_scaled(C.byref(self.layer.desc), sp["planes"].data_ptr(), None, sp["np"], sp["descale"], 1.0, stream),
-                      "cp_conv2d_fwd_split(%s)" % self.layer.name)
-                return
-        check(lib.cp_conv2d_fwd_f32(C.byref(self.layer.desc), stream), "cp_conv2d_fwd_f32(%s)" % self.layer.name)
+            check(lib.cp_head1x1_fwd_f32(t.data.data_ptr(), ld, px, L.master.data_ptr(), L.cout, st_.data_ptr() + 4 * off, old_, stream),
+                  "cp_head1x1_fwd_f32(%s)" % L.name)
+        elif route == "stem_split":
+            check(lib.cp_conv2d_fwd_stem_split_scaled(C.byref(d), L.split.planes.data_ptr(), L.split.arith, L.split.out_scale, stream),
+                  "cp_conv2d_fwd_stem_split(%s)" % L.name)
+        elif route == "split":
+            check(lib.cp_conv2d_fwd_split_scaled(C.byref(d), L.split.planes.data_ptr(), None, L.split.arith, L.split.out_scale, 1.0, stream),
+                  "cp_conv2d_fwd_split(%s)" % L.name)
+        else:
+            check(lib.cp_conv2d_fwd_f32(C.byref(d), stream), "cp_conv2d_fwd_f32(%s)" % L.name)
 
     def executed_flops(self) -> Dict[str, float]:
         """FLOPs this op's launches EXECUTE per step, by matrix pipe: {"f32": fp32-MFMA FLOPs, "bf16": bf16-MFMA FLOPs} -- a Winograd layer counts
-        its grouped GEMMs (36 planes x padded tiles), an exact three-way split counts six bf16 products per fp32 product; forward + weight
-        gradient + every data gradient.  (bench.py --mode train prices the step against the two pipes' peaks with it.)"""
-        from .engine import TRAIN_WINO_GEMM_SPLIT
-
+        its grouped GEMMs (36 planes x padded tiles), an arithmetic counts its PRODUCTS per fp32 product; forward + weight gradient + every data
+        gradient.  (bench.py --mode train prices the step against the two pipes' peaks with it.)  The forward and the weight gradient are priced
+        from forward_route / wgrad_route / wgrad_arith and the weight records, the answers their launches read.  The DATA gradient is not: its
+        launch decides per call (a 1x1 GEMM only while the source has no gradient yet, cp_conv_bf16_deep_applicable with the residual set,
+        cp_conv_split_applicable per launch) and is priced here from the records alone, without those fallbacks."""
         L = self.layer
-        lib = _lib.load()
         out = {"f32": 0.0, "bf16": 0.0}
-        m_out = float(self.batch * self.out_h * self.out_w)
-        cin = sum(s[1] for s in L.sources)
-        direct = 2.0 * m_out * L.k * L.k * cin * L.cout
-        wino_pipe, wino_mult = ("bf16", 3.0 if self.layer.mode_planes == 1 else 6.0) if TRAIN_WINO_GEMM_SPLIT else ("f32", 1.0)
+        direct = 2.0 * float(self.batch * self.out_h * self.out_w) * L.k * L.k * self._cin * L.cout
 
-        def split_pipe(sp):
-            return ("bf16", {3: 6.0, _lib.PLANES_F16X2: 3.0}.get(sp["np"], 1.0))   # products per fp32 product: exact bf16 split, fp16 two-way split, bf16
+        def add(sw: Optional[SplitWeights], flops: float):   # a launch reading split weights runs on the bf16 pipe, one without on the fp32 MFMA
+            out["f32" if sw is None else "bf16"] += (1.0 if sw is None else sw.products) * flops
 
-        if self.gemm is not None:
-            gm = self.gemm
-            mult = 6.0 if gm["planes"] == 3 else 3.0
-            out["bf16"] += (3.0 if gm["fwd_planes"] == _lib.PLANES_F16X2 else mult) * direct     # forward
-            if gm["Us_d"] is not None:
-                out["bf16"] += mult * direct                                                      # data gradient
-            if gm["wgrad"]:
-                out["bf16"] += (1.0 if self.layer.mode_planes == 1 else 6.0) * direct
-            else:
-                out["f32"] += direct
-            return out
-        if self.wino_fwd is not None:
-            w = self.wino_fwd
-            g = 2.0 * 36 * w["tp"] * w["ktot"] * w["cout"]
-            out[wino_pipe] += (3.0 if (L.fwd_f16x2 and TRAIN_WINO_GEMM_SPLIT) else wino_mult) * g      # forward GEMM
-            if self.wino_wgrad_split():          # weight gradient: grouped GEMM over the 36 planes, exact splits / f16x2 on the 2-byte pipe or fp32 MFMA
-                wg16 = w.get("wg16") is not None and w["wg16"].e is not None and L.fwd_f16x2
-                out["bf16"] += (1.0 if self.layer.mode_planes == 1 else (3.0 if wg16 else 6.0)) * g
-            else:
-                out["f32"] += g
+        fwd = self.forward_route()
+        w = self.wino_fwd
+        gemm = 2.0 * 36 * w.tp * w.ktot * w.cout if w is not None else direct
+        add({"gemm": self.gemm and self.gemm.fwd, "wino": w and w.split, "stem_split": L.split, "split": L.split}.get(fwd), gemm)
+        route = self.wgrad_route()
+        arith = self.wgrad_arith(route)
+        if route == "direct_split":   # conv_wgrad_split.hip takes the 32-multiple sources; the image source stays on the fp32 MFMA
+            big = sum(s[1] for s in L.sources if s[0] != 4)
+            out["bf16"] += PRODUCTS[arith] * direct * big / self._cin
+            out["f32"] += direct * (self._cin - big) / self._cin
         else:
-            if L.split is not None and (lib.cp_conv_split_applicable(C.byref(L.desc)) or (L.split.get("stem") and getattr(self, "_stem_fwd", True))):
-                pipe, mult = split_pipe(L.split)
-                out[pipe] += mult * direct
-            else:
-                out["f32"] += direct
-            wp = self.wgrad_planes()             # weight gradient: conv_wgrad_split.hip (32-multiple sources; the image source stays fp32) or fp32 MFMA
-            if wp:
-                big = sum(s[1] for s in L.sources if s[0] != 4)
-                out["bf16"] += ((3.0 if self.wgrad_f16x2() else 6.0) if wp == 3 else 1.0) * direct * big / cin
-                out["f32"] += direct * (cin - big) / cin
-            else:
-                out["f32"] += direct
-        c0 = 0
+            out["bf16" if arith else "f32"] += (PRODUCTS[arith] if arith else 1.0) * gemm
+        if self.gemm is not None:
+            if self.gemm.dgrad is not None:
+                add(self.gemm.dgrad, direct)
+            return out
+        m_in = float(self.batch * self.in_h * self.in_w)
         for s, (ent, (cp, cr)) in enumerate(zip(L.dgrad, L.sources)):
             if ent is None:
                 continue
-            if ent.get("deep") and ent["split"] is not None:
-                out["bf16"] += 2.0 * float(self.batch * self.in_h * self.in_w) * L.k * L.k * ent["cin"] * cr
+            d = 2.0 * m_in * L.k * L.k * ent.cin * cr
+            if ent.deep and ent.split is not None:
+                out["bf16"] += d
             elif s in self.wino_dgrad:
                 w = self.wino_dgrad[s]
-                f16 = w.get("f16") is not None and w["f16"].e is not None
-                out[wino_pipe] += (3.0 if f16 else wino_mult) * 2.0 * 36 * w["tp"] * w["ktot"] * w["cout"]
+                add(w.split, 2.0 * 36 * w.tp * w.ktot * w.cout)
             else:
-                m_in = float(self.batch * self.in_h * self.in_w)
-                d = 2.0 * m_in * L.k * L.k * ent["cin"] * cr
-                if ent["split"] is not None and self.stride == 1 and self.dil == 1 and L.k == 3:
-                    pipe, mult = split_pipe(ent["split"])
-                    out[pipe] += mult * d
-                else:
-                    out["f32"] += d
+                add(ent.split if self.stride == 1 and self.dil == 1 and L.k == 3 else None, d)
         return out
 
     def wino_wgrad_split(self) -> bool:
         """True when this Winograd layer's weight-gradient GEMM runs on the bf16 matrix pipe: the default wherever the Winograd GEMMs do
         (CASAPOSE_WINO_GEMM != f32) and the shape fits (cout, cin multiples of 128); CASAPOSE_WINO_WGRAD=f32 keeps the fp32 grouped GEMM."""
-        from .engine import TRAIN_WINO_GEMM_SPLIT
-
         w = self.wino_fwd
-        if w is None or not TRAIN_WINO_GEMM_SPLIT or os.environ.get("CASAPOSE_WINO_WGRAD", "split") == "f32":
+        if w is None or w.split is None or os.environ.get("CASAPOSE_WINO_WGRAD", "split") == "f32":
             return False
-        return bool(_lib.load().cp_wino_wgrad_split_applicable(36, w["tp"], self.layer.cout, w["ktot"]))
+        return bool(_lib.load().cp_wino_wgrad_split_applicable(36, w.tp, self.layer.cout, w.ktot))
 
     def wgrad_planes(self) -> int:
         """3 / 1 when this op's weight gradient runs on the bf16 matrix pipe (CASAPOSE_CONV_MODE split / bf16 and a descriptor that
@@ -891,66 +898,53 @@ class ConvOp:
         L = self.layer
         dy, dy_ld = self._dy()
         d = L.desc  # one op per layer: filled by this op's constructor
-        if self.head_fast and self.pre_bn is not None:   # the activated input is recomputed from the raw tensor
+        acc = 1 if self.accumulate_master else 0
+        px = self.batch * self.out_h * self.out_w
+        route = self.wgrad_route()
+        if route == "head_affine":   # the activated input is recomputed from the raw tensor
             bn = self.pre_bn
-            px = self.batch * self.out_h * self.out_w
             check(lib.cp_head1x1_wgrad_affine_f32(bn.x.data.data_ptr(), bn.x.c, bn.scale.data_ptr(), bn.shift.data_ptr(), _ptr(bn.labels), bn.classes, bn.act,
-                                                  dy, dy_ld, px, L.cout, L.master_grad.data_ptr(), 1 if self.accumulate_master else 0, stream),
-                  "cp_head1x1_wgrad_affine_f32(%s)" % L.name)
-            return
-        if self.head_fast:
+                                                  dy, dy_ld, px, L.cout, L.master_grad.data_ptr(), acc, stream), "cp_head1x1_wgrad_affine_f32(%s)" % L.name)
+        elif route == "head":
             t, ld = self.srcs[0]
-            px = self.batch * self.out_h * self.out_w
-            check(lib.cp_head1x1_wgrad_f32(t.data.data_ptr(), ld, dy, dy_ld, px, L.cout, L.master_grad.data_ptr(), 1 if self.accumulate_master else 0, stream),
-                  "cp_head1x1_wgrad_f32(%s)" % L.name)
-            return
-        if self.gemm is not None and self.gemm["wgrad"]:
+            check(lib.cp_head1x1_wgrad_f32(t.data.data_ptr(), ld, dy, dy_ld, px, L.cout, L.master_grad.data_ptr(), acc, stream), "cp_head1x1_wgrad_f32(%s)" % L.name)
+        elif route == "gemm_split":
             # dU[co][ci] = sum_rows dY[row][co] A[row][ci] on the bf16 pipe, then through the transpose map into the master gradient [ci][co]
             g = self.gemm
-            check(lib.cp_wino_wgrad_split_f32(dy, self.srcs[0][0].data.data_ptr(), g["dU"].data_ptr(), 1, g["rows"], L.cout, g["cin"],
-                                              1 if self.layer.mode_planes == 1 else 3, stream), "cp_wino_wgrad_split_f32(%s)" % L.name)
-            check(lib.cp_scatter_f32(g["dU"].data_ptr(), g["idx_t"].data_ptr(), g["idx_t"].numel(), L.master_grad.data_ptr(), 1 if self.accumulate_master else 0,
-                                     stream), "cp_scatter_f32(%s)" % L.name)
-            return
-        if self.wino_fwd is not None:
+            check(lib.cp_wino_wgrad_split_f32(dy, self.srcs[0][0].data.data_ptr(), g.dU.data_ptr(), 1, g.rows, L.cout, g.cin, self.wgrad_arith(route), stream),
+                  "cp_wino_wgrad_split_f32(%s)" % L.name)
+            check(lib.cp_scatter_f32(g.dU.data_ptr(), g.idx_t.data_ptr(), g.idx_t.numel(), L.master_grad.data_ptr(), acc, stream), "cp_scatter_f32(%s)" % L.name)
+        elif route in ("wino_split", "wino_f32"):
             # weight gradient through the Winograd planes: a quarter of the MFMA work of the direct kernel (V kept from the forward)
             w = self.wino_fwd
             cin, cout = self._cin, L.cout
-            f = w.get("wg16") if self.wino_wgrad_split() else None
+            f = w.slot if route == "wino_split" else None
             with armed(f.mon if f is not None and not f.dead else None):   # the transform reports max |dM|
                 check(lib.cp_wino_dy_transform_f32(dy, dy_ld, cout, self.batch, self.in_h, self.in_w, self.dil, self._wM.data_ptr(), stream),
                       "cp_wino_dy_transform_f32(%s)" % L.name)
-            if self.wino_wgrad_split():   # the grouped GEMM dU[p] = dM[p]^T V[p] on the bf16 matrix pipe (exact splits; csrc/wino_wgrad_split.hip)
-                # exact splits (fp32-equivalent) by default; CASAPOSE_CONV_MODE=bf16 rounds the operands of this GEMM to bf16 like the other weight gradients
-                if f is not None and f.e is not None and L.fwd_f16x2:
-                    # fp16 two-way split (train_bwd_f16x2): dM x 2^e from its monitor slot; V as it is -- the forward's monitor keeps it in the band
-                    # (a forward that left the band is demoted: L.fwd_f16x2 turns False and this GEMM returns to the exact split with it)
-                    check(lib.cp_wino_wgrad_split_scaled_f32(self._wM.data_ptr(), w["V"].data_ptr(), w["dU"].data_ptr(), 36, w["tp"], cout, w["ktot"],
-                                                             _lib.PLANES_F16X2, 2.0 ** f.e, 1.0, stream), "cp_wino_wgrad_split_scaled_f32(%s)" % L.name)
-                else:
-                    check(lib.cp_wino_wgrad_split_f32(self._wM.data_ptr(), w["V"].data_ptr(), w["dU"].data_ptr(), 36, w["tp"], cout, w["ktot"],
-                                                      1 if self.layer.mode_planes == 1 else 3, stream),
-                          "cp_wino_wgrad_split_f32(%s)" % L.name)
+            arith = self.wgrad_arith(route)
+            if arith == _lib.PLANES_F16X2:   # the grouped GEMM dU[p] = dM[p]^T V[p] on the 2-byte pipe (csrc/wino_wgrad_split.hip): fp16 pairs, dM x 2^e
+                check(lib.cp_wino_wgrad_split_scaled_f32(self._wM.data_ptr(), w.V.data_ptr(), w.dU.data_ptr(), 36, w.tp, cout, w.ktot, arith, 2.0 ** f.e, 1.0, stream),
+                      "cp_wino_wgrad_split_scaled_f32(%s)" % L.name)
+            elif arith:   # ... exact splits (fp32-equivalent), or operands rounded to bf16
+                check(lib.cp_wino_wgrad_split_f32(self._wM.data_ptr(), w.V.data_ptr(), w.dU.data_ptr(), 36, w.tp, cout, w.ktot, arith, stream),
+                      "cp_wino_wgrad_split_f32(%s)" % L.name)
             else:
-                check(lib.cp_conv2d_wgrad_f32(C.byref(w["wdesc"]), self._wM.data_ptr(), cout, w["dU"].data_ptr(), 0, stream), "cp_conv2d_wgrad_f32(wino %s)" % L.name)
+                check(lib.cp_conv2d_wgrad_f32(C.byref(w.wdesc), self._wM.data_ptr(), cout, w.dU.data_ptr(), 0, stream), "cp_conv2d_wgrad_f32(wino %s)" % L.name)
             c0 = k0 = 0
             for cp_, cr in L.sources:
-                check(lib.cp_wino_weight_grad_f32(w["dU"].data_ptr(), cr, cout, w["ktot"], k0, 3 * cin * cout, cin * cout, cout, 1,
-                                                  L.master_grad.data_ptr() + 4 * c0 * cout, 1 if self.accumulate_master else 0, stream),
-                      "cp_wino_weight_grad_f32(%s)" % L.name)
+                check(lib.cp_wino_weight_grad_f32(w.dU.data_ptr(), cr, cout, w.ktot, k0, 3 * cin * cout, cin * cout, cout, 1,
+                                                  L.master_grad.data_ptr() + 4 * c0 * cout, acc, stream), "cp_wino_weight_grad_f32(%s)" % L.name)
                 c0 += cr
                 k0 += cp_
         else:
-            planes = self.wgrad_planes()
-            if planes == 3 and self.wgrad_f16x2():
-                planes = _lib.PLANES_F16X2   # both operands inside fp16's band: X watched by the forward's monitor, dY carrying the loss factor
-            if planes:   # bf16 matrix pipe (csrc/conv_wgrad_split.hip): same packed result
-                with armed(self.bw16.mon if planes == _lib.PLANES_F16X2 else None):   # (the fp16 pair: dY's overflow guard, every step)
-                    check(lib.cp_conv2d_wgrad_split(C.byref(d), dy, dy_ld, L.dwp.data_ptr(), 0, planes, stream), "cp_conv2d_wgrad_split(%s)" % L.name)
+            arith = self.wgrad_arith(route)
+            if arith:   # bf16 matrix pipe (csrc/conv_wgrad_split.hip): same packed result
+                with armed(self.bw16.mon if arith == _lib.PLANES_F16X2 else None):   # (the fp16 pair: dY's overflow guard, every step)
+                    check(lib.cp_conv2d_wgrad_split(C.byref(d), dy, dy_ld, L.dwp.data_ptr(), 0, arith, stream), "cp_conv2d_wgrad_split(%s)" % L.name)
             else:
                 check(lib.cp_conv2d_wgrad_f32(C.byref(d), dy, dy_ld, L.dwp.data_ptr(), 0, stream), "cp_conv2d_wgrad_f32(%s)" % L.name)
-            check(lib.cp_scatter_f32(L.dwp.data_ptr(), L.idx_fwd.data_ptr(), L.idx_fwd.numel(), L.master_grad.data_ptr(), 1 if self.accumulate_master else 0,
-                                     stream), "cp_scatter_f32")
+            check(lib.cp_scatter_f32(L.dwp.data_ptr(), L.idx_fwd.data_ptr(), L.idx_fwd.numel(), L.master_grad.data_ptr(), acc, stream), "cp_scatter_f32")
 
     def backward_dgrad(self, stream: int):
         lib = _lib.load()
@@ -971,38 +965,38 @@ class ConvOp:
             if ent is None:
                 continue
             t, _ = self.srcs[s]
-            if self.gemm is not None and self.gemm["Us_d"] is not None and not t.has_grad:
+            if self.gemm is not None and self.gemm.dgrad is not None and not t.has_grad:
                 # dA[row][ci] = sum_co dY[row][co] W[ci][co]; the GEMM writes (no accumulation): the plan runs this op's backward BEFORE the
                 # other consumers of its input (TrainPlan puts the shortcut after conv1 in the tape), which then accumulate into it
                 g = self.gemm
-                check(lib.cp_wino_gemm_split_planes_f32(dy, g["Us_d"].data_ptr(), t.grad.data_ptr(), g["rows"], g["rows"], L.cout, g["cin"], g["planes"], stream),
+                check(lib.cp_wino_gemm_split_planes_f32(dy, g.dgrad.planes.data_ptr(), t.grad.data_ptr(), g.rows, g.rows, L.cout, g.cin, g.dgrad.arith, stream),
                       "cp_wino_gemm_split_planes_f32(dgrad %s)" % L.name)
                 t.has_grad = True
                 continue
-            if ent.get("deep") and ent["split"] is not None:
-                g = ent["desc"]
+            if ent.deep and ent.split is not None:
+                g = ent.desc
                 g.src[0].data, g.src[0].ld = dy, dy_ld
                 g.residual = t.grad.data_ptr() if t.has_grad else None
                 if lib.cp_conv_bf16_deep_applicable(C.byref(g)):
-                    check(lib.cp_conv2d_fwd_bf16_deep(C.byref(g), ent["split"]["planes"].data_ptr(), stream), "dgrad bf16 deep(%s)" % L.name)
+                    check(lib.cp_conv2d_fwd_bf16_deep(C.byref(g), ent.split.planes.data_ptr(), stream), "dgrad bf16 deep(%s)" % L.name)
                     t.has_grad = True
                     continue
             if s in self.wino_dgrad:  # stride 1, so the data gradient lives on the forward's input grid
                 w = self.wino_dgrad[s]
-                f = w.get("f16")
-                pre = {0: (w["ps"].data_ptr(), None, _lib.ACT_NONE)} if f is not None and f.e is not None else None   # (a factor only: no shift table)
+                f = w.slot
+                pre = {0: (w.ps.data_ptr(), None, _lib.ACT_NONE)} if f is not None and f.e is not None else None   # (a factor only: no shift table)
                 self._wino_run(w, [(dy, dy_ld, L.cout)], t.grad.data_ptr() if t.has_grad else None, t.grad.data_ptr(), stream, pre=pre,
                                mon=f.mon if f is not None and not f.dead else None)
                 t.has_grad = True
                 continue
-            g = ent["desc"]
+            g = ent.desc
             g.src[0].data, g.src[0].ld = dy, dy_ld
             g.residual = t.grad.data_ptr() if t.has_grad else None
-            sp = ent["split"]
+            sp = ent.split
             if sp is not None and lib.cp_conv_split_applicable(C.byref(g)):
                 # the fp16 pair runs armed on every step: max |dY| into the op's backward slot, and its overflow guard
-                with armed(self.bw16.mon if sp["np"] == _lib.PLANES_F16X2 and self.bw16 is not None else None):
-                    check(lib.cp_conv2d_fwd_split_scaled(C.byref(g), sp["planes"].data_ptr(), None, sp["np"], sp["descale"], 1.0, stream), "dgrad split(%s)" % L.name)
+                with armed(self.bw16.mon if sp.arith == _lib.PLANES_F16X2 and self.bw16 is not None else None):
+                    check(lib.cp_conv2d_fwd_split_scaled(C.byref(g), sp.planes.data_ptr(), None, sp.arith, sp.out_scale, 1.0, stream), "dgrad split(%s)" % L.name)
             else:
                 check(lib.cp_conv2d_fwd_f32(C.byref(g), stream), "dgrad(%s)" % L.name)
             t.has_grad = True
@@ -1402,7 +1396,7 @@ class TrainPlan:
         # the backward GEMMs on fp16 pairs (train_bwd_f16x2), one slot each behind the forward's: Winograd data / weight gradients, direct 3x3 layers
         slots = []
         for op in (op for op in self.ops if isinstance(op, ConvOp)):
-            slots += [r for r in [w.get("f16") for w in op.wino_dgrad.values()] + [(op.wino_fwd or {}).get("wg16")] if r is not None]
+            slots += [w.slot for w in list(op.wino_dgrad.values()) + [op.wino_fwd] if w is not None and w.slot is not None]
             if op.direct_dgrad_split() or (train_bwd_f16x2() and op.wgrad_planes() == 3):
                 op.bw16 = BwdSlot("direct", op)
                 slots.append(op.bw16)

@@ -102,7 +102,7 @@ def test_conv_wgrad_dgrad(device, case):
 
         op.setup_gemm()
         if conv_split_planes():   # CASAPOSE_CONV_MODE=f32 keeps these layers on the fp32-MFMA kernels
-            assert op.gemm is not None and op.gemm["wgrad"] == ("small" not in name and os.environ.get("CASAPOSE_WINO_WGRAD", "split") != "f32")
+            assert op.gemm is not None and op.gemm.wgrad == ("small" not in name and os.environ.get("CASAPOSE_WINO_WGRAD", "split") != "f32")
         else:
             assert op.gemm is None
     if "winograd" in name:  # what TrainPlan does for the deep layers: Winograd forward + data gradient
@@ -1418,7 +1418,7 @@ def test_direct_fp16_pair_gradients_of_every_layer_match_fp64(device, monkeypatc
             exact = [None if t.grad is None else t.grad.double().cpu().clone() for t, _ in op.srcs]
         c0 = 0
         for s, (ent, (cp_, cr)) in enumerate(zip(L.dgrad, L.sources)):
-            direct = ent is not None and ent["split"] is not None and not ent.get("deep") and s not in getattr(op, "wino_dgrad", {})
+            direct = ent is not None and ent.split is not None and not ent.deep and s not in getattr(op, "wino_dgrad", {})
             if direct:
                 g = got[s].reshape(op.batch, op.in_h, op.in_w, -1)[..., :cr]
                 if simple:
@@ -1487,3 +1487,51 @@ def test_a_second_plan_on_the_same_store_runs_past_a_reading(device, monkeypatch
     steps(plan2, 10, 1, 96, 128, 2)
     torch.cuda.synchronize()
     assert plan2.f16x2_checks >= 1 and plan2.f16x2_skipped_steps == 0 and int(store.skip[1]) == 0
+
+
+@pytest.mark.gpu
+def test_accounting_follows_a_plan_taken_back_to_the_exact_split(device, monkeypatch):
+    """executed_flops reads the arithmetic from the records the launches read: a default plan (two steps: the second backward runs on fp16 pairs)
+    taken back to the exact split -- every forward demoted, every backward GEMM switched off -- is priced, op by op and pipe by pipe, like a plan
+    built with CASAPOSE_TRAIN_FWD=split CASAPOSE_TRAIN_BWD=split, and every weight set of it is a three-way split with output factor 1."""
+    from casapose_amd.train_engine import ConvOp, TrainPlan
+
+    for v_ in ("CASAPOSE_TRAIN_FWD", "CASAPOSE_CONV_MODE", "CASAPOSE_TRAIN_BWD"):
+        monkeypatch.delenv(v_, raising=False)
+    k, b, h, w = 4, 1, 96, 128
+    params, store, plan, img, lab, kpts = _setup(device, b, h, w, k)
+    stream = torch.cuda.current_stream(device).cuda_stream
+    plan.refresh_weights(stream)
+    imgd, labd, kpd = torch.from_numpy(img).to(device), torch.from_numpy(lab).to(device), torch.from_numpy(kpts).to(device)
+    for _ in range(2):
+        plan.train_step(imgd, labd, labd, kpd, 1e-4, cond_labels=labd, weights=(1.0, 0.5, 0.015), filter_with_segmentation=False)
+    torch.cuda.synchronize()
+    slots = plan._bwd_slots()
+    assert any(r.on or r.e is not None for _, r, _ in slots), "no backward GEMM moved to fp16 pairs: nothing to take back"
+    ops_a = [op for op in plan.ops if isinstance(op, ConvOp)]
+    for op in ops_a:
+        op.demote_forward_to_exact_split(stream)
+        if op.bw16 is not None:
+            op.set_direct_dgrad_f16x2(False, stream)
+    for op, r, entry in slots:
+        if r.kind == "wino_dgrad":
+            op.set_dgrad_exponent(entry, None, stream)
+        elif r.kind == "wino_wgrad":
+            r.e = None
+    monkeypatch.setenv("CASAPOSE_TRAIN_FWD", "split")
+    monkeypatch.setenv("CASAPOSE_TRAIN_BWD", "split")
+    plan_b = TrainPlan(store, k, 27, b, h, w, partial=(True,) * 5, guided=(False, True, True, True, False), bilinear=(False,) * 5)
+    ops_b = [op for op in plan_b.ops if isinstance(op, ConvOp)]
+    assert [op.layer.name for op in ops_a] == [op.layer.name for op in ops_b]
+    for a, c in zip(ops_a, ops_b):
+        # (the dilated 128 -> 256 layer takes the Winograd route only where the forward starts on fp16 pairs, setup_winograd: plan A keeps that route
+        # on the exact split, {"bf16": 5435817984, "f32": 0}, plan B runs the direct kernels, {"bf16": 1811939328, "f32": 226492416})
+        if a.layer.name != "stage3_unit1_conv1":
+            assert a.executed_flops() == c.executed_flops(), a.layer.name
+    sets = []
+    for op in ops_a:
+        sets += [(op.layer.name, sw) for sw in op.layer._splits() + [g.split for g in op._wino_gemms()] + ([op.gemm.fwd, op.gemm.dgrad] if op.gemm is not None else [])
+                 if sw is not None]
+    assert sets
+    for name, sw in sets:
+        assert sw.arith == 3 and sw.out_scale == 1.0, (name, sw.arith, sw.out_scale)
