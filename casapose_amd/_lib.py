@@ -261,6 +261,9 @@ SYMBOLS = [
     ("cp_pose_eval_workspace_bytes", C.c_size_t, [_i, _i, _i]),
     ("cp_pose_eval_est_tile", _i, []),
     ("cp_pose_eval_f32", _i, [_vp, _vp, _vp, _i, _i, _vp, _i, _f, _vp, _vp, _vp, _vp, _vp]),
+    # ---- device PnP (csrc/pnp.hip) and its host twin ----
+    ("cp_pnp_f64", _i, [_vp, _vp, _vp, _i, _vp, _vp, _vp, _i, _i, _i, _i, _f, _vp, _vp, _vp, _vp]),
+    ("cp_pnp_host_f64", _i, [_vp, _vp, _vp, _i, _vp, _vp, _vp, _i, _i, _i, _i, _f, _vp, _vp, _vp]),
 ]
 
 _lib: Optional[C.CDLL] = None

@@ -1,0 +1,150 @@
+"""PnP on the device: voted keypoints -> [3,4] poses for every (image, object) pair of a batch in one launch (`cp_pnp_f64`, csrc/pnp.hip).
+
+The counterpart of the host path `pnp.pnp` (ransac_voting.pnp :13-57 of the reference: RANSAC-EPnP, then iterative refinement over all points).
+`DevicePnP` replaces the random sampling by a fixed table of 5-point hypotheses, all of them when there are at most 256, and takes the consensus by
+a total order, so a call is reproducible bit for bit.  Its final pose is the Levenberg-Marquardt optimum of the same all-point reprojection error
+as the host's: the same optimum, not the same bits.  `solve_host` runs the same code on the CPU (`cp_pnp_host_f64`).  There is
+no host fall-back: a failing call raises `CasaposeHipError`.
+"""
+from __future__ import annotations
+
+import itertools
+import os
+from typing import Optional
+
+import numpy as np
+import torch
+
+from .. import _lib
+from .pose_evaluation import _np
+
+MIN_POINTS, MAX_POINTS, SET_POINTS, MAX_HYPOTHESES = 5, 16, 5, 256
+STATUS_OK, STATUS_SKIPPED, STATUS_NONFINITE_INPUT, STATUS_DEGENERATE, STATUS_NO_SOLUTION = range(5)
+
+
+def hypothesis_table(n_points: int) -> np.ndarray:
+    """uint8 [H, 5]: every 5-subset of n points in lexicographic order when there are at most 256 of them (n <= 10), otherwise 256 distinct
+    subsets drawn with np.random.default_rng(0), sorted."""
+    n = int(n_points)
+    if n < MIN_POINTS:
+        raise ValueError("the device PnP needs at least %d keypoints (got %d); fewer stay with the host path (pnp.pnp)" % (MIN_POINTS, n))
+    if n > MAX_POINTS:
+        raise ValueError("the device PnP takes at most %d keypoints (got %d); more stay with the host path (pnp.pnp)" % (MAX_POINTS, n))
+    rows = list(itertools.combinations(range(n), SET_POINTS))
+    if len(rows) > MAX_HYPOTHESES:
+        keep = np.sort(np.random.default_rng(0).choice(len(rows), MAX_HYPOTHESES, replace=False))
+        rows = [rows[i] for i in keep]
+    return np.asarray(rows, np.uint8).reshape(-1, SET_POINTS)
+
+
+def affine_from_offsets(offsets) -> np.ndarray:
+    """float64 [b, 6]: transform_points_back (pose_evaluation.py) as x' = a0 x + a1 y + a2, y' = a3 x + a4 y + a5."""
+    o = _np(offsets).reshape(-1, 10)
+    hc, wc, dx, dy, ang, sc, sx, sy = o[:, 0], o[:, 1], o[:, 4], o[:, 5], o[:, 6], o[:, 7], o[:, 8], o[:, 9]
+    ar = -ang * (np.pi / 180.0)
+    a, b = np.cos(ar), np.sin(ar)
+    c = (1.0 - a) * (sx / 2.0) - b * (sy / 2.0)
+    d = b * (sx / 2.0) + (1.0 - a) * (sy / 2.0)
+    tx, ty = wc - dx, hc - dy   # p = xy / sc + (tx, ty)
+    return np.stack([a / sc, b / sc, a * tx + b * ty + c, -b / sc, a / sc, -b * tx + a * ty + d], axis=1)
+
+
+class DevicePnP:
+    """device: a torch device, or None for a solver that only offers solve_host (no GPU needed)."""
+
+    def __init__(self, device, n_points: int, reprojection_error: float = 12.0):
+        self.table_host = hypothesis_table(n_points)
+        self._lib = _lib.load()
+        self.n_points, self.hypotheses = int(n_points), int(self.table_host.shape[0])
+        self.reprojection_error = float(reprojection_error)
+        self.device = None if device is None else torch.device(device)
+        self.table = None if self.device is None else torch.from_numpy(self.table_host).to(self.device)
+        self.last_info: Optional[np.ndarray] = None
+        self.last_cost: Optional[np.ndarray] = None
+        self.last_poses = None
+
+    def _shapes(self, points_xy, points_3d, K, solve_mask, affine):
+        if points_xy.ndim != 4 or points_xy.shape[2] != self.n_points or points_xy.shape[3] != 2:
+            raise ValueError("points_xy must be [b, oc, %d, 2] (got %s)" % (self.n_points, tuple(points_xy.shape)))
+        b, oc = int(points_xy.shape[0]), int(points_xy.shape[1])
+        if tuple(points_3d.shape) != (b, oc, self.n_points, 3):
+            raise ValueError("points_3d must be [%d, %d, %d, 3] (got %s)" % (b, oc, self.n_points, tuple(points_3d.shape)))
+        if tuple(K.shape) not in ((3, 3), (b, 3, 3)):
+            raise ValueError("K must be [3, 3] or [%d, 3, 3] (got %s)" % (b, tuple(K.shape)))
+        if tuple(solve_mask.shape) != (b, oc):
+            raise ValueError("solve_mask must be [%d, %d] (got %s)" % (b, oc, tuple(solve_mask.shape)))
+        if affine is not None and tuple(affine.shape) != (b, 6):
+            raise ValueError("affine must be [%d, 6] (got %s)" % (b, tuple(affine.shape)))
+        return b, oc
+
+    def _device_tensor(self, a, dtype):
+        if not hasattr(a, "detach"):
+            a = torch.from_numpy(np.ascontiguousarray(np.asarray(a)))
+        return a.to(device=self.device, dtype=dtype).contiguous()
+
+    def launch(self, xy, x3, K, mask, affine, poses, info, cost) -> None:
+        """cp_pnp_f64 on the current stream over contiguous device tensors of the right types."""
+        b, oc = int(xy.shape[0]), int(xy.shape[1])
+        stream = torch.cuda.current_stream(self.device).cuda_stream
+        _lib.check(self._lib.cp_pnp_f64(xy.data_ptr(), x3.data_ptr(), K.data_ptr(), int(K.dim() == 3), None if affine is None else affine.data_ptr(),
+                                        mask.data_ptr(), self.table.data_ptr(), b, oc, self.n_points, self.hypotheses, self.reprojection_error,
+                                        poses.data_ptr(), info.data_ptr(), cost.data_ptr(), stream), "cp_pnp_f64")
+
+    def solve(self, points_xy, points_3d, K, solve_mask, affine=None):
+        """points_xy [b,oc,n,2] (x,y), points_3d [b,oc,n,3], K [3,3] or [b,3,3], solve_mask [b,oc] (0: the zero pose), affine None or [b,6]
+        (affine_from_offsets): device tensors, or host arrays that are uploaded.  -> poses, a device tensor [b,oc,3,4].  `last_info` int32
+        [b,oc,4] (status, winning hypothesis, inlier count, LM iterations) and `last_cost` float32 [b,oc,2] are downloaded with it."""
+        if self.device is None:
+            raise _lib.CasaposeHipError("this DevicePnP was built without a device: only solve_host is available")
+        with torch.cuda.device(self.device):
+            xy, x3 = self._device_tensor(points_xy, torch.float32), self._device_tensor(points_3d, torch.float32)
+            Kd, mask = self._device_tensor(K, torch.float32), self._device_tensor(solve_mask, torch.int32)
+            aff = None if affine is None else self._device_tensor(affine, torch.float64)
+            b, oc = self._shapes(xy, x3, Kd, mask, aff)
+            poses = torch.empty((b, oc, 3, 4), dtype=torch.float32, device=self.device)
+            info = torch.empty((b, oc, 4), dtype=torch.int32, device=self.device)
+            cost = torch.empty((b, oc, 2), dtype=torch.float32, device=self.device)
+            self.launch(xy, x3, Kd, mask, aff, poses, info, cost)
+            self.last_info, self.last_cost = info.cpu().numpy(), cost.cpu().numpy()   # the copies synchronise
+        self.last_poses = poses
+        return poses
+
+    def solve_host(self, points_xy, points_3d, K, solve_mask, affine=None) -> np.ndarray:
+        """The host twin of solve() on NumPy arrays: the same code, serially, without a GPU.  -> poses float32 [b,oc,3,4]."""
+        xy, x3 = np.ascontiguousarray(_np(points_xy, np.float32)), np.ascontiguousarray(_np(points_3d, np.float32))
+        Kh, mask = np.ascontiguousarray(_np(K, np.float32)), np.ascontiguousarray(_np(solve_mask, np.int32))
+        aff = None if affine is None else np.ascontiguousarray(_np(affine, np.float64))
+        b, oc = self._shapes(xy, x3, Kh, mask, aff)
+        poses, info, cost = np.empty((b, oc, 3, 4), np.float32), np.empty((b, oc, 4), np.int32), np.empty((b, oc, 2), np.float32)
+        _lib.check(self._lib.cp_pnp_host_f64(xy.ctypes.data, x3.ctypes.data, Kh.ctypes.data, int(Kh.ndim == 3), None if aff is None else aff.ctypes.data,
+                                             mask.ctypes.data, self.table_host.ctypes.data, b, oc, self.n_points, self.hypotheses,
+                                             self.reprojection_error, poses.ctypes.data, info.ctypes.data, cost.ctypes.data), "cp_pnp_host_f64")
+        self.last_info, self.last_cost, self.last_poses = info, cost, poses
+        return poses
+
+
+class HostTwinPnP(DevicePnP):
+    """A solver whose solve() is the host twin: the callers' rules (pose_evaluation.py) can be exercised without a GPU."""
+
+    def __init__(self, n_points: int, reprojection_error: float = 12.0):
+        super().__init__(None, n_points, reprojection_error)
+
+    def solve(self, points_xy, points_3d, K, solve_mask, affine=None):
+        return torch.from_numpy(self.solve_host(points_xy, points_3d, K, solve_mask, affine))
+
+
+_from_environment = None   # (n_points, device, solver) of the last solver_from_environment call
+
+
+def solver_from_environment(n_points: int, device) -> Optional[DevicePnP]:
+    """CASAPOSE_DEVICE_PNP=1: the solver for n_points keypoints on `device`, built on the first call and kept while both stay the same.  Anything
+    else: None, the host path.  Says `pnp: device` when it builds one."""
+    global _from_environment
+    if os.environ.get("CASAPOSE_DEVICE_PNP", "0") != "1":
+        return None
+    device = torch.device(device)
+    c = _from_environment
+    if c is None or c[0] != int(n_points) or c[1] != device:
+        _from_environment = (int(n_points), device, DevicePnP(device, n_points))
+        print("pnp: device")
+    return _from_environment[2]

@@ -3,7 +3,9 @@
 Counterparts of estimate_poses / evaluate_poses / map_estimates (casapose/pose_estimation/ransac_voting.py:487-687)
 and of estimate_and_evaluate_poses / evaluate_pose_estimates / poses_pnp (pose_evaluation.py:11-217).  The reference runs
 these through tf.map_fn + tf.numpy_function (PnP under the GIL); here they are plain NumPy fp64 over the tiny
-[B, objects, kp] tensors the GPU voters hand back -- the PnP solve stays on the host by design (north_star).
+[B, objects, kp] tensors the GPU voters hand back -- the PnP solve is on the host by default (north_star).  Opt-in: a `solver`
+(device_pnp.DevicePnP) solves every (image, object) pair of the batch in one launch on the GPU; which pairs are solved is decided here, by the
+same rules as on the host path.
 Inputs may be torch tensors (any device) or arrays; outputs are NumPy float32 like the reference's.
 """
 from __future__ import annotations
@@ -44,17 +46,33 @@ def project(xyz: np.ndarray, K: np.ndarray, RT: np.ndarray) -> Tuple[np.ndarray,
     return np.where(z != 0, pix[:, :2] / np.where(z != 0, z, 1.0), 0.0), cam
 
 
-def estimate_poses(points, keypoints, camera_matrixes, valid_points_filter, offsets, rng=None):
+def _solved_poses(solver, points_xy, points_3d, cams, mask, affine) -> np.ndarray:
+    """One solver call for the batch -> float32 [b,oc,3,4] on the host.  A pair that was asked for and came back without a pose (a non-finite or
+    degenerate keypoint set) has the zero pose, like the host path's failed solve (ransac_voting.py:48-49)."""
+    poses = solver.solve(points_xy, points_3d, cams, mask, affine=affine)
+    poses = poses.detach().cpu().numpy() if hasattr(poses, "detach") else np.asarray(poses)
+    return poses.astype(np.float32, copy=False).reshape(mask.shape[0], mask.shape[1], 3, 4)
+
+
+def estimate_poses(points, keypoints, camera_matrixes, valid_points_filter, offsets, rng=None, solver=None):
     """points [b,oc,vn,2] (x,y) crop pixels; keypoints [b,oc,ic,vn,3]; camera_matrixes [b,3,3]; valid_points_filter [b,oc];
     offsets [b,10]  ->  (poses [b,oc,3,4], false_positive [oc]).  A point set summing to |.| < 0.01 means "object not
     voted" and yields the zero pose (map_offsets / map_pnp, :488-515); a non-empty vote for an object that is not in the
-    ground truth counts as a false positive (:518-523)."""
+    ground truth counts as a false positive (:518-523).  solver: a DevicePnP solves the voted pairs in one call instead of the loop
+    over pnp.pnp; the zero poses and the false-positive counts follow the same rules."""
     pts = _np(points)
     kp3 = _np(keypoints)
     cams = _np(camera_matrixes)
     valid = _np(valid_points_filter)
     offs = _np(offsets)
     b, oc, vn, _ = pts.shape
+    if solver is not None:
+        from .device_pnp import affine_from_offsets
+
+        sums = pts.sum(axis=(2, 3))
+        false_pos = ((valid.reshape(b, oc) == 0) & (sums > 0)).sum(axis=0).astype(np.float32)
+        mask = (np.abs(sums) >= 0.01).astype(np.int32)
+        return _solved_poses(solver, pts, kp3[:, :, 0], cams, mask, affine_from_offsets(offs)), false_pos
     poses = np.zeros((b, oc, 3, 4), np.float32)
     false_pos = np.zeros(oc, np.float32)
     for n in range(b):
@@ -170,9 +188,9 @@ def evaluate_pose_estimates(points_estimated, poses, poses_gt, target_seg, objec
 
 def estimate_and_evaluate_poses(output_seg, target_seg, output_vertex, poses_gt, object_points_3d, camera_data, diameters, offsets,
                                 evaluation_points=None, object_points_3d_count=None, points_estimated=None, min_num: int = 20,
-                                draws=None, evaluator=None):
+                                draws=None, evaluator=None, solver=None):
     """pose_evaluation.py:11-97: RANSAC keypoint voting on the arg-max mask (unless points are given), host PnP, then
-    evaluate_poses (on the GPU with a DevicePoseEvaluator as `evaluator`).  output_seg [b,h,w,K], output_vertex [b,h,w,2*kp] device tensors."""
+    evaluate_poses (on the GPU with a DevicePoseEvaluator as `evaluator`); `solver`: a DevicePnP replaces the host PnP.  output_seg [b,h,w,K], output_vertex [b,h,w,2*kp] device tensors."""
     import torch
 
     from .ransac_voting import ransac_voting_layer_all_masks
@@ -196,7 +214,7 @@ def estimate_and_evaluate_poses(output_seg, target_seg, output_vertex, poses_gt,
         points_estimated = ransac_voting_layer_all_masks(onehot, vert, 512, inlier_thresh=0.99, max_iter=20, min_num=min_num, max_num=30000, **kw)
     else:
         points_estimated = _np(points_estimated) * np.array([[[[h, w]]]], np.float64)
-    poses, false_positive_mask = estimate_poses(points_estimated, object_points_3d, camera_data, avail, offsets)
+    poses, false_positive_mask = estimate_poses(points_estimated, object_points_3d, camera_data, avail, offsets, solver=solver)
     if evaluator is not None:
         e2, e3, v2, v3, miss, vcount, fp = evaluator.evaluate(poses, G, camera_data, diameters, avail, 5.0)
     else:
@@ -205,10 +223,16 @@ def estimate_and_evaluate_poses(output_seg, target_seg, output_vertex, poses_gt,
     return [v2, v3, vcount, false_positive_mask, e2, e3, miss, fp], poses, points_estimated
 
 
-def poses_pnp(points_estimated, seg_estimated, object_points_3d, camera_data, no_objects: int, min_num: int = 20, rng=None):
+def poses_pnp(points_estimated, seg_estimated, object_points_3d, camera_data, no_objects: int, min_num: int = 20, rng=None, solver=None):
     """pose_evaluation.py:164-217: voted keypoints [b,oc,vc,2] in (y,x) -> poses [b,oc,1,3,4]; objects with <= min_num
-    estimated pixels get the zero pose; the pose is negated when t_z < 0."""
+    estimated pixels get the zero pose; the pose is negated when t_z < 0.  solver: a DevicePnP solves the batch in one call; None asks
+    device_pnp.solver_from_environment (CASAPOSE_DEVICE_PNP=1, a segmentation on a GPU), and without one the host loop below runs."""
     import torch
+
+    if solver is None and hasattr(seg_estimated, "detach") and seg_estimated.is_cuda:
+        from .device_pnp import solver_from_environment
+
+        solver = solver_from_environment(_np(points_estimated).shape[2], seg_estimated.device)   # None unless CASAPOSE_DEVICE_PNP=1
 
     pts = _np(points_estimated)[..., ::-1]  # tf.reverse: (y,x) -> (x,y)
     kp3 = _np(object_points_3d)
@@ -216,6 +240,13 @@ def poses_pnp(points_estimated, seg_estimated, object_points_3d, camera_data, no
     lab = torch.argmax(seg_estimated, dim=3) if hasattr(seg_estimated, "detach") else torch.from_numpy(np.argmax(seg_estimated, axis=3))
     cam = _np(camera_data)
     cam = cam[0] if cam.ndim == 3 else cam
+    if solver is not None:
+        mask = np.array([[int((lab[n] == o + 1).sum()) > min_num for o in range(oc)] for n in range(b)], np.int32)
+        poses = _solved_poses(solver, np.ascontiguousarray(pts[:, :oc]), kp3.reshape(b, -1, pts.shape[2], 3)[:, :oc], cam, mask, None)
+        bad = np.argwhere((mask != 0) & np.isin(np.asarray(solver.last_info)[..., 0], (2, 4)))   # a degenerate keypoint set (3) is the zero pose
+        if len(bad):
+            raise FloatingPointError("poses_pnp: non-finite pose for image %d object %d" % (bad[0][0], bad[0][1]))
+        return poses[:, :, None]
     out = np.zeros((b, oc, 1, 3, 4), np.float32)
     for n in range(b):
         for o in range(oc):

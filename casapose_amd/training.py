@@ -191,10 +191,11 @@ def train_step(net, batch: Dict[str, torch.Tensor], loss_factors, optimizer: Opt
     return [float(total), float(s[0]), float(s[1]), float(s[2]), kpv]
 
 
-def poses_from_coords(coords_yx, objects_available, batch, rng=None) -> Tuple[np.ndarray, np.ndarray]:
+def poses_from_coords(coords_yx, objects_available, batch, rng=None, solver=None) -> Tuple[np.ndarray, np.ndarray]:
     """The pose branch of keypoint_reprojection_loss (loss_functions.py:229,264-315): voted keypoints (y,x) in crop
     pixels -> (x,y) -> original image pixels (transform_points_back) -> host PnP -> pose negated if t_z < 0 -> zeroed for
-    unavailable objects.  Returns (poses [B,oc,1,3,4], image-space points [B,oc,kp,2]) as float32 arrays."""
+    unavailable objects.  Returns (poses [B,oc,1,3,4], image-space points [B,oc,kp,2]) as float32 arrays.  solver: a DevicePnP
+    (pose_estimation/device_pnp.py) solves the available pairs in one call on the GPU instead of the host loop."""
     from .pose_estimation import pnp as _pnp
     from .pose_estimation.pose_evaluation import transform_points_back
 
@@ -213,18 +214,29 @@ def poses_from_coords(coords_yx, objects_available, batch, rng=None) -> Tuple[np
             if avail[n, o] == 0:
                 continue
             pts[n, o] = xy
+            if solver is not None:
+                continue
             p6 = _pnp.pnp_rvec_t(p3d[n, o], xy, cam, rng=rng)
             if not np.all(np.isfinite(p6)):
                 raise FloatingPointError("PnP returned a non-finite pose (image %d, object %d)" % (n, o))  # tf.Assert, loss_functions.py:299-304
             R, t = _pnp.rodrigues(p6[:3]), p6[3:].astype(np.float64)
             P = np.concatenate([R, t.reshape(3, 1)], axis=1)
             poses[n, o, 0] = -P if t[2] < 0 else P
+    if solver is not None:
+        from .pose_estimation.device_pnp import affine_from_offsets
+
+        mask = (avail != 0).astype(np.int32)
+        solved = solver.solve(np.ascontiguousarray(c[..., ::-1]), p3d, cam, mask, affine=affine_from_offsets(offs))
+        bad = np.argwhere((mask != 0) & np.isin(np.asarray(solver.last_info)[..., 0], (2, 4)))   # a degenerate keypoint set (3) is the zero pose
+        if len(bad):
+            raise FloatingPointError("PnP returned a non-finite pose (image %d, object %d)" % (bad[0][0], bad[0][1]))
+        poses[:, :, 0] = solved.detach().cpu().numpy()
     return poses, pts
 
 
 def test_step(net, batch, opt, loss_factors, evaluation_points=None, object_points_3d_count=None, evaluator=None):
     """One evaluation step of test_casapose.py (:268-384): inference forward, (component-filtered) LS keypoint voting or
-    RANSAC voting, host PnP, losses and the eight per-object pose statistics (computed on the GPU with a DevicePoseEvaluator as `evaluator`, or,
+    RANSAC voting, PnP (on the host, or with CASAPOSE_DEVICE_PNP=1 on the GPU: device_pnp.solver_from_environment), losses and the eight per-object pose statistics (computed on the GPU with a DevicePoseEvaluator as `evaluator`, or,
     with CASAPOSE_DEVICE_EVAL=1 and evaluation meshes, with the one device_evaluation.evaluator_from_environment keeps for them).
     Returns (losses [5 floats], pose_stats [8 arrays of oc], poses [B,oc,3,4], points, seconds)."""
     import time
@@ -240,6 +252,9 @@ def test_step(net, batch, opt, loss_factors, evaluation_points=None, object_poin
     img = batch["img"].to(device=dev, dtype=torch.float32).contiguous()
     seg = batch["target_seg"].to(device=dev, dtype=torch.float32)
     K, kp = net.seg_dim, int(getattr(opt, "no_points", 9))
+    from .pose_estimation.device_pnp import solver_from_environment
+
+    solver = solver_from_environment(kp, dev)   # None unless CASAPOSE_DEVICE_PNP=1
     with_gt = bool(getattr(opt, "train_vectors_with_ground_truth", False))
     torch.cuda.synchronize(dev)
     t0 = time.perf_counter()
@@ -258,7 +273,7 @@ def test_step(net, batch, opt, loss_factors, evaluation_points=None, object_poin
                         min_num_gt=1, filter_with_gt=bool(getattr(opt, "filter_test_with_gt", False)))
     if coords is not None:
         plan, _ = net.training_plan(img.shape[0], img.shape[1], img.shape[2])
-        poses, pts = poses_from_coords(coords, plan.objects_available, batch)
+        poses, pts = poses_from_coords(coords, plan.objects_available, batch, solver=solver)
         stats, poses, pts = evaluate_pose_estimates(pts, poses, batch["poses_gt"], seg, batch["keypoints3d"], batch["cam_mat"], batch["diameters"],
                                                     evaluation_points=evaluation_points, object_points_3d_count=object_points_3d_count, min_num=1,
                                                     evaluator=evaluator)
@@ -266,7 +281,7 @@ def test_step(net, batch, opt, loss_factors, evaluation_points=None, object_poin
     else:
         stats, poses, pts = estimate_and_evaluate_poses(o_seg, seg, o_dirs, batch["poses_gt"], batch["keypoints3d"], batch["cam_mat"], batch["diameters"],
                                                         batch["offsets"], evaluation_points=evaluation_points, object_points_3d_count=object_points_3d_count,
-                                                        min_num=1, evaluator=evaluator)
+                                                        min_num=1, evaluator=evaluator, solver=solver)
     torch.cuda.synchronize(dev)
     return losses, stats, poses, pts, time.perf_counter() - t0
 

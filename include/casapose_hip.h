@@ -798,6 +798,32 @@ int cp_pose_eval_est_tile(void);
 int cp_pose_eval_f32(const float* points, const int32_t* counts, const int32_t* symmetric, int objects, int vmax, const float* pairs, int batch,
                      float allowed_error_2d, void* workspace, float* records, float* point_err2, float* point_err3, void* stream);
 
+/* ---- device PnP (csrc/pnp.hip, csrc/pnp_math.h) -----------------------------------------------------------------------------------
+ * Voted keypoints -> [3,4] poses for every (image, object) pair of a batch: casapose_amd/pose_estimation/pnp.py restated in fp64.  One block per
+ * pair, one thread per hypothesis: EPnP on a 5-point set, inliers at <= reprojection_error over all n points; the consensus is the hypothesis
+ * with the most inliers, then the smallest sum of squared inlier errors, then the lowest index (no atomics: two calls give the same bits).  Then
+ * EPnP on the consensus set (on all points when it has fewer than 5), Levenberg-Marquardt over all n points, (rvec, t) rounded to fp32, and the
+ * pose negated when t_z < 0.  pair = image * oc + object; everything is device memory for cp_pnp_f64 and host memory for cp_pnp_host_f64.
+ *   points_xy  fp32 [b*oc][n][2]   keypoints (x, y), crop pixels when `affine` is given, image pixels otherwise
+ *   points_3d  fp32 [b*oc][n][3]   model keypoints
+ *   K          fp32 [b][9] (k_per_image != 0) or [9] shared by all images (k_per_image == 0), row-major
+ *   affine     fp64 [b][6] or NULL: image x = a0 x + a1 y + a2, image y = a3 x + a4 y + a5 (what transform_points_back computes from `offsets`)
+ *   solve      int32 [b*oc]        0: write the zero pose and status 1 without reading the pair's points
+ *   table      uint8 [H][5]        the hypotheses: point indices < n (a row that names another point is a hypothesis without a pose)
+ *   poses      fp32 [b*oc][12]     row-major [3,4]
+ *   info       int32 [b*oc][4]     status, winning hypothesis, its inlier count, LM iterations.  Status: 0 solved; 1 not asked for (solve == 0);
+ *                                  2 a non-finite input; 3 degenerate (all 2-D points coincide, or the 3-D points lie on one line); 4 no finite
+ *                                  solution.  Every status but 0 comes with the zero pose, winner -1 and zeros.
+ *   cost       fp32 [b*oc][2]      the all-point squared reprojection error before and after LM
+ * 5 <= n <= 16, 1 <= H <= 256, at most 65535 pairs per call.  Every loop has a fixed trip count (30 Jacobi sweeps, 10 Gauss-Newton steps, 20 LM
+ * iterations of 10 damping tries).  cp_pnp_host_f64 runs the same code serially and launches nothing: it works without a GPU.  A hypothesis
+ * is not comparable with pnp.py's (the null space of a 5-point system has dimension >= 2 and the eigen-solvers return different bases of it);
+ * the final pose is the same local optimum.  Added in ABI 302 without changing any earlier entry point. */
+int cp_pnp_f64(const float* points_xy, const float* points_3d, const float* K, int k_per_image, const double* affine, const int32_t* solve,
+               const uint8_t* table, int b, int oc, int n, int H, float reprojection_error, float* poses, int32_t* info, float* cost, void* stream);
+int cp_pnp_host_f64(const float* points_xy, const float* points_3d, const float* K, int k_per_image, const double* affine, const int32_t* solve,
+                    const uint8_t* table, int b, int oc, int n, int H, float reprojection_error, float* poses, int32_t* info, float* cost);
+
 #ifdef __cplusplus
 }
 #endif
