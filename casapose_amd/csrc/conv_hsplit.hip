@@ -99,6 +99,13 @@ __device__ unsigned long long hs_trace[2][2048];
 #define HST(tag)
 #define HS_BARRIER() CP_BARRIER()
 #endif
+// -DHS_SPILL_MARK (the compile of tools/debug/hs_spills.py only): a comment in the assembly behind the barrier of the loaders' phase loops, by which
+// that tool finds the loader role.  The library is built without it.
+#ifdef HS_SPILL_MARK
+#define HS_LOADER_MARK() asm volatile("; HS_LOADER_PHASE")
+#else
+#define HS_LOADER_MARK()
+#endif
 #ifndef HS_EPI_AUX
 #define HS_EPI_AUX 0   // cache policy bits of the generic epilogue's stores (variant builds: 2 = nt, 1 = sc0, 16 = sc1)
 #endif
@@ -191,6 +198,82 @@ __host__ __device__ constexpr int hs_group_taps(int tn, int np) { return tn == 1
 #else
 __host__ __device__ constexpr int hs_group_taps(int tn, int np) { return tn == 1 ? 9 : (tn == 2 ? (np <= 2 ? 9 : 3) : 1); }
 #endif
+
+// Scalar state by role.  The kernel holds 106 SGPRs and had 230-340 more spilled to VGPR lanes: every descriptor and every HSplitK field that either
+// role reads anywhere was live through both roles' loops, and the compiler keeps kernel arguments as the 4- and 8-dword tuples it loaded them in, so
+// one use of p.H reloaded eight lanes (a quarter of the loaders' instructions, tools/debug/hs_spills.py).  Now
+//   * the epilogue's operands are one record (HSEpi), built from the kernel arguments by the role that runs the epilogue, where it runs it;
+//   * the loaders read what they need once per tile or phase through hs_kernarg(): the kernel-argument segment behind a pointer the compiler
+//     cannot see through, so a field costs a scalar load at its use and no register between uses.
+struct HSEpi {
+    __amdgpu_buffer_rsrc_t r_tab_s, r_tab_b, r_res, r_raw, r_act, r_head, r_hlab;
+    int H, Wd, Cout, res_ld, raw_ld, act_ld, head_ld, head_cout, head_pre_n, head_lab_classes, clade, norm, act;
+    float descale, head_descale;
+    bool has_res, has_tab, has_raw, has_act, has_hlab, tab_lds, head, mon;
+};
+
+typedef const __attribute__((address_space(4))) HSplitK* HSKArg;
+__device__ __forceinline__ HSKArg hs_kernarg() {   // (HSplitK is the kernel's only argument: offset 0 of the segment)
+    HSKArg k = (HSKArg)__builtin_amdgcn_kernarg_segment_ptr();
+    asm volatile("" : "+s"(k));
+    return k;
+}
+
+// a scalar of its own: the compiler otherwise keeps -- and spills, and reloads -- the whole tuple of kernel arguments a field was loaded with
+template <class T>
+__device__ __forceinline__ T hs_own(T v) {
+    static_assert(sizeof(T) == 4, "one SGPR");
+    unsigned u = __builtin_bit_cast(unsigned, v);
+    asm("" : "+s"(u));
+    return __builtin_bit_cast(T, u);
+}
+
+// k: hs_kernarg(); the fields become scalars of their own.  Buffers that do not exist get the weights' address and a range of zero
+// bytes (every access is dropped).
+template <int TN, bool HEADK, int TAB_C, class KP>
+__device__ __forceinline__ HSEpi hs_epi_operands(KP k, bool tab_lds, bool head) {   // tab_lds, head: the kernel's own (it staged the table / the head's weights by them)
+    HSEpi e;
+    const unsigned char* W = k->W;
+    const float *scale = k->scale, *shift = k->shift, *residual = k->residual;
+    float *out_raw = k->out_raw, *out_act = k->out_act, *head_out = k->head_out;
+    uint8_t* head_lab = k->head_lab;
+    e.H = k->H; e.Wd = k->Wd; e.Cout = k->Cout;
+    e.res_ld = k->res_ld; e.raw_ld = k->raw_ld; e.act_ld = k->act_ld; e.head_ld = k->head_ld;
+    e.head_cout = k->head_cout; e.head_pre_n = k->head_pre_n; e.head_lab_classes = k->head_lab_classes;
+    e.clade = k->clade; e.norm = k->norm; e.act = k->act;
+    e.descale = k->descale; e.head_descale = k->head_descale;
+    {
+        e.H = hs_own(e.H); e.Wd = hs_own(e.Wd); e.Cout = hs_own(e.Cout);
+        e.res_ld = hs_own(e.res_ld); e.raw_ld = hs_own(e.raw_ld); e.act_ld = hs_own(e.act_ld); e.head_ld = hs_own(e.head_ld);
+        e.head_cout = hs_own(e.head_cout); e.head_pre_n = hs_own(e.head_pre_n); e.head_lab_classes = hs_own(e.head_lab_classes);
+        e.clade = hs_own(e.clade); e.norm = hs_own(e.norm); e.act = hs_own(e.act);
+        e.descale = hs_own(e.descale); e.head_descale = hs_own(e.head_descale);
+    }
+    const int B = k->B;
+    const unsigned npix = (unsigned)(B * e.H * e.Wd);
+    e.head = head;
+    e.mon = k->mon != nullptr;
+    e.tab_lds = tab_lds;
+    const unsigned tab_b = scale ? (unsigned)((e.clade ? 256 : 1) * e.Cout * 4) : 0u;
+    e.r_tab_s = __builtin_amdgcn_make_buffer_rsrc((void*)(scale ? (const void*)scale : (const void*)W), 0, tab_b, 0x00020000);
+    e.r_tab_b = __builtin_amdgcn_make_buffer_rsrc((void*)(scale ? (const void*)shift : (const void*)W), 0, tab_b, 0x00020000);
+    e.r_res = __builtin_amdgcn_make_buffer_rsrc((void*)(residual ? (const void*)residual : (const void*)W), 0, residual ? npix * (unsigned)e.res_ld * 4u : 0u, 0x00020000);
+    e.r_raw = __builtin_amdgcn_make_buffer_rsrc((void*)(out_raw ? (void*)out_raw : (void*)W), 0, out_raw ? npix * (unsigned)e.raw_ld * 4u : 0u, 0x00020000);
+    e.r_act = __builtin_amdgcn_make_buffer_rsrc((void*)(out_act ? (void*)out_act : (void*)W), 0, out_act ? npix * (unsigned)e.act_ld * 4u : 0u, 0x00020000);
+    e.r_head = __builtin_amdgcn_make_buffer_rsrc((void*)(e.head ? (void*)head_out : (void*)W), 0, e.head ? npix * (unsigned)e.head_ld * 4u : 0u, 0x00020000);
+    e.has_hlab = e.head && head_lab != nullptr;
+    e.r_hlab = __builtin_amdgcn_make_buffer_rsrc((void*)(e.has_hlab ? (void*)head_lab : (void*)W), 0, e.has_hlab ? npix : 0u, 0x00020000);
+#if defined(HS_EPI_NOSTORE)   // timing experiments (variant builds only)
+    e.has_res = residual != nullptr; e.has_tab = scale != nullptr; e.has_raw = out_raw != nullptr && B < 0; e.has_act = out_act != nullptr && B < 0;
+#elif defined(HS_EPI_NORES)
+    e.has_res = residual != nullptr && B < 0; e.has_tab = scale != nullptr; e.has_raw = out_raw != nullptr; e.has_act = out_act != nullptr;
+#elif defined(HS_EPI_NORAW)
+    e.has_res = residual != nullptr; e.has_tab = scale != nullptr; e.has_raw = out_raw != nullptr && B < 0; e.has_act = out_act != nullptr;
+#else
+    e.has_res = residual != nullptr; e.has_tab = scale != nullptr; e.has_raw = out_raw != nullptr; e.has_act = out_act != nullptr;
+#endif
+    return e;
+}
 
 template <int TN, int NP, int MODE>
 __global__ __launch_bounds__(512, 2) void conv_hsplit_kernel(const HSplitK p) {
@@ -287,17 +370,20 @@ __global__ __launch_bounds__(512, 2) void conv_hsplit_kernel(const HSplitK p) {
     }
     const int d_tx = g % p.tiles_x, d_ty = (g / p.tiles_x) % p.tiles_y, d_n = g / (p.tiles_x * p.tiles_y);
     const int d_pass = d_n / p.B, d_nb = d_n - d_pass * p.B;
-    auto next_tile = [&](TilePos& t) {
+    // Both roles read kernel arguments at their uses (hs_kernarg above); the lambdas below take the arguments as `k`
+    auto K = [&]() { return hs_kernarg(); };
+    auto next_tile = [&](TilePos& t, auto k) {
+        const int tiles_x = k->tiles_x, tiles_y = k->tiles_y, B = k->B;
         t.tx += d_tx;
         int cy = 0;
-        if (t.tx >= p.tiles_x) { t.tx -= p.tiles_x; cy = 1; }
+        if (t.tx >= tiles_x) { t.tx -= tiles_x; cy = 1; }
         t.ty += d_ty + cy;
         int cn = 0;
-        if (t.ty >= p.tiles_y) { t.ty -= p.tiles_y; cn = 1; }
+        if (t.ty >= tiles_y) { t.ty -= tiles_y; cn = 1; }
         t.n += d_n + cn;
         t.nb += d_nb + cn;
         t.pass += d_pass;
-        if (t.nb >= p.B) { t.nb -= p.B; ++t.pass; }
+        if (t.nb >= B) { t.nb -= B; ++t.pass; }
     };
     // TilePos.n runs over passes * B: pass = n / B selects 32*TN output channels (and their weight stream), n % B the image
     const int tile_w_bytes = (p.nch * 9 + (has_img ? 3 : 0)) * TN * (int)FRAG_B;   // one pass's weight stream
@@ -318,19 +404,9 @@ __global__ __launch_bounds__(512, 2) void conv_hsplit_kernel(const HSplitK p) {
     // ---- epilogue machinery, shared by both roles (round 5): a consumer wave w and the loader wave w + 4 can each take rows of the same tile ----
     const int ew = wave & 3;
     const unsigned wlane = (unsigned)lane * 16u;
-    const unsigned npix = (unsigned)(p.B * p.H * p.Wd);
     const bool has_lab = PARTIAL || p.clade;
-    const unsigned tab_b = p.scale ? (unsigned)((p.clade ? 256 : 1) * p.Cout * 4) : 0u;
-    const __amdgpu_buffer_rsrc_t r_tab_s = __builtin_amdgcn_make_buffer_rsrc((void*)(p.scale ? (const void*)p.scale : (const void*)p.W), 0, tab_b, 0x00020000);
-    const __amdgpu_buffer_rsrc_t r_tab_b = __builtin_amdgcn_make_buffer_rsrc((void*)(p.scale ? (const void*)p.shift : (const void*)p.W), 0, tab_b, 0x00020000);
-    const __amdgpu_buffer_rsrc_t r_res = __builtin_amdgcn_make_buffer_rsrc((void*)(p.residual ? (const void*)p.residual : (const void*)p.W), 0,
-                                                                            p.residual ? npix * (unsigned)p.res_ld * 4u : 0u, 0x00020000);
-    const __amdgpu_buffer_rsrc_t r_raw = __builtin_amdgcn_make_buffer_rsrc((void*)(p.out_raw ? (void*)p.out_raw : (void*)p.W), 0,
-                                                                            p.out_raw ? npix * (unsigned)p.raw_ld * 4u : 0u, 0x00020000);
-    const __amdgpu_buffer_rsrc_t r_act = __builtin_amdgcn_make_buffer_rsrc((void*)(p.out_act ? (void*)p.out_act : (void*)p.W), 0,
-                                                                            p.out_act ? npix * (unsigned)p.act_ld * 4u : 0u, 0x00020000);
-    const __amdgpu_buffer_rsrc_t r_head = __builtin_amdgcn_make_buffer_rsrc((void*)(head ? (void*)p.head_out : (void*)p.W), 0,
-                                                                             head ? npix * (unsigned)p.head_ld * 4u : 0u, 0x00020000);
+    // The epilogue's operands: built at every use (one epilogue row of one tile) by the role that runs it, nothing of them live through the loops
+    auto epi_operands = [&]() { return hs_epi_operands<TN, HEADK, TAB_C>(K(), tab_lds, head); };
     int pmask[2] = {0x1ff, 0x1ff}, clab[2] = {0, 0};
     // labels of a tile come from the label halo the loaders staged with the tile's first slice: no global latency, no registers held
     auto read_labels = [&](int parity) {
@@ -354,17 +430,6 @@ __global__ __launch_bounds__(512, 2) void conv_hsplit_kernel(const HSplitK p) {
     // s_and_saveexec / s_cbranch_execz regions (87 of them in the two rows of a tile, each a dozen issue slots with the matrix pipe idle).  Now:
     // conditions are combined bitwise and select an offset (an out-of-range buffer offset drops the access), operands that do not exist are
     // skipped by UNIFORM branches only, and the head's stores are chosen by uniform comparisons with head_cout.  Same expressions, same results.
-    const __amdgpu_buffer_rsrc_t r_hlab = __builtin_amdgcn_make_buffer_rsrc((void*)((head && p.head_lab) ? (void*)p.head_lab : (void*)p.W), 0,
-                                                                             (head && p.head_lab) ? npix : 0u, 0x00020000);
-#if defined(HS_EPI_NOSTORE)   // timing experiments (variant builds only)
-    const bool has_res = p.residual != nullptr, has_tab = p.scale != nullptr, has_raw = p.out_raw != nullptr && p.B < 0, has_act = p.out_act != nullptr && p.B < 0;
-#elif defined(HS_EPI_NORES)
-    const bool has_res = p.residual != nullptr && p.B < 0, has_tab = p.scale != nullptr, has_raw = p.out_raw != nullptr, has_act = p.out_act != nullptr;
-#elif defined(HS_EPI_NORAW)
-    const bool has_res = p.residual != nullptr, has_tab = p.scale != nullptr, has_raw = p.out_raw != nullptr && p.B < 0, has_act = p.out_act != nullptr;
-#else
-    const bool has_res = p.residual != nullptr, has_tab = p.scale != nullptr, has_raw = p.out_raw != nullptr, has_act = p.out_act != nullptr;
-#endif
     // HEADK: the per-channel table of a layer without CLADE, loaded once; where no partial-convolution factor exists the weights' power-of-two
     // descale is folded into its scale column (exact: a power of two commutes with the rounding of the product)
     float4 hk_sc[4], hk_sh[4];
@@ -373,9 +438,11 @@ __global__ __launch_bounds__(512, 2) void conv_hsplit_kernel(const HSplitK p) {
         for (int g4 = 0; g4 < 4; ++g4) {
             hk_sc[g4] = make_float4(0.f, 0.f, 0.f, 0.f);
             hk_sh[g4] = hk_sc[g4];
-            if (!p.clade) {
-                hk_sc[g4] = __builtin_bit_cast(float4, __builtin_amdgcn_raw_buffer_load_b128(r_tab_s, (g4 * 8 + kh * 4) * 4, 0, 0));
-                hk_sh[g4] = __builtin_bit_cast(float4, __builtin_amdgcn_raw_buffer_load_b128(r_tab_b, (g4 * 8 + kh * 4) * 4, 0, 0));
+            if (!p.clade) {   // (a head layer has a table: its descriptors live for these loads only)
+                const HSEpi te = epi_operands();   // (live for these loads only)
+                const __amdgpu_buffer_rsrc_t r_s = te.r_tab_s, r_b = te.r_tab_b;
+                hk_sc[g4] = __builtin_bit_cast(float4, __builtin_amdgcn_raw_buffer_load_b128(r_s, (g4 * 8 + kh * 4) * 4, 0, 0));
+                hk_sh[g4] = __builtin_bit_cast(float4, __builtin_amdgcn_raw_buffer_load_b128(r_b, (g4 * 8 + kh * 4) * 4, 0, 0));
                 if constexpr (NP == 2 && !PARTIAL) {
                     hk_sc[g4].x *= p.descale; hk_sc[g4].y *= p.descale; hk_sc[g4].z *= p.descale; hk_sc[g4].w *= p.descale;
                 }
@@ -388,36 +455,37 @@ __global__ __launch_bounds__(512, 2) void conv_hsplit_kernel(const HSplitK p) {
         if (hst_on) { hs_trace[hst_role][2046] = __builtin_amdgcn_s_memrealtime(); hs_trace[hst_role][2047] = ((unsigned long long)hst_i << 48) | (__builtin_readcyclecounter() & 0xffffffffffffull); }
 #endif
         if constexpr (NP == 2) {
-            if (p.mon) {   // uniform
-                cp::monitor_flush(p.mon, l_amax);
-                cp::monitor_flush(p.mon + 2, e_amax, false);
-                cp::monitor_count_launch(p.mon, threadIdx.x == 0);
+            uint32_t* mon = K()->mon;
+            if (mon) {   // uniform
+                cp::monitor_flush(mon, l_amax);
+                cp::monitor_flush(mon + 2, e_amax, false);
+                cp::monitor_count_launch(mon, threadIdx.x == 0);
             }
         }
     };
     // pieces: bit j * 4 + g4 set = this call handles that group of four channels (generic form; a head layer's row is one piece)
-    auto epilogue = [&](f32x16 (&acc)[2][TN], int r_begin, int r_end, int n, int y0, int x0, int cbase, unsigned pieces) __attribute__((always_inline)) {
+    auto epilogue = [&](const HSEpi& ep, f32x16 (&acc)[2][TN], int r_begin, int r_end, int n, int y0, int x0, int cbase, unsigned pieces) __attribute__((always_inline)) {
         asm volatile("" : "+s"(n), "+s"(y0), "+s"(x0), "+s"(cbase));   // (pins the tile-dependent arithmetic below to this point: see epilogue_t)
 #pragma unroll
         for (int r = 0; r < 2; ++r) {
             if (r < r_begin || r >= r_end) continue;   // (uniform: the rows of a tile can be divided between a consumer wave and its loader twin)
             const int y = y0 + 2 * ew + r, x = x0 + lrow;
-            const bool pok = (y < p.H) & (x < p.Wd);
-            const unsigned pix = (unsigned)((n * p.H + y) * p.Wd + x);
+            const bool pok = (y < ep.H) & (x < ep.Wd);
+            const unsigned pix = (unsigned)((n * ep.H + y) * ep.Wd + x);
             // whole output records (head_pre_n > 0, HS_HEADK): the record's first floats come from dense rows another head wrote.  Requested here, stored
             // behind the head's own columns: lane half kh moves floats 4 kh .. 4 kh + 3, half 0 also floats 8 .. head_pre_n - 1 (8 <= head_pre_n <= 12)
             u32x4 pre4 = {0u, 0u, 0u, 0u}, pre8 = {0u, 0u, 0u, 0u};
             if constexpr (PREFIX) {
                 {
-                    const unsigned po = pix * (unsigned)p.res_ld * 4u;
-                    pre4 = __builtin_amdgcn_raw_buffer_load_b128(r_res, (int)(pok ? po + 16u * (unsigned)kh : OOB), 0, 0);
-                    if (p.head_pre_n > 8) pre8 = __builtin_amdgcn_raw_buffer_load_b128(r_res, (int)((pok & (kh == 0)) ? po + 32u : OOB), 0, 0);
+                    const unsigned po = pix * (unsigned)ep.res_ld * 4u;
+                    pre4 = __builtin_amdgcn_raw_buffer_load_b128(ep.r_res, (int)(pok ? po + 16u * (unsigned)kh : OOB), 0, 0);
+                    if (ep.head_pre_n > 8) pre8 = __builtin_amdgcn_raw_buffer_load_b128(ep.r_res, (int)((pok & (kh == 0)) ? po + 32u : OOB), 0, 0);
                 }
             }
             float f = 1.f;
-            if constexpr (PARTIAL) f = p.norm ? 9.0f / (float)max(__popc(pmask[r]), 1) : 1.0f;
-            if constexpr (NP == 2) f *= p.descale;   // the weights' power-of-two scale, undone exactly
-            const unsigned tab_row = (unsigned)(clab[r] * (p.clade ? p.Cout : 0));
+            if constexpr (PARTIAL) f = ep.norm ? 9.0f / (float)max(__popc(pmask[r]), 1) : 1.0f;
+            if constexpr (NP == 2) f *= ep.descale;   // the weights' power-of-two scale, undone exactly
+            const unsigned tab_row = (unsigned)(clab[r] * (ep.clade ? ep.Cout : 0));
             float4 keep[4];
             if constexpr (HEADK) {
                 // t = leaky((acc * f) * scale + shift), the generic form's expressions without the operands this layer does not have; pixels
@@ -426,11 +494,11 @@ __global__ __launch_bounds__(512, 2) void conv_hsplit_kernel(const HSplitK p) {
 #pragma unroll
                 for (int g4 = 0; g4 < 4; ++g4) {
                     float4 sc = hk_sc[g4], sh = hk_sh[g4];
-                    if (p.clade) {
+                    if (ep.clade) {
                         const unsigned to = (tab_row + (unsigned)(g4 * 8 + kh * 4)) * 4u;
-                        sc = __builtin_bit_cast(float4, __builtin_amdgcn_raw_buffer_load_b128(r_tab_s, (int)to, 0, 0));
-                        sh = __builtin_bit_cast(float4, __builtin_amdgcn_raw_buffer_load_b128(r_tab_b, (int)to, 0, 0));
-                        if (fold) { sc.x *= p.descale; sc.y *= p.descale; sc.z *= p.descale; sc.w *= p.descale; }
+                        sc = __builtin_bit_cast(float4, __builtin_amdgcn_raw_buffer_load_b128(ep.r_tab_s, (int)to, 0, 0));
+                        sh = __builtin_bit_cast(float4, __builtin_amdgcn_raw_buffer_load_b128(ep.r_tab_b, (int)to, 0, 0));
+                        if (fold) { sc.x *= ep.descale; sc.y *= ep.descale; sc.z *= ep.descale; sc.w *= ep.descale; }
                     }
                     float4 t;
                     if (fold) {
@@ -458,48 +526,48 @@ __global__ __launch_bounds__(512, 2) void conv_hsplit_kernel(const HSplitK p) {
                 for (int g4 = g0; g4 < g0 + PRE; ++g4) {
                     if (!((pieces >> (j * 4 + g4)) & 1u)) continue;
                     const int ch = cbase + j * 32 + g4 * 8 + kh * 4;
-                    const bool cok = ch < p.Cout;
+                    const bool cok = ch < ep.Cout;
                     res[g4] = make_float4(0.f, 0.f, 0.f, 0.f);
                     esc[g4] = res[g4];
                     esh[g4] = res[g4];
-                    if (has_res)   // uniform branches: a layer without these operands issues no loads and waits for none
-                        res[g4] = __builtin_bit_cast(float4, __builtin_amdgcn_raw_buffer_load_b128(r_res, (int)((pok & cok) ? (pix * (unsigned)p.res_ld + (unsigned)ch) * 4u : OOB), 0, 0));
-                    if (tab_lds) {
+                    if (ep.has_res)   // uniform branches: a layer without these operands issues no loads and waits for none
+                        res[g4] = __builtin_bit_cast(float4, __builtin_amdgcn_raw_buffer_load_b128(ep.r_res, (int)((pok & cok) ? (pix * (unsigned)ep.res_ld + (unsigned)ch) * 4u : OOB), 0, 0));
+                    if (ep.tab_lds) {
                         const int cl = ch < TAB_C - 3 ? ch : 0;   // (channels past Cout are not stored; keep the read inside the table)
                         esc[g4] = *reinterpret_cast<const float4*>(tabl + cl);
                         esh[g4] = *reinterpret_cast<const float4*>(tabl + TAB_C + cl);
-                    } else if (has_tab) {
+                    } else if (ep.has_tab) {
                         const unsigned to = cok ? (tab_row + (unsigned)ch) * 4u : OOB;
-                        esc[g4] = __builtin_bit_cast(float4, __builtin_amdgcn_raw_buffer_load_b128(r_tab_s, (int)to, 0, 0));
-                        esh[g4] = __builtin_bit_cast(float4, __builtin_amdgcn_raw_buffer_load_b128(r_tab_b, (int)to, 0, 0));
+                        esc[g4] = __builtin_bit_cast(float4, __builtin_amdgcn_raw_buffer_load_b128(ep.r_tab_s, (int)to, 0, 0));
+                        esh[g4] = __builtin_bit_cast(float4, __builtin_amdgcn_raw_buffer_load_b128(ep.r_tab_b, (int)to, 0, 0));
                     }
                 }
 #pragma unroll
                 for (int g4 = g0; g4 < g0 + PRE; ++g4) {
                     if (!((pieces >> (j * 4 + g4)) & 1u)) continue;
                     const int ch = cbase + j * 32 + g4 * 8 + kh * 4;
-                    const bool ok = pok & (ch < p.Cout);
+                    const bool ok = pok & (ch < ep.Cout);
                     float4 v;
                     v.x = acc[r][j][g4 * 4 + 0] * f + res[g4].x;
                     v.y = acc[r][j][g4 * 4 + 1] * f + res[g4].y;
                     v.z = acc[r][j][g4 * 4 + 2] * f + res[g4].z;
                     v.w = acc[r][j][g4 * 4 + 3] * f + res[g4].w;
-                    if (has_raw)
-                        __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, v), r_raw, (int)(ok ? (pix * (unsigned)p.raw_ld + (unsigned)ch) * 4u : OOB), 0, HS_EPI_AUX);
+                    if (ep.has_raw)
+                        __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, v), ep.r_raw, (int)(ok ? (pix * (unsigned)ep.raw_ld + (unsigned)ch) * 4u : OOB), 0, HS_EPI_AUX);
                     float4 t = v;
-                    if (has_tab) {
+                    if (ep.has_tab) {
                         t.x = v.x * esc[g4].x + esh[g4].x;
                         t.y = v.y * esc[g4].y + esh[g4].y;
                         t.z = v.z * esc[g4].z + esh[g4].z;
                         t.w = v.w * esc[g4].w + esh[g4].w;
                     }
-                    if (p.act == CP_ACT_RELU) {
+                    if (ep.act == CP_ACT_RELU) {
                         t.x = fmaxf(t.x, 0.f); t.y = fmaxf(t.y, 0.f); t.z = fmaxf(t.z, 0.f); t.w = fmaxf(t.w, 0.f);
-                    } else if (p.act == CP_ACT_LEAKY01) {
+                    } else if (ep.act == CP_ACT_LEAKY01) {
                         t.x = leaky01(t.x); t.y = leaky01(t.y); t.z = leaky01(t.z); t.w = leaky01(t.w);
                     }
-                    if (has_act)
-                        __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, t), r_act, (int)(ok ? (pix * (unsigned)p.act_ld + (unsigned)ch) * 4u : OOB), 0, HS_EPI_AUX);
+                    if (ep.has_act)
+                        __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, t), ep.r_act, (int)(ok ? (pix * (unsigned)ep.act_ld + (unsigned)ch) * 4u : OOB), 0, HS_EPI_AUX);
                     if (j == 0) {
                         keep[g4].x = ok ? t.x : 0.f;
                         keep[g4].y = ok ? t.y : 0.f;
@@ -511,8 +579,8 @@ __global__ __launch_bounds__(512, 2) void conv_hsplit_kernel(const HSplitK p) {
             }
             }   // !HEADK
             if constexpr (TN == 1) {
-                if (head) {
-                    if (NP == 2 && p.mon) {   // (uniform) the head's operand as it is converted below; pixels outside the image compute with padding and are not stored
+                if (ep.head) {
+                    if (NP == 2 && ep.mon) {   // (uniform) the head's operand as it is converted below; pixels outside the image compute with padding and are not stored
 #pragma unroll
                         for (int g4 = 0; g4 < 4; ++g4) e_amax = pok ? cp::amax4(e_amax, keep[g4]) : e_amax;
                     }
@@ -552,38 +620,38 @@ __global__ __launch_bounds__(512, 2) void conv_hsplit_kernel(const HSplitK p) {
                     }
                     if constexpr (NP == 2) {
 #pragma unroll
-                        for (int e = 0; e < 16; ++e) a2[e] *= p.head_descale;
+                        for (int e = 0; e < 16; ++e) a2[e] *= ep.head_descale;
                     }
                     // stores: register g4 * 4 + e of lane half kh is head channel q = 8 g4 + 4 kh + e.  A group of eight channels that lies wholly
                     // below head_cout goes out as one 16-byte store per lane; the group that straddles it as single dwords, one store per e that
                     // ANY lane half still owns -- which stores exist is decided by uniform comparisons, which lanes take part by the offset
-                    const unsigned hbase = (pix * (unsigned)p.head_ld + (unsigned)(kh * 4 + (PREFIX ? p.head_pre_n : 0))) * 4u;
+                    const unsigned hbase = (pix * (unsigned)ep.head_ld + (unsigned)(kh * 4 + (PREFIX ? ep.head_pre_n : 0))) * 4u;
 #pragma unroll
                     for (int g4 = 0; g4 < 4; ++g4) {
                         const unsigned o = hbase + (unsigned)(g4 * 32);
-                        if (p.head_cout >= g4 * 8 + 8) {
+                        if (ep.head_cout >= g4 * 8 + 8) {
                             __builtin_amdgcn_raw_buffer_store_b128(u32x4{__builtin_bit_cast(unsigned, (float)a2[g4 * 4 + 0]), __builtin_bit_cast(unsigned, (float)a2[g4 * 4 + 1]),
                                                                          __builtin_bit_cast(unsigned, (float)a2[g4 * 4 + 2]), __builtin_bit_cast(unsigned, (float)a2[g4 * 4 + 3])},
-                                                                   r_head, (int)(pok ? o : OOB), 0, 0);
-                        } else if (p.head_cout > g4 * 8) {
-                            const int left = p.head_cout - g4 * 8 - kh * 4;   // channels of this group this lane half still owns (<= 0: none)
+                                                                   ep.r_head, (int)(pok ? o : OOB), 0, 0);
+                        } else if (ep.head_cout > g4 * 8) {
+                            const int left = ep.head_cout - g4 * 8 - kh * 4;   // channels of this group this lane half still owns (<= 0: none)
 #pragma unroll
                             for (int e = 0; e < 4; ++e)
-                                if (p.head_cout > g4 * 8 + e)   // lane half 0 owns q = 8 g4 + e
-                                    __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, (float)a2[g4 * 4 + e]), r_head, (int)((pok & (e < left)) ? o + 4u * e : OOB), 0, 0);
+                                if (ep.head_cout > g4 * 8 + e)   // lane half 0 owns q = 8 g4 + e
+                                    __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, (float)a2[g4 * 4 + e]), ep.r_head, (int)((pok & (e < left)) ? o + 4u * e : OOB), 0, 0);
                         }
                     }
                     if constexpr (PREFIX) {
                         {   // the copied floats complete the record's lines (each role copies the rows it finishes: handing row 1's copy to the consumer
                             // wave as well was measured slower, 0.56 -> 0.66 ms for block 10)
-                            const unsigned ro = pix * (unsigned)p.head_ld * 4u;
-                            __builtin_amdgcn_raw_buffer_store_b128(pre4, r_head, (int)(pok ? ro + 16u * (unsigned)kh : OOB), 0, 0);
+                            const unsigned ro = pix * (unsigned)ep.head_ld * 4u;
+                            __builtin_amdgcn_raw_buffer_store_b128(pre4, ep.r_head, (int)(pok ? ro + 16u * (unsigned)kh : OOB), 0, 0);
 #pragma unroll
                             for (int e = 0; e < 4; ++e)
-                                if (8 + e < p.head_pre_n) __builtin_amdgcn_raw_buffer_store_b32(pre8[e], r_head, (int)((pok & (kh == 0)) ? ro + 32u + 4u * e : OOB), 0, 0);
+                                if (8 + e < ep.head_pre_n) __builtin_amdgcn_raw_buffer_store_b32(pre8[e], ep.r_head, (int)((pok & (kh == 0)) ? ro + 32u + 4u * e : OOB), 0, 0);
                         }
                     }
-                    if (p.head_lab) {   // the hard label map straight from the head's registers: first maximum wins (cp_argmax_labels)
+                    if (ep.has_hlab) {   // the hard label map straight from the head's registers: first maximum wins (cp_argmax_labels)
                         float best = -__builtin_inff();
                         int bi = 0x7fffffff;
 #pragma unroll
@@ -592,7 +660,7 @@ __global__ __launch_bounds__(512, 2) void conv_hsplit_kernel(const HSplitK p) {
                             for (int e = 0; e < 4; ++e) {
                                 const int q = g4 * 8 + kh * 4 + e;
                                 const float vq = a2[g4 * 4 + e];
-                                const bool take = (q < p.head_lab_classes) & (vq > best);
+                                const bool take = (q < ep.head_lab_classes) & (vq > best);
                                 best = take ? vq : best;
                                 bi = take ? q : bi;
                             }
@@ -601,7 +669,7 @@ __global__ __launch_bounds__(512, 2) void conv_hsplit_kernel(const HSplitK p) {
                         const bool other = (ob > best) | ((ob == best) & (oi < bi));
                         bi = other ? oi : bi;
                         bi = (bi == 0x7fffffff) ? 0 : bi;
-                        __builtin_amdgcn_raw_buffer_store_b8((unsigned char)bi, r_hlab, (int)(((kh == 0) & pok) ? pix : OOB), 0, 0);
+                        __builtin_amdgcn_raw_buffer_store_b8((unsigned char)bi, ep.r_hlab, (int)(((kh == 0) & pok) ? pix : OOB), 0, 0);
                     }
                 }
             }
@@ -610,9 +678,12 @@ __global__ __launch_bounds__(512, 2) void conv_hsplit_kernel(const HSplitK p) {
 
     if constexpr (NP == 2) cp::f16_overflow_clamps();
     if (loader) {
+        // (the set-up below reads the arguments through the opaque pointer too: a direct read of `p` here keeps the 8-dword tuples of the kernel's
+        // entry alive -- or re-loaded -- across the role split, and left a dead stack slot, i.e. a private segment, in the MODE 0 instantiations)
+        const auto kl = K();
         // ------------------------------------------------------------------ loaders ------------------------------------------------------
 #ifdef HS_LOADER_IDLE
-        if (p.B > 0) {   // timing experiment: the consumers alone (LDS holds whatever it held)
+        if (kl->B > 0) {   // timing experiment: the consumers alone (LDS holds whatever it held)
             if constexpr (BILINEAR) HS_BARRIER();
             HS_BARRIER();
             for (int gg = 0; gg < total_groups; ++gg) HS_BARRIER();
@@ -650,18 +721,23 @@ __global__ __launch_bounds__(512, 2) void conv_hsplit_kernel(const HSplitK p) {
                             accl[1][j][g4 * 4 + 0] = v.x; accl[1][j][g4 * 4 + 1] = v.y; accl[1][j][g4 * 4 + 2] = v.z; accl[1][j][g4 * 4 + 3] = v.w;
                             accl[0][j][g4 * 4 + 0] = v.x; accl[0][j][g4 * 4 + 1] = v.y; accl[0][j][g4 * 4 + 2] = v.z; accl[0][j][g4 * 4 + 3] = v.w;
                         }
-                    epilogue(accl, 1, 2, e_n, e_y0, e_x0, e_cbase, pieces);
+                    const HSEpi le = epi_operands();   // built here, once per owed row: nothing of it is live in the other phases
+                    epilogue(le, accl, 1, 2, e_n, e_y0, e_x0, e_cbase, pieces);
                 }
                 if (last || phase == ngroups_tile - 1) {   // this tile's row is done: the next one is owed
-                    next_tile(etile);
+                    next_tile(etile, K());
                     ++e_k;
                 }
             }
         };
-        const __amdgpu_buffer_rsrc_t rs0 = __builtin_amdgcn_make_buffer_rsrc((void*)p.s[0].data, 0, p.s[0].bytes, 0x00020000);
-        const __amdgpu_buffer_rsrc_t rs1 = __builtin_amdgcn_make_buffer_rsrc((void*)(p.s[1].data ? p.s[1].data : p.s[0].data), 0,
-                                                                              p.s[1].data ? p.s[1].bytes : 0u, 0x00020000);
-        const __amdgpu_buffer_rsrc_t rsi = __builtin_amdgcn_make_buffer_rsrc((void*)(has_img ? p.img : p.s[0].data), 0, has_img ? p.img_bytes : 0u, 0x00020000);
+        const __amdgpu_buffer_rsrc_t rs0 = __builtin_amdgcn_make_buffer_rsrc((void*)kl->s[0].data, 0, kl->s[0].bytes, 0x00020000);
+        const __amdgpu_buffer_rsrc_t rs1 = __builtin_amdgcn_make_buffer_rsrc((void*)(kl->s[1].data ? kl->s[1].data : kl->s[0].data), 0,
+                                                                              kl->s[1].data ? kl->s[1].bytes : 0u, 0x00020000);
+        // (these two serve every slice and stay in registers; the descriptors of the per-tile requests -- image, labels, selection bytes -- and of the
+        // weight stream are built from `k` where the request is made)
+        const bool has_lab_l = PARTIAL || kl->clade;
+        const bool mon_on = kl->mon != nullptr;
+        const int nch0 = kl->nch0;
         // halo element `it` of a thread: float4 number it*256 + tid = (pixel, channel quad)
         int e_hy[NIT], e_hx[NIT];
         unsigned e_lds[NIT];
@@ -683,30 +759,30 @@ __global__ __launch_bounds__(512, 2) void conv_hsplit_kernel(const HSplitK p) {
 #pragma unroll
         for (int it = 0; it < NIT; ++it) {
             e_ok[it] = e_hy[it] < 0x4000;
-            e_pof[it] = e_ok[it] ? e_hy[it] * p.Wd + e_hx[it] : 0;
-            e_sof[it] = (SEL && e_ok[it]) ? ((e_hy[it] - 1) >> 1) * p.s[0].Ws + ((e_hx[it] - 1) >> 1) : 0;
+            e_pof[it] = e_ok[it] ? e_hy[it] * kl->Wd + e_hx[it] : 0;
+            e_sof[it] = (SEL && e_ok[it]) ? ((e_hy[it] - 1) >> 1) * kl->s[0].Ws + ((e_hx[it] - 1) >> 1) : 0;
         }
-        auto tile_interior = [&](const TilePos& tp) { return tp.ty > 0 && tp.tx > 0 && tp.ty * TH + TH + 1 <= p.H && tp.tx * 32 + 33 <= p.Wd; };
+        auto tile_interior = [&](const TilePos& tp, auto k) { return tp.ty > 0 && tp.tx > 0 && tp.ty * TH + TH + 1 <= k->H && tp.tx * 32 + 33 <= k->Wd; };
         float4 lv[NIT][NV];
         float4 liv[NIMG];
         int selb[NIT];       // SEL: the selection byte of this element's pixel (constant over the slices of a tile)
-        const __amdgpu_buffer_rsrc_t rss = __builtin_amdgcn_make_buffer_rsrc((void*)(SEL ? (const void*)p.s[0].sel : (const void*)p.W), 0,
-                                                                              SEL ? p.lab_bytes : 0u, 0x00020000);
         // Round 6: the selection bytes of a tile are requested ONE TILE AHEAD (selb_nx).  They feed the tile's element offsets, so requesting them with
         // the tile itself put a whole memory round trip into the loaders' path once per tile -- 4-6 k cycles of the 19 k a tile of block 10 takes,
         // with the consumers waiting at the barrier meanwhile (tools/debug/hs_trace.py: the "issue" section of that phase 6.0 k against 0.6-0.9 k).
         int selb_nx[NIT];
-        auto issue_sel = [&](const TilePos& tp) {
+        auto issue_sel = [&](const TilePos& tp, auto k) {
             if constexpr (SEL) {
-                const int tb = (tp.nb * p.H + tp.ty * TH - 1) * p.Wd + tp.tx * 32 - 1;   // (uniform)
-                if (tile_interior(tp)) {
+                const int H = k->H, Wd = k->Wd;
+                const __amdgpu_buffer_rsrc_t rss = __builtin_amdgcn_make_buffer_rsrc((void*)k->s[0].sel, 0, k->lab_bytes, 0x00020000);
+                const int tb = (tp.nb * H + tp.ty * TH - 1) * Wd + tp.tx * 32 - 1;   // (uniform)
+                if (tile_interior(tp, k)) {
 #pragma unroll
                     for (int it = 0; it < NIT; ++it) selb_nx[it] = __builtin_amdgcn_raw_buffer_load_b8(rss, e_ok[it] ? tb + e_pof[it] : (int)OOB, 0, 0);
                 } else {
 #pragma unroll
                     for (int it = 0; it < NIT; ++it) {
                         const int y = tp.ty * TH - 1 + e_hy[it], x = tp.tx * 32 - 1 + e_hx[it];
-                        const bool inb = ((unsigned)y < (unsigned)p.H) & ((unsigned)x < (unsigned)p.Wd);
+                        const bool inb = ((unsigned)y < (unsigned)H) & ((unsigned)x < (unsigned)Wd);
                         selb_nx[it] = __builtin_amdgcn_raw_buffer_load_b8(rss, inb ? tb + e_pof[it] : (int)OOB, 0, 0);
                     }
                 }
@@ -715,18 +791,19 @@ __global__ __launch_bounds__(512, 2) void conv_hsplit_kernel(const HSplitK p) {
         // byte offsets of this thread's halo elements for the tile being fetched (channel 0 of the slice's 16; OOB outside the image), computed
         // once per tile: a slice only adds its uniform channel offset through the load's scalar offset -- no per-slice address arithmetic
         unsigned eo0[NIT][NV], eo1[NIT];
-        auto tile_offsets = [&](const TilePos& tp) {
+        auto tile_offsets = [&](const TilePos& tp, auto k) {
+            const int H = k->H, Wd = k->Wd, Ws0 = k->s[0].Ws;
             const int y0 = tp.ty * TH, x0 = tp.tx * 32;
-            const int tb = (tp.nb * p.H + y0 - 1) * p.Wd + x0 - 1;                                           // (uniform) pixel of the halo's corner
-            const int sb = SEL ? (tp.nb * p.s[0].Hs + (TH / 2) * tp.ty) * p.s[0].Ws + 16 * tp.tx : 0;        // ... and of its half-resolution source
-            const unsigned ld0b = (unsigned)p.s[0].ld * 4u, ld1b = (unsigned)p.s[1].ld * 4u, q4b = (unsigned)q4 * 4u;
-            const bool interior = tile_interior(tp);
+            const int tb = (tp.nb * H + y0 - 1) * Wd + x0 - 1;                                               // (uniform) pixel of the halo's corner
+            const int sb = SEL ? (tp.nb * k->s[0].Hs + (TH / 2) * tp.ty) * Ws0 + 16 * tp.tx : 0;             // ... and of its half-resolution source
+            const unsigned ld0b = (unsigned)k->s[0].ld * 4u, ld1b = (unsigned)k->s[1].ld * 4u, q4b = (unsigned)q4 * 4u;
+            const bool interior = tile_interior(tp, k);
 #pragma unroll
             for (int it = 0; it < NIT; ++it) {
                 bool inb = e_ok[it];
                 if (!interior) {   // (uniform)
                     const int y = y0 - 1 + e_hy[it], x = x0 - 1 + e_hx[it];
-                    inb = ((unsigned)y < (unsigned)p.H) & ((unsigned)x < (unsigned)p.Wd);
+                    inb = ((unsigned)y < (unsigned)H) & ((unsigned)x < (unsigned)Wd);
                 }
                 const unsigned pixel = (unsigned)(tb + e_pof[it]);
                 eo1[it] = inb ? pixel * ld1b + q4b : OOB;
@@ -734,7 +811,7 @@ __global__ __launch_bounds__(512, 2) void conv_hsplit_kernel(const HSplitK p) {
                     eo0[it][0] = OOB;   // source 0 goes through the low-resolution LDS tile (bilinear loader below)
                 } else if constexpr (SEL) {
                     const int sl = selb[it];
-                    const unsigned sp = (unsigned)(sb + e_sof[it] + ((sl & 2) ? p.s[0].Ws : 0) + (sl & 1));
+                    const unsigned sp = (unsigned)(sb + e_sof[it] + ((sl & 2) ? Ws0 : 0) + (sl & 1));
                     eo0[it][0] = inb ? sp * ld0b + q4b : OOB;
                 } else {
                     eo0[it][0] = inb ? pixel * ld0b + q4b : OOB;
@@ -745,10 +822,10 @@ __global__ __launch_bounds__(512, 2) void conv_hsplit_kernel(const HSplitK p) {
         // GPS weight-group phases of the slice before it; part = -1: all of them)
         auto issue_slice = [&](const TilePos& tp, int c, int part = -1, int nparts = 1) {
             (void)tp;
-            const int si = c >= p.nch0 ? 1 : 0;
-            const int cs = (c - (si ? p.nch0 : 0)) * 64;   // uniform byte offset of the slice's first channel
+            const int si = c >= nch0 ? 1 : 0;
+            const int cs = (c - (si ? nch0 : 0)) * 64;   // uniform byte offset of the slice's first channel
 #ifdef HS_NOLOAD
-            if (p.B > 0) return;   // timing experiment
+            if (kl->B > 0) return;   // timing experiment
 #endif
             if (si == 0) {
 #pragma unroll
@@ -767,10 +844,10 @@ __global__ __launch_bounds__(512, 2) void conv_hsplit_kernel(const HSplitK p) {
         };
         auto store_slice = [&](int stage, int part = -1, int nparts = 1) {
 #ifdef HS_NOSTORE
-            if (p.B > 0) return;   // timing experiment
+            if (kl->B > 0) return;   // timing experiment
 #endif
             unsigned char* h = halo + stage * (NP * PLANE_B);
-            if (NP == 2 && p.mon) {   // (uniform; out-of-range elements loaded zeros)
+            if (NP == 2 && mon_on) {   // (uniform; out-of-range elements loaded zeros)
 #pragma unroll
                 for (int it = 0; it < NIT; ++it) l_amax = cp::amax4(l_amax, lv[it][0]);
             }
@@ -790,25 +867,26 @@ __global__ __launch_bounds__(512, 2) void conv_hsplit_kernel(const HSplitK p) {
             i_ok[it] = pix < HP;
             i_hy[it] = pix / COLS;
             i_hx[it] = pix % COLS;
-            i_pof[it] = i_ok[it] ? i_hy[it] * p.Wd + i_hx[it] : 0;
+            i_pof[it] = i_ok[it] ? i_hy[it] * kl->Wd + i_hx[it] : 0;
         }
-        auto pixel_inb = [&](const TilePos& tp, int it, bool interior) -> bool {
+        auto pixel_inb = [&](const TilePos& tp, int it, bool interior, auto k) -> bool {
             if (interior) return i_ok[it];
             const int y = tp.ty * TH - 1 + i_hy[it], x = tp.tx * 32 - 1 + i_hx[it];
-            return i_ok[it] & ((unsigned)y < (unsigned)p.H) & ((unsigned)x < (unsigned)p.Wd);
+            return i_ok[it] & ((unsigned)y < (unsigned)k->H) & ((unsigned)x < (unsigned)k->Wd);
         };
-        auto issue_img = [&](const TilePos& tp) {
-            const int tb = (tp.nb * p.H + tp.ty * TH - 1) * p.Wd + tp.tx * 32 - 1;
-            const bool interior = tile_interior(tp);
+        auto issue_img = [&](const TilePos& tp, auto k) {   // (only called with an image source)
+            const __amdgpu_buffer_rsrc_t rsi = __builtin_amdgcn_make_buffer_rsrc((void*)k->img, 0, k->img_bytes, 0x00020000);
+            const int tb = (tp.nb * k->H + tp.ty * TH - 1) * k->Wd + tp.tx * 32 - 1;
+            const bool interior = tile_interior(tp, k);
 #pragma unroll
             for (int it = 0; it < NIMG; ++it) {
-                const bool inb = pixel_inb(tp, it, interior);
+                const bool inb = pixel_inb(tp, it, interior, k);
                 liv[it] = __builtin_bit_cast(float4, __builtin_amdgcn_raw_buffer_load_b128(rsi, (int)(inb ? (unsigned)(tb + i_pof[it]) * 16u : OOB), 0, 0));
             }
         };
         auto store_img = [&](int parity) {
             unsigned char* h = imgh + parity * (NP * IPLANE_B);
-            if (NP == 2 && p.mon) {
+            if (NP == 2 && mon_on) {
 #pragma unroll
                 for (int it = 0; it < NIMG; ++it) l_amax = cp::amax4(l_amax, liv[it]);
             }
@@ -819,16 +897,14 @@ __global__ __launch_bounds__(512, 2) void conv_hsplit_kernel(const HSplitK p) {
                 store_planes<NP>(h + pix * 8, IPLANE_B, liv[it]);
             }
         };
-        const bool has_lab_l = PARTIAL || p.clade;
-        const __amdgpu_buffer_rsrc_t rsl_l = __builtin_amdgcn_make_buffer_rsrc((void*)(has_lab_l ? (const void*)p.label : (const void*)p.W), 0,
-                                                                                has_lab_l ? p.lab_bytes : 0u, 0x00020000);
         int llab[NIMG], llab_out[NIMG];
-        auto issue_lab = [&](const TilePos& tp) {
-            const int tb = (tp.nb * p.H + tp.ty * TH - 1) * p.Wd + tp.tx * 32 - 1;
-            const bool interior = tile_interior(tp);
+        auto issue_lab = [&](const TilePos& tp, auto k) {   // (only called with a label map)
+            const __amdgpu_buffer_rsrc_t rsl_l = __builtin_amdgcn_make_buffer_rsrc((void*)k->label, 0, k->lab_bytes, 0x00020000);
+            const int tb = (tp.nb * k->H + tp.ty * TH - 1) * k->Wd + tp.tx * 32 - 1;
+            const bool interior = tile_interior(tp, k);
 #pragma unroll
             for (int it = 0; it < NIMG; ++it) {
-                const bool inb = pixel_inb(tp, it, interior);
+                const bool inb = pixel_inb(tp, it, interior, k);
                 llab[it] = __builtin_amdgcn_raw_buffer_load_b8(rsl_l, inb ? tb + i_pof[it] : (int)OOB, 0, 0);
                 llab_out[it] = inb ? 0 : 0xff00;   // (round 6: OR-ed in by store_lab -- here the OR waited for the load just issued, a round trip per tile)
             }
@@ -841,21 +917,23 @@ __global__ __launch_bounds__(512, 2) void conv_hsplit_kernel(const HSplitK p) {
             }
         };
         // weight groups: the tile's fragment stream is contiguous in memory, GROUP_B bytes per group; every tile reads the same stream
-        const __amdgpu_buffer_rsrc_t rsw_l = __builtin_amdgcn_make_buffer_rsrc((void*)p.W, 0, p.w_bytes, 0x00020000);
         u32x4 lw[NWL];
         // the weight cursor: groups are requested strictly in order (0, 1, 2, ...), so (group within the tile, pass of the tile) advance by
         // increments -- round 4 divided by ngroups_tile and by tiles_per_pass for every group (two emulated integer divisions per phase)
-        int w_lg = 0, w_pass = bid / p.tiles_per_pass, w_rem = bid % p.tiles_per_pass;
-        const int g_q = g / p.tiles_per_pass, g_r = g % p.tiles_per_pass;
+        int w_lg = 0, w_pass = bid / kl->tiles_per_pass, w_rem = bid % kl->tiles_per_pass;
+        const int g_q = g / kl->tiles_per_pass, g_r = g % kl->tiles_per_pass;
         auto issue_w = [&](int gg) {   // global group index -> group of the tile (wide groups first, the image block's group last)
             (void)gg;   // (groups are requested in order)
             if (wres) return;   // (uniform) the whole stream is resident
+            const auto k = K();
+            const __amdgpu_buffer_rsrc_t rsw_l = __builtin_amdgcn_make_buffer_rsrc((void*)k->W, 0, k->w_bytes, 0x00020000);
             const int lgw = w_lg, pass = w_pass;   // this block's current tile belongs to that pass of output channels
             if (++w_lg == ngroups_tile) {
                 w_lg = 0;
                 w_pass += g_q;
                 w_rem += g_r;
-                if (w_rem >= p.tiles_per_pass) { w_rem -= p.tiles_per_pass; ++w_pass; }
+                const int tpp = k->tiles_per_pass;
+                if (w_rem >= tpp) { w_rem -= tpp; ++w_pass; }
             }
             const unsigned base = (unsigned)(pass * tile_w_bytes) + (unsigned)lgw * GROUP_B;
             const unsigned len = (lgw < nslices * GPS) ? GROUP_B : IGROUP_B;
@@ -882,23 +960,24 @@ __global__ __launch_bounds__(512, 2) void conv_hsplit_kernel(const HSplitK p) {
             if (++fc == nslices) {
                 fc = 0;
                 ++fk;
-                next_tile(ftile);
+                next_tile(ftile, K());
             }
         };
         auto issue_tile_extras = [&]() {   // with slice 0 of a tile: its element offsets, image halo, label halo; the NEXT tile's selection bytes
             if (fc != 0) return;
+            const auto k = K();   // one look at the kernel arguments per tile
             if constexpr (SEL) {
 #pragma unroll
                 for (int it = 0; it < NIT; ++it) selb[it] = selb_nx[it];   // requested a tile ago
             }
-            tile_offsets(ftile);
+            tile_offsets(ftile, k);
             if constexpr (SEL) {
                 TilePos nt = ftile;
-                next_tile(nt);       // (past the block's last tile: a valid address of some other tile, or out of range -- never used)
-                issue_sel(nt);
+                next_tile(nt, k);    // (past the block's last tile: a valid address of some other tile, or out of range -- never used)
+                issue_sel(nt, k);
             }
-            if (has_img) issue_img(ftile);
-            if (has_lab_l) issue_lab(ftile);
+            if (has_img) issue_img(ftile, k);
+            if (has_lab_l) issue_lab(ftile, k);
             img_pending = true;
         };
         auto store_tile_extras = [&]() {   // stages of tile fk: read last during tile fk - 2
@@ -909,12 +988,13 @@ __global__ __launch_bounds__(512, 2) void conv_hsplit_kernel(const HSplitK p) {
         };
         if constexpr (HEADK) {
             if (wres) {   // the tile's whole fragment stream, staged once (group g at g * GROUP_B, the image block's group behind the slices')
+                const __amdgpu_buffer_rsrc_t rsw_l = __builtin_amdgcn_make_buffer_rsrc((void*)kl->W, 0, kl->w_bytes, 0x00020000);   // (once: before the loop)
                 for (unsigned o = (unsigned)tid * 16u; o < (unsigned)tile_w_bytes; o += 256u * 16u)
                     *reinterpret_cast<u32x4*>(wst + o) = __builtin_amdgcn_raw_buffer_load_b128(rsw_l, (int)o, 0, 0);
             }
         }
         if (head) {   // the fused head's weights: 2 steps x NP KB, staged once
-            const __amdgpu_buffer_rsrc_t rsh = __builtin_amdgcn_make_buffer_rsrc((void*)p.head_w, 0, 2u * NP * 1024u, 0x00020000);
+            const __amdgpu_buffer_rsrc_t rsh = __builtin_amdgcn_make_buffer_rsrc((void*)kl->head_w, 0, 2u * NP * 1024u, 0x00020000);
             for (unsigned o = (unsigned)tid * 16u; o < 2u * NP * 1024u; o += 256u * 16u)
                 *reinterpret_cast<u32x4*>(hwl + o) = __builtin_amdgcn_raw_buffer_load_b128(rsh, (int)o, 0, 0);
         }
@@ -926,9 +1006,9 @@ __global__ __launch_bounds__(512, 2) void conv_hsplit_kernel(const HSplitK p) {
             // slice list one, two and three slices ahead of the consumers.
             constexpr int NLO = (LOW_P * 4 + 255) / 256;
             struct Cur { TilePos t; int c, k, s; };   // tile, slice within the tile, tile index of this block, global slice index
-            auto step = [&](Cur& u) {
+            auto step = [&](Cur& u, auto k) {
                 ++u.s;
-                if (++u.c == nslices) { u.c = 0; ++u.k; next_tile(u.t); }
+                if (++u.c == nslices) { u.c = 0; ++u.k; next_tile(u.t, k); }
             };
             bool l_ok[NLO];
             int l_r[NLO], l_c[NLO];
@@ -944,25 +1024,25 @@ __global__ __launch_bounds__(512, 2) void conv_hsplit_kernel(const HSplitK p) {
             float4 llow[NLO];
             unsigned elo[NLO];
             int elo_k = -1, eo1_k = -1;
-            auto issue_low = [&](const Cur& u) {
+            auto issue_low = [&](const Cur& u, auto k) {
                 if (u.k != elo_k) {   // first low-resolution slice of a tile: the tile's source offsets (edge-clamped, as the reference's resize)
                     elo_k = u.k;
                     const int n = u.t.nb, ys0 = u.t.ty * (TH / 2) - 1, xs0 = u.t.tx * 16 - 1;
-                    const int Hs = p.s[0].Hs, Ws = p.s[0].Ws;
+                    const int Hs = k->s[0].Hs, Ws = k->s[0].Ws, ld0 = k->s[0].ld;
 #pragma unroll
                     for (int it = 0; it < NLO; ++it) {
                         const int ys = min(max(ys0 + l_r[it], 0), Hs - 1), xs = min(max(xs0 + l_c[it], 0), Ws - 1);
-                        elo[it] = l_ok[it] ? (unsigned)((((n * Hs + ys) * Ws + xs) * p.s[0].ld + q4) * 4) : OOB;
+                        elo[it] = l_ok[it] ? (unsigned)((((n * Hs + ys) * Ws + xs) * ld0 + q4) * 4) : OOB;
                     }
                 }
 #ifdef HS_NOLOAD
-                if (p.B > 0) return;   // timing experiment
+                if (kl->B > 0) return;   // timing experiment
 #endif
 #pragma unroll
                 for (int it = 0; it < NLO; ++it) llow[it] = __builtin_bit_cast(float4, __builtin_amdgcn_raw_buffer_load_b128(rs0, (int)elo[it], u.c * 64, 0));
             };
             auto store_low = [&](int stage) {
-                if (NP == 2 && p.mon) {   // the low-resolution source bounds its x2 interpolation (a convex combination)
+                if (NP == 2 && mon_on) {   // the low-resolution source bounds its x2 interpolation (a convex combination)
 #pragma unroll
                     for (int it = 0; it < NLO; ++it) l_amax = l_ok[it] ? cp::amax4(l_amax, llow[it]) : l_amax;
                 }
@@ -991,17 +1071,18 @@ __global__ __launch_bounds__(512, 2) void conv_hsplit_kernel(const HSplitK p) {
                     t_out[sl][o] = (unsigned)(pix * 32 + (((q >> 1) ^ ((pix >> 3) & 1)) * 16) + (q & 1) * 8);
                 }
             }
-            auto interp = [&](const Cur& u) {   // low-resolution stage u.s & 1 -> halo stage u.s & 1
+            auto interp = [&](const Cur& u, auto k) {   // low-resolution stage u.s & 1 -> halo stage u.s & 1
                 const unsigned char* lo = lowb + (u.s & 1) * LOW_B;
                 unsigned char* h = halo + (u.s & 1) * (NP * PLANE_B);
                 const int y0 = u.t.ty * TH - 1, x0 = u.t.tx * 32 - 1;
+                const int H = k->H, Wd = k->Wd;
                 // zero padding of the convolution applies to the UPSAMPLED map: only tiles on the image border have halo pixels outside it
-                const bool edge = (y0 < 0) | (x0 < 0) | (y0 + HR > p.H) | (x0 + COLS > p.Wd);
+                const bool edge = (y0 < 0) | (x0 < 0) | (y0 + HR > H) | (x0 + COLS > Wd);
 #pragma unroll
                 for (int sl = 0; sl < NT; ++sl) {
                     if (t_by[sl] < 0) continue;
 #ifdef HS_NOINTERP
-                    if (p.B > 0) { for (int o = 0; o < 4; ++o) store_planes<NP>(h + t_out[sl][o], PLANE_B, make_float4(1.f, 2.f, 3.f, 4.f)); continue; }   // timing experiment
+                    if (kl->B > 0) { for (int o = 0; o < 4; ++o) store_planes<NP>(h + t_out[sl][o], PLANE_B, make_float4(1.f, 2.f, 3.f, 4.f)); continue; }   // timing experiment
 #endif
                     const float4 v00 = *reinterpret_cast<const float4*>(lo + t_low[sl]), v01 = *reinterpret_cast<const float4*>(lo + t_low[sl] + 64);
                     const float4 v10 = *reinterpret_cast<const float4*>(lo + t_low[sl] + LOW_C * 64), v11 = *reinterpret_cast<const float4*>(lo + t_low[sl] + LOW_C * 64 + 64);
@@ -1022,7 +1103,7 @@ __global__ __launch_bounds__(512, 2) void conv_hsplit_kernel(const HSplitK p) {
 #pragma unroll
                         for (int o = 0; o < 4; ++o) {
                             const int y = y0 + 2 * t_by[sl] + (o >> 1), x = x0 + 2 * t_bx[sl] + (o & 1);
-                            const bool inb = ((unsigned)y < (unsigned)p.H) & ((unsigned)x < (unsigned)p.Wd);
+                            const bool inb = ((unsigned)y < (unsigned)H) & ((unsigned)x < (unsigned)Wd);
                             out[o][0] = inb ? out[o][0] : f32x2{0.f, 0.f};
                             out[o][1] = inb ? out[o][1] : f32x2{0.f, 0.f};
                         }
@@ -1031,55 +1112,55 @@ __global__ __launch_bounds__(512, 2) void conv_hsplit_kernel(const HSplitK p) {
                     for (int o = 0; o < 4; ++o) store_planes<NP>(h + t_out[sl][o], PLANE_B, make_float4(out[o][0].x, out[o][0].y, out[o][1].x, out[o][1].y));
                 }
             };
-            auto issue_direct = [&](const Cur& u) {
+            auto issue_direct = [&](const Cur& u, auto k) {
                 if (u.k != eo1_k) {
                     eo1_k = u.k;
-                    tile_offsets(u.t);
+                    tile_offsets(u.t, k);
                 }
                 issue_slice(u.t, u.c);
             };
             // A-step (one phase before): the halo stage
-            auto step_a = [&](const Cur& u) {
+            auto step_a = [&](const Cur& u, auto k) {
                 if (u.s >= total_slices) return;
-                if (u.c < p.nch0) interp(u);
+                if (u.c < nch0) interp(u, k);
                 else store_slice(u.s & 1);
                 if (u.c == 0) {
                     if (has_img) store_img(u.k & 1);
                     if (has_lab_l) store_lab(u.k & 1);
                 }
             };
-            auto step_c = [&](const Cur& u) {
-                if (u.s < total_slices && u.c < p.nch0) issue_low(u);
+            auto step_c = [&](const Cur& u, auto k) {
+                if (u.s < total_slices && u.c < nch0) issue_low(u, k);
             };
             Cur ca{first, 0, 0, 0};
-            issue_low(ca);          // slice 0 is always a source-0 slice
-            if (has_img) issue_img(ca.t);
-            if (has_lab_l) issue_lab(ca.t);
+            issue_low(ca, K());     // slice 0 is always a source-0 slice
+            if (has_img) issue_img(ca.t, K());
+            if (has_lab_l) issue_lab(ca.t, K());
             store_low(0);
             Cur cb = ca;
-            step(cb);               // slice 1
-            step_c(cb);
+            step(cb, K());           // slice 1
+            step_c(cb, K());
             issue_w(0);
             HS_BARRIER();           // (the consumers run the same extra barrier) low-resolution stage 0 is complete
-            step_a(ca);             // interpolate slice 0, store tile 0's image / label halo
+            step_a(ca, K());         // interpolate slice 0, store tile 0's image / label halo
             store_w(0);
             if (cb.s < total_slices) {   // slice 1: its B-step without the extras of slice 0's tile being issued twice
                 if (cb.c == 0) {
-                    if (has_img) issue_img(cb.t);
-                    if (has_lab_l) issue_lab(cb.t);
+                    if (has_img) issue_img(cb.t, K());
+                    if (has_lab_l) issue_lab(cb.t, K());
                 }
-                if (cb.c < p.nch0) store_low(1);
-                else issue_direct(cb);
+                if (cb.c < nch0) store_low(1);
+                else issue_direct(cb, K());
             }
             Cur cc = cb;
-            step(cc);               // slice 2
-            step_c(cc);
+            step(cc, K());           // slice 2
+            step_c(cc, K());
             if (total_groups > 1) issue_w(1);
             HS_BARRIER();
             // from here: ca = slice gs + 1, cb = gs + 2, cc = gs + 3 at the first group of slice gs
             ca = cb;
             cb = cc;
-            step(cc);
+            step(cc, K());
             int lg = 0;
             HSP_DECL;
             // (stores before issues inside a phase, as in the generic loop below: a wait then only meets loads that are a phase old)
@@ -1093,39 +1174,41 @@ __global__ __launch_bounds__(512, 2) void conv_hsplit_kernel(const HSplitK p) {
                 // with a full memory latency (the loader's "work" time did not move when the interpolation itself got 2x cheaper).
                 const bool a_live = slice_phase && ca.s < total_slices;
                 if (a_live) {
-                    if (ca.c >= p.nch0) store_slice(ca.s & 1);
+                    if (ca.c >= nch0) store_slice(ca.s & 1);
                     if (ca.c == 0) {
                         if (has_img) store_img(ca.k & 1);
                         if (has_lab_l) store_lab(ca.k & 1);
                     }
                 }
-                if (slice_phase && cb.s < total_slices && cb.c < p.nch0) store_low(cb.s & 1);
+                if (slice_phase && cb.s < total_slices && cb.c < nch0) store_low(cb.s & 1);
                 HSP(0);
                 HST(2);
                 if (more_w && gg + 2 < total_groups) issue_w(gg + 2);
                 if (slice_phase) {
+                    const auto k = K();   // one look at the kernel arguments per slice
                     if (cb.s < total_slices) {
                         if (cb.c == 0) {
-                            if (has_img) issue_img(cb.t);
-                            if (has_lab_l) issue_lab(cb.t);
+                            if (has_img) issue_img(cb.t, k);
+                            if (has_lab_l) issue_lab(cb.t, k);
                         }
-                        if (cb.c >= p.nch0) issue_direct(cb);
+                        if (cb.c >= nch0) issue_direct(cb, k);
                     }
-                    step_c(cc);
+                    step_c(cc, k);
                     HSP(2);
                     HST(3);
-                    if (a_live && ca.c < p.nch0) interp(ca);
+                    if (a_live && ca.c < nch0) interp(ca, k);
                     HSP(3);
                     HST(4);
-                    step(ca);
-                    step(cb);
-                    step(cc);
+                    step(ca, k);
+                    step(cb, k);
+                    step(cc, k);
                 }
                 if (esplit && gg >= ngroups_tile) loader_epilogue(lg, false);   // row 1 of the tile before, beside the consumers' work on this one
                 if (++lg == ngroups_tile) lg = 0;
                 HSP(2);
                 HST(5);
                 HS_BARRIER();
+                HS_LOADER_MARK();
                 HSP(1);
             }
             if (esplit) loader_epilogue(0, true);   // the last tile's
@@ -1133,7 +1216,7 @@ __global__ __launch_bounds__(512, 2) void conv_hsplit_kernel(const HSplitK p) {
             flush_mon();
             return;
         }
-        issue_sel(first);
+        issue_sel(first, K());
         issue_tile_extras();
         issue_slice(ftile, 0);
         issue_w(0);
@@ -1188,6 +1271,7 @@ __global__ __launch_bounds__(512, 2) void conv_hsplit_kernel(const HSplitK p) {
             if (++lg == ngroups_tile) lg = 0;
             HSP(0);
             HS_BARRIER();
+            HS_LOADER_MARK();
             HSP(1);
         }
         if (esplit) loader_epilogue(0, true);   // the last tile's
@@ -1235,7 +1319,8 @@ __global__ __launch_bounds__(512, 2) void conv_hsplit_kernel(const HSplitK p) {
                 ++dump_k;
             }
         }
-        epilogue(acc, 0, esplit ? 1 : 2, n, y0, x0, cbase, 0xffffffffu);
+        const HSEpi ce = epi_operands();
+        epilogue(ce, acc, 0, esplit ? 1 : 2, n, y0, x0, cbase, 0xffffffffu);
     };
 
     // one (tap, cout block) sub-step: NPROD x 2 MFMAs; smallest terms first
@@ -1257,7 +1342,7 @@ __global__ __launch_bounds__(512, 2) void conv_hsplit_kernel(const HSplitK p) {
         const int pass = ctile.pass;
         const int n = ctile.nb, y0 = ctile.ty * TH, x0 = ctile.tx * 32;
         const int cbase = pass * 32 * TN;   // first output channel of this pass
-        next_tile(ctile);
+        next_tile(ctile, K());
         if (has_lab) read_labels(k & 1);
 #pragma unroll
         for (int r = 0; r < 2; ++r)
