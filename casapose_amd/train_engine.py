@@ -1154,10 +1154,9 @@ class TrainPlan:
         self.group, self.world_size = group, world_size
         self.monitor: Optional[SlotBuffer] = None   # range monitor (_arm_f16x2): slot i <-> self.ops[i], then the backward slots (self.bwd)
         self._f16x2_steps, self.f16x2_checks, self.f16x2_demoted, self._bwd_calibrated, self._dout_scale = 0, 0, [], False, 1.0
-        self.comm_timing = None   # start_comm_timing()
-        self.comm_log = None      # start_comm_log()
-        self._buckets = None
-        self._pending: List = []
+        # the data-parallel exchange of a step: which slice of the flat gradient goes out after which op is planned from the finished tape
+        self.exchange = parallel.StepExchange(store.grad, group, world_size, lambda: parallel.gradient_buckets(
+            store.offsets, store.size, [self._op_keys(op) for op in self.ops], forward_order(), BUCKET_STARTS), self._unscale_grads)
         self.update_moving = True
         dev = store.device
         f32 = dict(dtype=torch.float32, device=dev)
@@ -1501,80 +1500,40 @@ class TrainPlan:
                 op.materialize(stream)   # a fused layer never stored y: evaluate the forward's expression once for the pattern
         return {op.name: (op.y.data > 0).cpu() for op in self.ops if isinstance(op, BnActOp) and op.act != _lib.ACT_NONE}
 
-    # ---- distributed hooks ---------------------------------------------------------------------------
+    # ---- distributed hooks: the step's exchange, its log and its timing live in parallel.StepExchange ------------------
+    @staticmethod
+    def _op_keys(op) -> List[str]:
+        """the parameter keys whose gradients are final once the backward has executed `op`"""
+        return [op.layer.key] if isinstance(op, ConvOp) else ([k for k in (op.gamma_key, op.beta_key) if k] if isinstance(op, BnActOp) else [])
+
     def all_reduce_stats(self, table: torch.Tensor, local_pixels: int) -> int:
         """SUM the fp64 statistic table over the replicas; returns the global pixel count."""
-        if self.comm_log is not None:   # structure of the step's exchanges (comm_structure()): recorded with or without replicas
-            self.comm_log.append(("syncbn", table.numel() * table.element_size(), "blocking", "compute"))
-        if self.comm_timing is not None and self.group is not None:
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            e0.record()
-            parallel.all_reduce_sum_(table, self.group, self.world_size)
-            e1.record()
-            self.comm_timing["syncbn"].append((e0, e1))
-        else:
-            parallel.all_reduce_sum_(table, self.group, self.world_size)
+        self.exchange.reduce_stats(table)
         return local_pixels * self.world_size
 
-    # ---- structure of the step's exchanges (round 6): what is launched, in which order, on which stream ---------------------------------
+    @property
+    def comm_log(self):
+        return self.exchange.log
+
+    @comm_log.setter
+    def comm_log(self, log):
+        self.exchange.log = log
+
     def start_comm_log(self):
-        """From the next step on, record every exchange point of a step in launch order: ("syncbn", bytes, "blocking", "compute") for a statistic
-        table all-reduce (the next kernel needs it), ("op", index) for every backward op, ("grad_bucket", bytes, "async", stream id of the
-        compute stream at launch, first op index) where a gradient bucket's all-reduce is launched, ("grad_wait", n) where the compute stream
-        waits for the buckets.  Recorded with or without replicas (a single replica launches no collective but passes the same points), so that
-        the overlap of the data-parallel step can be asserted structurally (tests/test_gpu_dp.py) and counted (bench.py --mode train)."""
-        self.comm_log = []
+        self.exchange.start_log()
 
     def comm_structure(self) -> dict:
-        """Per step, from the log of the LAST logged step: blocking collectives (SyncBN tables) and their payload, gradient buckets, their payload and
-        how many backward ops are launched AFTER each bucket's all-reduce (what its exchange can hide behind)."""
-        log = self.comm_log or []
-        last = len(log) - 1 - next((i for i, e in enumerate(reversed(log)) if e[0] == "step_begin"), len(log) - 1)
-        step = log[last + 1:] if log and log[last][0] == "step_begin" else log
-        bn = [e for e in step if e[0] == "syncbn"]
-        buckets, after = [], []
-        for i, e in enumerate(step):
-            if e[0] == "grad_bucket":
-                buckets.append(e)
-                after.append(sum(1 for x in step[i + 1:] if x[0] == "op"))
-        return {"blocking_collectives_per_step": len(bn), "blocking_payload_bytes_per_step": int(sum(e[1] for e in bn)),
-                "gradient_buckets": len(buckets), "gradient_payload_bytes_per_step": int(sum(e[1] for e in buckets)),
-                "backward_ops_launched_after_each_bucket": after, "backward_ops": sum(1 for e in step if e[0] == "op"),
-                "note": "structure of the data-parallel step, identical for every world size: the blocking calls sit on the critical path (global-batch "
-                        "statistics, as the reference's SyncBatchNormalization), each gradient bucket's all-reduce is launched asynchronously when the "
-                        "backward has passed the bucket's first layer"}
+        return self.exchange.structure()
 
-    # ---- communication accounting (bench.py --mode train with N > 1 ranks; tests/test_gpu_dp.py) ------------------
     def start_comm_timing(self):
-        """From the next step on, bracket every collective the step WAITS for with events on the compute stream: the 58 SyncBN table
-        all-reduces (blocking: the next kernel needs the global statistics) and the wait for the gradient buckets in all_reduce_grads()
-        (whatever of their exchange the backward did not cover).  comm_report() turns them into milliseconds per step."""
-        self.comm_timing = {"syncbn": [], "grad_wait": [], "steps": 0}
+        self.exchange.start_timing()
 
     def comm_report(self) -> dict:
-        """{"syncbn_ms", "syncbn_calls", "grad_wait_ms", "exposed_ms", "grad_total_ms", "grad_hidden_ms", "grad_bytes"} per step.  exposed =
-        time the compute stream spent inside / waiting for collectives; grad_total = the same gradient buckets all-reduced back to back on an
-        idle GPU (measured here, after the steps), so grad_hidden = grad_total - grad_wait is what the overlap with the backward bought."""
-        t = self.comm_timing
-        torch.cuda.synchronize(self.store.device)
-        steps = max(t["steps"], 1)
-        bn = sum(a.elapsed_time(b) for a, b in t["syncbn"]) / steps
-        gw = sum(a.elapsed_time(b) for a, b in t["grad_wait"]) / steps
-        total, nbytes = 0.0, 0
-        if self.group is not None and self._buckets:
-            scratch = torch.zeros_like(self.store.grad)
-            for rep in range(3):
-                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                e0.record()
-                hs = [parallel.all_reduce_sum_async(scratch[a:e], self.group) for _, a, e in self._buckets]
-                for h in hs:
-                    h.wait()
-                e1.record()
-                e1.synchronize()
-                total = e0.elapsed_time(e1)   # the last repetition (the first pays RCCL's lazy set-up)
-            nbytes = 4 * scratch.numel()
-        return {"syncbn_ms": round(bn, 4), "syncbn_calls": len(t["syncbn"]) // steps, "grad_wait_ms": round(gw, 4), "exposed_ms": round(bn + gw, 4),
-                "grad_total_ms": round(total, 4), "grad_hidden_ms": round(max(total - gw, 0.0), 4), "grad_bytes": nbytes}
+        return self.exchange.report()
+
+    def all_reduce_grads(self):
+        """Complete the gradient exchange started by backward() (or run it as one all-reduce if none is pending)."""
+        self.exchange.wait()
 
     # ---- one step ------------------------------------------------------------------------------------
     def refresh_weights(self, stream: int):
@@ -1768,46 +1727,14 @@ class TrainPlan:
         self._keep_coef = coef
         return loss
 
-    def _gradient_buckets(self):
-        """[(first op index, start, end)] of the contiguous slices of the flat gradient that are final once the backward has executed
-        the op `first op index` (ops run in reverse): decoder 2 | decoder 1 | stage 4 | the rest of the encoder."""
-        st = self.store
-        rank = {n: i for i, n in enumerate(forward_order())}
-        starts = sorted(rank[b] for b in BUCKET_STARTS if b in rank)
-
-        def bucket_of(layer):
-            r = rank.get(layer, len(rank))
-            return max([i for i, s0 in enumerate(starts) if r >= s0] + [0])
-
-        nb = len(starts)
-        lo, hi, first = [st.size] * nb, [0] * nb, [len(self.ops)] * nb
-        for name, (off, shape) in st.offsets.items():
-            b = bucket_of(name.split(".")[0])
-            n = int(np.prod(shape))
-            lo[b], hi[b] = min(lo[b], off), max(hi[b], off + n + ((-n) % 4))
-        for i, op in enumerate(self.ops):
-            keys = [op.layer.key] if isinstance(op, ConvOp) else ([k for k in (op.gamma_key, op.beta_key) if k] if isinstance(op, BnActOp) else [])
-            for k in keys:
-                b = bucket_of(k.split(".")[0])
-                first[b] = min(first[b], i)
-        out = [(first[b], lo[b], hi[b]) for b in range(nb) if hi[b] > lo[b]]
-        covered = sorted((a, e) for _, a, e in out)
-        assert covered[0][0] == 0 and covered[-1][1] == st.size and all(covered[i][1] == covered[i + 1][0] for i in range(len(covered) - 1)), \
-            "gradient buckets must tile the flat buffer"
-        return out
-
     def backward(self):
         """Back-propagate self.dout through the tape into store.grad.  With replicas, the SUM all-reduce of each gradient bucket is
         launched (asynchronously, on the collective library's stream) as soon as the backward has passed the bucket's first layer, so
-        the exchange of the decoders' gradients overlaps the encoder's backward convolutions; all_reduce_grads() waits for them."""
+        the exchange of the decoders' gradients overlaps the encoder's backward convolutions (self.exchange); all_reduce_grads() waits for them."""
         stream = torch.cuda.current_stream(self.out.device).cuda_stream
         for t in self.tensors:
             t.has_grad = False
-        self._pending = []
-        multi = self.group is not None and (self.world_size > 1 or parallel.force_collectives())
-        log = self.comm_log
-        if (multi or log is not None) and self._buckets is None:
-            self._buckets = self._gradient_buckets()
+        multi = self.exchange.begin_backward()
         # the direct data gradients' operand range: max |dY| by a reduction pass of its own, on the step before a reading of the slots only
         check_now = self.monitor is not None and (not self._bwd_calibrated or self._f16x2_steps >= F16X2_TRAIN_CHECK_EVERY - 1)
         for i in range(len(self.ops) - 1, -1, -1):
@@ -1817,17 +1744,7 @@ class TrainPlan:
                 dy_, ld_ = op._dy()
                 check(_lib.load().cp_amax_f32(dy_, op.batch * op.out_h * op.out_w, ld_, op.layer.cout, b.mon, stream), "cp_amax_f32(dY %s)" % op.layer.name)
             op.backward(stream)
-            if log is not None:
-                log.append(("op", i))
-            if multi or log is not None:
-                for first, a, e in self._buckets:
-                    if first == i and not (a == 0):  # the bucket holding bn_data.beta is completed below
-                        if log is not None:
-                            log.append(("grad_bucket", 4 * (e - a), "async", stream, first))
-                        if not multi:
-                            continue
-                        self._unscale_grads(stream, a, e)   # (the loss factor is this replica's own: out before the sum over replicas)
-                        self._pending.append(parallel.all_reduce_sum_async(self.store.grad[a:e], self.group))
+            self.exchange.after_op(i, stream)   # (the bucket holding bn_data.beta is completed below)
         if not self._bwd_calibrated:
             self._calibrate_bwd(stream)   # (this backward ran on the exact split)
             if self.store.skip is not None:
@@ -1841,14 +1758,7 @@ class TrainPlan:
         W0 = self.store.view("conv0.kernel").reshape(49, 3, 64)               # [tap][c][cout]
         dbeta = torch.einsum("tco,to->c", W0.double(), G.double())
         self.store.grad_view("bn_data.beta").copy_(dbeta)
-        if multi or log is not None:
-            for first, a, e in self._buckets:
-                if a == 0:
-                    if log is not None:
-                        log.append(("grad_bucket", 4 * (e - a), "async", stream, first))
-                    if multi:
-                        self._unscale_grads(stream, a, e)
-                        self._pending.append(parallel.all_reduce_sum_async(self.store.grad[a:e], self.group))
+        self.exchange.finish_backward(stream)
         # the loss carried a power of two (loss_exp): it leaves the flat gradient here -- bucket by bucket in front of each exchange above (the
         # buckets tile the buffer; every replica has its OWN factor, so it must be gone before replicas are summed), in one piece otherwise
         if not multi:
@@ -1860,32 +1770,12 @@ class TrainPlan:
             g = self.store.grad[a:e]
             check(_lib.load().cp_axpby_f32(g.data_ptr(), 1.0 / self._dout_scale, g.data_ptr(), 0.0, e - a, g.data_ptr(), stream), "cp_axpby_f32(gradient / loss factor)")
 
-    def all_reduce_grads(self):
-        """Complete the gradient exchange started by backward() (or run it as one all-reduce if none is pending)."""
-        timed = self.comm_timing is not None and self.group is not None
-        if timed:
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            e0.record()
-        if self.comm_log is not None:
-            self.comm_log.append(("grad_wait", len(getattr(self, "_pending", None) or [])))
-        if getattr(self, "_pending", None):
-            for h in self._pending:
-                h.wait()
-            self._pending = []
-        else:
-            parallel.all_reduce_sum_(self.store.grad, self.group, self.world_size)
-        if timed:
-            e1.record()
-            self.comm_timing["grad_wait"].append((e0, e1))
-            self.comm_timing["steps"] += 1
-
     def train_step(self, img, labels_ce, labels_fg, keypoints_yx, lr: float, cond_labels=None, weights=(1.0, 1.0, 1.0),
                    filter_with_segmentation=True, kp_args: Optional[dict] = None):
         """One optimisation step.  kp_args (optional): keyword arguments of kp_loss_and_grad.  Returns the fp64 device
         vector [mask, vertex, proxy] (and, with kp_args, the keypoint loss as a second value)."""
         stream = torch.cuda.current_stream(img.device).cuda_stream
-        if self.comm_log is not None:
-            self.comm_log.append(("step_begin",))
+        self.exchange.begin_step()
         self.forward(img, cond_labels)
         sums = self.loss_and_grad(labels_ce, labels_fg, keypoints_yx, *weights, filter_with_segmentation=filter_with_segmentation)
         kp_loss = self.kp_loss_and_grad(**kp_args) if kp_args is not None else None

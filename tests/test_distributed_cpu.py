@@ -180,3 +180,142 @@ def test_three_rank_packed_logging_and_source_sharding():
     for rank, mean, st, mean2, none2, ncalls, _, n in res:
         assert np.allclose(mean, want_mean) and np.allclose(mean2, want_mean) and np.allclose(st, want_st) and none2
         assert ncalls == 2 and n == 1                     # exactly one all-reduce per logged step
+
+
+# --------------------------------------------------------------------------------------------------
+# the data-parallel exchange of a training step (parallel.StepExchange) without a GPU or the shared library
+# --------------------------------------------------------------------------------------------------
+def test_gradient_buckets_tile_the_real_parameter_layout():
+    """Four buckets (decoder 2 | decoder 1 | stage 4 | the rest) over the flat buffer of the real network: contiguous, 16-byte aligned,
+    each one final after an EARLIER op than the bucket behind it (the backward runs the ops in reverse), whatever the order of the dict."""
+    import random
+
+    import casapose_oracle as O
+    import numpy as np
+
+    from casapose_amd.parallel import gradient_buckets
+    from casapose_amd.train_engine import BUCKET_STARTS, ParamStore, forward_order
+
+    st = ParamStore(O.init_params(4, 27, seed=1, dtype=np.float32), torch.device("cpu"))
+    order = forward_order()
+    op_keys = [[k for k in st.offsets if k.split(".")[0] == layer] for layer in order]   # one op per layer
+    buckets = gradient_buckets(st.offsets, st.size, op_keys, order, BUCKET_STARTS)
+    by_offset = sorted(buckets, key=lambda b: b[1])
+    assert len(buckets) == 4
+    assert by_offset[0][1] == 0 and by_offset[-1][2] == st.size and all(by_offset[i][2] == by_offset[i + 1][1] for i in range(3))
+    assert all(a % 4 == 0 and e % 4 == 0 and e > a for _, a, e in buckets)
+    assert by_offset[0][0] == 0
+    firsts = [f for f, _, _ in by_offset]
+    assert all(firsts[i] < firsts[i + 1] for i in range(3))
+    items = list(st.offsets.items())
+    for shuffled in (items[::-1], random.Random(3).sample(items, len(items))):
+        assert gradient_buckets(dict(shuffled), st.size, op_keys, order, BUCKET_STARTS) == buckets
+
+
+_EX_BUCKETS = [(0, 0, 16), (2, 16, 28), (5, 28, 48), (6, 48, 64)]   # (first op, start, end) over eight ops; the backward runs 7..0
+_EX_KINDS = (["step_begin", "syncbn"] + ["op", "op", "grad_bucket", "op", "grad_bucket", "op", "op", "op", "grad_bucket", "op", "op", "grad_bucket"]
+             + ["grad_wait"])
+
+
+def _drive_exchange(ex, table):
+    """One step as TrainPlan.train_step / backward() drive it."""
+    ex.start_log()
+    ex.begin_step()
+    ex.reduce_stats(table)
+    running = ex.begin_backward()
+    for i in range(7, -1, -1):
+        ex.after_op(i, 0)
+    ex.finish_backward(0)
+    ex.wait()
+    return running
+
+
+def _exchange_integers(rank):
+    import numpy as np
+
+    return torch.from_numpy(np.random.default_rng(10 + rank).integers(-8, 9, 64).astype(np.float32))
+
+
+def _exchange_worker(rank, world, port, q):
+    os.environ.update(RANK=str(rank), LOCAL_RANK=str(rank), WORLD_SIZE=str(world), MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port))
+    from casapose_amd import parallel
+
+    parallel.init_from_env("gloo")
+    factor = 2.0 ** (3 + rank)                           # every replica's OWN loss factor
+    grad = _exchange_integers(rank) * factor
+    sent, waits = [], []
+
+    def before_send(stream, a, e):
+        sent.append((a, e, len(ex.pending)))
+        grad[a:e] /= factor
+
+    real_async = parallel.all_reduce_sum_async
+
+    class _Spy:
+        def __init__(self, h):
+            self.h = h
+
+        def wait(self):
+            waits.append(len(ex.log))
+            return self.h.wait()
+
+    parallel.all_reduce_sum_async = lambda t, group=None: _Spy(real_async(t, group))
+    ex = parallel.StepExchange(grad, torch.distributed.group.WORLD, world, lambda: list(_EX_BUCKETS), before_send)
+    table = torch.full((6,), 1.0 + rank, dtype=torch.float64)
+    running = _drive_exchange(ex, table)
+    q.put((rank, running, grad.numpy(), table.numpy(), list(ex.log), len(ex.pending), ex.structure(), sent, waits))
+    torch.distributed.destroy_process_group()
+
+
+def test_two_rank_step_exchange_protocol():
+    """Each bucket goes out right after the op that completes it, with the replica's own power-of-two factor already out of the slice;
+    nobody waits for a handle before wait(); afterwards both replicas hold the exact sum (small integers: no rounding anywhere)."""
+    import numpy as np
+
+    world = 2
+    ctx = mp.get_context("spawn")
+    q = ctx.Queue()
+    port = _free_port()
+    procs = [ctx.Process(target=_exchange_worker, args=(r, world, port, q)) for r in range(world)]
+    for p in procs:
+        p.start()
+    res = sorted((q.get(timeout=120) for _ in range(world)), key=lambda t: t[0])
+    for p in procs:
+        p.join(timeout=60)
+        assert p.exitcode == 0
+    want = (_exchange_integers(0) + _exchange_integers(1)).numpy()
+    for rank, running, grad, table, log, npending, st, sent, waits in res:
+        assert running
+        assert np.array_equal(grad, want) and np.array_equal(table, np.full(6, 3.0))
+        assert npending == 0
+        assert [e[0] for e in log] == _EX_KINDS and log[1] == ("syncbn", 48, "blocking", "compute") and log[-1] == ("grad_wait", 4)
+        bidx = [i for i, e in enumerate(log) if e[0] == "grad_bucket"]
+        assert len(waits) == 4 and all(w == len(log) for w in waits)       # every handle is waited for after ("grad_wait", 4), the last entry
+        assert [log[i] for i in bidx] == [("grad_bucket", 4 * (e - a), "async", 0, first) for first, a, e in reversed(_EX_BUCKETS)]
+        assert all(log[i - 1] == ("op", log[i][4]) for i in bidx)          # directly behind the op that completes it; offset 0 behind ("op", 0), last
+        assert log[bidx[-1]][4] == 0 and bidx[-1] == len(log) - 2
+        assert sent == [(a, e, k) for k, (_, a, e) in enumerate(reversed(_EX_BUCKETS))]   # the factor leaves a slice once, before its own send
+        assert st["backward_ops_launched_after_each_bucket"] == [6, 5, 2, 0] and st["backward_ops"] == 8
+        assert st["gradient_buckets"] == 4 and st["gradient_payload_bytes_per_step"] == 4 * 64
+        assert st["blocking_collectives_per_step"] == 1 and st["blocking_payload_bytes_per_step"] == 48
+
+
+def test_step_exchange_without_a_group_sends_nothing_and_logs_the_same_structure(monkeypatch):
+    """The structure of a step is identical for every world size (bench.py prints it from a single-replica run): the same log entries,
+    no collective, and the loss factor is left to the plan's single-replica unscale."""
+    from casapose_amd import parallel
+
+    def refuse(*a, **k):
+        raise AssertionError("a single replica starts no collective")
+
+    monkeypatch.setattr(parallel, "all_reduce_sum_async", refuse)
+    monkeypatch.setattr(torch.distributed, "all_reduce", refuse)
+    grad = _exchange_integers(0) * 8.0
+    before = grad.clone()
+    table = torch.full((6,), 1.0, dtype=torch.float64)
+    ex = parallel.StepExchange(grad, None, 1, lambda: list(_EX_BUCKETS), refuse)
+    assert not _drive_exchange(ex, table)
+    assert torch.equal(grad, before) and torch.equal(table, torch.full((6,), 1.0, dtype=torch.float64)) and not ex.pending
+    assert [e[0] for e in ex.log] == _EX_KINDS and ex.log[-1] == ("grad_wait", 0)
+    st = ex.structure()
+    assert st["backward_ops_launched_after_each_bucket"] == [6, 5, 2, 0] and st["gradient_payload_bytes_per_step"] == 4 * 64

@@ -245,7 +245,7 @@ def _rccl_worker(port, outdir):
             self.h = h
 
         def wait(self):
-            waits.append(len(plan.comm_log))
+            waits.append(len(plan.exchange.log))
             return self.h.wait()
 
     parallel.all_reduce_sum_async = lambda t, group=None: _Spy(real_async(t, group))
@@ -254,9 +254,9 @@ def _rccl_worker(port, outdir):
         out, sums, grad = _run(plan, dev, img, lab, kpts, before_second=lambda: (plan.start_comm_log(), waits.clear()))
     finally:
         parallel.all_reduce_sum_async = real_async
-    assert plan._buckets is not None and len(plan._buckets) == 4 and not plan._pending
+    assert plan.exchange.buckets is not None and len(plan.exchange.buckets) == 4 and not plan.exchange.pending
     # STRUCTURE of the exchange (round-5 verdict, item 8): the overlap with the backward is by construction, not assumed
-    log = plan.comm_log
+    log = plan.exchange.log
     compute = torch.cuda.current_stream(dev).cuda_stream
     bidx = [i for i, e in enumerate(log) if e[0] == "grad_bucket"]
     widx = [i for i, e in enumerate(log) if e[0] == "grad_wait"]
