@@ -264,6 +264,10 @@ SYMBOLS = [
     # ---- device PnP (csrc/pnp.hip) and its host twin ----
     ("cp_pnp_f64", _i, [_vp, _vp, _vp, _i, _vp, _vp, _vp, _i, _i, _i, _i, _f, _vp, _vp, _vp, _vp]),
     ("cp_pnp_host_f64", _i, [_vp, _vp, _vp, _i, _vp, _vp, _vp, _i, _i, _i, _i, _f, _vp, _vp, _vp]),
+    # ---- BPnP keypoint loss (csrc/bpnp.hip) and its host twin ----
+    ("cp_bpnp_loss_workspace_bytes", C.c_size_t, [_i, _i, _i]),
+    ("cp_bpnp_loss_f64", _i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _f, _f, _f, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    ("cp_bpnp_loss_host_f64", _i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _f, _f, _f, _vp, _vp, _vp, _vp, _vp, _vp]),
 ]
 
 _lib: Optional[C.CDLL] = None

@@ -2,21 +2,22 @@
 // (casapose_amd/pose_estimation/pnp.py restated in fp64); this file is the parallel schedule around it.
 //
 // pnp_kernel: one block of 256 threads per pair, one thread per hypothesis (a 5-point minimal set from the caller's table, H <= 256).
-//   The pair's points are loaded once into LDS (fp64, crop->image affine applied).  Thread h runs EPnP on its five points and scores the pose
-//   on all n points; the scores go to LDS and a tree reduction with a total order (most inliers, smallest sum of squared inlier errors,
+//   The pair's points are loaded once into LDS (fp64, crop->image affine applied).  The consensus stage (pnp_consensus.h, shared with
+//   bpnp.hip): thread h runs EPnP on its five points and scores the pose on all n points; the scores go to LDS and a tree reduction with a total order (most inliers, smallest sum of squared inlier errors,
 //   lowest index; idle slots lose against everything) picks the consensus.  No atomics: two calls give the same bits.  Thread 0 then runs
 //   EPnP on the consensus set and LM over all points -- a few thousand fp64 operations, not worth a second schedule.
 //   The working set of EPnP (the 12x12 M^T M, its eigenvectors, the barycentric coordinates: ~500 doubles) is private memory, i.e. scratch:
 //   the problem is a few thousand threads per batch, and every loop has a fixed trip count, so the kernel ends whatever its input.
 // cp_pnp_host_f64: the same functions in a serial loop over pairs and hypotheses, on host pointers; it launches nothing.
 #include "common.h"
+#include "pnp_consensus.h"
 #include "pnp_math.h"
 
 namespace {
 
 using namespace cp_pnp;
 
-constexpr int THREADS = MAX_HYPOTHESES;
+constexpr int THREADS = CONSENSUS_THREADS;
 
 __global__ void __launch_bounds__(THREADS) pnp_kernel(const float* __restrict__ points_xy, const float* __restrict__ points_3d,
                                                       const float* __restrict__ K, int k_per_image, const double* __restrict__ affine,
@@ -24,10 +25,7 @@ __global__ void __launch_bounds__(THREADS) pnp_kernel(const float* __restrict__ 
                                                       double reprojection_error, float* __restrict__ poses, int32_t* __restrict__ info,
                                                       float* __restrict__ cost) {
     __shared__ Problem P;
-    __shared__ int s_status;
-    __shared__ int s_count[THREADS], s_index[THREADS];
-    __shared__ double s_sse[THREADS];
-    __shared__ uint32_t s_mask[THREADS];
+    __shared__ Consensus S;
     const int pair = blockIdx.x, tid = threadIdx.x, image = pair / oc;
     float* pose = poses + (size_t)pair * 12;
     int32_t* inf = info + (size_t)pair * 4;
@@ -40,32 +38,14 @@ __global__ void __launch_bounds__(THREADS) pnp_kernel(const float* __restrict__ 
     if (tid < 9) P.K[tid] = (double)K[(k_per_image ? (size_t)image * 9 : 0) + tid];
     if (tid == 0) P.n = n;
     __syncthreads();
-    if (tid == 0) s_status = check_problem(P);
-    __syncthreads();
-    if (s_status != OK) {   // block-uniform
-        if (tid == 0) zero_outputs(s_status, pose, inf, cst);
+    const int status = consensus_stage(P, S, table, H, reprojection_error);
+    if (status != OK) {   // block-uniform
+        if (tid == 0) zero_outputs(status, pose, inf, cst);
         return;
     }
-    Score s = {-2, 0.0, 0u};   // an idle slot: below a hypothesis without a pose (-1)
-    if (tid < H) s = score_hypothesis(P, table + (size_t)tid * SET_POINTS, reprojection_error);
-    s_count[tid] = s.count;
-    s_sse[tid] = s.sse;
-    s_mask[tid] = s.mask;
-    s_index[tid] = tid;
-    __syncthreads();
-#pragma unroll 1
-    for (int half = THREADS / 2; half >= 1; half >>= 1) {
-        if (tid < half && better(s_count[tid + half], s_sse[tid + half], s_index[tid + half], s_count[tid], s_sse[tid], s_index[tid])) {
-            s_count[tid] = s_count[tid + half];
-            s_sse[tid] = s_sse[tid + half];
-            s_mask[tid] = s_mask[tid + half];
-            s_index[tid] = s_index[tid + half];
-        }
-        __syncthreads();
-    }
     if (tid == 0) {
-        const Score best = {s_count[0], s_sse[0], s_mask[0]};
-        finish_pair(P, s_index[0], best, pose, inf, cst);
+        const Score best = {S.count[0], S.sse[0], S.mask[0]};
+        finish_pair(P, S.index[0], best, pose, inf, cst);
     }
 }
 

@@ -1,4 +1,5 @@
-// PnP arithmetic shared by the device kernel (pnp.hip), its host twin (cp_pnp_host_f64) and the stand-alone self-test (pnp_selftest.cpp):
+// PnP arithmetic shared by the device kernels (pnp.hip; bpnp.hip through bpnp_math.h), their host twins (cp_pnp_host_f64,
+// cp_bpnp_loss_host_f64) and the stand-alone self-tests (pnp_selftest.cpp, bpnp_selftest.cpp):
 // casapose_amd/pose_estimation/pnp.py restated function by function in fp64, as __host__ __device__ code without any library call beyond
 // <math.h>.  Everything is bounded: the Jacobi sweeps, the Gauss-Newton steps, the LM iterations and the damping retries have fixed trip
 // counts, and a non-finite intermediate ends in a status word, never in another round.
@@ -452,9 +453,9 @@ PNP_HD bool epnp(const Problem& P, const uint8_t* idx, int m, Pose& best) {
 }
 
 // ---- LM on the all-point reprojection error in (rvec, t) (pnp.refine_lm) ------------------------------------------------------------------
-// pnp._residual_and_jacobian, folded into the normal equations: cost = r.r, A = J^T J, g = J^T r
-PNP_HD double residual_normal(const Problem& P, const double* p, double* A, double* g) {
-    double R[9], Jl[9], Kx[9], K2[9];
+// R(rvec) and the left Jacobian J_l of the rotation: R(rvec + d) ~ exp(J_l d) R
+PNP_HD void rotation_and_left_jacobian(const double* p, double* R, double* Jl) {
+    double Kx[9], K2[9];
     rodrigues(p, R);
     const double th = sqrt(p[0] * p[0] + p[1] * p[1] + p[2] * p[2]);
     if (th < 1e-8) {
@@ -467,26 +468,39 @@ PNP_HD double residual_normal(const Problem& P, const double* p, double* A, doub
         const double a = (1.0 - cos(th)) / th, b = 1.0 - sin(th) / th;
         for (int i = 0; i < 9; ++i) Jl[i] = (i % 4 == 0 ? 1.0 : 0.0) + a * Kx[i] + b * K2[i];
     }
+}
+
+// point i of pnp._residual_and_jacobian: the residual (ru, rv) = projection - keypoint and its two Jacobian rows in (rvec, t)
+PNP_HD void point_residual(const Problem& P, const double* p, const double* R, const double* Jl, int i, double& ru, double& rv, double* ju, double* jv) {
     const double fu = P.K[0], fv = P.K[4], sk = P.K[1];
+    const double* X = P.X + 3 * i;
+    const double Xr[3] = {R[0] * X[0] + R[1] * X[1] + R[2] * X[2], R[3] * X[0] + R[4] * X[1] + R[5] * X[2], R[6] * X[0] + R[7] * X[1] + R[8] * X[2]};
+    const double cx = Xr[0] + p[3], cy = Xr[1] + p[4], z = Xr[2] + p[5];
+    ru = fu * cx / z + P.K[2] + sk * cy / z - P.x[2 * i];
+    rv = fv * cy / z + P.K[5] - P.x[2 * i + 1];
+    const double du[3] = {fu / z, sk / z, -(fu * cx + sk * cy) / (z * z)}, dv[3] = {0.0, fv / z, -fv * cy / (z * z)};
+    double S[9], D[9];   // d cam / d rvec = -[Xr]x J_l
+    skew(Xr, S);
+    mul3(S, Jl, D);
+    for (int c = 0; c < 3; ++c) {
+        ju[c] = -(du[0] * D[c] + du[1] * D[3 + c] + du[2] * D[6 + c]);
+        jv[c] = -(dv[0] * D[c] + dv[1] * D[3 + c] + dv[2] * D[6 + c]);
+        ju[3 + c] = du[c];
+        jv[3 + c] = dv[c];
+    }
+}
+
+// pnp._residual_and_jacobian, folded into the normal equations: cost = r.r, A = J^T J, g = J^T r
+PNP_HD double residual_normal(const Problem& P, const double* p, double* A, double* g) {
+    double R[9], Jl[9];
+    rotation_and_left_jacobian(p, R, Jl);
     for (int i = 0; i < 36; ++i) A[i] = 0.0;
     for (int i = 0; i < 6; ++i) g[i] = 0.0;
     double cost = 0.0;
 #pragma unroll 1
     for (int i = 0; i < P.n; ++i) {
-        const double* X = P.X + 3 * i;
-        const double Xr[3] = {R[0] * X[0] + R[1] * X[1] + R[2] * X[2], R[3] * X[0] + R[4] * X[1] + R[5] * X[2], R[6] * X[0] + R[7] * X[1] + R[8] * X[2]};
-        const double cx = Xr[0] + p[3], cy = Xr[1] + p[4], z = Xr[2] + p[5];
-        const double ru = fu * cx / z + P.K[2] + sk * cy / z - P.x[2 * i], rv = fv * cy / z + P.K[5] - P.x[2 * i + 1];
-        const double du[3] = {fu / z, sk / z, -(fu * cx + sk * cy) / (z * z)}, dv[3] = {0.0, fv / z, -fv * cy / (z * z)};
-        double S[9], D[9], ju[6], jv[6];   // d cam / d rvec = -[Xr]x J_l
-        skew(Xr, S);
-        mul3(S, Jl, D);
-        for (int c = 0; c < 3; ++c) {
-            ju[c] = -(du[0] * D[c] + du[1] * D[3 + c] + du[2] * D[6 + c]);
-            jv[c] = -(dv[0] * D[c] + dv[1] * D[3 + c] + dv[2] * D[6 + c]);
-            ju[3 + c] = du[c];
-            jv[3 + c] = dv[c];
-        }
+        double ru, rv, ju[6], jv[6];
+        point_residual(P, p, R, Jl, i, ru, rv, ju, jv);
         cost += ru * ru + rv * rv;
         for (int a = 0; a < 6; ++a) {
             g[a] += ju[a] * ru + jv[a] * rv;
@@ -496,15 +510,15 @@ PNP_HD double residual_normal(const Problem& P, const double* p, double* A, doub
     return cost;
 }
 
-// lam 1e-3, x0.1 on success, x10 on failure, <= 10 tries per iteration, 20 iterations, relative stop 1e-10.  p = (rvec, t) in and out;
-// returns the iterations entered; cost[0] = the squared error at the start, cost[1] at the end.
-PNP_HD int refine_lm(const Problem& P, double* p, double* cost2) {
+// lam 1e-3, x0.1 on success, x10 on failure, <= 10 tries per iteration, at most max_iters iterations (pnp.pnp: 20), relative stop eps
+// (pnp.pnp: 1e-10).  p = (rvec, t) in and out; returns the iterations entered; cost[0] = the squared error at the start, cost[1] at the end.
+PNP_HD int refine_lm(const Problem& P, double* p, double* cost2, int max_iters = LM_ITERS, double eps = LM_EPS) {
     double A[36], g[6], A2[36], g2[6], B[36], rhs[6], step[6], q[6];
     double lam = 1e-3, cost = residual_normal(P, p, A, g);
     cost2[0] = cost;
     int iters = 0;
 #pragma unroll 1
-    for (int it = 0; it < LM_ITERS; ++it) {
+    for (int it = 0; it < max_iters; ++it) {
         ++iters;
         bool improved = false, done = false;
 #pragma unroll 1
@@ -524,7 +538,7 @@ PNP_HD int refine_lm(const Problem& P, double* p, double* cost2) {
                 for (int i = 0; i < 6; ++i) { p[i] = q[i]; g[i] = g2[i]; }
                 for (int i = 0; i < 36; ++i) A[i] = A2[i];
                 lam = dmax(lam * 0.1, 1e-12);
-                done = (cost - c2) < LM_EPS * dmax(cost, 1e-30);
+                done = (cost - c2) < eps * dmax(cost, 1e-30);
                 cost = c2;
                 improved = true;
                 break;
@@ -618,9 +632,9 @@ PNP_HD void zero_outputs(int status, float* pose, int32_t* info, float* cost) {
     cost[0] = cost[1] = 0.f;
 }
 
-// EPnP on the consensus set (all points when it has fewer than 5, as pnp.pnp_rvec_t), LM over all points, then pnp.pnp's ending: (rvec, t)
-// rounded to fp32, the pose negated when t_z < 0, a non-finite result replaced by the zero pose
-PNP_HD void finish_pair(const Problem& P, int winner, const Score& sc, float* pose, int32_t* info, float* cost) {
+// EPnP on the consensus set (all points when it has fewer than 5, as pnp.pnp_rvec_t), then LM over all points: p = (rvec, t) in fp64,
+// c2 = the squared error before and after LM.  false: no finite pose
+PNP_HD bool consensus_pose(const Problem& P, const Score& sc, double* p, double* c2, int& iters) {
     uint8_t idx[MAX_POINTS];
     int m = 0;
     if (sc.count >= SET_POINTS)
@@ -632,23 +646,24 @@ PNP_HD void finish_pair(const Problem& P, int winner, const Score& sc, float* po
         for (int i = 0; i < P.n; ++i) idx[i] = (uint8_t)i;
         ok = epnp(P, idx, P.n, q);
     }
-    if (!ok) {
-        zero_outputs(NO_SOLUTION, pose, info, cost);
-        return;
-    }
-    double p[6], c2[2], R[9];
+    if (!ok) return false;
     rodrigues_inverse(q.R, p);
     for (int d = 0; d < 3; ++d) p[3 + d] = q.t[d];
-    const int iters = refine_lm(P, p, c2);
+    iters = refine_lm(P, p, c2);
     bool fin = finite(c2[0]) && finite(c2[1]);
-    for (int i = 0; i < 6; ++i) {
-        fin = fin && finite(p[i]);
-        p[i] = (double)(float)p[i];
-    }
-    if (!fin) {
+    for (int i = 0; i < 6; ++i) fin = fin && finite(p[i]);
+    return fin;
+}
+
+// consensus_pose, then pnp.pnp's ending: (rvec, t) rounded to fp32, the pose negated when t_z < 0, a non-finite result replaced by the zero pose
+PNP_HD void finish_pair(const Problem& P, int winner, const Score& sc, float* pose, int32_t* info, float* cost) {
+    double p[6], c2[2], R[9];
+    int iters = 0;
+    if (!consensus_pose(P, sc, p, c2, iters)) {
         zero_outputs(NO_SOLUTION, pose, info, cost);
         return;
     }
+    for (int i = 0; i < 6; ++i) p[i] = (double)(float)p[i];
     rodrigues(p, R);
     const double sgn = p[5] < 0.0 ? -1.0 : 1.0;
     for (int r = 0; r < 3; ++r) {
@@ -658,6 +673,20 @@ PNP_HD void finish_pair(const Problem& P, int winner, const Score& sc, float* po
     info[0] = OK; info[1] = winner; info[2] = sc.count < 0 ? 0 : sc.count; info[3] = iters;
     cost[0] = (float)c2[0];
     cost[1] = (float)c2[1];
+}
+
+// the consensus over the H hypotheses of the table, serially: what the kernels' blocks find with one thread per hypothesis
+PNP_HD int consensus_serial(const Problem& P, const uint8_t* table, int H, double reprojection_error, Score& best) {
+    best = {-2, 0.0, 0u};
+    int winner = -1;
+    for (int h = 0; h < H; ++h) {
+        const Score s = score_hypothesis(P, table + SET_POINTS * h, reprojection_error);
+        if (winner < 0 || better(s.count, s.sse, h, best.count, best.sse, winner)) {
+            best = s;
+            winner = h;
+        }
+    }
+    return winner;
 }
 
 // the whole of one pair, serially: what the kernel's block computes with one thread per hypothesis
@@ -672,15 +701,8 @@ PNP_HD void solve_pair_serial(const float* xy, const float* xyz, const float* K,
         zero_outputs(status, pose, info, cost);
         return;
     }
-    Score best = {-2, 0.0, 0u};
-    int winner = -1;
-    for (int h = 0; h < H; ++h) {
-        const Score s = score_hypothesis(P, table + SET_POINTS * h, reprojection_error);
-        if (winner < 0 || better(s.count, s.sse, h, best.count, best.sse, winner)) {
-            best = s;
-            winner = h;
-        }
-    }
+    Score best;
+    const int winner = consensus_serial(P, table, H, reprojection_error, best);
     finish_pair(P, winner, best, pose, info, cost);
 }
 

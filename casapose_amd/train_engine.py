@@ -1195,6 +1195,11 @@ class TrainPlan:
         self.ls_coords = torch.zeros(B, oc, kp, 2, **f32)
         self.ls_g = torch.zeros(B, oc, kp, 2, **f32)
         self.kp_loss_val = torch.zeros(1, dtype=torch.float64, device=dev)
+        # what kp_loss_and_grad(device_loss=...) leaves: poses, cp_pnp_f64's info words and {solved, available but unsolved}; the running count of
+        # unsolved pairs is kept by training.train_step
+        self.bpnp_poses = self.bpnp_info = self.bpnp_counts = None
+        self.bpnp_unsolved = 0
+        self.device_bpnp = {}   # keypoint count -> DeviceBPnPLoss (training.device_bpnp_from_environment)
 
         def layer(rec, grad_sources):
             L = TrainConv(store, rec.key, rec.layout, rec.k, rec.cout, rec.sources, grad_sources)
@@ -1673,14 +1678,19 @@ class TrainPlan:
     def kp_loss_and_grad(self, labels_gt: torch.Tensor, gt_xy: torch.Tensor, affine: torch.Tensor, kp_w: float, max_pixel_error: float = 25.0,
                          min_num: int = 50, confidence_regularization: bool = False, vote_with_gt: bool = True, kp: int = 9,
                          min_num_gt: Optional[int] = None, filter_with_gt: bool = True, coords: Optional[torch.Tensor] = None,
-                         backward: bool = True, host_loss: Optional[Callable] = None) -> torch.Tensor:
+                         backward: bool = True, host_loss: Optional[Callable] = None, device_loss=None) -> torch.Tensor:
         """keypoint_reprojection_loss (loss_functions.py:207-344, use_bpnp_reprojection_loss=False) on the last forward's
         output; ADDS kp_w * d loss / d output to self.dout (call after loss_and_grad).  gt_xy [B,oc,kp,2]: projected
         ground-truth keypoints in image pixels; affine [B,6]: crop->image map (crop_to_image_affine).  Returns the
         fp64 loss value (device scalar).  `coords` (optional, [B,oc,kp,2] (y,x)) replaces the internal vote (evaluation with the
         component-filtered voter; implies backward=False); min_num_gt / filter_with_gt as in loss_functions.py:221-222,246-252.
         `host_loss(coords, avail) -> (loss, g_yx)` replaces the reprojection kernel (the BPnP variant, whose PnP solve and
-        implicit gradient run on the host like the reference's BPNP_fast)."""
+        implicit gradient run on the host like the reference's BPNP_fast).  `device_loss` (a pose_estimation.device_bpnp.DeviceBPnPLoss with
+        its targets bound) computes the same variant on the device, straight into ls_g and kp_loss_val, without a host round trip; it leaves
+        bpnp_poses [B,oc,1,3,4], bpnp_info [B,oc,4] and bpnp_counts [2] (solved, available but unsolved) as device tensors.  An available pair
+        it cannot solve counts as unavailable there, where host_loss raises.  The two are mutually exclusive."""
+        if host_loss is not None and device_loss is not None:
+            raise ValueError("kp_loss_and_grad takes host_loss or device_loss, not both")
         lib = _lib.load()
         B, h, w, K = self.batch, self.h, self.w, self.seg_dim
         oc = K - 1
@@ -1707,6 +1717,9 @@ class TrainPlan:
             lv, g = host_loss(self.ls_coords, avail)
             self.ls_g.copy_(torch.from_numpy(np.ascontiguousarray(g, dtype=np.float32)).reshape(B, oc, kp, 2))
             self.kp_loss_val.fill_(float(lv))
+        elif device_loss is not None:
+            self.bpnp_poses, self.bpnp_info, self.bpnp_counts = device_loss.run(self.ls_coords, gt_xy, affine, avail, max_pixel_error, kp_w, self.ls_g,
+                                                                                self.kp_loss_val)
         else:
             check(lib.cp_kp_reproj_loss_f32(self.ls_coords.data_ptr(), gt_xy.data_ptr(), affine.data_ptr(), avail.data_ptr(), B, oc, kp, max_pixel_error,
                                             kp_w, self.ls_g.data_ptr(), self.kp_loss_val.data_ptr(), stream), "cp_kp_reproj_loss_f32")

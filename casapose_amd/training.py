@@ -12,6 +12,8 @@ reference's batch tuple and option names onto it.  Data parallelism
 """
 from __future__ import annotations
 
+import os
+import warnings
 from typing import Callable, Dict, Optional, Sequence, Tuple, Union
 
 import numpy as np
@@ -124,6 +126,26 @@ def bpnp_reprojection_loss_host(coords_yx, gt_xy, affine, avail, points_3d, cam,
     return float(loss), (weight * g).astype(np.float32), poses
 
 
+_said_bpnp_device = False
+
+
+def device_bpnp_from_environment(plan, n_points: int, device):
+    """CASAPOSE_DEVICE_BPNP=1: the DeviceBPnPLoss of this plan for n_points keypoints, built on the first call and kept on the plan.  Anything
+    else: None, the host path.  Says `bpnp: device` once."""
+    global _said_bpnp_device
+    if os.environ.get("CASAPOSE_DEVICE_BPNP", "0") != "1":
+        return None
+    from .pose_estimation.device_bpnp import DeviceBPnPLoss
+
+    kept = plan.device_bpnp
+    if int(n_points) not in kept:
+        kept[int(n_points)] = DeviceBPnPLoss(device, n_points)
+        if not _said_bpnp_device:
+            print("bpnp: device")
+            _said_bpnp_device = True
+    return kept[int(n_points)]
+
+
 def train_step(net, batch: Dict[str, torch.Tensor], loss_factors, optimizer: Optional[Adam], opt, group=None, world_size: int = 1,
                train: bool = True, coords: Optional[torch.Tensor] = None, min_num: int = 50, min_num_gt: Optional[int] = None,
                filter_with_gt: bool = True):
@@ -161,14 +183,18 @@ def train_step(net, batch: Dict[str, torch.Tensor], loss_factors, optimizer: Opt
     kp_loss = None
     if getattr(opt, "estimate_coords", False):
         gt_xy, aff, cam, p3d = _kp_targets(batch, B, oc, dev)
-        host_loss = None
+        host_loss = device_loss = None
         if getattr(opt, "use_bpnp_reprojection_loss", False):
-            def host_loss(c, av):  # noqa: E306
-                return bpnp_reprojection_loss_host(c, gt_xy, aff, av, p3d, cam, float(getattr(opt, "max_keypoint_pixel_error", 25.0)), kp_w)[:2]
+            device_loss = device_bpnp_from_environment(plan, kpts.shape[2], dev)   # None unless CASAPOSE_DEVICE_BPNP=1
+            if device_loss is not None:
+                device_loss.bind(p3d, cam)
+            else:
+                def host_loss(c, av):  # noqa: E306
+                    return bpnp_reprojection_loss_host(c, gt_xy, aff, av, p3d, cam, float(getattr(opt, "max_keypoint_pixel_error", 25.0)), kp_w)[:2]
         kp_loss = plan.kp_loss_and_grad(labels, gt_xy, aff, kp_w, max_pixel_error=float(getattr(opt, "max_keypoint_pixel_error", 25.0)), min_num=min_num,
                                         confidence_regularization=bool(getattr(opt, "confidence_regularization", False)) and train,
                                         vote_with_gt=with_gt, min_num_gt=min_num_gt, filter_with_gt=filter_with_gt, coords=coords, backward=train,
-                                        host_loss=host_loss)
+                                        host_loss=host_loss, device_loss=device_loss)
     if train:
         stream = torch.cuda.current_stream(dev).cuda_stream
         plan.backward()
@@ -187,6 +213,12 @@ def train_step(net, batch: Dict[str, torch.Tensor], loss_factors, optimizer: Opt
         net.mark_trained()
     s = sums.cpu().numpy()
     kpv = float(kp_loss.item()) if kp_loss is not None else 0.0
+    if kp_loss is not None and device_loss is not None:   # (the reads above have synchronised)
+        unsolved = int(plan.bpnp_counts.cpu()[1])
+        if unsolved and not plan.bpnp_unsolved:
+            warnings.warn("the device BPnP loss left %d available (image, object) pair(s) of this step unsolved: they were treated as unavailable "
+                          "(plan.bpnp_info holds their status; plan.bpnp_unsolved keeps the running count)" % unsolved, UserWarning, stacklevel=2)
+        plan.bpnp_unsolved += unsolved
     total = wts[0] * s[0] + wts[1] * s[1] + wts[2] * s[2] + kp_w * kpv
     return [float(total), float(s[0]), float(s[1]), float(s[2]), kpv]
 

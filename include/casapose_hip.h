@@ -824,6 +824,41 @@ int cp_pnp_f64(const float* points_xy, const float* points_3d, const float* K, i
 int cp_pnp_host_f64(const float* points_xy, const float* points_3d, const float* K, int k_per_image, const double* affine, const int32_t* solve,
                     const uint8_t* table, int b, int oc, int n, int H, float reprojection_error, float* poses, int32_t* info, float* cost);
 
+/* ---- BPnP keypoint loss (csrc/bpnp.hip, csrc/bpnp_math.h) ----------------------------------------------------------------------------
+ * keypoint_reprojection_loss with use_bpnp_reprojection_loss = 1 (loss_functions.py:264-323) and its gradient, on the device:
+ * training.bpnp_reprojection_loss_host restated in fp64.  Per available (image, object) pair: the voted keypoints go through the crop->image
+ * affine, the consensus EPnP + LM of cp_pnp_f64 gives the pose (before its fp32 rounding), a second LM (30 iterations, relative stop 1e-14)
+ * tightens it to the optimum y; r = project(points_3d, y), e = (|r - p'| + |gt - r|) / 2, smooth L1 with the soft cap at max_pixel_error, the
+ * mean over the keypoints.  The gradient is the explicit term plus the implicit-function term through the PnP optimum: H v = J^T g_r with
+ * H = d(J^T r)/dy by central differences (h = 1e-6 max(1, |y_k|), symmetrised), then g_direct + J v, back through the 2x2 linear part of the
+ * affine, as (y, x).  Two launches on `stream` (one block per pair, then one block), no atomics: two calls give the same bits.
+ *   coords_yx  fp32 [batch*objects][kp][2]  voted keypoints (y, x) in crop pixels
+ *   gt_xy      fp32 [batch*objects][kp][2]  projected ground-truth keypoints (x, y) in image pixels
+ *   affine     fp32 [batch][6]              image x = a0 x + a1 y + a2, image y = a3 x + a4 y + a5 (as for cp_kp_reproj_loss_f32)
+ *   avail      fp32 [batch*objects]         0: the pair takes no part (status 1, zero gradient, zero pose)
+ *   points_3d  fp32 [batch*objects][kp][3]  model keypoints
+ *   K          fp32 [9]                     one camera for the whole batch, row-major (the reference uses camera_data[0])
+ *   table      uint8 [H][5]                 the hypotheses of cp_pnp_f64
+ *   g_yx       fp32 [batch*objects][kp][2]  weight x d loss / d coords_yx; every element is written
+ *   loss_out   fp64 [1]                     sum of the solved pairs' losses / their number na; 0 when na == 0
+ *   poses      fp32 [batch*objects][12]     row-major [3,4] of the tightened optimum, negated when t_z < 0; zero for every pair that is not solved
+ *   info       int32 [batch*objects][4]     cp_pnp_f64's words: status, winning hypothesis, its inlier count, iterations of the first LM.  Status 4
+ *                                           also covers a singular H or a non-finite loss
+ *   counts     int32 [2]                    {solved pairs (na), available pairs that are not solved}
+ *   workspace  cp_bpnp_loss_workspace_bytes(batch, objects, kp) bytes, 8-byte aligned; needs no initialisation
+ * A pair is solved when avail != 0 and its status is 0.  An available pair that is not solved (a collapsed vote, a non-finite keypoint, no finite
+ * optimum) is treated as unavailable: no loss, no gradient, not in na -- where the host path raises FloatingPointError for the whole step.
+ * 5 <= kp <= 16, 1 <= H <= 256, at most 65535 pairs per call, reprojection_error > 0, max_pixel_error > 0.  cp_bpnp_loss_host_f64 runs the same
+ * code serially on host pointers, launches nothing and also checks that the table names points below kp.  Added in ABI 302 without changing
+ * any earlier entry point. */
+size_t cp_bpnp_loss_workspace_bytes(int batch, int objects, int kp);
+int cp_bpnp_loss_f64(const float* coords_yx, const float* gt_xy, const float* affine, const float* avail, const float* points_3d, const float* K,
+                     const uint8_t* table, int batch, int objects, int kp, int H, float reprojection_error, float max_pixel_error, float weight,
+                     float* g_yx, double* loss_out, float* poses, int32_t* info, int32_t* counts, void* workspace, void* stream);
+int cp_bpnp_loss_host_f64(const float* coords_yx, const float* gt_xy, const float* affine, const float* avail, const float* points_3d, const float* K,
+                          const uint8_t* table, int batch, int objects, int kp, int H, float reprojection_error, float max_pixel_error, float weight,
+                          float* g_yx, double* loss_out, float* poses, int32_t* info, int32_t* counts, void* workspace);
+
 #ifdef __cplusplus
 }
 #endif
