@@ -268,6 +268,10 @@ SYMBOLS = [
     ("cp_bpnp_loss_workspace_bytes", C.c_size_t, [_i, _i, _i]),
     ("cp_bpnp_loss_f64", _i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _f, _f, _f, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     ("cp_bpnp_loss_host_f64", _i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _f, _f, _f, _vp, _vp, _vp, _vp, _vp, _vp]),
+    # ---- synthetic scenes (csrc/scenes.hip) and the host twin ----
+    ("cp_render_scenes_record_words", C.c_size_t, [_i]),
+    ("cp_render_scenes_f32", _i, [_vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp]),
+    ("cp_render_scenes_host_f32", _i, [_vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp]),
 ]
 
 _lib: Optional[C.CDLL] = None

@@ -3,7 +3,12 @@
 // (op slot, pixel, channel, 0): a halo pixel recomputed by a neighbouring tile draws exactly what its owner draws, and results do not depend
 // on tiling, launch shape or shard.
 #pragma once
+#if defined(__HIPCC__)
 #include <hip/hip_runtime.h>
+#define CP_PHILOX_HD __host__ __device__ __forceinline__
+#else   // a plain host compiler (csrc/scenes_selftest.cpp)
+#define CP_PHILOX_HD inline
+#endif
 
 #include <cstdint>
 
@@ -13,7 +18,7 @@ struct philox4 {
     uint32_t v[4];
 };
 
-__host__ __device__ __forceinline__ philox4 philox4x32_10(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint64_t key) {
+CP_PHILOX_HD philox4 philox4x32_10(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint64_t key) {
     uint32_t k0 = (uint32_t)key, k1 = (uint32_t)(key >> 32);
 #pragma unroll
     for (int r = 0; r < 10; ++r) {
@@ -30,6 +35,6 @@ __host__ __device__ __forceinline__ philox4 philox4x32_10(uint32_t c0, uint32_t 
 }
 
 // uniform in the open interval (0, 1) from 24 bits
-__host__ __device__ __forceinline__ float u01(uint32_t x) { return (float)(x >> 8) * (1.f / 16777216.f) + (0.5f / 16777216.f); }
+CP_PHILOX_HD float u01(uint32_t x) { return (float)(x >> 8) * (1.f / 16777216.f) + (0.5f / 16777216.f); }
 
 }  // namespace cp

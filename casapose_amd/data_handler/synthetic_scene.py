@@ -15,6 +15,9 @@ Geometry: object o is the ellipsoid x^2/a^2 + y^2/b^2 + z^2/c^2 = 1 in its own f
 the 8 corners of its bounding box (the reference's farthest-point keypoints are likewise spread over the object); the
 evaluation mesh is a Fibonacci sampling of the surface.  A camera with the LINEMOD intrinsics renders 480x640; crops
 follow the reference's offsets convention [h_crop, w_crop, -, -, dx, dy, angle, scale, 640, 480].
+
+The pictures are ray-cast here in NumPy fp64, one image at a time; `batch(..., device=)` / `generate_dataset(..., device=)` hand the per-pixel part
+to the GPU instead (device_scenes.py, csrc/scenes.hip): the same draws, labels, poses and keypoints, other noise samples of the same distribution.
 """
 from __future__ import annotations
 
@@ -59,12 +62,14 @@ class SyntheticSceneDataset:
         self.mesh_vertex_array = sph[None] * self.axes[:, None, :]                  # [oc,V,3]
         self.mesh_vertex_count = np.full((no_objects, 1), mesh_vertices, np.int32)
         self.diameters = 2.0 * self.axes.max(axis=1)                                 # largest vertex distance
+        self._device_scenes: Dict[str, object] = {}
 
     def __len__(self):
         return self.length
 
     # ---- one image ------------------------------------------------------------------------------------
-    def _render(self, rng) -> Dict[str, np.ndarray]:
+    def _draw(self, rng) -> Tuple[int, int, np.ndarray]:
+        """The draws of one image, in this order: the crop origin, then per object z, u, v and the rotation -> (hc, wc, poses [oc,3,4])."""
         oc = self.oc
         H, W = self.size
         if (H, W) == (FULL_H, FULL_W):
@@ -82,6 +87,14 @@ class SyntheticSceneDataset:
             v = rng.uniform(hc + 0.12 * H, hc + 0.88 * H)
             poses[o, :, :3] = _rot(rng)
             poses[o, :, 3] = [(u - K[0, 2]) * z / K[0, 0], (v - K[1, 2]) * z / K[1, 1], z]
+        return hc, wc, poses
+
+    def _pixels(self, rng, hc: int, wc: int, poses: np.ndarray, noise: bool = True) -> Tuple[np.ndarray, np.ndarray]:
+        """The per-pixel part of one image -> (img [H,W,3] float64 in [-1,1], label [H,W] uint8).  With noise it draws N(0, 0.02) for the background
+        and then N(0, 0.01) for every pixel from `rng`; without, it draws nothing.  csrc/scene_math.h restates this function."""
+        oc = self.oc
+        H, W = self.size
+        K = CAMERA
         # ray casting on the crop
         ys, xs = np.mgrid[hc:hc + H, wc:wc + W].astype(np.float64) + 0.5
         rays = np.stack([(xs - K[0, 2]) / K[0, 0], (ys - K[1, 2]) / K[1, 1], np.ones_like(xs)], axis=-1)  # camera frame
@@ -105,43 +118,82 @@ class SyntheticSceneDataset:
             label = np.where(nearer, o + 1, label).astype(np.uint8)
             shade = np.where(nearer, 0.55 + 0.45 * np.abs(nrm[..., 2]), shade)
         img = np.empty((H, W, 3))
-        bg = 0.35 + 0.1 * np.sin(xs / 37.0)[..., None] * np.cos(ys / 53.0)[..., None] + rng.normal(0, 0.02, (H, W, 3))
+        bg = 0.35 + 0.1 * np.sin(xs / 37.0)[..., None] * np.cos(ys / 53.0)[..., None]
+        if noise:
+            bg = bg + rng.normal(0, 0.02, (H, W, 3))
         col = np.concatenate([np.zeros((1, 3)), self.colors])[label]
         img[:] = np.where(label[..., None] > 0, col * shade[..., None], bg)
-        img = np.clip(img + rng.normal(0, 0.01, img.shape), 0, 1) * 2.0 - 1.0        # normal = [0.5, 0.5] -> [-1, 1]
-        # 2-D keypoints in crop pixels, (y,x)
+        if noise:
+            img = img + rng.normal(0, 0.01, img.shape)
+        img = np.clip(img, 0, 1) * 2.0 - 1.0        # normal = [0.5, 0.5] -> [-1, 1]
+        return img, label
+
+    def _keypoints(self, hc: int, wc: int, poses: np.ndarray) -> Tuple[np.ndarray, np.ndarray]:
+        """(kp2 [oc,kp,2]: the 2-D keypoints in crop pixels (y,x), offsets [10])"""
+        oc = self.oc
+        K = CAMERA
         kp2 = np.zeros((oc, self.kp, 2))
         for o in range(oc):
             cam = self.keypoints3d[o] @ poses[o, :, :3].T + poses[o, :, 3]
             uv = (cam @ K.T)
             uv = uv[:, :2] / uv[:, 2:]
             kp2[o, :, 0], kp2[o, :, 1] = uv[:, 1] - hc, uv[:, 0] - wc
+        return kp2, np.array([hc, wc, 0, 0, 0, 0, 0, 1, FULL_W, FULL_H], np.float32)
+
+    def _render(self, rng, noise: bool = True) -> Dict[str, np.ndarray]:
+        oc = self.oc
+        hc, wc, poses = self._draw(rng)
+        img, label = self._pixels(rng, hc, wc, poses, noise)
+        kp2, offsets = self._keypoints(hc, wc, poses)
         counts = np.array([(label == o + 1).sum() for o in range(oc)], np.int32)
-        return dict(img=img.astype(np.float32), label=label, poses=poses, kp2=kp2, counts=counts,
-                    offsets=np.array([hc, wc, 0, 0, 0, 0, 0, 1, FULL_W, FULL_H], np.float32))
+        return dict(img=img.astype(np.float32), label=label, poses=poses, kp2=kp2, counts=counts, offsets=offsets)
 
-    def batch(self, index: int, batchsize: int, shard: Tuple[int, int] = (0, 1)) -> Dict[str, torch.Tensor]:
-        """Deterministic batch `index` (images index*batchsize ... of the endless stream seeded by `seed`).  `shard = (rank, world)`
-        renders only that replica's contiguous slice of the global batch (casapose_amd.parallel.shard_range) -- image i of the
-        stream is the same picture whichever replica draws it."""
-        from ..parallel import shard_range
-
-        begin, end = shard_range(batchsize, shard[0], shard[1])
-        items = [self._render(np.random.default_rng([self.seed, index * batchsize + i])) for i in range(begin, end)]
-        K1 = self.oc + 1
-        lab = np.stack([it["label"] for it in items])
-        seg = np.eye(K1, dtype=np.float32)[lab]
-        b = end - begin
+    def _small_arrays(self, items) -> Dict[str, torch.Tensor]:
+        """The batch entries that do not depend on pixels, from per-image dicts with "kp2", "offsets" and "poses"."""
+        b = len(items)
         return dict(
-            img=torch.from_numpy(np.stack([it["img"] for it in items])),
-            target_seg=torch.from_numpy(seg),
             keypoints3d=torch.from_numpy(np.tile(self.keypoints3d[None, :, None], (b, 1, 1, 1, 1)).astype(np.float32)),
             target_vert=torch.from_numpy(np.stack([it["kp2"] for it in items])[:, :, None].astype(np.float32)),
             cam_mat=torch.from_numpy(np.tile(CAMERA[None], (b, 1, 1)).astype(np.float32)),
             diameters=torch.from_numpy(np.tile(self.diameters[None, :, None, None], (b, 1, 1, 1)).astype(np.float32)),
             offsets=torch.from_numpy(np.stack([it["offsets"] for it in items])),
-            filtered_seg=torch.from_numpy(lab[..., None].astype(np.int32)),
             poses_gt=torch.from_numpy(np.stack([it["poses"] for it in items])[:, :, None].astype(np.float32)),
+        )
+
+    def device_scenes(self, device, prefetch: int = 1):
+        """The DeviceScenes (device_scenes.py) that renders this dataset on `device`, built on first use and kept."""
+        from .device_scenes import DeviceScenes
+
+        key = str(torch.device(device))
+        if key not in self._device_scenes:
+            self._device_scenes[key] = DeviceScenes(self, device, prefetch)
+        return self._device_scenes[key]
+
+    def batch(self, index: int, batchsize: int, shard: Tuple[int, int] = (0, 1), device=None) -> Dict[str, torch.Tensor]:
+        """Deterministic batch `index` (images index*batchsize ... of the endless stream seeded by `seed`).  `shard = (rank, world)`
+        renders only that replica's contiguous slice of the global batch (casapose_amd.parallel.shard_range) -- image i of the
+        stream is the same picture whichever replica draws it.  With a `device` the pixels are rendered there (device_scenes.py): the same
+        labels, poses and keypoints, other noise samples of the same distribution; img / target_seg / filtered_seg are device tensors."""
+        from ..parallel import shard_range
+
+        begin, end = shard_range(batchsize, shard[0], shard[1])
+        if device is not None:
+            return self.device_scenes(device).render(range(index * batchsize + begin, index * batchsize + end))
+        items = [self._render(np.random.default_rng([self.seed, index * batchsize + i])) for i in range(begin, end)]
+        K1 = self.oc + 1
+        lab = np.stack([it["label"] for it in items])
+        seg = np.eye(K1, dtype=np.float32)[lab]
+        small = self._small_arrays(items)
+        return dict(
+            img=torch.from_numpy(np.stack([it["img"] for it in items])),
+            target_seg=torch.from_numpy(seg),
+            keypoints3d=small["keypoints3d"],
+            target_vert=small["target_vert"],
+            cam_mat=small["cam_mat"],
+            diameters=small["diameters"],
+            offsets=small["offsets"],
+            filtered_seg=torch.from_numpy(lab[..., None].astype(np.int32)),
+            poses_gt=small["poses_gt"],
             pixel_gt_count=torch.from_numpy(np.stack([it["counts"] for it in items]).astype(np.float32)[:, :, None, None]),
         )
 
@@ -149,15 +201,25 @@ class SyntheticSceneDataset:
         """(vertex_array [oc,V,3], vertex_count [oc,1]) like VectorfieldDataset.generate_object_vertex_array."""
         return self.mesh_vertex_array.astype(np.float32), self.mesh_vertex_count
 
-    def generate_dataset(self, batchsize: int, epochs: int = 1, *_unused, shard: Tuple[int, int] = (0, 1), **_unused_kw) -> Tuple[Iterator[Dict[str, torch.Tensor]], int]:
+    def generate_dataset(self, batchsize: int, epochs: int = 1, prefetch: int = 0, *_unused, shard: Tuple[int, int] = (0, 1), device=None,
+                         **_unused_kw) -> Tuple[Iterator[Dict[str, torch.Tensor]], int]:
         """(iterator over epochs*batches batches, batches per epoch) -- the shape of VectorfieldDataset.generate_dataset
         (vectorfield_dataset.py:905-1013).  The same `length` images are revisited every epoch.  `batchsize` is the GLOBAL batch
-        (vectorfield_dataset.py:923,1002); with shard = (rank, world) every replica produces only its own slice of each batch."""
+        (vectorfield_dataset.py:923,1002); with shard = (rank, world) every replica produces only its own slice of each batch.  With a
+        `device` the batches are rendered there, up to max(prefetch, 1) of them ahead of the consumer (device_scenes.py).  A caller that
+        names no device gets the host path, unless CASAPOSE_DEVICE_SCENES=1 is set: then the current GPU renders, and one line says so
+        (test_casapose.py, which passes no device, is switched this way)."""
+        if device is None:
+            from . import device_scenes
+
+            device = device_scenes.device_from_environment()
         n = self.length // batchsize
 
-        def it():
+        def indices():
             for _ in range(max(epochs, 1) + 1):
                 for i in range(n):
-                    yield self.batch(i, batchsize, shard)
+                    yield i
 
-        return it(), n
+        if device is not None:
+            return self.device_scenes(device, prefetch).batches(indices(), batchsize, shard, prefetch), n
+        return (self.batch(i, batchsize, shard) for i in indices()), n

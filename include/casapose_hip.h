@@ -859,6 +859,30 @@ int cp_bpnp_loss_host_f64(const float* coords_yx, const float* gt_xy, const floa
                           const uint8_t* table, int batch, int objects, int kp, int H, float reprojection_error, float max_pixel_error, float weight,
                           float* g_yx, double* loss_out, float* poses, int32_t* info, int32_t* counts, void* workspace);
 
+/* ---- synthetic scenes (csrc/scenes.hip, csrc/scene_math.h) ------------------------------------------------------------------------------
+ * SyntheticSceneDataset._render (data_handler/synthetic_scene.py) on the device: ray-cast ellipsoids, the background wave, the noise, the label
+ * map, the one-hot target and the visible-pixel counts of b images in one launch.  All geometry is fp64 without FMA contraction; the image is
+ * rounded to fp32 once.
+ *   records    fp64 [b][cp_render_scenes_record_words(oc)]  one record per image, built on the host: words 0-1 the crop origin (row hc, column
+ *              wc), 2-5 the camera fx, fy, cx, cy, 6 the image seed (the bit pattern of a uint64), 7 the number of objects in this image
+ *              (0..oc; anything else renders the background alone), then per object R [9] row-major, t [3], 1 / semi-axes [3], colour [3]
+ *   noise      0: the noise-free image; otherwise N(0, 0.02) per channel on background pixels, then N(0, 0.01) per channel everywhere, from
+ *              Philox4x32-10 keyed by the image seed and counted by (pixel, draw), Box-Muller in fp32: the six normals of a pixel depend on
+ *              (image seed, pixel) alone, not on the batch, the position in it or the launch shape
+ *   img        fp32 [b][H][W][3] in [-1, 1]
+ *   label      uint8 [b][H][W]    0 the background, o + 1 object o (the nearest hit; index order with a strict <)
+ *   target_seg fp32 [b][H][W][oc + 1]  one-hot of label
+ *   counts     int32 [b][oc]      visible pixels per object; zeroed inside the call, integer atomics only
+ * 1 <= oc <= 254, 1 <= b <= 65535, H * W < 2^31; records 8-byte aligned, img / target_seg / counts 4-byte aligned.  Widths that are a multiple
+ * of 4 with 16-byte aligned img / target_seg and 4-byte aligned label take 16-byte stores; every other case stores element by element.  No
+ * floating-point atomics: two calls with the same records give the same bits.  cp_render_scenes_host_f32 runs the same code serially on host
+ * pointers and launches nothing: it works without a GPU.  Added in ABI 302 without changing any earlier entry point. */
+size_t cp_render_scenes_record_words(int oc);
+int cp_render_scenes_f32(const double* records, int b, int oc, int H, int W, int noise, float* img, uint8_t* label, float* target_seg,
+                         int32_t* counts, void* stream);
+int cp_render_scenes_host_f32(const double* records, int b, int oc, int H, int W, int noise, float* img, uint8_t* label, float* target_seg,
+                              int32_t* counts);
+
 #ifdef __cplusplus
 }
 #endif

@@ -118,8 +118,14 @@ def main(argv=None):
         from casapose_amd.data_handler.device_pipeline import describe
 
         print("training input: " + describe(train_ds))
-    trainingdata, train_batches = gen(train_ds, **({"device": device} if device_input else {})) if train_ds else (None, 0)
-    testingdata, test_batches = gen(test_ds) if test_ds else (None, 0)
+    # CASAPOSE_DEVICE_SCENES=1: `synthetic` sources are ray-cast on the GPU (data_handler/device_scenes.py); without it nothing changes
+    from casapose_amd.data_handler import device_scenes
+
+    train_scenes, test_scenes = (isinstance(d, SyntheticSceneDataset) and device_scenes.from_environment() for d in (train_ds, test_ds))
+    if train_scenes or test_scenes:
+        print(device_scenes.describe())
+    trainingdata, train_batches = gen(train_ds, **({"device": device} if device_input or train_scenes else {})) if train_ds else (None, 0)
+    testingdata, test_batches = gen(test_ds, **({"device": device} if test_scenes else {})) if test_ds else (None, 0)
     print("training data: {} batches".format(train_batches))
     print("testing data: {} batches".format(test_batches))
 
