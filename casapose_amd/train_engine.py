@@ -304,9 +304,8 @@ class GemmRoute:
     idx_t: torch.Tensor               # [co][ci] -> master [ci][co]
     Uf: torch.Tensor                  # the transposed weights, fp32
     fwd: SplitWeights                 # planes of Uf
-    dgrad: Optional[SplitWeights]     # planes of the master itself (None: the source needs no gradient)
-    wgrad: bool                       # weight gradient on the transposed GEMM (csrc/wino_wgrad_split.hip) into dU
-    dU: Optional[torch.Tensor] = None
+    dgrad: Optional[SplitWeights]     # planes of the master itself (None: no gradient wanted, or a later op of the tape reads the source too)
+    dU: Optional[torch.Tensor] = None   # the weight gradient of the transposed GEMM (csrc/wino_wgrad_split.hip), where Routes.wgrad is gemm_split
 
 
 @dataclass(eq=False)
@@ -326,6 +325,17 @@ class WinoGemm:
     wdesc: Optional[ConvDesc] = None
     c0: int = 0
     ps: Optional[torch.Tensor] = None
+
+
+@dataclass(frozen=True)
+class Routes:
+    """The kernel family of every launch of a ConvOp, decided once (ConvOp.routes): constants of a finished plan -- shapes, pointers, leading
+    dimensions, alignment, the tape order and the environment switches as they stood when the plan was built.  The ARITHMETIC of a family (fp16
+    pair / exact split / exponents) moves at run time and stays in the SplitWeights / BwdSlot records.  dgrad has one entry per source; head_bn:
+    pre_bn's backward recomputes the head's data gradient and the op launches nothing."""
+    forward: str                        # gemm / wino / head_record / head_affine / head / stem_split / split / f32
+    wgrad: str                          # head_affine / head / gemm_split / wino_split / wino_f32 / direct_split / f32
+    dgrad: Tuple[Optional[str], ...]    # per source: None (no gradient wanted) / head_bn / head / gemm / deep / wino / split / f32
 
 
 class TrainConv:
@@ -495,7 +505,7 @@ class ConvOp:
         self.wino_dgrad: Dict[int, WinoGemm] = {}
         self._wV = self._wM = None                    # the plan's shared Winograd scratch (bind_winograd)
         self._cin = sum(s[1] for s in layer.sources)
-        self._stem_fwd = self._split_fwd = None       # the forward's applicability probes, asked once (forward_route)
+        self._routes: Optional[Routes] = None         # the kernel family of every launch (routes): resolved once, by the plan or on first use
         self.mon_ptr: Optional[int] = None        # the f16x2 forward's monitor slot (TrainPlan._arm_f16x2)
         self.bw16: Optional[BwdSlot] = None   # the direct data / weight gradients' backward slot record (TrainPlan._finish_plan)
         # data-gradient descriptors
@@ -522,12 +532,14 @@ class ConvOp:
             g.out_act_ld = t.c
 
     # ---- 1x1 / stride-1 shortcuts as plain GEMMs on the bf16 matrix pipe -----------------------------------------------------------------
-    def setup_gemm(self):
+    def setup_gemm(self, first_writer: bool = True):
         """The stage shortcuts with stride 1 (resnet.py:214-220 at output stride 8: stage 1, 3 and 4) are GEMMs rows x cin x cout.  In the conv modes
         `split` / `bf16` the forward and the data gradient run on the bf16-pipe GEMM of the Winograd path (csrc/wino_gemm_split.hip: exact
         three-way splits, or hi + mid planes in the bf16 mode) and, where cin and cout are multiples of 128, the weight gradient on its
         transposed partner (csrc/wino_wgrad_split.hip) -- instead of the fp32-MFMA implicit-GEMM kernel (84 TFLOP/s on the 256 -> 512 shortcut).
-        CASAPOSE_SC_GEMM=0 keeps the fp32 kernels."""
+        CASAPOSE_SC_GEMM=0 keeps the fp32 kernels.  The GEMM data gradient writes without accumulating: it exists only for the FIRST writer of the
+        source's gradient (first_writer: no later op of the tape reads the source; a stand-alone op is the only reader)."""
+        assert self._routes is None, "the routes of %s are resolved" % self.layer.name
         L = self.layer
         planes = self.layer.mode_planes
         if not planes or os.environ.get("CASAPOSE_SC_GEMM", "1") == "0":
@@ -540,18 +552,14 @@ class ConvOp:
                 or self.head_fast or ld_ != L.cout or L.layout != 0 or self.out is None
                 or (self.dy_ptr_ld is not None and (self.dy_ptr_ld[1] != 0 or self.dy_ptr_ld[2] != L.cout))):
             return
-        lib = _lib.load()
         dev = L.master.device
         idx_t = (np.arange(cin, dtype=np.int32)[None, :] * L.cout + np.arange(L.cout, dtype=np.int32)[:, None]).reshape(-1)   # [co][ci] -> master [ci][co]
         exact = 3 if planes == 3 else 2
         Uf = torch.empty(L.cout * cin, dtype=torch.float32, device=dev)
-        g = GemmRoute(rows=rows, cin=cin, idx_t=torch.from_numpy(idx_t).to(dev), Uf=Uf,
-                      fwd=SplitWeights(Uf, _lib.PLANES_F16X2 if L.fwd_f16x2 else exact, (1, L.cout, cin)),   # U[co][ci] = W[ci][co]
-                      dgrad=SplitWeights(L.master, exact, (1, cin, L.cout)) if L.dgrad[0] is not None else None,   # U[ci][co]: the master itself
-                      wgrad=bool(lib.cp_wino_wgrad_split_applicable(1, rows, L.cout, cin)) and os.environ.get("CASAPOSE_WINO_WGRAD", "split") != "f32")
-        if g.wgrad:
-            g.dU = torch.empty(L.cout * cin, dtype=torch.float32, device=dev)
-        self.gemm = g
+        self.gemm = GemmRoute(rows=rows, cin=cin, idx_t=torch.from_numpy(idx_t).to(dev), Uf=Uf,
+                              fwd=SplitWeights(Uf, _lib.PLANES_F16X2 if L.fwd_f16x2 else exact, (1, L.cout, cin)),   # U[co][ci] = W[ci][co]
+                              # U[ci][co]: the master itself
+                              dgrad=SplitWeights(L.master, exact, (1, cin, L.cout)) if L.dgrad[0] is not None and first_writer else None)
         L.refresh_hooks.append(self._refresh_gemm)
 
     def _refresh_gemm(self, stream: int):
@@ -567,6 +575,7 @@ class ConvOp:
         scratch sizes (floats of V, floats of M) they need; bind_winograd() completes the descriptors."""
         from .engine import TRAIN_WINO_GEMM_SPLIT, WinoConv, wino_eligible
 
+        assert self._routes is None, "the routes of %s are resolved" % self.layer.name
         L = self.layer
         nv = nm = 0
         if L.k != 3 or self.stride != 1 or self.pad != self.dil or self.tap_label is not None or L.layout != 0:
@@ -639,24 +648,13 @@ class ConvOp:
         """the direct weight gradient on fp16 pairs: dY inside the band (the switch its data gradient uses) and X too (the forward still f16x2)"""
         return self.bw16 is not None and self.bw16.on and not self.bw16.dead and self.layer.fwd_f16x2
 
-    def _direct_dgrad_splits(self) -> List[SplitWeights]:
-        """the data gradients that run on conv_hsplit as an exact three-way split or as the fp16 pair (not a Winograd / deep-bf16 route)"""
-        return [ent.split for s, ent in enumerate(self.layer.dgrad) if ent is not None and ent.split is not None and not ent.deep
-                and s not in self.wino_dgrad and ent.split.arith in (3, _lib.PLANES_F16X2)]
-
-    def direct_dgrad_split(self) -> bool:
-        """True when this op has a data gradient that runs on conv_hsplit as an exact three-way split and may move to the fp16 pair
-        (train_bwd_f16x2): 3x3 / stride 1 / no dilation, not a Winograd / deep-bf16 / 1x1-GEMM route"""
-        L = self.layer
-        if not (train_bwd_f16x2() and L.mode_planes == 3 and L.k == 3 and self.stride == 1 and self.dil == 1) or self.gemm is not None:
-            return False
-        return bool(self._direct_dgrad_splits())
-
     def set_direct_dgrad_f16x2(self, on: bool, stream: int):
-        """the direct data gradients of this op on the fp16 two-way split (weights x 2^k re-packed as two fp16 planes) or back on the exact split"""
+        """the data gradients of this op on conv_hsplit (route split) on the fp16 two-way split (weights x 2^k re-packed as two fp16 planes) or back on
+        the exact split"""
         self.bw16.on = on
-        for sp in self._direct_dgrad_splits():
-            sp.set_arith(_lib.PLANES_F16X2 if on else 3)
+        for s, route in enumerate(self.routes.dgrad):
+            if route == "split":
+                self.layer.dgrad[s].split.set_arith(_lib.PLANES_F16X2 if on else 3)
         self.layer._refresh_split(stream)
 
     def set_dgrad_exponent(self, w: WinoGemm, e: Optional[int], stream: int):
@@ -727,39 +725,69 @@ class ConvOp:
                                                      None, 0, out_ptr, w.cout, None, w.cout, stats, stream),
               "cp_wino_output_transform_stats_f32(%s)" % self.layer.name)
 
-    # ---- which kernel family a launch takes: asked by the launch and by the accounting alike ------------------------------------------------
-    def forward_route(self) -> str:
-        """gemm / wino / head_record / head_affine / head / stem_split / split / f32"""
-        if self.gemm is not None:
-            return "gemm"
-        if self.wino_fwd is not None:
-            return "wino"
-        if self.head_fast:
-            return "head" if self.pre_bn is None else ("head_affine" if self.record_prefix is None else "head_record")
-        L = self.layer
-        if L.split is not None and L.k == 7:
-            if self._stem_fwd is None:   # stride 2 / pad 3 / one 4-channel source: the range of the stem kernels
-                self._stem_fwd = _lib.load().cp_conv_selected_tile(C.byref(L.desc)) == _lib.TILE_STEM
-            return "stem_split" if self._stem_fwd else "f32"
-        if L.split is not None:
-            if self._split_fwd is None:
-                self._split_fwd = bool(_lib.load().cp_conv_split_applicable(C.byref(L.desc)))
-            return "split" if self._split_fwd else "f32"
-        return "f32"
+    # ---- which kernel family a launch takes: decided once, read by the launches and by the accounting alike ---------------------------------
+    def __setattr__(self, name, value):
+        assert name not in ("pre_bn", "record_prefix") or getattr(self, "_routes", None) is None, "the routes of %s are resolved" % self.layer.name
+        object.__setattr__(self, name, value)
 
-    def wgrad_route(self) -> str:
-        """head_affine / head / gemm_split / wino_split / wino_f32 / direct_split / f32"""
-        if self.head_fast:
-            return "head" if self.pre_bn is None else "head_affine"
-        if self.gemm is not None and self.gemm.wgrad:
-            return "gemm_split"
-        if self.wino_fwd is not None:
-            return "wino_split" if self.wino_wgrad_split() else "wino_f32"
-        return "direct_split" if self.wgrad_planes() else "f32"
+    @property
+    def routes(self) -> Routes:
+        """TrainPlan._finish_plan resolves every op once its records stand (fused heads, whole records, the 1x1 GEMMs, Winograd and its fused
+        normalisation); a stand-alone op resolves on first use.  setup_gemm, setup_winograd, pre_bn and record_prefix are closed from then on."""
+        if self._routes is None:
+            self._routes = self._resolve_routes()
+        return self._routes
 
-    def wgrad_arith(self, route: str) -> int:
-        """the arithmetic a weight gradient on `route` runs in NOW (a key of PRODUCTS; 0: the fp32 MFMA)"""
-        L = self.layer
+    def _resolve_routes(self) -> Routes:
+        lib, L, g, w = _lib.load(), self.layer, self.gemm, self.wino_fwd
+        head = self.head_fast and ("head" if self.pre_bn is None else "head_affine")
+        if g is not None:
+            fwd = "gemm"
+        elif w is not None:
+            fwd = "wino"
+        elif head:
+            fwd = head if self.record_prefix is None else "head_record"
+        elif L.split is not None and L.k == 7:   # stride 2 / pad 3 / one 4-channel source: the range of the stem kernels
+            fwd = "stem_split" if lib.cp_conv_selected_tile(C.byref(L.desc)) == _lib.TILE_STEM else "f32"
+        else:
+            fwd = "split" if L.split is not None and lib.cp_conv_split_applicable(C.byref(L.desc)) else "f32"
+        # the weight-gradient GEMMs on the bf16 matrix pipe (csrc/wino_wgrad_split.hip: cout and cin multiples of 128) are the default wherever the
+        # forward's GEMM is; CASAPOSE_WINO_WGRAD=f32 keeps the fp32 kernels.  conv_wgrad_split.hip covers 3x3 / stride 1 / pad 1, 32-multiple
+        # sources + optional image, cout % 32 == 0
+        wgemm = os.environ.get("CASAPOSE_WINO_WGRAD", "split") != "f32"
+        if head:
+            wgrad = head
+        elif g is not None and wgemm and lib.cp_wino_wgrad_split_applicable(1, g.rows, L.cout, g.cin):
+            wgrad = "gemm_split"
+            g.dU = torch.empty(L.cout * g.cin, dtype=torch.float32, device=L.master.device)
+        elif w is not None:
+            wgrad = "wino_split" if w.split is not None and wgemm and lib.cp_wino_wgrad_split_applicable(36, w.tp, L.cout, w.ktot) else "wino_f32"
+        else:
+            wgrad = "direct_split" if L.mode_planes and lib.cp_conv_wgrad_split_applicable(C.byref(L.desc)) else "f32"
+        dgrad: List[Optional[str]] = []
+        for s, ent in enumerate(L.dgrad):
+            if ent is None or head:
+                dgrad.append(None if ent is None else "head" if self.pre_bn is None else "head_bn")
+                continue
+            # the descriptor as the launch hands it over, asked once.  The residual (the source's gradient, set by the launch only when another op
+            # has written it) is probed SET, the stricter form with the same answer: it shares pointer and leading dimension with out_raw, and
+            # ent.split exists only for cr % 4 == 0
+            d = ent.desc
+            d.src[0].data, d.src[0].ld = self._dy_at()
+            d.residual = self.srcs[s][0].grad.data_ptr()
+            if g is not None and g.dgrad is not None:
+                dgrad.append("gemm")
+            elif ent.deep and ent.split is not None and lib.cp_conv_bf16_deep_applicable(C.byref(d)):
+                dgrad.append("deep")
+            elif s in self.wino_dgrad:
+                dgrad.append("wino")
+            else:
+                dgrad.append("split" if ent.split is not None and lib.cp_conv_split_applicable(C.byref(d)) else "f32")
+        return Routes(fwd, wgrad, tuple(dgrad))
+
+    def wgrad_arith(self) -> int:
+        """the arithmetic this op's weight gradient runs in NOW (a key of PRODUCTS; 0: the fp32 MFMA)"""
+        L, route = self.layer, self.routes.wgrad
         if route == "gemm_split":
             return 1 if L.mode_planes == 1 else 3   # CASAPOSE_CONV_MODE=bf16 rounds the operands of this GEMM to bf16 like the other weight gradients
         if route == "wino_split":
@@ -774,12 +802,12 @@ class ConvOp:
 
     def forward(self, stream: int):
         """The forward launch(es) of this layer; an f16x2 forward runs armed when the plan has given the op a monitor slot (mon_ptr)."""
-        with armed(self.mon_ptr if self.layer.fwd_f16x2 and self.wino_fwd is None else None):   # (a Winograd forward arms its input transforms)
+        with armed(self.mon_ptr if self.layer.fwd_f16x2 and self.routes.forward != "wino" else None):   # (a Winograd forward arms its input transforms)
             self._forward(stream)
 
     def _forward(self, stream: int):
         lib = _lib.load()
-        L, d, route = self.layer, self.layer.desc, self.forward_route()
+        L, d, route = self.layer, self.layer.desc, self.routes.forward
         px = self.batch * self.out_h * self.out_w
         st_, off, old_ = self._out_ptr_ld
         if route == "gemm":
@@ -824,69 +852,50 @@ class ConvOp:
     def executed_flops(self) -> Dict[str, float]:
         """FLOPs this op's launches EXECUTE per step, by matrix pipe: {"f32": fp32-MFMA FLOPs, "bf16": bf16-MFMA FLOPs} -- a Winograd layer counts
         its grouped GEMMs (36 planes x padded tiles), an arithmetic counts its PRODUCTS per fp32 product; forward + weight gradient + every data
-        gradient.  (bench.py --mode train prices the step against the two pipes' peaks with it.)  The forward and the weight gradient are priced
-        from forward_route / wgrad_route / wgrad_arith and the weight records, the answers their launches read.  The DATA gradient is not: its
-        launch decides per call (a 1x1 GEMM only while the source has no gradient yet, cp_conv_bf16_deep_applicable with the residual set,
-        cp_conv_split_applicable per launch) and is priced here from the records alone, without those fallbacks."""
-        L = self.layer
+        gradient.  (bench.py --mode train prices the step against the two pipes' peaks with it.)  Every launch is priced from routes, wgrad_arith
+        and the weight records: the answers the launches read."""
+        L, r = self.layer, self.routes
         out = {"f32": 0.0, "bf16": 0.0}
         direct = 2.0 * float(self.batch * self.out_h * self.out_w) * L.k * L.k * self._cin * L.cout
 
         def add(sw: Optional[SplitWeights], flops: float):   # a launch reading split weights runs on the bf16 pipe, one without on the fp32 MFMA
             out["f32" if sw is None else "bf16"] += (1.0 if sw is None else sw.products) * flops
 
-        fwd = self.forward_route()
         w = self.wino_fwd
-        gemm = 2.0 * 36 * w.tp * w.ktot * w.cout if w is not None else direct
-        add({"gemm": self.gemm and self.gemm.fwd, "wino": w and w.split, "stem_split": L.split, "split": L.split}.get(fwd), gemm)
-        route = self.wgrad_route()
-        arith = self.wgrad_arith(route)
-        if route == "direct_split":   # conv_wgrad_split.hip takes the 32-multiple sources; the image source stays on the fp32 MFMA
+        gemm = 2.0 * 36 * w.tp * w.ktot * w.cout if r.forward == "wino" else direct
+        add({"gemm": self.gemm and self.gemm.fwd, "wino": w and w.split, "stem_split": L.split, "split": L.split}.get(r.forward), gemm)
+        arith = self.wgrad_arith()
+        if r.wgrad == "direct_split":   # conv_wgrad_split.hip takes the 32-multiple sources; the image source stays on the fp32 MFMA
             big = sum(s[1] for s in L.sources if s[0] != 4)
             out["bf16"] += PRODUCTS[arith] * direct * big / self._cin
             out["f32"] += direct * (self._cin - big) / self._cin
         else:
             out["bf16" if arith else "f32"] += (PRODUCTS[arith] if arith else 1.0) * gemm
-        if self.gemm is not None:
-            if self.gemm.dgrad is not None:
-                add(self.gemm.dgrad, direct)
-            return out
         m_in = float(self.batch * self.in_h * self.in_w)
-        for s, (ent, (cp, cr)) in enumerate(zip(L.dgrad, L.sources)):
-            if ent is None:
+        for s, route in enumerate(r.dgrad):
+            if route is None:
                 continue
-            d = 2.0 * m_in * L.k * L.k * ent.cin * cr
-            if ent.deep and ent.split is not None:
+            ent = L.dgrad[s]
+            d = 2.0 * m_in * L.k * L.k * ent.cin * ent.cout
+            if route == "deep":
                 out["bf16"] += d
-            elif s in self.wino_dgrad:
+            elif route == "wino":
                 w = self.wino_dgrad[s]
                 add(w.split, 2.0 * 36 * w.tp * w.ktot * w.cout)
-            else:
-                add(ent.split if self.stride == 1 and self.dil == 1 and L.k == 3 else None, d)
+            else:   # (the heads' streaming kernels, head_bn's recomputation included, are fp32 like the generic kernel)
+                add({"gemm": self.gemm and self.gemm.dgrad, "split": ent.split}.get(route), d)
         return out
 
-    def wino_wgrad_split(self) -> bool:
-        """True when this Winograd layer's weight-gradient GEMM runs on the bf16 matrix pipe: the default wherever the Winograd GEMMs do
-        (CASAPOSE_WINO_GEMM != f32) and the shape fits (cout, cin multiples of 128); CASAPOSE_WINO_WGRAD=f32 keeps the fp32 grouped GEMM."""
-        w = self.wino_fwd
-        if w is None or w.split is None or os.environ.get("CASAPOSE_WINO_WGRAD", "split") == "f32":
-            return False
-        return bool(_lib.load().cp_wino_wgrad_split_applicable(36, w.tp, self.layer.cout, w.ktot))
-
-    def wgrad_planes(self) -> int:
-        """3 / 1 when this op's weight gradient runs on the bf16 matrix pipe (CASAPOSE_CONV_MODE split / bf16 and a descriptor that
-        cp_conv2d_wgrad_split covers: 3x3 / stride 1 / pad 1, 32-multiple sources + optional image, cout % 32 == 0), else 0 = fp32 MFMA."""
-        planes = self.layer.mode_planes
-        if not planes or self.wino_fwd is not None:
-            return 0
-        return planes if _lib.load().cp_conv_wgrad_split_applicable(C.byref(self.layer.desc)) else 0
-
-    def _dy(self):
+    def _dy_at(self) -> Tuple[int, int]:
+        """(address, leading dimension) of the output's gradient: a constant of the plan"""
         if self.dy_ptr_ld is not None:
             st, off, ld = self.dy_ptr_ld
             return st.data_ptr() + 4 * off, ld
-        assert self.out.has_grad, "gradient of %s not produced" % self.layer.name
         return self.out.grad.data_ptr(), self.out.c
+
+    def _dy(self):
+        assert self.dy_ptr_ld is not None or self.out.has_grad, "gradient of %s not produced" % self.layer.name
+        return self._dy_at()
 
     def backward(self, stream: int):
         """weight gradient, then the data gradient of every source"""
@@ -900,7 +909,7 @@ class ConvOp:
         d = L.desc  # one op per layer: filled by this op's constructor
         acc = 1 if self.accumulate_master else 0
         px = self.batch * self.out_h * self.out_w
-        route = self.wgrad_route()
+        route = self.routes.wgrad
         if route == "head_affine":   # the activated input is recomputed from the raw tensor
             bn = self.pre_bn
             check(lib.cp_head1x1_wgrad_affine_f32(bn.x.data.data_ptr(), bn.x.c, bn.scale.data_ptr(), bn.shift.data_ptr(), _ptr(bn.labels), bn.classes, bn.act,
@@ -911,7 +920,7 @@ class ConvOp:
         elif route == "gemm_split":
             # dU[co][ci] = sum_rows dY[row][co] A[row][ci] on the bf16 pipe, then through the transpose map into the master gradient [ci][co]
             g = self.gemm
-            check(lib.cp_wino_wgrad_split_f32(dy, self.srcs[0][0].data.data_ptr(), g.dU.data_ptr(), 1, g.rows, L.cout, g.cin, self.wgrad_arith(route), stream),
+            check(lib.cp_wino_wgrad_split_f32(dy, self.srcs[0][0].data.data_ptr(), g.dU.data_ptr(), 1, g.rows, L.cout, g.cin, self.wgrad_arith(), stream),
                   "cp_wino_wgrad_split_f32(%s)" % L.name)
             check(lib.cp_scatter_f32(g.dU.data_ptr(), g.idx_t.data_ptr(), g.idx_t.numel(), L.master_grad.data_ptr(), acc, stream), "cp_scatter_f32(%s)" % L.name)
         elif route in ("wino_split", "wino_f32"):
@@ -922,7 +931,7 @@ class ConvOp:
             with armed(f.mon if f is not None and not f.dead else None):   # the transform reports max |dM|
                 check(lib.cp_wino_dy_transform_f32(dy, dy_ld, cout, self.batch, self.in_h, self.in_w, self.dil, self._wM.data_ptr(), stream),
                       "cp_wino_dy_transform_f32(%s)" % L.name)
-            arith = self.wgrad_arith(route)
+            arith = self.wgrad_arith()
             if arith == _lib.PLANES_F16X2:   # the grouped GEMM dU[p] = dM[p]^T V[p] on the 2-byte pipe (csrc/wino_wgrad_split.hip): fp16 pairs, dM x 2^e
                 check(lib.cp_wino_wgrad_split_scaled_f32(self._wM.data_ptr(), w.V.data_ptr(), w.dU.data_ptr(), 36, w.tp, cout, w.ktot, arith, 2.0 ** f.e, 1.0, stream),
                       "cp_wino_wgrad_split_scaled_f32(%s)" % L.name)
@@ -938,7 +947,7 @@ class ConvOp:
                 c0 += cr
                 k0 += cp_
         else:
-            arith = self.wgrad_arith(route)
+            arith = self.wgrad_arith()
             if arith:   # bf16 matrix pipe (csrc/conv_wgrad_split.hip): same packed result
                 with armed(self.bw16.mon if arith == _lib.PLANES_F16X2 else None):   # (the fp16 pair: dY's overflow guard, every step)
                     check(lib.cp_conv2d_wgrad_split(C.byref(d), dy, dy_ld, L.dwp.data_ptr(), 0, arith, stream), "cp_conv2d_wgrad_split(%s)" % L.name)
@@ -950,55 +959,38 @@ class ConvOp:
         lib = _lib.load()
         L = self.layer
         dy, dy_ld = self._dy()
-        if self.head_fast and self.pre_bn is not None:
-            return   # pre_bn's backward recomputes this head's data gradient inside its two passes (cp_head1x1_bn_bwd_*)
-        if self.head_fast:
-            t, ld = self.srcs[0]
-            px = self.batch * self.out_h * self.out_w
-            readable = (self.dy_ptr_ld[2] - self.dy_ptr_ld[1] % self.dy_ptr_ld[2]) if self.dy_ptr_ld is not None else self.out.c
-            if t.needs_grad:
-                check(lib.cp_head1x1_dgrad_f32(dy, dy_ld, min(32, readable), px, L.master.data_ptr(), L.cout, t.grad.data_ptr(), t.c, 1 if t.has_grad else 0, stream),
-                      "cp_head1x1_dgrad_f32(%s)" % L.name)
-                t.has_grad = True
-            return
-        for s, ent in enumerate(L.dgrad):
-            if ent is None:
+        for s, route in enumerate(self.routes.dgrad):
+            if route is None or route == "head_bn":   # (pre_bn's backward recomputes the head's data gradient inside its two passes, cp_head1x1_bn_bwd_*)
                 continue
-            t, _ = self.srcs[s]
-            if self.gemm is not None and self.gemm.dgrad is not None and not t.has_grad:
-                # dA[row][ci] = sum_co dY[row][co] W[ci][co]; the GEMM writes (no accumulation): the plan runs this op's backward BEFORE the
-                # other consumers of its input (TrainPlan puts the shortcut after conv1 in the tape), which then accumulate into it
+            ent, (t, _) = L.dgrad[s], self.srcs[s]
+            if route == "head":
+                readable = (self.dy_ptr_ld[2] - self.dy_ptr_ld[1] % self.dy_ptr_ld[2]) if self.dy_ptr_ld is not None else self.out.c
+                check(lib.cp_head1x1_dgrad_f32(dy, dy_ld, min(32, readable), self.batch * self.out_h * self.out_w, L.master.data_ptr(), L.cout,
+                                               t.grad.data_ptr(), t.c, 1 if t.has_grad else 0, stream), "cp_head1x1_dgrad_f32(%s)" % L.name)
+            elif route == "gemm":
+                # dA[row][ci] = sum_co dY[row][co] W[ci][co]; the GEMM writes (no accumulation): no later op of the tape reads this source
+                # (setup_gemm's first_writer), so this backward runs BEFORE the other consumers of its input, which then accumulate into it
+                assert not t.has_grad, "the GEMM data gradient of %s is not the first writer of its source's gradient" % L.name
                 g = self.gemm
                 check(lib.cp_wino_gemm_split_planes_f32(dy, g.dgrad.planes.data_ptr(), t.grad.data_ptr(), g.rows, g.rows, L.cout, g.cin, g.dgrad.arith, stream),
                       "cp_wino_gemm_split_planes_f32(dgrad %s)" % L.name)
-                t.has_grad = True
-                continue
-            if ent.deep and ent.split is not None:
-                g = ent.desc
-                g.src[0].data, g.src[0].ld = dy, dy_ld
-                g.residual = t.grad.data_ptr() if t.has_grad else None
-                if lib.cp_conv_bf16_deep_applicable(C.byref(g)):
-                    check(lib.cp_conv2d_fwd_bf16_deep(C.byref(g), ent.split.planes.data_ptr(), stream), "dgrad bf16 deep(%s)" % L.name)
-                    t.has_grad = True
-                    continue
-            if s in self.wino_dgrad:  # stride 1, so the data gradient lives on the forward's input grid
+            elif route == "wino":  # stride 1, so the data gradient lives on the forward's input grid
                 w = self.wino_dgrad[s]
                 f = w.slot
                 pre = {0: (w.ps.data_ptr(), None, _lib.ACT_NONE)} if f is not None and f.e is not None else None   # (a factor only: no shift table)
                 self._wino_run(w, [(dy, dy_ld, L.cout)], t.grad.data_ptr() if t.has_grad else None, t.grad.data_ptr(), stream, pre=pre,
                                mon=f.mon if f is not None and not f.dead else None)
-                t.has_grad = True
-                continue
-            g = ent.desc
-            g.src[0].data, g.src[0].ld = dy, dy_ld
-            g.residual = t.grad.data_ptr() if t.has_grad else None
-            sp = ent.split
-            if sp is not None and lib.cp_conv_split_applicable(C.byref(g)):
-                # the fp16 pair runs armed on every step: max |dY| into the op's backward slot, and its overflow guard
-                with armed(self.bw16.mon if sp.arith == _lib.PLANES_F16X2 and self.bw16 is not None else None):
-                    check(lib.cp_conv2d_fwd_split_scaled(C.byref(g), sp.planes.data_ptr(), None, sp.arith, sp.out_scale, 1.0, stream), "dgrad split(%s)" % L.name)
             else:
-                check(lib.cp_conv2d_fwd_f32(C.byref(g), stream), "dgrad(%s)" % L.name)
+                g, sp = ent.desc, ent.split   # (its source: dY, set when the routes were resolved)
+                g.residual = t.grad.data_ptr() if t.has_grad else None
+                if route == "deep":
+                    check(lib.cp_conv2d_fwd_bf16_deep(C.byref(g), sp.planes.data_ptr(), stream), "dgrad bf16 deep(%s)" % L.name)
+                elif route == "split":
+                    # the fp16 pair runs armed on every step: max |dY| into the op's backward slot, and its overflow guard
+                    with armed(self.bw16.mon if sp.arith == _lib.PLANES_F16X2 and self.bw16 is not None else None):
+                        check(lib.cp_conv2d_fwd_split_scaled(C.byref(g), sp.planes.data_ptr(), None, sp.arith, sp.out_scale, 1.0, stream), "dgrad split(%s)" % L.name)
+                else:
+                    check(lib.cp_conv2d_fwd_f32(C.byref(g), stream), "dgrad(%s)" % L.name)
             t.has_grad = True
         if self.residual is not None:
             add_grad(self.residual, dy, self.out.pixels * self.out.c, stream)
@@ -1120,6 +1112,16 @@ class FnOp:
     def __init__(self, fwd, bwd, reads=()):
         self.forward, self.backward = fwd, bwd
         self.reads = tuple(reads)   # tensors the closure reads (TrainPlan._consumers)
+
+
+def tape_readers(ops: Sequence, t: TT) -> List[int]:
+    """tape indices of the ops that READ tensor t, one per read: convolution sources / residuals, normalisation inputs, the pooling / resampling closures"""
+    def reads(op):
+        if isinstance(op, ConvOp):
+            return [s for s, _ in op.srcs] + [op.residual]
+        return [op.x] if isinstance(op, BnActOp) else list(getattr(op, "reads", ()))
+
+    return [i for i, op in enumerate(ops) for r in reads(op) if r is t]
 
 
 # ------------------------------------------------------------------------------------------------
@@ -1372,9 +1374,9 @@ class TrainPlan:
         self.fuse_norm = fuse == "1"
         if self.fuse_norm:
             self._fuse_heads()
-        for op in self.ops:
-            if isinstance(op, ConvOp):
-                op.setup_gemm()
+        for i, op in enumerate(self.ops):
+            if isinstance(op, ConvOp):   # the backward runs the tape in reverse: a later reader of the source has written its gradient first
+                op.setup_gemm(first_writer=max(tape_readers(self.ops, op.srcs[0][0])) == i)
         # Winograd for the deep 3x3 layers (forward and data gradient); shared scratch sized for the largest of them
         self.use_winograd = os.environ.get("CASAPOSE_NO_WINOGRAD", "0") != "1"
         self.wino_V = self.wino_M = None
@@ -1400,8 +1402,9 @@ class TrainPlan:
         # the backward GEMMs on fp16 pairs (train_bwd_f16x2), one slot each behind the forward's: Winograd data / weight gradients, direct 3x3 layers
         slots = []
         for op in (op for op in self.ops if isinstance(op, ConvOp)):
+            r = op.routes   # resolved here, once: every record the kernel families depend on stands by now
             slots += [w.slot for w in list(op.wino_dgrad.values()) + [op.wino_fwd] if w is not None and w.slot is not None]
-            if op.direct_dgrad_split() or (train_bwd_f16x2() and op.wgrad_planes() == 3):
+            if op.layer.mode_planes == 3 and train_bwd_f16x2() and ("split" in r.dgrad or r.wgrad == "direct_split"):
                 op.bw16 = BwdSlot("direct", op)
                 slots.append(op.bw16)
         for j, r in enumerate(slots):
@@ -1414,17 +1417,8 @@ class TrainPlan:
     _f16x2_mon = property(lambda self: self.monitor and self.monitor.dev)   # the slot words (int32 [4 * slots]) on the device
 
     def _consumers(self, t: TT) -> int:
-        """ops that READ tensor t (convolution sources / residuals, normalisation inputs, the pooling / resampling closures); taps are
-        checked by the caller."""
-        n = 0
-        for op in self.ops:
-            if isinstance(op, ConvOp):
-                n += sum(1 for s, _ in op.srcs if s is t) + (1 if op.residual is t else 0)
-            elif isinstance(op, BnActOp):
-                n += 1 if op.x is t else 0
-            elif isinstance(op, FnOp):
-                n += sum(1 for r in op.reads if r is t)
-        return n
+        """ops that READ tensor t; taps are checked by the caller."""
+        return len(tape_readers(self.ops, t))
 
     def _fuse_heads(self):
         """Blocks 5 / 10 -> head: the normalisation op directly before a streaming 1x1 head whose activated output nobody else reads hands its

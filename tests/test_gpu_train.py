@@ -94,15 +94,27 @@ def test_conv_wgrad_dgrad(device, case):
                 cnt += lp[:, ky:ky + h, kx:kx + w] == (lab + 1)
         pn = (9.0 / cnt).astype(np.float32)
         pn_t = torch.from_numpy(pn).to(device)
-    op = ConvOp(layer, [(t, t.c) for t in tts], (out.data, 0, ldo), b, h, w, stride=stride, dilation=dil, pad=pad, tap_label=lab_t, row_scale=pn_t,
-                out=out, dy_ptr_ld=(out.grad, 0, ldo))
+
+    def conv_op(layer):
+        return ConvOp(layer, [(t, t.c) for t in tts], (out.data, 0, ldo), b, h, w, stride=stride, dilation=dil, pad=pad, tap_label=lab_t, row_scale=pn_t,
+                      out=out, dy_ptr_ld=(out.grad, 0, ldo))
+
+    op = acc_op = conv_op(layer)
     stream = torch.cuda.current_stream(device).cuda_stream
     if "gemm_route" in name:  # what TrainPlan does for the 1x1 / stride-1 shortcuts
         from casapose_amd.train_engine import conv_split_planes
 
         op.setup_gemm()
         if conv_split_planes():   # CASAPOSE_CONV_MODE=f32 keeps these layers on the fp32-MFMA kernels
-            assert op.gemm is not None and op.gemm.wgrad == ("small" not in name and os.environ.get("CASAPOSE_WINO_WGRAD", "split") != "f32")
+            assert op.gemm is not None and op.routes.dgrad == ("gemm",)
+            assert (op.routes.wgrad == "gemm_split") == ("small" not in name and os.environ.get("CASAPOSE_WINO_WGRAD", "split") != "f32")
+            # the GEMM data gradient only writes: where a later op of the tape reads the source too, the plan sets the shortcut up without it
+            # (first_writer=False) and the accumulating fp32 kernel runs -- the op of the accumulation check below
+            layer_acc = TrainConv(store, "L.kernel", 0, k, cout, sources, needs)
+            acc_op = conv_op(layer_acc)
+            acc_op.setup_gemm(first_writer=False)
+            assert acc_op.gemm.dgrad is None and acc_op.routes.dgrad == ("f32",) and acc_op.routes.wgrad == op.routes.wgrad
+            layer_acc.refresh(stream)
         else:
             assert op.gemm is None
     if "winograd" in name:  # what TrainPlan does for the deep layers: Winograd forward + data gradient
@@ -141,7 +153,7 @@ def test_conv_wgrad_dgrad(device, case):
         if t.needs_grad:
             t.grad.fill_(1.0)
             t.has_grad = True
-    op.backward(stream)
+    acc_op.backward(stream)
     torch.cuda.synchronize()
     for t, x64, ng in zip(tts, xr, needs):
         if ng:
@@ -645,11 +657,14 @@ def test_train_forward_backward_bf16_conv_mode_within_its_gates(device, monkeypa
     an output error of 1-2 % of range turns into ~20 % relative L2 on every variable (measured identically with the Winograd GEMMs in fp32,
     `tools/debug/bf16_grad_probe.py`), so they are held to a sanity gate only -- right direction, right size -- while each bf16 kernel has its
     own 2e-2 / 3e-2 parity test (tests/test_gpu_hsplit.py, tests/test_gpu_wgrad_split.py, tests/test_gpu_conv.py)."""
+    from casapose_amd.train_engine import ConvOp
+
     monkeypatch.setenv("CASAPOSE_CONV_MODE", "bf16")
     b, h, w, k = 2, 64, 96, 4
     part, guid = O.VARIANTS["casapose_c_gcu5"]
     params, store, plan, img, lab, kpts = _setup(device, b, h, w, k, partial=part, guided=guid, bilinear=(False,) * 5, sharing={})
-    assert any(getattr(op, "wgrad_planes", lambda: 0)() == 1 for op in plan.ops), "the bf16 weight-gradient kernel is not on the path"
+    assert any(isinstance(op, ConvOp) and op.routes.wgrad == "direct_split" and op.layer.mode_planes == 1 for op in plan.ops), \
+        "the bf16 weight-gradient kernel is not on the path"
     stream = torch.cuda.current_stream(device).cuda_stream
     plan.refresh_weights(stream)
     labd = torch.from_numpy(lab).to(device)
@@ -716,13 +731,16 @@ def test_bf16_conv_mode_converges_like_the_fp32_equivalent_mode(device, monkeypa
     plan's default (exact three-way bf16 splits, fp32-equivalent) and once with CASAPOSE_CONV_MODE=bf16 (operands of the 3x3 layers rounded
     to bf16 in forward, data gradient and weight gradient; Winograd GEMMs on hi + mid planes).  The bf16 run must train: its loss curve stays
     within 3 % (+ 0.01 absolute) of the fp32-equivalent curve at EVERY step (measured: <= 0.4 %) and ends below 60 % of the initial loss."""
+    from casapose_amd.train_engine import ConvOp
+
     b, h, w, k, steps = 4, 64, 64, 4, 30
     curves = {}
     for mode in ("split", "bf16"):
         monkeypatch.setenv("CASAPOSE_CONV_MODE", mode)
         params, store, plan, img, lab, kpts = _setup(device, b, h, w, k, seed=77)
         if mode == "bf16":
-            assert any(getattr(op, "wgrad_planes", lambda: 0)() == 1 for op in plan.ops), "the bf16 kernels are not on the path"
+            assert any(isinstance(op, ConvOp) and op.routes.wgrad == "direct_split" and op.layer.mode_planes == 1 for op in plan.ops), \
+                "the bf16 kernels are not on the path"
         stream = torch.cuda.current_stream(device).cuda_stream
         plan.refresh_weights(stream)
         imgd, labd, kd = torch.from_numpy(img).to(device), torch.from_numpy(lab).to(device), torch.from_numpy(kpts).to(device)
@@ -1367,7 +1385,7 @@ def test_direct_fp16_pair_gradients_of_every_layer_match_fp64(device, monkeypatc
     plan.loss_and_grad(labd, labd, torch.from_numpy(kpts).to(device), 1.0, 0.5, 0.015)
     plan.backward()   # calibrates: the slots are armed
     torch.cuda.synchronize()
-    ops = [op for op in plan.ops if isinstance(op, TE.ConvOp) and getattr(op, "bw16", None) is not None and op.direct_dgrad_split()]
+    ops = [op for op in plan.ops if isinstance(op, TE.ConvOp) and getattr(op, "bw16", None) is not None and "split" in op.routes.dgrad]
     assert len(ops) >= 5 and {32, 64, 128} <= {op.layer.cout for op in ops}, [(op.layer.name, op.layer.cout) for op in ops]
     base = plan._f16x2_mon.data_ptr()
     mon4 = plan._f16x2_mon.view(-1, 4)
@@ -1418,8 +1436,7 @@ def test_direct_fp16_pair_gradients_of_every_layer_match_fp64(device, monkeypatc
             exact = [None if t.grad is None else t.grad.double().cpu().clone() for t, _ in op.srcs]
         c0 = 0
         for s, (ent, (cp_, cr)) in enumerate(zip(L.dgrad, L.sources)):
-            direct = ent is not None and ent.split is not None and not ent.deep and s not in getattr(op, "wino_dgrad", {})
-            if direct:
+            if op.routes.dgrad[s] == "split":
                 g = got[s].reshape(op.batch, op.in_h, op.in_w, -1)[..., :cr]
                 if simple:
                     wt = W[:, :, c0:c0 + cr, :].permute(3, 2, 0, 1).contiguous()   # [cout][cr][ky][kx]
@@ -1432,7 +1449,7 @@ def test_direct_fp16_pair_gradients_of_every_layer_match_fp64(device, monkeypatc
                 worst = max(worst, e)
                 assert e < 1e-5, "%s source %d (cout %d): fp16-pair data gradient %.2e from the %s" % (L.name, s, cout, e, "fp64" if simple else "exact split")
             c0 += cr
-        if op.layer.fwd_f16x2 and op.wgrad_planes() == 3 and getattr(op, "wino_fwd", None) is None and getattr(op, "gemm", None) is None:
+        if op.layer.fwd_f16x2 and op.routes.wgrad == "direct_split":
             gw = run_wgrad(op, True)
             assert op.wgrad_f16x2() and int(mon4[slot, 3]) >= 0, L.name
             gx = run_wgrad(op, False)   # the exact split of the same op
@@ -1535,3 +1552,147 @@ def test_accounting_follows_a_plan_taken_back_to_the_exact_split(device, monkeyp
     assert sets
     for name, sw in sets:
         assert sw.arith == 3 and sw.out_scale == 1.0, (name, sw.arith, sw.out_scale)
+
+
+# route -> the launch labels it stands for (%s: the layer name; "_scaled" dropped from an entry point's name: the same kernel family with a factor)
+_WINO_LABELS = {"cp_wino_input_transform_pre_f32(%s)", "cp_wino_gemm_split_f32(%s)", "cp_wino_output_transform_stats_f32(%s)"}
+ROUTE_LABELS = {
+    "forward": {"gemm": {"cp_wino_gemm_split_f32(%s)"}, "wino": _WINO_LABELS, "head_record": {"cp_head1x1_fwd_affine_record_f32(%s)"},
+                "head_affine": {"cp_head1x1_fwd_affine_f32(%s)"}, "head": {"cp_head1x1_fwd_f32(%s)"}, "stem_split": {"cp_conv2d_fwd_stem_split(%s)"},
+                "split": {"cp_conv2d_fwd_split(%s)"}, "f32": {"cp_conv2d_fwd_f32(%s)"}},
+    "wgrad": {"head_affine": {"cp_head1x1_wgrad_affine_f32(%s)"}, "head": {"cp_head1x1_wgrad_f32(%s)"},
+              "gemm_split": {"cp_wino_wgrad_split_f32(%s)", "cp_scatter_f32(%s)"},
+              "wino_split": {"cp_wino_dy_transform_f32(%s)", "cp_wino_wgrad_split_f32(%s)", "cp_wino_weight_grad_f32(%s)"},
+              "wino_f32": {"cp_wino_dy_transform_f32(%s)", "cp_conv2d_wgrad_f32(wino %s)", "cp_wino_weight_grad_f32(%s)"},
+              "direct_split": {"cp_conv2d_wgrad_split(%s)"}, "f32": {"cp_conv2d_wgrad_f32(%s)"}},
+    "dgrad": {None: set(), "head_bn": set(), "head": {"cp_head1x1_dgrad_f32(%s)"}, "gemm": {"cp_wino_gemm_split_planes_f32(dgrad %s)"},
+              "deep": {"dgrad bf16 deep(%s)"}, "wino": _WINO_LABELS, "split": {"dgrad split(%s)"}, "f32": {"dgrad(%s)"}},
+}
+# the label that counts a data-gradient route's launches (one per source on that route)
+DGRAD_COUNTED = {"head": "cp_head1x1_dgrad_f32(%s)", "gemm": "cp_wino_gemm_split_planes_f32(dgrad %s)", "deep": "dgrad bf16 deep(%s)",
+                 "wino": "cp_wino_output_transform_stats_f32(%s)", "split": "dgrad split(%s)", "f32": "dgrad(%s)"}
+
+ROUTE_SETTINGS = {"default": {}, "split": {"CASAPOSE_TRAIN_FWD": "split", "CASAPOSE_TRAIN_BWD": "split"}, "bf16": {"CASAPOSE_CONV_MODE": "bf16"},
+                  "f32": {"CASAPOSE_CONV_MODE": "f32"}}
+
+# (forward, wgrad, dgrad) -> the layers on it, per setting at b = 2, 96 x 128, K = 4: written down from the launch labels of the commit before
+# ConvOp.routes existed (the route -> label table above read backwards), not from the code under test
+EXPECTED_ROUTES = {
+    "default": {("f32", "f32", ("f32",)): ["stage2_unit1_conv1", "stage2_unit1_sc"],
+         ("gemm", "f32", ("gemm",)): ["stage1_unit1_sc"],
+         ("gemm", "gemm_split", ("f32",)): ["stage3_unit1_sc"],
+         ("gemm", "gemm_split", ("gemm",)): ["stage4_unit1_sc"],
+         ("head_affine", "head_affine", ("head_bn",)): ["pv_final_conv_segmentation", "pv_final_conv_vertex"],
+         ("split", "direct_split", ("split",)): ["pv_block_6_prepare_conv2d", "stage1_unit1_conv1", "stage1_unit1_conv2", "stage1_unit2_conv1",
+                                                 "stage1_unit2_conv2", "stage2_unit1_conv2", "stage2_unit2_conv1", "stage2_unit2_conv2"],
+         ("split", "direct_split", ("split", None)): ["pv_block_10_prepare_conv2d", "pv_block_5_conv2d"],
+         ("split", "direct_split", ("split", "split")): ["pv_block_3_conv2d", "pv_block_4_conv2d", "pv_block_7_prepare_conv2d",
+                                                         "pv_block_8_prepare_conv2d", "pv_block_9_prepare_conv2d"],
+         ("stem_split", "f32", (None,)): ["conv0"],
+         ("wino", "wino_split", ("f32", "f32")): ["pv_block_2_conv2d"],
+         ("wino", "wino_split", ("wino",)): ["pv_block_1_conv2d", "stage3_unit1_conv1", "stage3_unit1_conv2", "stage3_unit2_conv1", "stage3_unit2_conv2",
+                                             "stage4_unit1_conv1", "stage4_unit1_conv2", "stage4_unit2_conv1", "stage4_unit2_conv2"]},
+    "split": {("f32", "f32", ("f32",)): ["stage2_unit1_conv1", "stage2_unit1_sc"],
+         ("f32", "f32", ("wino",)): ["stage3_unit1_conv1"],
+         ("gemm", "f32", ("gemm",)): ["stage1_unit1_sc"],
+         ("gemm", "gemm_split", ("f32",)): ["stage3_unit1_sc"],
+         ("gemm", "gemm_split", ("gemm",)): ["stage4_unit1_sc"],
+         ("head_affine", "head_affine", ("head_bn",)): ["pv_final_conv_segmentation", "pv_final_conv_vertex"],
+         ("split", "direct_split", ("split",)): ["pv_block_6_prepare_conv2d", "stage1_unit1_conv1", "stage1_unit1_conv2", "stage1_unit2_conv1",
+                                                 "stage1_unit2_conv2", "stage2_unit1_conv2", "stage2_unit2_conv1", "stage2_unit2_conv2"],
+         ("split", "direct_split", ("split", None)): ["pv_block_10_prepare_conv2d", "pv_block_5_conv2d"],
+         ("split", "direct_split", ("split", "split")): ["pv_block_3_conv2d", "pv_block_4_conv2d", "pv_block_7_prepare_conv2d",
+                                                         "pv_block_8_prepare_conv2d", "pv_block_9_prepare_conv2d"],
+         ("stem_split", "f32", (None,)): ["conv0"],
+         ("wino", "wino_split", ("f32", "f32")): ["pv_block_2_conv2d"],
+         ("wino", "wino_split", ("wino",)): ["pv_block_1_conv2d", "stage3_unit1_conv2", "stage3_unit2_conv1", "stage3_unit2_conv2", "stage4_unit1_conv1",
+                                             "stage4_unit1_conv2", "stage4_unit2_conv1", "stage4_unit2_conv2"]},
+    "bf16": {("f32", "f32", ("f32",)): ["stage2_unit1_conv1", "stage2_unit1_sc"],
+         ("gemm", "f32", ("gemm",)): ["stage1_unit1_sc"],
+         ("gemm", "gemm_split", ("f32",)): ["stage3_unit1_sc"],
+         ("gemm", "gemm_split", ("gemm",)): ["stage4_unit1_sc"],
+         ("head_affine", "head_affine", ("head_bn",)): ["pv_final_conv_segmentation", "pv_final_conv_vertex"],
+         ("split", "direct_split", ("split",)): ["pv_block_6_prepare_conv2d", "stage1_unit1_conv1", "stage1_unit1_conv2", "stage1_unit2_conv1",
+                                                 "stage1_unit2_conv2", "stage2_unit1_conv2", "stage2_unit2_conv1", "stage2_unit2_conv2"],
+         ("split", "direct_split", ("split", None)): ["pv_block_10_prepare_conv2d", "pv_block_5_conv2d"],
+         ("split", "direct_split", ("split", "split")): ["pv_block_3_conv2d", "pv_block_4_conv2d", "pv_block_7_prepare_conv2d",
+                                                         "pv_block_8_prepare_conv2d", "pv_block_9_prepare_conv2d"],
+         ("stem_split", "f32", (None,)): ["conv0"],
+         ("wino", "wino_split", ("deep",)): ["pv_block_1_conv2d", "stage3_unit1_conv2", "stage3_unit2_conv1", "stage3_unit2_conv2", "stage4_unit1_conv1",
+                                             "stage4_unit1_conv2", "stage4_unit2_conv1", "stage4_unit2_conv2"],
+         ("wino", "wino_split", ("deep", "deep")): ["pv_block_2_conv2d"],
+         ("wino", "wino_split", ("wino",)): ["stage3_unit1_conv1"]},
+    "f32": {("f32", "f32", (None,)): ["conv0"],
+         ("f32", "f32", ("f32",)): ["pv_block_6_prepare_conv2d", "stage1_unit1_conv1", "stage1_unit1_conv2", "stage1_unit1_sc", "stage1_unit2_conv1",
+                                    "stage1_unit2_conv2", "stage2_unit1_conv1", "stage2_unit1_conv2", "stage2_unit1_sc", "stage2_unit2_conv1",
+                                    "stage2_unit2_conv2", "stage3_unit1_sc", "stage4_unit1_sc"],
+         ("f32", "f32", ("f32", "f32")): ["pv_block_3_conv2d", "pv_block_4_conv2d", "pv_block_7_prepare_conv2d", "pv_block_8_prepare_conv2d",
+                                          "pv_block_9_prepare_conv2d"],
+         ("f32", "f32", ("f32", None)): ["pv_block_10_prepare_conv2d", "pv_block_5_conv2d"],
+         ("f32", "f32", ("wino",)): ["stage3_unit1_conv1"],
+         ("head_affine", "head_affine", ("head_bn",)): ["pv_final_conv_segmentation", "pv_final_conv_vertex"],
+         ("wino", "wino_split", ("f32", "f32")): ["pv_block_2_conv2d"],
+         ("wino", "wino_split", ("wino",)): ["pv_block_1_conv2d", "stage3_unit1_conv2", "stage3_unit2_conv1", "stage3_unit2_conv2", "stage4_unit1_conv1",
+                                             "stage4_unit1_conv2", "stage4_unit2_conv1", "stage4_unit2_conv2"]},
+}
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("setting", list(ROUTE_SETTINGS))
+def test_every_launch_takes_the_route_the_plan_resolved(device, monkeypatch, setting):
+    """ConvOp.routes is the one answer to "which kernel family": the launch labels of a step (the kernel entry point and the layer name, collected
+    through train_engine.check) agree with it for the forward, the weight gradient and every source's data gradient of every convolution, in the four
+    arithmetic settings bench.py switches between in one process.  b = 2 at 96 x 128 is the smallest shape at which the 1x1 shortcuts take the GEMM
+    route (output stride 8: 2 * 12 * 16 = 384 rows, a multiple of 128).  A shortcut whose source a later op of the tape reads too (a stage's first
+    unit reads `a`, also a decoder tap: the decoder's backward has written a.grad first) must not be on the GEMM data gradient, which only writes."""
+    from casapose_amd import engine as E
+    from casapose_amd import train_engine as TE
+
+    for v_ in ("CASAPOSE_TRAIN_FWD", "CASAPOSE_TRAIN_BWD", "CASAPOSE_CONV_MODE", "CASAPOSE_WINO_WGRAD", "CASAPOSE_SC_GEMM", "CASAPOSE_HEAD_CONV",
+               "CASAPOSE_BF16_DEEP", "CASAPOSE_STEM_SPLIT", "CASAPOSE_TRAIN_WINO_DILATED_128", "CASAPOSE_FUSE_NORM", "CASAPOSE_NO_WINOGRAD",
+               "CASAPOSE_HEAD_RECORDS"):
+        monkeypatch.delenv(v_, raising=False)
+    monkeypatch.setattr(E, "TRAIN_WINO_GEMM_SPLIT", True)   # (CASAPOSE_WINO_GEMM, read at import)
+    for v_, val in ROUTE_SETTINGS[setting].items():
+        monkeypatch.setenv(v_, val)
+    b, h, w, k = 2, 96, 128, 4
+    params, store, plan, img, lab, kpts = _setup(device, b, h, w, k)
+    labels, real_check = [], TE.check
+
+    def spy(status, what=""):
+        labels.append(what.replace("_scaled", ""))
+        return real_check(status, what)
+
+    monkeypatch.setattr(TE, "check", spy)
+    stream = torch.cuda.current_stream(device).cuda_stream
+    plan.refresh_weights(stream)
+    imgd, labd, kpd = torch.from_numpy(img).to(device), torch.from_numpy(lab).to(device), torch.from_numpy(kpts).to(device)
+    for _ in range(2):
+        del labels[:]
+        plan.train_step(imgd, labd, labd, kpd, 1e-4, cond_labels=labd, weights=(1.0, 0.5, 0.015))
+    torch.cuda.synchronize()
+    cut = labels.index("cp_pose_loss_f32")
+    phases = {"forward": labels[:cut], "backward": labels[cut:]}
+    ops = [(i, op) for i, op in enumerate(plan.ops) if isinstance(op, TE.ConvOp)]
+    assert len({op.layer.name for _, op in ops}) == len(ops)
+    known = {lb for table in ROUTE_LABELS.values() for lbs in table.values() for lb in lbs}
+    got = {}
+    for i, op in ops:
+        name, r = op.layer.name, op.routes
+        named = {t % name for t in known}
+        mine = {ph: [lb for lb in seq if lb in named] for ph, seq in phases.items()}
+        assert set(mine["forward"]) == {t % name for t in ROUTE_LABELS["forward"][r.forward]}, (name, r, mine["forward"])
+        want = set(ROUTE_LABELS["wgrad"][r.wgrad]).union(*[ROUTE_LABELS["dgrad"][d] for d in r.dgrad])
+        assert set(mine["backward"]) == {t % name for t in want}, (name, r, mine["backward"])
+        for route, t in DGRAD_COUNTED.items():   # one launch per source on the route; none for a None / head_bn entry (no label left over above)
+            assert mine["backward"].count(t % name) == r.dgrad.count(route), (name, r, route, mine["backward"])
+        got.setdefault((r.forward, r.wgrad, r.dgrad), []).append(name)
+    # the GEMM data gradient writes without accumulating: never where a later op of the tape reads the shortcut's source too
+    shortcuts = [(i, op) for i, op in ops if op.layer.name.endswith("_sc")]
+    later = [op.layer.name for i, op in shortcuts if max(TE.tape_readers(plan.ops, op.srcs[0][0])) > i]
+    assert len(shortcuts) == 4 and later, later
+    for _, op in shortcuts:
+        assert op.layer.name not in later or op.routes.dgrad[0] != "gemm", (op.layer.name, op.routes)
+    # (CASAPOSE_CONV_MODE=f32 keeps every shortcut on the fp32 kernels)
+    assert setting == "f32" or any(op.routes.dgrad[0] == "gemm" for _, op in shortcuts)
+    assert {key: sorted(names) for key, names in got.items()} == EXPECTED_ROUTES[setting]

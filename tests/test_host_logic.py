@@ -426,3 +426,23 @@ def test_model_registry_equals_the_reference_registry():
         assert mine.models[key].__name__ == cls_name, (key, mine.models[key].__name__, cls_name)
     with pytest.raises(ValueError, match="No such model"):
         mine.get("casapose_does_not_exist")
+
+
+def test_tape_readers_lists_every_read_in_tape_order():
+    """train_engine.tape_readers: the tape indices of the ops reading a tensor -- what TrainPlan uses to count a tensor's consumers and to give the
+    1x1 GEMM data gradient (which writes without accumulating) only to the LAST reader in the tape, the first writer of the backward."""
+    from casapose_amd.train_engine import TT, FnOp, tape_readers
+
+    t, other = TT(torch.zeros(1, 2, 2, 4), name="t"), TT(torch.zeros(1, 2, 2, 4), name="other")
+
+    def op(*reads):
+        return FnOp(lambda stream: None, lambda stream: None, reads=reads)
+
+    me = op(t)
+    for ops, want in (([op(t), me, op(other)], [0, 1]),          # a reader before: this op is still the last reader, the first writer
+                      ([op(other), me, op(t, t)], [1, 2, 2]),    # a reader after (two reads of one op count twice): its gradient is written first
+                      ([op(other), me, op()], [1])):             # no other reader
+        got = tape_readers(ops, t)
+        assert got == want
+        assert (max(got) == ops.index(me)) == (want[-1] == 1)
+    assert tape_readers([op(other)], t) == []
