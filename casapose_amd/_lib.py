@@ -272,6 +272,12 @@ SYMBOLS = [
     ("cp_render_scenes_record_words", C.c_size_t, [_i]),
     ("cp_render_scenes_f32", _i, [_vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp]),
     ("cp_render_scenes_host_f32", _i, [_vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp]),
+    # ---- segmentation masks of BOP frames (csrc/masks.hip) and the host twin ----
+    ("cp_render_masks_workspace_bytes", C.c_size_t, [_i, _i, _i, _i]),
+    ("cp_render_masks_u8", _i, [_vp, _vp, _i, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, C.c_double, C.c_double, C.c_double, _vp, _vp,
+                                _vp, C.c_size_t, _vp]),
+    ("cp_render_masks_host_u8", _i, [_vp, _vp, _i, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, C.c_double, C.c_double, C.c_double, _vp,
+                                     _vp, _vp, C.c_size_t]),
 ]
 
 _lib: Optional[C.CDLL] = None

@@ -125,6 +125,108 @@ def read_vertices(path: str) -> np.ndarray:
         return np.stack([data["x"], data["y"], data["z"]], axis=1).astype(np.float64)
 
 
+_PLY_TYPES = {"float": "<f4", "float32": "<f4", "double": "<f8", "float64": "<f8", "uchar": "u1", "uint8": "u1", "char": "i1", "int8": "i1",
+              "short": "<i2", "int16": "<i2", "ushort": "<u2", "uint16": "<u2", "int": "<i4", "int32": "<i4", "uint": "<u4", "uint32": "<u4"}
+
+
+def _fan(poly) -> List[Tuple[int, int, int]]:
+    return [(poly[0], poly[k], poly[k + 1]) for k in range(1, len(poly) - 1)]
+
+
+def read_faces(path: str) -> np.ndarray:
+    """Triangles [T, 3] int32 of a .ply (ascii or binary_little_endian; `element face` with `property list uchar int|uint vertex_indices` or
+    `vertex_index`) or .obj file (`f` lines, the vertex index before any `/`, 1-based or negative).  Polygons are fan-triangulated; the other
+    properties of a face and every other element are skipped by size.  A file without faces gives [0, 3]."""
+    if path.lower().endswith(".obj"):
+        tris, vertices = [], 0
+        for line in open(path):
+            tok = line.split()
+            if tok and tok[0] == "v":
+                vertices += 1
+            elif tok and tok[0] == "f":
+                idx = [int(t.split("/")[0]) for t in tok[1:]]
+                tris += _fan([i - 1 if i > 0 else vertices + i for i in idx])
+        return np.asarray(tris, np.int32).reshape(-1, 3)
+    if not path.lower().endswith(".ply"):
+        raise ValueError("%s: read_faces reads .ply and .obj files" % path)
+    with open(path, "rb") as f:
+        if f.readline().strip() != b"ply":
+            raise ValueError("%s: not a PLY file" % path)
+        fmt, elements = None, []   # elements: [name, count, [(kind, ...)]] in file order
+        while True:
+            line = f.readline()
+            if not line:
+                raise ValueError("%s: truncated PLY header" % path)
+            tok = line.decode("ascii", "replace").split()
+            if not tok:
+                continue
+            if tok[0] == "format":
+                fmt = tok[1]
+            elif tok[0] == "element":
+                elements.append([tok[1], int(tok[2]), []])
+            elif tok[0] == "property" and elements:
+                if tok[1] == "list":
+                    elements[-1][2].append(("list", tok[2], tok[3], tok[4]))
+                else:
+                    elements[-1][2].append(("scalar", tok[1], tok[2]))
+            elif tok[0] == "end_header":
+                break
+        if fmt not in ("ascii", "binary_little_endian"):
+            raise ValueError("%s: unsupported PLY format %s" % (path, fmt))
+        for _, _, props in elements:
+            for p in props:
+                for t in p[1:-1]:
+                    if t not in _PLY_TYPES:
+                        raise ValueError("%s: unsupported PLY property type %s" % (path, t))
+        tris: List[Tuple[int, int, int]] = []
+        for name, count, props in elements:
+            face = name == "face"
+            if face:
+                lists = [p for p in props if p[0] == "list" and p[3] in ("vertex_indices", "vertex_index")]
+                if len(lists) != 1 or lists[0][1] not in ("uchar", "uint8") or lists[0][2] not in ("int", "int32", "uint", "uint32"):
+                    raise ValueError("%s: element face needs one `property list uchar int|uint vertex_indices|vertex_index`" % path)
+            if fmt == "ascii":
+                for _ in range(count):
+                    row = f.readline().split()
+                    if not face:
+                        continue
+                    at = 0
+                    for p in props:
+                        if p[0] == "scalar":
+                            at += 1
+                            continue
+                        n = int(row[at])
+                        if p[3] in ("vertex_indices", "vertex_index"):
+                            tris += _fan([int(t) for t in row[at + 1:at + 1 + n]])
+                        at += 1 + n
+                continue
+            if all(p[0] == "scalar" for p in props):   # fixed-size rows: skipped (or, never for a face, read) in one step
+                f.seek(count * sum(np.dtype(_PLY_TYPES[p[1]]).itemsize for p in props), 1)
+                continue
+            if face and sum(p[0] == "list" for p in props) == 1:   # all triangles (the common case): one structured read
+                dt = np.dtype([("f%d" % i, _PLY_TYPES[p[1]]) if p[0] == "scalar" else ("tri", [("n", _PLY_TYPES[p[1]]), ("i", _PLY_TYPES[p[2]], (3,))])
+                               for i, p in enumerate(props)])
+                start = f.tell()
+                raw = f.read(count * dt.itemsize)
+                if len(raw) == count * dt.itemsize:
+                    rows = np.frombuffer(raw, dt)["tri"]
+                    if (rows["n"] == 3).all():
+                        tris += [tuple(r) for r in rows["i"].astype(np.int64).tolist()]
+                        continue
+                f.seek(start)
+            for _ in range(count):
+                for p in props:
+                    if p[0] == "scalar":
+                        f.seek(np.dtype(_PLY_TYPES[p[1]]).itemsize, 1)
+                        continue
+                    ct, it = np.dtype(_PLY_TYPES[p[1]]), np.dtype(_PLY_TYPES[p[2]])
+                    n = int(np.frombuffer(f.read(ct.itemsize), ct)[0])
+                    data = f.read(n * it.itemsize)
+                    if face and p[3] in ("vertex_indices", "vertex_index"):
+                        tris += _fan(np.frombuffer(data, it).astype(np.int64).tolist())
+        return np.asarray(tris, np.int32).reshape(-1, 3)
+
+
 def _bbox_corners(v: np.ndarray) -> np.ndarray:
     lo, hi = v.min(0), v.max(0)
     return np.array([[x, y, z] for x in (lo[0], hi[0]) for y in (lo[1], hi[1]) for z in (lo[2], hi[2])], np.float64)

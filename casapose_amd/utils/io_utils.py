@@ -22,6 +22,37 @@ BOP_HEADER = "scene_id,im_id,obj_id,score,R,t,time\n"
 POSE_HEADER = "#r11 r12 r13 r21 r22 r23 r31 r32 r33 tx ty tz\n"
 
 
+def to_json(o, level=0, INDENT=4, SPACE=" ", NEWLINE="\n") -> str:
+    """The reference's JSON text (casapose/utils/io_utils.py:9-51): dicts one key per line, a list on one line unless its LAST element is a
+    list, floats as %.16g, NumPy arrays flattened without spaces.  Nested calls use the default layout, as there."""
+    pad = SPACE * INDENT
+    if isinstance(o, dict):
+        head = (NEWLINE + pad * level if level != 0 else "") + "{" + NEWLINE
+        rows = [pad * (level + 1) + '"' + str(k) + '":' + SPACE + to_json(v, level + 1) for k, v in o.items()]
+        return head + ",\n".join(rows) + NEWLINE + pad * level + "}"
+    if isinstance(o, str):
+        return '"' + o + '"'
+    if isinstance(o, list):
+        parts = [to_json(e, level + 1) for e in o]
+        if not (o and isinstance(o[-1], list)):
+            return "[ " + ", ".join(parts) + " ]"
+        inner = NEWLINE + pad * (level + 1)
+        return "[ " + inner + (", " + inner).join(parts) + NEWLINE + pad * level + " ]"
+    if isinstance(o, bool):
+        return "true" if o else "false"
+    if isinstance(o, int):
+        return str(o)
+    if isinstance(o, float):
+        return "%.16g" % o
+    if isinstance(o, np.ndarray) and np.issubdtype(o.dtype, np.integer):
+        return "[" + ",".join(map(str, o.flatten().tolist())) + "]"
+    if isinstance(o, np.ndarray) and np.issubdtype(o.dtype, np.inexact):
+        return "[" + ",".join("%.16g" % x for x in o.flatten().tolist()) + "]"
+    if o is None:
+        return "null"
+    raise TypeError("Unknown type '%s' for json serialization" % str(type(o)))
+
+
 def _text(x) -> str:
     while isinstance(x, (list, tuple, np.ndarray)):
         x = x[0]

@@ -883,6 +883,38 @@ int cp_render_scenes_f32(const double* records, int b, int oc, int H, int W, int
 int cp_render_scenes_host_f32(const double* records, int b, int oc, int H, int W, int noise, float* img, uint8_t* label, float* target_seg,
                               int32_t* counts);
 
+/* ---- segmentation masks of BOP frames (csrc/masks.hip, csrc/mask_math.h) ----------------------------------------------------------------
+ * The compute step of the dataset converter (data_handler/bop_converter.py, the reference's create_ndds_mask): every instance's mesh
+ * rasterised at its ground-truth pose with a z-buffer, each pixel labelled with its nearest instance, for a batch of frames.
+ *   verts        fp32 [objects][Vmax][3]   vert_counts int32 [objects]   the meshes; an object uses its first vert_counts vertices
+ *   faces        int32 [objects][Tmax][3]  face_counts int32 [objects]   triangles as indices into the object's vertices
+ *   cams         fp64 [frames][4]          fx, fy, cx, cy
+ *   inst_counts  int32 [frames]            instances of the frame, clamped to [0, instances_max]
+ *   inst_obj     int32 [frames][instances_max]      object index     inst_label int32 [frames][instances_max]  label 0..255
+ *   poses        fp64 [frames][instances_max][12]   row-major [3,4] model -> camera
+ *   label        uint8 [frames][H][W]      the label of the nearest instance (lowest index on an exact fp32 tie), 0 where nothing was hit
+ *   records      int32 [frames][instances_max][11]  px_count_all, px_count_visib, bbox_obj (x, y, w, h), bbox_visib (x, y, w, h),
+ *                dropped_triangles; w = xmax - xmin, h = ymax - ymin (the BOP toolkit's boxes), (-1, -1, -1, -1) for an empty pixel set;
+ *                slots at or above the frame's instance count hold an empty record
+ *   workspace    cp_render_masks_workspace_bytes(frames, instances_max, H, W) bytes, 4-byte aligned: one uint32 depth plane per
+ *                (frame, instance); needs no initialisation
+ * The arithmetic is fixed (camera points and depths in fp64 without contraction, vertices snapped to 1/256 pixel, exact int64 edge functions,
+ * closed edges, both windings; pixel (i, j) sampled at (j + sample_offset, i + sample_offset)) and listed in csrc/mask_math.h.  A triangle with a
+ * vertex at Z < near, with a face index outside its object's vertices or projecting beyond 2^20 pixels is dropped whole and counted in
+ * dropped_triangles; an instance whose object index or label is out of range renders nothing.  Integer atomics only: two calls with the same
+ * inputs give the same bytes.  1 <= frames <= 65535, 1 <= instances_max <= 256, H, W <= 16384, 0 < near <= far, 0 <= sample_offset <= 1.
+ * cp_render_masks_workspace_bytes returns 0 for sizes outside these limits.  cp_render_masks_host_u8 runs the same code serially on host
+ * pointers and launches nothing: it works without a GPU.  Added in ABI 302 without changing any earlier entry point. */
+size_t cp_render_masks_workspace_bytes(int frames, int instances_max, int H, int W);
+int cp_render_masks_u8(const float* verts, const int32_t* vert_counts, int Vmax, const int32_t* faces, const int32_t* face_counts, int Tmax,
+                       int objects, const double* cams, const int32_t* inst_counts, const int32_t* inst_obj, const int32_t* inst_label,
+                       const double* poses, int frames, int instances_max, int H, int W, double near, double far, double sample_offset,
+                       uint8_t* label, int32_t* records, void* workspace, size_t workspace_bytes, void* stream);
+int cp_render_masks_host_u8(const float* verts, const int32_t* vert_counts, int Vmax, const int32_t* faces, const int32_t* face_counts, int Tmax,
+                            int objects, const double* cams, const int32_t* inst_counts, const int32_t* inst_obj, const int32_t* inst_label,
+                            const double* poses, int frames, int instances_max, int H, int W, double near, double far, double sample_offset,
+                            uint8_t* label, int32_t* records, void* workspace, size_t workspace_bytes);
+
 #ifdef __cplusplus
 }
 #endif
