@@ -278,6 +278,10 @@ SYMBOLS = [
                                 _vp, C.c_size_t, _vp]),
     ("cp_render_masks_host_u8", _i, [_vp, _vp, _i, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, C.c_double, C.c_double, C.c_double, _vp,
                                      _vp, _vp, C.c_size_t]),
+    # ---- keypoints and models_info of a mesh set (csrc/models.hip) and the host twin ----
+    ("cp_model_prep_workspace_bytes", C.c_size_t, [_i, _ll]),
+    ("cp_model_prep_f32", _i, [_vp, _ll, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, C.c_size_t, _vp]),
+    ("cp_model_prep_host_f32", _i, [_vp, _ll, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, C.c_size_t]),
 ]
 
 _lib: Optional[C.CDLL] = None

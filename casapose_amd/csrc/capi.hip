@@ -120,6 +120,23 @@ extern "C" int cp_device_count(void) {
     return n;
 }
 
+// ---- keypoints and models_info of a mesh set: the kernels, the argument checks and the host twin are models.hip ------------------------------
+extern "C" size_t cp_model_prep_workspace_bytes(int objects, long long total) { return cp::model_prep_workspace_bytes(objects, total); }
+
+extern "C" int cp_model_prep_f32(const float* verts, long long total, const long long* offsets, const int32_t* counts, int objects, int no_points,
+                                 double* diameter_sq, float* box, float* keypoints, int32_t* indices, int32_t* status, void* workspace,
+                                 size_t workspace_bytes, void* stream) {
+    return cp::model_prep_device(verts, total, offsets, counts, objects, no_points, diameter_sq, box, keypoints, indices, status, workspace,
+                                 workspace_bytes, (hipStream_t)stream);
+}
+
+extern "C" int cp_model_prep_host_f32(const float* verts, long long total, const long long* offsets, const int32_t* counts, int objects, int no_points,
+                                      double* diameter_sq, float* box, float* keypoints, int32_t* indices, int32_t* status, void* workspace,
+                                      size_t workspace_bytes) {
+    return cp::model_prep_host(verts, total, offsets, counts, objects, no_points, diameter_sq, box, keypoints, indices, status, workspace,
+                               workspace_bytes);
+}
+
 // ---- matrix-pipe probe -------------------------------------------------------------------------------------------------------------
 // A bare stream of MFMAs on every SIMD (one wave per SIMD, nine accumulators in rotation, no memory traffic): what the part SUSTAINS under
 // its power limit, as opposed to the datasheet peak the roofline entries are priced against.  bench.py times it with HIP events and prints

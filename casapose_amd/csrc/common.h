@@ -149,4 +149,12 @@ __device__ __forceinline__ int head_argmax(const V& a2, int half, int classes) {
 // conv_wgrad.hip: the fp32 weight-gradient kernel over the packed K chunks [first_chunk, ktot / 32) only, accumulating
 int wgrad_f32_chunks(const cp_conv_desc* d, const float* dy, int dy_ld, float* dw_packed, int first_chunk, hipStream_t st);
 
+// models.hip: what cp_model_prep_workspace_bytes, cp_model_prep_f32 and cp_model_prep_host_f32 (capi.hip) forward to
+size_t model_prep_workspace_bytes(int objects, long long total);
+int model_prep_device(const float* verts, long long total, const long long* offsets, const int32_t* counts, int objects, int no_points,
+                      double* diameter_sq, float* box, float* keypoints, int32_t* indices, int32_t* status, void* workspace, size_t workspace_bytes,
+                      hipStream_t st);
+int model_prep_host(const float* verts, long long total, const long long* offsets, const int32_t* counts, int objects, int no_points,
+                    double* diameter_sq, float* box, float* keypoints, int32_t* indices, int32_t* status, void* workspace, size_t workspace_bytes);
+
 }  // namespace cp

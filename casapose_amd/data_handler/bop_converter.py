@@ -6,7 +6,7 @@ create_ndds_mask :64-95).
     generate_data(dataset_path, dataset_path_out, settings, model_folder, model_folder_out, image_folder)
 
 `settings` keeps the reference's keys: near, far, width, height, filetype_in, mask ("reuse" builds NNNNNN.seg.png from mask_visib/, "render"
-renders it, anything else writes none), copy_meshes, draw_debug_image (refused: visualisation is not part of this build).  Three keys are new and
+renders it, anything else writes none), copy_meshes, draw_debug_image (refused: visualisation is not part of this build).  Six keys are new and
 default to the reference's behaviour:
     mask_sample_offset  0.5: where a pixel is sampled, in pixels from its integer coordinate.  0.5 is the reference (pyrender's GL window puts the
                         centre of pixel j at u = j + 0.5 while cx, cy are handed over unchanged); 0.0 is BOP's convention, centres at integers
@@ -14,6 +14,14 @@ default to the reference's behaviour:
                         "render": px_count_all, px_count_visib, visibility (= visib / all, 0 when all = 0), bounding_box and
                         bounding_box_visible from the renderer's records (px_count_valid is omitted); works with mask = "reuse" too
     renderer            "device" (default; needs a GPU, there is no fall-back) or "host", the kernel's serial twin
+    keypoints           "file": obj_NNNNNN_keypoints.ply beside each mesh, as the reference ships them for LM and HomebrewedDB;
+                        "generate": the box centre and farthest-point samples of the mesh vertices (model_prep.py, csrc/models.hip), so that any
+                        BOP dataset or folder of meshes converts; they feed the frame JSONs and, with copy_meshes, are written as
+                        <out>/<name>/<name>_keypoints.ply
+    models_info         "file": <models>/models_info.json must exist and is copied; "generate": diameter, min_* and size_* computed from the
+                        vertices and written, with copy_meshes, as <out>/models_info.json keyed by the mesh's name (what the reader looks up);
+                        an existing entry's other fields (symmetries) are carried over
+    no_points           9: keypoints per object in "generate" mode, the centre included
 
 Differences from the reference, all stated: `cuboid` / `projected_cuboid` come from the axis-aligned box of the mesh vertices (trimesh's
 bounding_box_oriented is not reproducible without trimesh; the reader does not read them); without scene_gt_info.json the reference's
@@ -344,11 +352,69 @@ def load_model_infos(files):
     return model_info, model_info_file
 
 
-def load_models_bop(path, path_root_out, copy_meshes=False):
+def _generate_models_bop(path, path_root_out, copy_meshes, settings):
+    """load_models_bop with settings["keypoints"] or settings["models_info"] = "generate": meshes and keypoint files are paired by name, never by
+    sorted position; what is generated comes from ModelPrep on settings["renderer"] and needs no file; nothing is written under `path`."""
+    from .model_prep import model_prep_for, write_keypoints_ply, write_models_info
+
+    kp_mode, info_mode = settings.get("keypoints", "file"), settings.get("models_info", "file")
+    for key, mode in (("keypoints", kp_mode), ("models_info", info_mode)):
+        if mode not in ("file", "generate"):
+            raise ValueError("settings[%r] must be 'file' or 'generate' (got %r)" % (key, mode))
+    info_file = os.path.join(path, "models_info.json")
+    existing = None
+    if os.path.isfile(info_file):
+        with open(info_file) as f:
+            existing = json.load(f)
+    if info_mode == "file" and not existing:
+        return None
+    files = [a for a in sorted(glob.glob(path + "/*.ply")) if not a.endswith("keypoints.ply")] or sorted(glob.glob(path + "/*.obj"))
+    model_files = {os.path.splitext(os.path.basename(a))[0]: a for a in files}
+    vertices, ids = {}, {}
+    for name, file in model_files.items():
+        digits = re.findall(r"\d+", name)
+        if len(digits) == 0:
+            print("no object id in the name: {}".format(os.path.basename(file)))
+            continue
+        ids[name], vertices[name] = int(digits[0]), read_vertices(file)
+    prepared = model_prep_for(settings.get("renderer", "device")).run(vertices, settings.get("no_points", 9), settings.get("renderer", "device"))
+    meshes = {}
+    for name in ids:
+        print(name)
+        file, v = model_files[name], vertices[name]
+        if kp_mode == "generate":
+            keypoints = prepared[name]["keypoints"].astype(np.float64)
+        else:
+            kp_file = os.path.join(os.path.dirname(file), name + "_keypoints.ply")
+            if not os.path.isfile(kp_file):
+                raise FileNotFoundError("%s: no keypoint file (settings['keypoints'] = 'generate' makes the keypoints from the mesh)" % kp_file)
+            keypoints = read_vertices(kp_file)
+        meshes[ids[name]] = {"name": name, "keypoints": keypoints, "volume": _bbox_corners(v), "volume_size": np.max(keypoints, 0) - np.min(keypoints, 0),
+                             "center": (np.max(keypoints, 0) + np.min(keypoints, 0)) / 2.0, "counter": 0, "fixed_model_transform": np.eye(4),
+                             "id": ids[name], "mesh": {"vertices": v, "faces": read_faces(file), "path": file}}
+        if copy_meshes:
+            path_out = os.path.join(path_root_out, name)
+            os.makedirs(path_out, exist_ok=True)
+            copyfile(file, os.path.join(path_out, name + os.path.splitext(file)[1].lower()))
+            write_keypoints_ply(os.path.join(path_out, name + "_keypoints.ply"), keypoints)
+    if copy_meshes:
+        out_file = os.path.join(path_root_out, "models_info.json")
+        if info_mode == "generate":
+            write_models_info(out_file, {name: prepared[name] for name in ids}, existing)
+        else:
+            print("Copy: " + info_file)
+            copyfile(info_file, out_file)
+    return meshes
+
+
+def load_models_bop(path, path_root_out, copy_meshes=False, settings=None):
     """dataset_converter.py:424-463: {object id: mesh record} of <path>/obj_NNNNNN.ply (else .obj) paired with obj_NNNNNN_keypoints.ply by
-    sorted position; with copy_meshes the reader's <out>/<name>/<name>.ply layout and models_info.json are written."""
+    sorted position; with copy_meshes the reader's <out>/<name>/<name>.ply layout and models_info.json are written.  With
+    settings["keypoints"] or settings["models_info"] = "generate" the missing files are computed from the meshes (_generate_models_bop)."""
     if not os.path.exists(path_root_out):
         os.mkdir(path_root_out)
+    if settings is not None and (settings.get("keypoints", "file") != "file" or settings.get("models_info", "file") != "file"):
+        return _generate_models_bop(path, path_root_out, copy_meshes, settings)
     model_infos, model_info_file = load_model_infos(sorted(glob.glob(path + "/*" + ".json")))
     if len(model_infos) == 0:
         return
@@ -565,7 +631,8 @@ def generate_data(dataset_path, dataset_path_out, settings, model_folder="models
         raise NotImplementedError("draw_debug_image: visualisation is not part of this build")
     if not os.path.exists(dataset_path_out):
         os.makedirs(dataset_path_out)
-    meshes = load_models_bop(os.path.join(dataset_path, model_folder), os.path.join(dataset_path_out, model_folder_out), settings["copy_meshes"])
+    meshes = load_models_bop(os.path.join(dataset_path, model_folder), os.path.join(dataset_path_out, model_folder_out), settings["copy_meshes"],
+                             settings)
     if meshes is None:
         raise FileNotFoundError("no models_info.json under %s" % os.path.join(dataset_path, model_folder))
     settings = dict(settings, _mask_renderer=None)

@@ -915,6 +915,36 @@ int cp_render_masks_host_u8(const float* verts, const int32_t* vert_counts, int 
                             const double* poses, int frames, int instances_max, int H, int W, double near, double far, double sample_offset,
                             uint8_t* label, int32_t* records, void* workspace, size_t workspace_bytes);
 
+/* ---- keypoints and models_info of a mesh set (csrc/models.hip, csrc/model_math.h) --------------------------------------------------------
+ * What the dataset converter needs per object and BOP archives do not hold (data_handler/model_prep.py): the axis-aligned box, the squared
+ * diameter (the largest squared distance over all vertex pairs) and no_points keypoints, the box centre followed by farthest-point samples of
+ * the vertices, for all objects of a model folder in one call.
+ *   verts        fp32 [total][3]           the vertices of all objects, back to back
+ *   offsets      int64 [objects]           first vertex of each object        counts  int32 [objects]  its vertex count N
+ *   diameter_sq  fp64 [objects]            max over pairs of (dx*dx + dy*dy) + dz*dz, differences, products and sums in fp64 without FMA
+ *   box          fp32 [objects][6]         min x, y, z, max x, y, z
+ *   keypoints    fp32 [objects][no_points][3]   keypoint 0 = 0.5 * ((double)min + (double)max) rounded to fp32; keypoint k >= 1 = the vertex
+ *                farthest from the centre and the earlier picks (largest minimum squared distance, lowest index among equals), unchanged
+ *   indices      int32 [objects][no_points - 1] the picked vertices' indices within their object
+ *   status       int32 [objects]           CP_MODEL_OK; CP_MODEL_BAD_COUNT: N outside [1, 2^22] or the vertex range outside [0, total) -- every
+ *                output of the object is zero and none of its vertices is read; CP_MODEL_TOO_FEW_DISTINCT: fewer distinct vertices than
+ *                keypoints -- the picks that could not be made are zero, box and diameter are valid
+ *   workspace    cp_model_prep_workspace_bytes(objects, total) bytes, 8-byte aligned; needs no initialisation
+ * 1 <= objects <= 1024, 2 <= no_points <= 32 (it counts the centre), 0 <= total <= 2^32; cp_model_prep_workspace_bytes returns 0 outside these
+ * limits.  Memory beyond an object's own N is never treated as a point.  Maxima and lowest-index arg-maxima only: two calls with the same inputs
+ * give the same bits.  cp_model_prep_host_f32 runs the same code serially on host pointers and launches nothing: it works without a GPU.
+ * Added in ABI 302 without changing any earlier entry point. */
+#define CP_MODEL_OK 0
+#define CP_MODEL_BAD_COUNT 1
+#define CP_MODEL_TOO_FEW_DISTINCT 2
+size_t cp_model_prep_workspace_bytes(int objects, long long total);
+int cp_model_prep_f32(const float* verts, long long total, const long long* offsets, const int32_t* counts, int objects, int no_points,
+                      double* diameter_sq, float* box, float* keypoints, int32_t* indices, int32_t* status, void* workspace,
+                      size_t workspace_bytes, void* stream);
+int cp_model_prep_host_f32(const float* verts, long long total, const long long* offsets, const int32_t* counts, int objects, int no_points,
+                           double* diameter_sq, float* box, float* keypoints, int32_t* indices, int32_t* status, void* workspace,
+                           size_t workspace_bytes);
+
 #ifdef __cplusplus
 }
 #endif

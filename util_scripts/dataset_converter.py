@@ -11,7 +11,8 @@ and, as a command (the settings the reference's trailing comments mark "ADD to c
 
 --mask reuse builds NNNNNN.seg.png from mask_visib/, --mask render renders it from the meshes on the GPU (--renderer host: on the CPU, the kernel's
 serial twin), --mask none writes no mask.  --gt_info render takes px_count_all, px_count_visib, visibility and both bounding boxes from the
-renderer instead of scene_gt_info.json.  The work is casapose_amd/data_handler/bop_converter.py."""
+renderer instead of scene_gt_info.json.  --keypoints generate and --models_info generate compute obj_NNNNNN_keypoints.ply and models_info.json
+from the meshes (--no_points keypoints, the centre included), for datasets that ship neither.  The work is casapose_amd/data_handler/bop_converter.py."""
 import argparse
 import os
 import sys
@@ -52,9 +53,15 @@ def main(argv=None):
     ap.add_argument("--mask_sample_offset", type=float, default=0.5, help="0.5: the reference's masks; 0.0: BOP's pixel centres at integers")
     ap.add_argument("--renderer", choices=("device", "host"), default="device")
     ap.add_argument("--copy_meshes", action="store_true")
+    ap.add_argument("--keypoints", choices=("file", "generate"), default="file",
+                    help="generate: the box centre and farthest-point samples of each mesh instead of obj_NNNNNN_keypoints.ply")
+    ap.add_argument("--models_info", choices=("file", "generate"), default="file",
+                    help="generate: diameter, min_* and size_* from the vertices instead of an existing models_info.json")
+    ap.add_argument("--no_points", type=int, default=9, help="keypoints per object with --keypoints generate, the centre included")
     a = ap.parse_args(argv)
     settings = dict(near=a.near, far=a.far, width=a.width, height=a.height, filetype_in=a.filetype_in, mask=a.mask, copy_meshes=a.copy_meshes,
-                    draw_debug_image=False, gt_info=a.gt_info, mask_sample_offset=a.mask_sample_offset, renderer=a.renderer)
+                    draw_debug_image=False, gt_info=a.gt_info, mask_sample_offset=a.mask_sample_offset, renderer=a.renderer, keypoints=a.keypoints,
+                    models_info=a.models_info, no_points=a.no_points)
     generate_data(a.dataset_path, a.dataset_path_out, settings, model_folder=a.model_folder, model_folder_out=a.model_folder_out,
                   image_folder=a.image_folder)
 
