@@ -8,6 +8,7 @@ from __future__ import annotations
 
 import ctypes as C
 import os
+import re
 from typing import Optional
 
 # PyTorch-ROCm ships its own libamdhip64; import it FIRST so that our library's dependency on
@@ -123,7 +124,6 @@ class AugImage(C.Structure):
     ]
 
 
-ABI_VERSION = 302  # CP_ABI_VERSION of include/casapose_hip.h
 PLANES_F16X2 = 0x12  # CP_PLANES_F16X2: the fp16 two-way split (three products, fp32-level accuracy)
 
 SRC_DIRECT, SRC_NEAREST_SEL, SRC_BILINEAR_X2, SRC_ZERO_INSERT_X2 = 0, 1, 2, 3
@@ -132,157 +132,78 @@ TILE_AUTO, TILE_128x128, TILE_64x128, TILE_128x64, TILE_128x32, TILE_64x64, TILE
 # host-side selectors (never passed to the library): the bf16-pipe kernel of csrc/conv_hsplit.hip with 3 planes (exact fp32 split) / 1 plane (bf16)
 TILE_SPLIT3, TILE_BF16, TILE_F16X2 = 100, 101, 102
 
-# every symbol include/casapose_hip.h declares: (name, restype, argtypes)
-_vp, _i, _ll, _f = C.c_void_p, C.c_int, C.c_longlong, C.c_float
-SYMBOLS = [
-    ("cp_last_error", C.c_char_p, []),
-    ("cp_version", _i, []),
-    ("cp_conv_desc_size", C.c_size_t, []),
-    ("cp_conv_source_size", C.c_size_t, []),
-    ("cp_device_count", _i, []),
-    ("cp_set_persistent_blocks", _i, [_i]),
-    ("cp_get_persistent_blocks", _i, []),
-    ("cp_mfma_probe_workspace_bytes", C.c_size_t, []),
-    ("cp_mfma_probe", _i, [_i, _i, _vp, C.POINTER(C.c_double), _vp]),
-    ("cp_conv_ktot", _i, [_i, _i, _i, C.POINTER(_i)]),
-    ("cp_conv_pack_weights_host", _i, [_vp, _i, _i, _i, _i, _i, C.POINTER(_i), C.POINTER(_i), _vp]),
-    ("cp_conv_halo_weight_floats", _i, [_i, _i, C.POINTER(_i)]),
-    ("cp_conv_pack_weights_halo_host", _i, [_vp, _i, _i, _i, C.POINTER(_i), C.POINTER(_i), _vp]),
-    ("cp_conv_pack_weights_stem_host", _i, [_vp, _i, _i, _vp]),
-    ("cp_conv_pack_head_weights_host", _i, [_vp, _i, _vp]),
-    ("cp_conv2d_fwd_f32", _i, [C.POINTER(ConvDesc), _vp]),
-    ("cp_conv_selected_tile", _i, [C.POINTER(ConvDesc)]),
-    ("cp_conv_split_applicable", _i, [C.POINTER(ConvDesc)]),
-    ("cp_conv_split_weight_floats", _i, [_i, _i, C.POINTER(_i)]),
-    ("cp_conv_split_weight_bytes", C.c_size_t, [_i, _i, C.POINTER(_i), _i]),
-    ("cp_conv_pack_weights_split_host", _i, [_vp, _i, _i, _i, C.POINTER(_i), C.POINTER(_i), _vp]),
-    ("cp_conv_split_weights_f32", _i, [_vp, _ll, _i, _vp, _vp]),
-    ("cp_conv_pack_head_split_host", _i, [_vp, _i, _vp]),
-    ("cp_conv2d_fwd_split", _i, [C.POINTER(ConvDesc), _vp, _vp, _i, _vp]),
-    ("cp_conv_split_weights_scaled_f32", _i, [_vp, _ll, _i, C.c_float, _vp, _vp]),
-    ("cp_conv2d_fwd_split_scaled", _i, [C.POINTER(ConvDesc), _vp, _vp, _i, C.c_float, C.c_float, _vp]),
-    ("cp_conv_bf16_deep_applicable", _i, [C.POINTER(ConvDesc)]),
-    ("cp_conv2d_fwd_bf16_deep", _i, [C.POINTER(ConvDesc), _vp, _vp]),
-    ("cp_pad_channels_3to4", _i, [_vp, _vp, _ll, _vp]),
-    ("cp_maxpool3x3s2_f32", _i, [_vp, _i, _i, _i, _i, _vp, _vp, _i, _vp, _vp]),
-    ("cp_upsample_bilinear_x2_f32", _i, [_vp, _i, _i, _i, _i, _vp, _vp]),
-    ("cp_guided_upsample_x2_f32", _i, [_vp, _vp, _i, _i, _i, _i, _vp, _vp]),
-    ("cp_mask_to_labels_f32", _i, [_vp, _i, _i, _i, _i, _vp, _vp, _vp]),
-    ("cp_argmax_labels", _i, [_vp, _i, _i, _ll, _vp, _vp]),
-    ("cp_label_pyramid", _i, [_vp, _i, _i, _i, C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_vp), _vp]),
-    ("cp_ls_vote_f32", _i, [_vp, _i, _i, _i, _i, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp]),
-    ("cp_ls_vote_w_f32", _i, [_vp, _i, _i, _i, _i, _vp, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp]),
-    ("cp_ls_vote_workspace_bytes", C.c_size_t, [_i, _i, _i]),
-    ("cp_ccl_filter_labels", _i, [_vp, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp]),
-    ("cp_ccl_workspace_bytes", C.c_size_t, [_i, _i, _i, _i]),
-    ("cp_ransac_vote_f32", _i, [_vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp, _i, _f, _f, _i, _i, _i, _vp, _vp, _vp, _vp]),
-    ("cp_ransac_vote_seeded_f32", _i, [_vp, _vp, _i, _i, _i, _i, _i, _i, _i, C.c_ulonglong, _i, _f, _f, _i, _i, _i, _vp, _vp, _vp, _vp]),
-    ("cp_ransac_workspace_bytes", C.c_size_t, [_i, _i, _i, _i, _i, _i]),
-    ("cp_guided_match_mask", _i, [_vp, _vp, _i, _i, _i, _vp, _vp]),
-    ("cp_guided_bilinear_upsample_x2_f32", _i, [_vp, _vp, _i, _i, _i, _i, _vp, _vp]),
-    ("cp_guided_bilinear_upsample_x2_bwd_f32", _i, [_vp, _i, _vp, _i, _i, _i, _i, _vp, _vp]),
-    ("cp_wino_tiles", _i, [_i, _i, _i, _i, C.POINTER(_i), C.POINTER(_i)]),
-    ("cp_wino_gemm_f32", _i, [_vp, _vp, _vp, _i, _i, _i, _i, _vp]),
-    ("cp_wino_gemm_split_f32", _i, [_vp, _vp, _vp, _i, _i, _i, _i, _vp]),
-    ("cp_wino_gemm_split_planes_f32", _i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _vp]),
-    ("cp_wino_split_weights_bytes", C.c_size_t, [_i, _i, _i]),
-    ("cp_wino_split_weights_f32", _i, [_vp, _i, _i, _i, _vp, _vp]),
-    ("cp_f16x2_weight_scale", C.c_float, [C.c_float]),
-    ("cp_f16x2_monitor_set", _i, [_vp]),
-    ("cp_f16x2_monitor_get", _vp, []),
-    ("cp_f16x2_range_check", _i, [C.c_float, C.c_float, C.c_float, C.POINTER(C.c_float)]),
-    ("cp_amax_f32", _i, [_vp, _ll, _ll, _ll, _vp, _vp]),
-    ("cp_wino_split_weights_scaled_f32", _i, [_vp, _i, _i, _i, _i, C.c_float, _vp, _vp]),
-    ("cp_wino_gemm_split_scaled_f32", _i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, C.c_float, _vp]),
-    ("cp_wino_pack_weights_host", _i, [_vp, _i, _i, _i, _i, _i, _i, _i, _vp]),
-    ("cp_wino_transform_weights_f32", _i, [_vp, _ll, _ll, _ll, _ll, _i, _i, _i, _i, _i, _vp, _vp]),
-    ("cp_wino_dy_transform_f32", _i, [_vp, _i, _i, _i, _i, _i, _i, _vp, _vp]),
-    ("cp_wino_weight_grad_f32", _i, [_vp, _i, _i, _i, _i, _ll, _ll, _ll, _ll, _vp, _i, _vp]),
-    ("cp_wino_wgrad_split_applicable", _i, [_i, _i, _i, _i]),
-    ("cp_wino_wgrad_split_f32", _i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _vp]),
-    ("cp_wino_wgrad_split_scaled_f32", _i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _f, _f, _vp]),
-    ("cp_wino_input_transform_f32", _i, [_vp, _i, _i, _i, _i, _i, _i, _vp, _i, _i, _vp]),
-    ("cp_wino_output_transform_f32", _i, [_vp, _i, _i, _i, _i, _i, _vp, _i, _vp, _vp, _vp, _i, _vp, _i, _vp, _i, _vp]),
-    ("cp_conv_stem_split_weight_floats", _i, []),
-    ("cp_conv_pack_weights_stem_split_host", _i, [_vp, _i, _i, _vp]),
-    ("cp_conv2d_fwd_stem_split", _i, [C.POINTER(ConvDesc), _vp, _i, _vp]),
-    ("cp_conv2d_fwd_stem_split_scaled", _i, [C.POINTER(ConvDesc), _vp, _i, C.c_float, _vp]),
-    ("cp_wino_output_input_applicable", _i, [_i, _i, _i, _i, _i]),
-    ("cp_wino_output_input_transform_f32", _i, [_vp, _i, _i, _i, _i, _i, _vp, _i, _vp, _vp, _i, _vp, _i, _vp, _i, _vp, _i, _i, _vp]),
-    ("cp_wino_output_transform_stats_f32", _i, [_vp, _i, _i, _i, _i, _i, _vp, _i, _vp, _vp, _vp, _i, _vp, _i, _vp, _i, _vp, _vp]),
-    ("cp_wino_input_transform_pre_f32", _i, [_vp, _i, _i, _i, _i, _i, _i, _vp, _i, _i, _vp, _vp, _i, _vp]),
-    # ---- training path ----
-    ("cp_conv2d_wgrad_f32", _i, [C.POINTER(ConvDesc), _vp, _i, _vp, _i, _vp]),
-    ("cp_conv_wgrad_split_applicable", _i, [C.POINTER(ConvDesc)]),
-    ("cp_head1x1_fwd_f32", _i, [_vp, _i, _ll, _vp, _i, _vp, _i, _vp]),
-    ("cp_head1x1_dgrad_f32", _i, [_vp, _i, _i, _ll, _vp, _i, _vp, _i, _i, _vp]),
-    ("cp_head1x1_wgrad_f32", _i, [_vp, _i, _vp, _i, _ll, _i, _vp, _i, _vp]),
-    ("cp_head1x1_fwd_affine_f32", _i, [_vp, _i, _ll, _vp, _vp, _vp, _i, _i, _vp, _i, _vp, _i, _vp]),
-    ("cp_head1x1_fwd_affine_record_f32", _i, [_vp, _i, _ll, _vp, _vp, _vp, _i, _i, _vp, _i, _vp, _i, _i, _vp, _i, _vp]),
-    ("cp_head1x1_wgrad_affine_f32", _i, [_vp, _i, _vp, _vp, _vp, _i, _i, _vp, _i, _ll, _i, _vp, _i, _vp]),
-    ("cp_head1x1_bn_bwd_reduce_f32", _i, [_vp, _i, _vp, _i, _i, _ll, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _vp, _vp, _vp]),
-    ("cp_head1x1_bn_bwd_apply_f32", _i, [_vp, _i, _vp, _i, _i, _ll, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _vp, C.c_double, _vp, _vp, _i, _vp]),
-    ("cp_conv2d_wgrad_split", _i, [C.POINTER(ConvDesc), _vp, _i, _vp, _i, _i, _vp]),
-    ("cp_bn_stats_f32", _i, [_vp, _ll, _i, _i, _vp, _vp]),
-    ("cp_bn_finalize_f32", _i, [_vp, C.c_double, _i, _i, _i, _vp, _vp, _f, _i, _f, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
-    ("cp_bn_param_grads_f32", _i, [_vp, _i, _i, _i, _vp, _vp, _vp]),
-    ("cp_affine_act_f32", _i, [_vp, _ll, _i, _i, _vp, _vp, _vp, _i, _vp, _i, _vp]),
-    ("cp_bn_act_bwd_reduce_f32", _i, [_vp, _i, _vp, _i, _ll, _i, _i, _vp, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp]),
-    ("cp_bn_act_bwd_apply_f32", _i, [_vp, _i, _vp, _i, _ll, _i, _vp, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, C.c_double, _vp, _vp, _i, _i, _vp]),
-    ("cp_maxpool3x3s2_bwd_f32", _i, [_vp, _vp, _i, _i, _i, _i, _vp, _i, _vp]),
-    ("cp_maxpool3x3s2_idx_f32", _i, [_vp, _i, _i, _i, _i, _vp, _vp, _vp]),
-    ("cp_maxpool3x3s2_bwd_idx_f32", _i, [_vp, _vp, _i, _i, _i, _i, _vp, _i, _vp]),
-    ("cp_upsample_bilinear_x2_bwd_f32", _i, [_vp, _i, _i, _i, _i, _i, _vp, _vp]),
-    ("cp_guided_upsample_x2_bwd_f32", _i, [_vp, _i, _vp, _i, _i, _i, _i, _vp, _vp]),
-    ("cp_gather_f32", _i, [_vp, _vp, _ll, _vp, _vp]),
-    ("cp_scatter_f32", _i, [_vp, _vp, _ll, _vp, _i, _vp]),
-    ("cp_axpby_f32", _i, [_vp, _f, _vp, _f, _ll, _vp, _vp]),
-    ("cp_adam_step_f32", _i, [_vp, _vp, _vp, _vp, _ll, _f, _f, _f, _f, _i, _f, _vp]),
-    ("cp_adam_step_masked_f32", _i, [_vp, _vp, _vp, _vp, _ll, _f, _f, _f, _f, _i, _f, _vp, _vp]),
-    ("cp_pose_loss_workspace_bytes", C.c_size_t, [_i, _i, _i]),
-    ("cp_ls_vote_bwd_f32", _i, [_vp, _i, _i, _i, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp]),
-    ("cp_kp_stats_f32", _i, [_vp, _i, _i, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp]),
-    ("cp_kp_reproj_loss_f32", _i, [_vp, _vp, _vp, _vp, _i, _i, _i, _f, _f, _vp, _vp, _vp]),
-    ("cp_pose_loss_sep_workspace_bytes", C.c_size_t, [_i, _i, _i, _i]),
-    ("cp_pose_loss_sep_f32", _i, [_vp, _i, _i, _i, _vp, _vp, _vp, _i, _i, _i, _i, _i, _f, _f, _f, _vp, _vp, _i, _i, _vp, _vp]),
-    ("cp_vector_field_f32", _i, [_vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _vp, _i, _vp]),
-    ("cp_smooth_l1_f32", _i, [_vp, _i, _vp, _i, _vp, _i, _i, _i, _i, _ll, _vp, _vp, _vp]),
-    ("cp_proxy_voting_f32", _i, [_vp, _i, _i, _vp, _vp, _i, _i, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
-    # ---- input pipeline (csrc/augment.hip) ----
-    ("cp_aug_image_size", C.c_size_t, []),
-    ("cp_aug_geometry", _i, [_vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp]),
-    ("cp_aug_photometric", _i, [_vp, _vp, _i, _i, _i, _i, _vp, _vp]),
-    ("cp_aug_resize", _i, [_vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp]),
-    ("cp_aug_channel_sums", _i, [_vp, _i, _ll, _vp, _vp]),
-    ("cp_aug_finish", _i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp]),
-    ("cp_frames_to_input_f32", _i, [_vp, _i, _i, _i, _i, _ll, _ll, _f, _f, _vp, _vp]),
-    ("cp_pose_loss_f32", _i, [_vp, _i, _i, _i, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _f, _f, _f, _vp, _vp, _i, _i, _vp, _vp, _vp]),
-    # ---- pose statistics (csrc/pose_eval.hip) ----
-    ("cp_pose_eval_workspace_bytes", C.c_size_t, [_i, _i, _i]),
-    ("cp_pose_eval_est_tile", _i, []),
-    ("cp_pose_eval_f32", _i, [_vp, _vp, _vp, _i, _i, _vp, _i, _f, _vp, _vp, _vp, _vp, _vp]),
-    # ---- device PnP (csrc/pnp.hip) and its host twin ----
-    ("cp_pnp_f64", _i, [_vp, _vp, _vp, _i, _vp, _vp, _vp, _i, _i, _i, _i, _f, _vp, _vp, _vp, _vp]),
-    ("cp_pnp_host_f64", _i, [_vp, _vp, _vp, _i, _vp, _vp, _vp, _i, _i, _i, _i, _f, _vp, _vp, _vp]),
-    # ---- BPnP keypoint loss (csrc/bpnp.hip) and its host twin ----
-    ("cp_bpnp_loss_workspace_bytes", C.c_size_t, [_i, _i, _i]),
-    ("cp_bpnp_loss_f64", _i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _f, _f, _f, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
-    ("cp_bpnp_loss_host_f64", _i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _f, _f, _f, _vp, _vp, _vp, _vp, _vp, _vp]),
-    # ---- synthetic scenes (csrc/scenes.hip) and the host twin ----
-    ("cp_render_scenes_record_words", C.c_size_t, [_i]),
-    ("cp_render_scenes_f32", _i, [_vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp]),
-    ("cp_render_scenes_host_f32", _i, [_vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp]),
-    # ---- segmentation masks of BOP frames (csrc/masks.hip) and the host twin ----
-    ("cp_render_masks_workspace_bytes", C.c_size_t, [_i, _i, _i, _i]),
-    ("cp_render_masks_u8", _i, [_vp, _vp, _i, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, C.c_double, C.c_double, C.c_double, _vp, _vp,
-                                _vp, C.c_size_t, _vp]),
-    ("cp_render_masks_host_u8", _i, [_vp, _vp, _i, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, C.c_double, C.c_double, C.c_double, _vp,
-                                     _vp, _vp, C.c_size_t]),
-    # ---- keypoints and models_info of a mesh set (csrc/models.hip) and the host twin ----
-    ("cp_model_prep_workspace_bytes", C.c_size_t, [_i, _ll]),
-    ("cp_model_prep_f32", _i, [_vp, _ll, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, C.c_size_t, _vp]),
-    ("cp_model_prep_host_f32", _i, [_vp, _ll, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, C.c_size_t]),
-]
+
+# ---- the binding table, read from include/casapose_hip.h (plain C, ours: a few regular expressions are the whole front end) ----
+HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "casapose_hip.h")
+_SCALARS = {"int": C.c_int, "long long": C.c_longlong, "int64_t": C.c_int64, "unsigned long long": C.c_ulonglong, "uint64_t": C.c_uint64,
+            "float": C.c_float, "double": C.c_double, "size_t": C.c_size_t}
+_POINTEE_ONLY = ("void", "char", "int32_t", "uint8_t", "uint32_t", "cp_conv_desc", "cp_aug_image")
+
+
+def _parse_type(decl: str, where: str, is_return: bool = False):
+    """One return type or parameter of a prototype -> (ctypes type, pointee type or None).  Pointers are c_void_p whatever they point to, except
+    cp_conv_desc* (POINTER(ConvDesc)) and a returned char* (c_char_p); `name[]` is a pointer."""
+    depth = decl.count("*") + decl.count("[]")
+    words = re.sub(r"\*|\[\]|\bconst\b", " ", decl).split()
+    bases = [" ".join(words[:n]) for n in (len(words), len(words) - 1)]   # a parameter may or may not be named
+    base = next((b for b in bases if b in _SCALARS or b in _POINTEE_ONLY), None)
+    if base is None or not all(re.fullmatch(r"\w+", w) for w in words):
+        raise CasaposeHipError("%s: cannot read the type of `%s`" % (where, " ".join(decl.split())))
+    if depth == 0:
+        if base in _SCALARS:
+            return _SCALARS[base], None
+        if base == "void" and is_return:
+            return None, None
+        raise CasaposeHipError("%s: `%s` is passed by value" % (where, " ".join(decl.split())))
+    if (base, depth) == ("cp_conv_desc", 1):
+        return C.POINTER(ConvDesc), base
+    return (C.c_char_p if is_return and (base, depth) == ("char", 1) else C.c_void_p), base + "*" * (depth - 1)
+
+
+def parse_header(text: str):
+    """Every function prototype of a header in the style of include/casapose_hip.h -> (symbols, pointees, return_pointees, twins):
+    symbols [(name, restype, argtypes)] in declaration order; pointees {name: per argument, what a pointer points to ("float", "void",
+    "uint8_t*", ...) or None for a scalar}; return_pointees {name: the same for the return value}; twins {X_T: X_host_T} for T in f32 / f64 /
+    u8 where both are declared -- X_host_T then must take X_T's parameters minus a trailing `void* stream`.  A statement that is no struct, enum
+    or readable prototype raises CasaposeHipError: nothing is skipped."""
+    text = re.sub(r"/\*.*?\*/", " ", text, flags=re.S)
+    text = re.sub(r"//[^\n]*|^[ \t]*#[^\n]*", " ", text, flags=re.M)
+    text = re.sub(r'extern\s+"C"\s*\{(.*)\}', r"\1", text, flags=re.S)
+    text = re.sub(r"\b(typedef\s+)?(struct|enum)\b[^{};]*\{[^{}]*\}[^;]*;", " ", text)
+    symbols, pointees, return_pointees = [], {}, {}
+    for stmt in text.split(";"):
+        stmt = " ".join(stmt.split())
+        if not stmt:
+            continue
+        m = re.fullmatch(r"(?P<ret>[\w\s*]+?)\b(?P<name>\w+) ?\((?P<params>[^()]*)\)", stmt)
+        if m is None:
+            raise CasaposeHipError("cannot read the declaration `%s`" % stmt)
+        name, params = m.group("name"), m.group("params").strip()
+        if name in pointees:
+            raise CasaposeHipError("%s is declared twice" % name)
+        restype, return_pointees[name] = _parse_type(m.group("ret"), name + ", return type", is_return=True)
+        parsed = [] if params in ("", "void") else [_parse_type(p, "%s, parameter %d" % (name, i)) for i, p in enumerate(params.split(","))]
+        symbols.append((name, restype, [t for t, _ in parsed]))
+        pointees[name] = tuple(p for _, p in parsed)
+    twins, argtypes = {}, {n: a for n, _, a in symbols}
+    for host in pointees:
+        m = re.fullmatch(r"(\w+)_host_(f32|f64|u8)", host)
+        device = m and "%s_%s" % m.groups()
+        if device in pointees:
+            if argtypes[device] != argtypes[host] + [C.c_void_p] or pointees[device] != pointees[host] + ("void",):
+                raise CasaposeHipError("%s must take the parameters of %s minus the trailing `void* stream`" % (host, device))
+            twins[device] = host
+    return symbols, pointees, return_pointees, twins
+
+
+with open(HEADER_PATH) as _f:
+    _header = _f.read()
+_m = re.search(r"^#define CP_ABI_VERSION (\d+)", _header, flags=re.M)
+if _m is None:
+    raise CasaposeHipError("%s does not define CP_ABI_VERSION" % HEADER_PATH)
+ABI_VERSION = int(_m.group(1))
+# every symbol the header declares: (name, restype, argtypes); what each pointer points to; the kernels that have a host twin
+SYMBOLS, POINTEES, RETURN_POINTEES, TWINS = parse_header(_header)
 
 _lib: Optional[C.CDLL] = None
 

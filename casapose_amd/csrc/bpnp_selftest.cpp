@@ -11,6 +11,7 @@
 #include <vector>
 
 #include "bpnp_math.h"
+#include "selftest.h"
 
 using namespace cp_pnp;
 
@@ -26,15 +27,6 @@ static double normal() { return std::sqrt(-2.0 * std::log(1.0 - uniform())) * st
 
 static const float K[9] = {572.4114f, 0.f, 325.2611f, 0.f, 573.57043f, 242.04899f, 0.f, 0.f, 1.f};
 static const float IDENTITY[6] = {1.f, 0.f, 0.f, 0.f, 1.f, 0.f};
-static int failures = 0;
-#define EXPECT(cond, ...)                    \
-    do {                                     \
-        if (!(cond)) {                       \
-            ++failures;                      \
-            std::printf("FAIL: " __VA_ARGS__); \
-            std::printf("\n");               \
-        }                                    \
-    } while (0)
 
 struct Pair {
     int n;
@@ -195,10 +187,5 @@ int main() {
             }
         EXPECT(largest > 0.0 && worst < 2e-2 * largest, "affine: gradient differs from central differences by %.3g of %.3g", worst, largest);
     }
-    if (failures) {
-        std::printf("bpnp_selftest: %d failure(s)\n", failures);
-        return 1;
-    }
-    std::printf("bpnp_selftest: ok (%d pairs: kp 5, 9 and 16, outliers, an unavailable pair, a collapsed vote, a NaN keypoint, a crop affine with central differences)\n", cases);
-    return 0;
+    SELFTEST_END("bpnp_selftest", "%d pairs: kp 5, 9 and 16, outliers, an unavailable pair, a collapsed vote, a NaN keypoint, a crop affine with central differences", cases);
 }

@@ -8,18 +8,10 @@
 #include <vector>
 
 #include "mask_math.h"
+#include "selftest.h"
 
 using namespace cp_mask;
 
-static int failures = 0;
-#define EXPECT(cond, ...)                    \
-    do {                                     \
-        if (!(cond)) {                       \
-            ++failures;                      \
-            std::printf("FAIL: " __VA_ARGS__); \
-            std::printf("\n");               \
-        }                                    \
-    } while (0)
 
 static const double F = 100.0;   // focal length; the principal point is given per case
 
@@ -159,10 +151,5 @@ int main() {
         EXPECT(s.rec(0, 0)[R_ALL] == 9 * 13 && s.rec(0, 0)[R_BOX_OBJ + 2] == 12 && s.rec(0, 1)[R_ALL] == 0 && s.rec(0, 1)[R_DROPPED] == 4, "full frame: %d pixels, %d dropped",
                s.rec(0, 0)[R_ALL], s.rec(0, 1)[R_DROPPED]);
     }
-    if (failures) {
-        std::printf("masks_selftest: %d failure(s)\n", failures);
-        return 1;
-    }
-    std::printf("masks_selftest: ok (%d scenes: a degenerate triangle, zero instances, a vertex behind the camera, an odd width, label 255)\n", cases);
-    return 0;
+    SELFTEST_END("masks_selftest", "%d scenes: a degenerate triangle, zero instances, a vertex behind the camera, an odd width, label 255", cases);
 }

@@ -9,18 +9,10 @@
 #include <vector>
 
 #include "model_math.h"
+#include "selftest.h"
 
 using namespace cp_model;
 
-static int failures = 0;
-#define EXPECT(cond, ...)                    \
-    do {                                     \
-        if (!(cond)) {                       \
-            ++failures;                      \
-            std::printf("FAIL: " __VA_ARGS__); \
-            std::printf("\n");               \
-        }                                    \
-    } while (0)
 
 static uint32_t rng_state = 12345u;
 static float rnd() {   // a small LCG: values in [950, 1050), far from the zeros a padded vertex would hold
@@ -166,10 +158,5 @@ int main() {
         check_object("identical", v.data(), 40, 9, o, 0);
         EXPECT(o.status[0] == ST_TOO_FEW && o.diam[0] == 0.0 && o.kps[0] == 1000.f && o.kps[3] == 0.f, "identical vertices: status %d", o.status[0]);
     }
-    if (failures) {
-        std::printf("%d failures\n", failures);
-        return 1;
-    }
-    std::printf("models_selftest ok\n");
-    return 0;
+    SELFTEST_END("models_selftest", "the pair <-> tile map, sizes around the tile, four objects of mixed sizes with an invalid one, a cube, identical vertices");
 }

@@ -9,6 +9,7 @@
 #include <vector>
 
 #include "pnp_math.h"
+#include "selftest.h"
 
 using namespace cp_pnp;
 
@@ -23,15 +24,6 @@ static double uniform(double a, double b) { return a + (b - a) * uniform(); }
 static double normal() { return std::sqrt(-2.0 * std::log(1.0 - uniform())) * std::cos(6.283185307179586 * uniform()); }
 
 static const float K[9] = {572.4114f, 0.f, 325.2611f, 0.f, 573.57043f, 242.04899f, 0.f, 0.f, 1.f};
-static int failures = 0;
-#define EXPECT(cond, ...)                    \
-    do {                                     \
-        if (!(cond)) {                       \
-            ++failures;                      \
-            std::printf("FAIL: " __VA_ARGS__); \
-            std::printf("\n");               \
-        }                                    \
-    } while (0)
 
 struct Case {
     float xy[18], xyz[27];
@@ -129,10 +121,5 @@ int main() {
         for (int i = 0; i < 12; ++i) d = std::fmax(d, std::fabs(pose[i] - ref[i]) / std::fmax(1.0, std::fabs(ref[i])));
         EXPECT(info[0] == OK && d <= 1e-5, "affine: status %d, relative pose difference %.3g", info[0], d);
     }
-    if (failures) {
-        std::printf("pnp_selftest: %d failure(s)\n", failures);
-        return 1;
-    }
-    std::printf("pnp_selftest: ok (8 noise-free, 18 noisy / outlier, 3 bounded-failure cases, 1 affine case; %d hypotheses each)\n", H);
-    return 0;
+    SELFTEST_END("pnp_selftest", "8 noise-free, 18 noisy / outlier, 3 bounded-failure cases, 1 affine case; %d hypotheses each", H);
 }

@@ -11,19 +11,11 @@
 #include <vector>
 
 #include "scene_math.h"
+#include "selftest.h"
 
 using namespace cp_scene;
 
 static const double FX = 572.4114, FY = 573.57043, CX = 325.2611, CY = 242.04899;
-static int failures = 0;
-#define EXPECT(cond, ...)                    \
-    do {                                     \
-        if (!(cond)) {                       \
-            ++failures;                      \
-            std::printf("FAIL: " __VA_ARGS__); \
-            std::printf("\n");               \
-        }                                    \
-    } while (0)
 
 struct Object {
     double u, v, z, axes[3], colour[3], angle;   // the centre projects to frame pixel (u, v) at depth z
@@ -166,10 +158,5 @@ int main() {
             check_consistent("oc 13, bad count", none, 0);
         }
     }
-    if (failures) {
-        std::printf("scenes_selftest: %d failure(s)\n", failures);
-        return 1;
-    }
-    std::printf("scenes_selftest: ok (%d scenes: an odd width, an object cut by the border, one behind the camera, two overlapping, oc = 1 and 13)\n", cases);
-    return 0;
+    SELFTEST_END("scenes_selftest", "%d scenes: an odd width, an object cut by the border, one behind the camera, two overlapping, oc = 1 and 13", cases);
 }

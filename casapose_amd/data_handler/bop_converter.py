@@ -42,7 +42,7 @@ from typing import Dict, Iterator, List, Optional, Sequence, Tuple
 
 import numpy as np
 
-from .. import _lib
+from .. import _lib, twin
 from ..utils.io_utils import to_json
 from .vectorfield_dataset import _bbox_corners, read_faces, read_vertices
 
@@ -162,40 +162,37 @@ class MaskRenderer:
             raise ValueError("one %d x %d frame with %d instances needs %d bytes of depth planes, the workspace cap is %d" % (H, W, instances_max, one, cap))
         return max(1, min(n, cap // one, 65535))
 
-    # ---- host twin --------------------------------------------------------------------------------
+    # ---- the library call, host twin or device ---------------------------------------------------------
+    def _render(self, mesh, p, n: int, H: int, W: int, near: float, far: float, sample_offset: float, workspace, workspace_bytes: int, device, stream):
+        """cp_render_masks_u8 on `stream` over device tensors, or (device None) its host twin over NumPy arrays: `mesh` = verts, vert_counts,
+        faces, face_counts and `p` = n packed frames, where the call runs -> (labels, records) there"""
+        imax = p["inst_obj"].shape[1]
+        out = twin.alloc(dict(labels=((n, H, W), np.uint8), records=((n, imax, RECORD), np.int32)), device)
+        twin.call("cp_render_masks_u8", mesh[0], mesh[1], self.vmax, mesh[2], mesh[3], self.tmax, len(self.ids), p["cams"], p["inst_counts"],
+                  p["inst_obj"], p["inst_label"], p["poses"], n, imax, H, W, float(near), float(far), float(sample_offset), out["labels"],
+                  out["records"], workspace, workspace_bytes, host=device is None, stream=stream)
+        return out["labels"], out["records"]
+
     def render_host(self, frames: Sequence[dict], height: int, width: int, near: float, far: float, sample_offset: float = 0.5,
                     instances_max: Optional[int] = None):
         p = self.pack(frames, instances_max)
         n, imax = len(frames), p["inst_obj"].shape[1]
-        labels, records = np.empty((n, height, width), np.uint8), np.empty((n, imax, RECORD), np.int32)
         if n == 0:
-            return labels, records
+            return np.empty((n, height, width), np.uint8), np.empty((n, imax, RECORD), np.int32)
         size = int(self.lib.cp_render_masks_workspace_bytes(n, imax, height, width))
-        ws = np.empty(max(size // 4, 1), np.uint32)
-        _lib.check(self.lib.cp_render_masks_host_u8(self.verts.ctypes.data, self.vert_counts.ctypes.data, self.vmax, self.faces.ctypes.data,
-                                                    self.face_counts.ctypes.data, self.tmax, len(self.ids), p["cams"].ctypes.data,
-                                                    p["inst_counts"].ctypes.data, p["inst_obj"].ctypes.data, p["inst_label"].ctypes.data,
-                                                    p["poses"].ctypes.data, n, imax, height, width, float(near), float(far), float(sample_offset),
-                                                    labels.ctypes.data, records.ctypes.data, ws.ctypes.data, size), "cp_render_masks_host_u8")
-        return labels, records
+        return self._render((self.verts, self.vert_counts, self.faces, self.face_counts), p, n, height, width, near, far, sample_offset,
+                            np.empty(max(size // 4, 1), np.uint32), size, None, None)
 
-    # ---- device -----------------------------------------------------------------------------------
     def _launch(self, p: Dict[str, np.ndarray], lo: int, hi: int, H: int, W: int, near: float, far: float, sample_offset: float, workspace):
         """frames [lo, hi) of the packed arrays on the side stream -> (pinned labels, pinned records, event)"""
         import torch
 
-        dev, st, n, imax = self.device, self.stream, hi - lo, p["inst_obj"].shape[1]
+        dev, st = self.device, self.stream
         with torch.cuda.stream(st):
             d = {k: torch.from_numpy(np.ascontiguousarray(a[lo:hi])).pin_memory().to(dev, non_blocking=True) for k, a in p.items()}
-            labels = torch.empty((n, H, W), dtype=torch.uint8, device=dev)
-            records = torch.empty((n, imax, RECORD), dtype=torch.int32, device=dev)
-            _lib.check(self.lib.cp_render_masks_u8(self.d_mesh[0].data_ptr(), self.d_mesh[1].data_ptr(), self.vmax, self.d_mesh[2].data_ptr(),
-                                                   self.d_mesh[3].data_ptr(), self.tmax, len(self.ids), d["cams"].data_ptr(), d["inst_counts"].data_ptr(),
-                                                   d["inst_obj"].data_ptr(), d["inst_label"].data_ptr(), d["poses"].data_ptr(), n, imax, H, W, float(near),
-                                                   float(far), float(sample_offset), labels.data_ptr(), records.data_ptr(), workspace.data_ptr(),
-                                                   workspace.numel(), st.cuda_stream), "cp_render_masks_u8")
-            h_labels = torch.empty((n, H, W), dtype=torch.uint8, pin_memory=True)
-            h_records = torch.empty((n, imax, RECORD), dtype=torch.int32, pin_memory=True)
+            labels, records = self._render(self.d_mesh, d, hi - lo, H, W, near, far, sample_offset, workspace, workspace.numel(), dev, st.cuda_stream)
+            h_labels = torch.empty(labels.shape, dtype=torch.uint8, pin_memory=True)
+            h_records = torch.empty(records.shape, dtype=torch.int32, pin_memory=True)
             h_labels.copy_(labels, non_blocking=True)
             h_records.copy_(records, non_blocking=True)
             done = torch.cuda.Event()

@@ -21,6 +21,7 @@ import numpy as np
 import torch
 
 from .. import _lib
+from .. import twin as _twin   # DeviceScenes.twin is public API
 from .synthetic_scene import CAMERA
 
 HEADER, OBJECT = 8, 18   # cp_scene::HEADER / OBJECT of csrc/scene_math.h
@@ -64,15 +65,18 @@ class DeviceScenes:
             records = records.pin_memory()
         return dict(records=records, small=self.ds._small_arrays([s for _, s in parts]))
 
+    def _render(self, records, noise: bool, device, stream) -> dict:
+        """cp_render_scenes_f32 on `stream` over device records, or (device None) its host twin over NumPy records: img, label, target_seg, counts"""
+        b, oc, (H, W) = records.shape[0], self.ds.oc, self.ds.size
+        out = _twin.alloc(dict(img=((b, H, W, 3), np.float32), label=((b, H, W), np.uint8), target_seg=((b, H, W, oc + 1), np.float32),
+                               counts=((b, oc), np.int32)), device)
+        _twin.call("cp_render_scenes_f32", records, b, oc, H, W, int(noise), out["img"], out["label"], out["target_seg"], out["counts"],
+                   host=device is None, stream=stream)
+        return out
+
     def twin(self, records: np.ndarray, noise: bool = True) -> Dict[str, np.ndarray]:
         """Host records [b, words] through cp_render_scenes_host_f32, the kernel's host twin (no GPU): img, label, target_seg, counts as NumPy arrays."""
-        b, oc, (H, W) = records.shape[0], self.ds.oc, self.ds.size
-        records = np.ascontiguousarray(records, np.float64)
-        out = dict(img=np.empty((b, H, W, 3), np.float32), label=np.empty((b, H, W), np.uint8), target_seg=np.empty((b, H, W, oc + 1), np.float32),
-                   counts=np.empty((b, oc), np.int32))
-        _lib.check(self.lib.cp_render_scenes_host_f32(records.ctypes.data, b, oc, H, W, int(noise), out["img"].ctypes.data, out["label"].ctypes.data,
-                                                      out["target_seg"].ctypes.data, out["counts"].ctypes.data), "cp_render_scenes_host_f32")
-        return out
+        return self._render(_twin.array(records, np.float64), noise, None, None)
 
     # ---- device half --------------------------------------------------------------------------------------------------------------
     def launch_records(self, records: torch.Tensor, noise: bool = True) -> Tuple[dict, torch.cuda.Event]:
@@ -81,21 +85,15 @@ class DeviceScenes:
         if self.stream is None:
             self.stream = torch.cuda.Stream(device=self.device)
         dev, st = self.device, self.stream
-        b, oc, (H, W) = records.shape[0], self.ds.oc, self.ds.size
         with torch.cuda.stream(st):
             rec = records.to(dev, non_blocking=True)
-            img = torch.empty((b, H, W, 3), dtype=torch.float32, device=dev)
-            label = torch.empty((b, H, W), dtype=torch.uint8, device=dev)
-            target = torch.empty((b, H, W, oc + 1), dtype=torch.float32, device=dev)
-            counts = torch.empty((b, oc), dtype=torch.int32, device=dev)
-            _lib.check(self.lib.cp_render_scenes_f32(rec.data_ptr(), b, oc, H, W, int(noise), img.data_ptr(), label.data_ptr(), target.data_ptr(),
-                                                     counts.data_ptr(), st.cuda_stream), "cp_render_scenes_f32")
-            counts_host = torch.empty((b, oc), dtype=torch.int32, pin_memory=True)
-            counts_host.copy_(counts, non_blocking=True)
-            filtered = label.to(torch.int32).unsqueeze(-1)   # filtered_seg of the batch dict
+            out = self._render(rec, noise, dev, st.cuda_stream)
+            counts_host = torch.empty(out["counts"].shape, dtype=torch.int32, pin_memory=True)
+            counts_host.copy_(out["counts"], non_blocking=True)
+            filtered = out["label"].to(torch.int32).unsqueeze(-1)   # filtered_seg of the batch dict
             done = torch.cuda.Event()
             done.record(st)
-        return dict(img=img, label=label, target_seg=target, filtered_seg=filtered, counts=counts, counts_host=counts_host, records=rec), done
+        return dict(out, filtered_seg=filtered, counts_host=counts_host, records=rec), done
 
     def _launch(self, host: dict, noise: bool = True) -> Tuple[dict, torch.cuda.Event]:
         out, done = self.launch_records(host["records"], noise)

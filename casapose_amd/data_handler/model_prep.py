@@ -12,6 +12,7 @@ The definitions (fp32 box, fp64 centre and squared distances without FMA, lowest
 requested and no GPU present ModelPrep raises; it never falls back to the host."""
 from __future__ import annotations
 
+import contextlib
 import json
 import os
 import re
@@ -19,7 +20,7 @@ from typing import Dict, Optional
 
 import numpy as np
 
-from .. import _lib
+from .. import _lib, twin
 
 MIN_POINTS, MAX_POINTS = 2, 32       # cp_model::MIN_POINTS, MAX_POINTS of csrc/model_math.h: the centre counts
 MAX_VERTICES = 1 << 22
@@ -52,9 +53,10 @@ class ModelPrep:
         return dict(verts=verts, total=int(counts.sum()), offsets=offsets, counts=np.minimum(counts, 2 ** 31 - 1).astype(np.int32))
 
     @staticmethod
-    def _outputs(objects: int, K: int):
-        return dict(diameter_sq=np.zeros(objects, np.float64), box=np.zeros((objects, 6), np.float32), keypoints=np.zeros((objects, K, 3), np.float32),
-                    indices=np.zeros((objects, K - 1), np.int32), status=np.zeros(objects, np.int32))
+    def _outputs(objects: int, K: int, device=None) -> dict:
+        """the library's output arrays, zeroed: tensors on `device`, or NumPy arrays"""
+        return twin.alloc(dict(diameter_sq=((objects,), np.float64), box=((objects, 6), np.float32), keypoints=((objects, K, 3), np.float32),
+                               indices=((objects, K - 1), np.int32), status=((objects,), np.int32)), device, zero=True)
 
     @staticmethod
     def _results(ids, out) -> Dict[object, dict]:
@@ -85,47 +87,36 @@ class ModelPrep:
     def outputs(self, meshes: Dict[object, np.ndarray], no_points: int = 9, host: bool = False) -> Dict[str, np.ndarray]:
         """The library's arrays for the objects of `meshes` in its order, statuses included and nothing raised for them: diameter_sq [n], box [n, 6],
         keypoints [n, K, 3], indices [n, K - 1], status [n], counts [n].  host: the serial twin; otherwise the kernels (no fall-back)."""
+        import torch
+
         if not host and self.device is None:
             raise _lib.CasaposeHipError("this ModelPrep was built without a device; there is no fall-back to the host twin (call prepare_host)")
         K, ids, parts = self._check_points(no_points), list(meshes), []
         for lo in range(0, len(ids), MAX_OBJECTS):
             part = ids[lo:lo + MAX_OBJECTS]
             p = self.pack(meshes, part)
-            size = int(self.lib.cp_model_prep_workspace_bytes(len(part), p["total"]))
-            if host:
-                out, ws = self._outputs(len(part), K), np.empty(max(size // 8, 1), np.int64)
-                _lib.check(self.lib.cp_model_prep_host_f32(p["verts"].ctypes.data, p["total"], p["offsets"].ctypes.data, p["counts"].ctypes.data,
-                                                           len(part), K, out["diameter_sq"].ctypes.data, out["box"].ctypes.data,
-                                                           out["keypoints"].ctypes.data, out["indices"].ctypes.data, out["status"].ctypes.data,
-                                                           ws.ctypes.data, size), "cp_model_prep_host_f32")
-            else:
-                import torch
-
-                with torch.cuda.device(self.device):
-                    d = self.upload(p, len(part), K)
-                    self.launch(d, len(part), p["total"], K, torch.cuda.current_stream(self.device).cuda_stream)
-                    out = {k: d[k].cpu().numpy() for k in ("diameter_sq", "box", "keypoints", "indices", "status")}
-            parts.append(dict(out, counts=p["counts"]))
+            with contextlib.nullcontext() if host else torch.cuda.device(self.device):
+                d = self._arrays(p, len(part), K, None if host else self.device)
+                self.launch(d, len(part), p["total"], K, None if host else torch.cuda.current_stream(self.device).cuda_stream)
+                parts.append(dict({k: twin.array(d[k], None) for k in self._outputs(0, K)}, counts=p["counts"]))   # a download synchronises
         if not parts:
             return dict(self._outputs(0, K), counts=np.zeros(0, np.int32))
         return {k: np.concatenate([part[k] for part in parts]) for k in parts[0]}
 
+    def _arrays(self, p: Dict[str, np.ndarray], objects: int, K: int, device) -> Dict[str, object]:
+        """the packed inputs, zeroed outputs and the workspace where the call runs: tensors on `device`, or NumPy arrays"""
+        size = max(int(self.lib.cp_model_prep_workspace_bytes(objects, p["total"])), 8)
+        d = {k: twin.array(p[k], p[k].dtype, device) for k in ("verts", "offsets", "counts")}
+        return dict(d, **self._outputs(objects, K, device), **twin.alloc(dict(workspace=((size,), np.uint8)), device))
+
     def upload(self, p: Dict[str, np.ndarray], objects: int, K: int) -> Dict[str, object]:
         """the packed inputs, zeroed outputs and the workspace as device tensors"""
-        import torch
+        return self._arrays(p, objects, K, self.device)
 
-        d = {k: torch.from_numpy(p[k]).to(self.device) for k in ("verts", "offsets", "counts")}
-        for k, a in self._outputs(objects, K).items():
-            d[k] = torch.from_numpy(a).to(self.device)
-        size = int(self.lib.cp_model_prep_workspace_bytes(objects, p["total"]))
-        d["workspace"] = torch.empty(max(size, 8), dtype=torch.uint8, device=self.device)
-        return d
-
-    def launch(self, d: Dict[str, object], objects: int, total: int, K: int, stream: int):
-        """one cp_model_prep_f32 call on `upload`'s tensors (tools/model_prep_times.py times this)"""
-        _lib.check(self.lib.cp_model_prep_f32(d["verts"].data_ptr(), total, d["offsets"].data_ptr(), d["counts"].data_ptr(), objects, K,
-                                              d["diameter_sq"].data_ptr(), d["box"].data_ptr(), d["keypoints"].data_ptr(), d["indices"].data_ptr(),
-                                              d["status"].data_ptr(), d["workspace"].data_ptr(), d["workspace"].numel(), stream), "cp_model_prep_f32")
+    def launch(self, d: Dict[str, object], objects: int, total: int, K: int, stream: Optional[int]):
+        """one cp_model_prep_f32 call on `upload`'s tensors (tools/model_prep_times.py times this); stream None: the host twin on NumPy arrays"""
+        twin.call("cp_model_prep_f32", d["verts"], total, d["offsets"], d["counts"], objects, K, d["diameter_sq"], d["box"], d["keypoints"],
+                  d["indices"], d["status"], d["workspace"], len(d["workspace"]), host=stream is None, stream=stream)
 
     def prepare(self, meshes: Dict[object, np.ndarray], no_points: int = 9) -> Dict[object, dict]:
         return self._results(list(meshes), self.outputs(meshes, no_points, host=False))

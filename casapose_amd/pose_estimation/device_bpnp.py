@@ -18,7 +18,7 @@ from typing import Optional, Tuple
 import numpy as np
 import torch
 
-from .. import _lib
+from .. import _lib, twin
 from .device_pnp import MAX_POINTS, MIN_POINTS, hypothesis_table
 from .pose_evaluation import _np
 
@@ -38,7 +38,7 @@ class DeviceBPnPLoss:
         self.device = None if device is None else torch.device(device)
         self.table = None if self.device is None else torch.from_numpy(self.table_host).to(self.device)
         self.points_3d = self.cam = None       # bind(): the targets TrainPlan.kp_loss_and_grad reads
-        self._buffers = {}                     # (b, oc) -> (poses, info, counts, workspace)
+        self._buffers = {}                     # (b, oc) -> run()'s poses, info, counts, workspace
         self._info = self._counts = None       # of the last call: device tensors (launch) or arrays (host twin)
 
     # ---- what the last call left, downloaded when asked for (the copy synchronises; nothing else here does) ----
@@ -65,35 +65,31 @@ class DeviceBPnPLoss:
                 raise ValueError("%s must hold %d values for b = %d, oc = %d, kp = %d (got %s)" % (name, want, b, oc, self.n_points, tuple(a.shape)))
         return b, oc
 
-    def _device_tensor(self, a, dtype=torch.float32):
-        if not hasattr(a, "detach"):
-            a = torch.from_numpy(np.ascontiguousarray(np.asarray(a)))
-        return a.to(device=self.device, dtype=dtype).contiguous()
-
-    def _outputs(self, b: int, oc: int):
-        if (b, oc) not in self._buffers:
-            dev = self.device
-            self._buffers[(b, oc)] = (torch.zeros((b, oc, 1, 3, 4), dtype=torch.float32, device=dev), torch.zeros((b, oc, 4), dtype=torch.int32, device=dev),
-                                      torch.zeros(2, dtype=torch.int32, device=dev), torch.empty(self.workspace_bytes(b, oc) // 8, dtype=torch.float64, device=dev))
-        return self._buffers[(b, oc)]
+    def _outputs(self, b: int, oc: int, device, zero: bool = False) -> dict:
+        """poses, info, counts and the workspace of one call, where it runs (a device, or None for NumPy arrays)"""
+        return twin.alloc(dict(poses=((b, oc, 1, 3, 4), np.float32), info=((b, oc, 4), np.int32), counts=((2,), np.int32),
+                               workspace=((self.workspace_bytes(b, oc) // 8,), np.float64)), device, zero)
 
     def bind(self, points_3d, cam) -> "DeviceBPnPLoss":
         """Upload the model keypoints [b,oc,kp,3] and the one camera matrix [3,3] that run() uses."""
         cam = _np(cam, np.float32)
-        self.points_3d = self._device_tensor(_np(points_3d, np.float32).reshape(-1, self.n_points, 3))
-        self.cam = self._device_tensor(cam[0] if cam.ndim == 3 else cam)
+        self.points_3d = twin.array(_np(points_3d, np.float32).reshape(-1, self.n_points, 3), np.float32, self.device)
+        self.cam = twin.array(cam[0] if cam.ndim == 3 else cam, np.float32, self.device)
         return self
+
+    def _call(self, coords_yx, gt_xy, affine, avail, points_3d, cam, max_pixel_error, weight, g_yx, loss, out: dict, host: bool) -> None:
+        """cp_bpnp_loss_f64 on the current stream, or its host twin: the one argument list of both"""
+        b, oc = int(coords_yx.shape[0]), int(coords_yx.shape[1])
+        twin.call("cp_bpnp_loss_f64", coords_yx, gt_xy, affine, avail, points_3d, cam, self.table_host if host else self.table, b, oc, self.n_points,
+                  self.hypotheses, self.reprojection_error, float(max_pixel_error), float(weight), g_yx, loss, out["poses"], out["info"], out["counts"],
+                  out["workspace"], host=host, stream=None if host else torch.cuda.current_stream(self.device).cuda_stream)
+        self._info, self._counts = out["info"], out["counts"]
 
     def launch(self, coords_yx, gt_xy, affine, avail, points_3d, cam, max_pixel_error: float, weight: float, g_yx, loss, poses, info, counts, workspace) -> None:
         """cp_bpnp_loss_f64 on the current stream over contiguous device tensors of the right types (fp32; loss fp64 [1]; info, counts int32;
         workspace of workspace_bytes(b, oc)).  It does not synchronise."""
-        b, oc = int(coords_yx.shape[0]), int(coords_yx.shape[1])
-        stream = torch.cuda.current_stream(self.device).cuda_stream
-        _lib.check(self._lib.cp_bpnp_loss_f64(coords_yx.data_ptr(), gt_xy.data_ptr(), affine.data_ptr(), avail.data_ptr(), points_3d.data_ptr(), cam.data_ptr(),
-                                              self.table.data_ptr(), b, oc, self.n_points, self.hypotheses, self.reprojection_error, float(max_pixel_error),
-                                              float(weight), g_yx.data_ptr(), loss.data_ptr(), poses.data_ptr(), info.data_ptr(), counts.data_ptr(),
-                                              workspace.data_ptr(), stream), "cp_bpnp_loss_f64")
-        self._info, self._counts = info, counts
+        self._call(coords_yx, gt_xy, affine, avail, points_3d, cam, max_pixel_error, weight, g_yx, loss,
+                   dict(poses=poses, info=info, counts=counts, workspace=workspace), host=False)
 
     def run(self, coords_yx, gt_xy, affine, avail, max_pixel_error: float, weight: float, g_yx, loss):
         """launch() with the bound targets into the caller's gradient [b,oc,kp,2] and fp64 loss [1]; -> (poses, info, counts), device tensors
@@ -103,9 +99,22 @@ class DeviceBPnPLoss:
         if self.points_3d is None:
             raise _lib.CasaposeHipError("DeviceBPnPLoss.run needs bind(points_3d, cam) first")
         b, oc = self._shapes(coords_yx, gt_xy, affine, avail, self.points_3d, self.cam)
-        poses, info, counts, workspace = self._outputs(b, oc)
-        self.launch(coords_yx, gt_xy, affine, avail, self.points_3d, self.cam, max_pixel_error, weight, g_yx, loss, poses, info, counts, workspace)
-        return poses, info, counts
+        if (b, oc) not in self._buffers:
+            self._buffers[(b, oc)] = self._outputs(b, oc, self.device, zero=True)
+        out = self._buffers[(b, oc)]
+        self._call(coords_yx, gt_xy, affine, avail, self.points_3d, self.cam, max_pixel_error, weight, g_yx, loss, out, host=False)
+        return out["poses"], out["info"], out["counts"]
+
+    def _loss_and_grad(self, coords_yx, gt_xy, affine, avail, points_3d, cam, max_pixel_error, weight, host: bool):
+        """the inputs converted and the outputs made where the call runs -> (loss [1], g_yx, poses)"""
+        dev = None if host else self.device
+        cam = cam if hasattr(cam, "detach") else _np(cam, np.float32)
+        c, gt, aff, av, x3, K = (twin.array(a, np.float32, dev) for a in (coords_yx, gt_xy, affine, avail, points_3d, cam[0] if cam.ndim == 3 else cam))
+        b, oc = self._shapes(c, gt, aff, av, x3, K)
+        out = self._outputs(b, oc, dev)
+        res = twin.alloc(dict(g=((b, oc, self.n_points, 2), np.float32), loss=((1,), np.float64)), dev)
+        self._call(c, gt, aff, av, x3, K, max_pixel_error, weight, res["g"], res["loss"], out, host)
+        return res["loss"], res["g"], out["poses"]
 
     def loss_and_grad(self, coords_yx, gt_xy, affine, avail, points_3d, cam, max_pixel_error: float = 25.0, weight: float = 1.0):
         """coords_yx [b,oc,kp,2] (y,x) crop pixels, gt_xy [b,oc,kp,2] (x,y) image pixels, affine [b,6] or [b,2,3], avail [b,oc], points_3d
@@ -114,32 +123,11 @@ class DeviceBPnPLoss:
         if self.device is None:
             raise _lib.CasaposeHipError("this DeviceBPnPLoss was built without a device: only loss_and_grad_host is available")
         with torch.cuda.device(self.device):
-            c, gt, aff, av = (self._device_tensor(a) for a in (coords_yx, gt_xy, affine, avail))
-            cam = _np(cam, np.float32) if not hasattr(cam, "detach") else cam
-            x3, Kd = self._device_tensor(points_3d), self._device_tensor(cam[0] if cam.ndim == 3 else cam)
-            b, oc = self._shapes(c, gt, aff, av, x3, Kd)
-            g = torch.empty((b, oc, self.n_points, 2), dtype=torch.float32, device=self.device)
-            loss = torch.empty(1, dtype=torch.float64, device=self.device)
-            poses = torch.empty((b, oc, 1, 3, 4), dtype=torch.float32, device=self.device)
-            info = torch.empty((b, oc, 4), dtype=torch.int32, device=self.device)
-            counts = torch.empty(2, dtype=torch.int32, device=self.device)
-            workspace = torch.empty(self.workspace_bytes(b, oc) // 8, dtype=torch.float64, device=self.device)
-            self.launch(c, gt, aff, av, x3, Kd, max_pixel_error, weight, g, loss, poses, info, counts, workspace)
+            loss, g, poses = self._loss_and_grad(coords_yx, gt_xy, affine, avail, points_3d, cam, max_pixel_error, weight, host=False)
         return loss[0], g, poses
 
     def loss_and_grad_host(self, coords_yx, gt_xy, affine, avail, points_3d, cam, max_pixel_error: float = 25.0, weight: float = 1.0):
         """The host twin of loss_and_grad() on NumPy arrays: the same code, serially, without a GPU.  -> (loss float, g_yx float32 [b,oc,kp,2],
         poses float32 [b,oc,1,3,4])."""
-        c, gt, aff, av, x3 = (np.ascontiguousarray(_np(a, np.float32)) for a in (coords_yx, gt_xy, affine, avail, points_3d))
-        Kh = _np(cam, np.float32)
-        Kh = np.ascontiguousarray(Kh[0] if Kh.ndim == 3 else Kh)
-        b, oc = self._shapes(c, gt, aff, av, x3, Kh)
-        g, loss = np.empty((b, oc, self.n_points, 2), np.float32), np.empty(1, np.float64)
-        poses, info, counts = np.empty((b, oc, 1, 3, 4), np.float32), np.empty((b, oc, 4), np.int32), np.empty(2, np.int32)
-        workspace = np.empty(self.workspace_bytes(b, oc) // 8, np.float64)
-        _lib.check(self._lib.cp_bpnp_loss_host_f64(c.ctypes.data, gt.ctypes.data, aff.ctypes.data, av.ctypes.data, x3.ctypes.data, Kh.ctypes.data,
-                                                   self.table_host.ctypes.data, b, oc, self.n_points, self.hypotheses, self.reprojection_error,
-                                                   float(max_pixel_error), float(weight), g.ctypes.data, loss.ctypes.data, poses.ctypes.data, info.ctypes.data,
-                                                   counts.ctypes.data, workspace.ctypes.data), "cp_bpnp_loss_host_f64")
-        self._info, self._counts = info, counts
+        loss, g, poses = self._loss_and_grad(coords_yx, gt_xy, affine, avail, points_3d, cam, max_pixel_error, weight, host=True)
         return float(loss[0]), g, poses

@@ -15,7 +15,7 @@ from typing import Optional
 import numpy as np
 import torch
 
-from .. import _lib
+from .. import _lib, twin
 from .pose_evaluation import _np
 
 MIN_POINTS, MAX_POINTS, SET_POINTS, MAX_HYPOTHESES = 5, 16, 5, 256
@@ -77,18 +77,27 @@ class DevicePnP:
             raise ValueError("affine must be [%d, 6] (got %s)" % (b, tuple(affine.shape)))
         return b, oc
 
-    def _device_tensor(self, a, dtype):
-        if not hasattr(a, "detach"):
-            a = torch.from_numpy(np.ascontiguousarray(np.asarray(a)))
-        return a.to(device=self.device, dtype=dtype).contiguous()
+    def _call(self, xy, x3, K, mask, affine, poses, info, cost, host: bool) -> None:
+        """cp_pnp_f64 on the current stream, or its host twin: the one argument list of both"""
+        b, oc = int(xy.shape[0]), int(xy.shape[1])
+        twin.call("cp_pnp_f64", xy, x3, K, int(K.ndim == 3), affine, mask, self.table_host if host else self.table, b, oc, self.n_points,
+                  self.hypotheses, self.reprojection_error, poses, info, cost, host=host,
+                  stream=None if host else torch.cuda.current_stream(self.device).cuda_stream)
 
     def launch(self, xy, x3, K, mask, affine, poses, info, cost) -> None:
         """cp_pnp_f64 on the current stream over contiguous device tensors of the right types."""
-        b, oc = int(xy.shape[0]), int(xy.shape[1])
-        stream = torch.cuda.current_stream(self.device).cuda_stream
-        _lib.check(self._lib.cp_pnp_f64(xy.data_ptr(), x3.data_ptr(), K.data_ptr(), int(K.dim() == 3), None if affine is None else affine.data_ptr(),
-                                        mask.data_ptr(), self.table.data_ptr(), b, oc, self.n_points, self.hypotheses, self.reprojection_error,
-                                        poses.data_ptr(), info.data_ptr(), cost.data_ptr(), stream), "cp_pnp_f64")
+        self._call(xy, x3, K, mask, affine, poses, info, cost, host=False)
+
+    def _solve(self, points_xy, points_3d, K, solve_mask, affine, host: bool) -> dict:
+        """the inputs converted and the outputs made where the call runs (this device, or NumPy arrays for the twin) -> poses, info, cost"""
+        dev = None if host else self.device
+        xy, x3, Kc = (twin.array(a, np.float32, dev) for a in (points_xy, points_3d, K))
+        mask = twin.array(solve_mask, np.int32, dev)
+        aff = None if affine is None else twin.array(affine, np.float64, dev)
+        b, oc = self._shapes(xy, x3, Kc, mask, aff)
+        out = twin.alloc(dict(poses=((b, oc, 3, 4), np.float32), info=((b, oc, 4), np.int32), cost=((b, oc, 2), np.float32)), dev)
+        self._call(xy, x3, Kc, mask, aff, out["poses"], out["info"], out["cost"], host)
+        return out
 
     def solve(self, points_xy, points_3d, K, solve_mask, affine=None):
         """points_xy [b,oc,n,2] (x,y), points_3d [b,oc,n,3], K [3,3] or [b,3,3], solve_mask [b,oc] (0: the zero pose), affine None or [b,6]
@@ -97,30 +106,16 @@ class DevicePnP:
         if self.device is None:
             raise _lib.CasaposeHipError("this DevicePnP was built without a device: only solve_host is available")
         with torch.cuda.device(self.device):
-            xy, x3 = self._device_tensor(points_xy, torch.float32), self._device_tensor(points_3d, torch.float32)
-            Kd, mask = self._device_tensor(K, torch.float32), self._device_tensor(solve_mask, torch.int32)
-            aff = None if affine is None else self._device_tensor(affine, torch.float64)
-            b, oc = self._shapes(xy, x3, Kd, mask, aff)
-            poses = torch.empty((b, oc, 3, 4), dtype=torch.float32, device=self.device)
-            info = torch.empty((b, oc, 4), dtype=torch.int32, device=self.device)
-            cost = torch.empty((b, oc, 2), dtype=torch.float32, device=self.device)
-            self.launch(xy, x3, Kd, mask, aff, poses, info, cost)
-            self.last_info, self.last_cost = info.cpu().numpy(), cost.cpu().numpy()   # the copies synchronise
-        self.last_poses = poses
-        return poses
+            out = self._solve(points_xy, points_3d, K, solve_mask, affine, host=False)
+            self.last_info, self.last_cost = out["info"].cpu().numpy(), out["cost"].cpu().numpy()   # the copies synchronise
+        self.last_poses = out["poses"]
+        return self.last_poses
 
     def solve_host(self, points_xy, points_3d, K, solve_mask, affine=None) -> np.ndarray:
         """The host twin of solve() on NumPy arrays: the same code, serially, without a GPU.  -> poses float32 [b,oc,3,4]."""
-        xy, x3 = np.ascontiguousarray(_np(points_xy, np.float32)), np.ascontiguousarray(_np(points_3d, np.float32))
-        Kh, mask = np.ascontiguousarray(_np(K, np.float32)), np.ascontiguousarray(_np(solve_mask, np.int32))
-        aff = None if affine is None else np.ascontiguousarray(_np(affine, np.float64))
-        b, oc = self._shapes(xy, x3, Kh, mask, aff)
-        poses, info, cost = np.empty((b, oc, 3, 4), np.float32), np.empty((b, oc, 4), np.int32), np.empty((b, oc, 2), np.float32)
-        _lib.check(self._lib.cp_pnp_host_f64(xy.ctypes.data, x3.ctypes.data, Kh.ctypes.data, int(Kh.ndim == 3), None if aff is None else aff.ctypes.data,
-                                             mask.ctypes.data, self.table_host.ctypes.data, b, oc, self.n_points, self.hypotheses,
-                                             self.reprojection_error, poses.ctypes.data, info.ctypes.data, cost.ctypes.data), "cp_pnp_host_f64")
-        self.last_info, self.last_cost, self.last_poses = info, cost, poses
-        return poses
+        out = self._solve(points_xy, points_3d, K, solve_mask, affine, host=True)
+        self.last_info, self.last_cost, self.last_poses = out["info"], out["cost"], out["poses"]
+        return self.last_poses
 
 
 class HostTwinPnP(DevicePnP):

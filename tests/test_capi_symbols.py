@@ -237,3 +237,87 @@ def test_armed_sets_the_slot_and_always_clears_it(lib):
     for slot in (None, 0):
         with armed(slot):
             assert lib.cp_f16x2_monitor_get() is None
+
+
+# ---- the binding table is derived from the header: known answers written by hand from include/casapose_hip.h as it stands ----
+_I, _LL, _ULL, _F, _D, _Z = C.c_int, C.c_longlong, C.c_ulonglong, C.c_float, C.c_double, C.c_size_t
+
+
+def _p(pointee):
+    return (C.c_void_p, pointee)
+
+
+def _known_signatures():
+    from casapose_amd._lib import ConvDesc
+
+    i, ll, f, d = (_I, None), (_LL, None), (_F, None), (_D, None)
+    fl, u8, i32, vd = _p("float"), _p("uint8_t"), _p("int32_t"), _p("void")
+    return {
+        # name: (restype, pointee of the return, [(argtype, pointee)])
+        "cp_conv2d_fwd_f32": (_I, None, [(C.POINTER(ConvDesc), "cp_conv_desc"), vd]),
+        "cp_amax_f32": (_I, None, [fl, ll, ll, ll, _p("uint32_t"), vd]),
+        "cp_ransac_vote_seeded_f32": (_I, None, [u8, fl, i, i, i, i, i, i, i, (_ULL, None), i, f, f, i, i, i, vd, fl, i32, vd]),
+        "cp_render_masks_u8": (_I, None, [fl, i32, i, i32, i32, i, i, _p("double"), i32, i32, i32, _p("double"), i, i, i, i, d, d, d, u8, i32, vd,
+                                          (_Z, None), vd]),
+        "cp_bn_finalize_f32": (_I, None, [_p("double"), d, i, i, i, fl, fl, f, i, f] + [fl] * 8 + [vd]),
+        "cp_conv_ktot": (_I, None, [i, i, i, _p("int")]),
+        "cp_label_pyramid": (_I, None, [u8, i, i, i, _p("uint8_t*"), _p("float*"), _p("uint8_t*"), vd]),
+        "cp_f16x2_weight_scale": (_F, None, [f]),
+        "cp_f16x2_monitor_get": (C.c_void_p, "uint32_t", []),
+        "cp_last_error": (C.c_char_p, "char", []),
+        "cp_bpnp_loss_workspace_bytes": (_Z, None, [i, i, i]),
+        "cp_conv_stem_split_weight_floats": (_I, None, []),
+    }
+
+
+def test_derived_signatures_match_known_answers():
+    from casapose_amd import _lib
+
+    table = {n: (r, a) for n, r, a in _lib.SYMBOLS}
+    for name, (restype, ret_pointee, args) in _known_signatures().items():
+        assert table[name][0] is restype, name
+        assert _lib.RETURN_POINTEES[name] == ret_pointee, name
+        assert table[name][1] == [t for t, _ in args], name
+        assert _lib.POINTEES[name] == tuple(p for _, p in args), name
+
+
+def test_no_prototype_is_dropped():
+    from casapose_amd import _lib
+
+    names = [n for n, _, _ in _lib.SYMBOLS]
+    assert len(names) == len(set(names)) == len(declared_functions())
+    assert set(_lib.POINTEES) == set(_lib.RETURN_POINTEES) == set(names)
+
+
+def test_unreadable_declarations_raise():
+    from casapose_amd import _lib
+
+    good = "int cp_a(const float* x, int n, void* stream);\n"
+    assert [n for n, _, _ in _lib.parse_header(good)[0]] == ["cp_a"]
+    for bad, what in ((good + "int cp_b(const float* x, int n;\nint cp_c(void);\n", "cp_b"),       # no closing parenthesis
+                      (good + "int cp_b(int (*callback)(int), void* stream);\n", "cp_b"),           # a function pointer
+                      (good + "int cp_b(const half_t* x, void* stream);\n", "cp_b, parameter 0"),   # an unknown type
+                      (good + "cp_thing cp_b(void);\n", "cp_b, return type"),
+                      (good + "int cp_b(float x[4]);\n", "cp_b, parameter 0")):
+        with pytest.raises(_lib.CasaposeHipError, match=re.escape(what)):
+            _lib.parse_header(bad)
+
+
+def test_host_twins_are_found_in_the_header():
+    from casapose_amd import _lib
+
+    assert _lib.TWINS == {"cp_pnp_f64": "cp_pnp_host_f64", "cp_bpnp_loss_f64": "cp_bpnp_loss_host_f64",
+                          "cp_render_scenes_f32": "cp_render_scenes_host_f32", "cp_render_masks_u8": "cp_render_masks_host_u8",
+                          "cp_model_prep_f32": "cp_model_prep_host_f32"}
+    table = {n: a for n, _, a in _lib.SYMBOLS}
+    for device, host in _lib.TWINS.items():
+        assert table[device] == table[host] + [C.c_void_p]
+        assert _lib.POINTEES[device] == _lib.POINTEES[host] + ("void",)
+    dev = "int cp_x_f32(const float* a, int n, float* out, void* stream);\n"
+    assert _lib.parse_header(dev + "int cp_x_host_f32(const float* a, int n, float* out);\n")[3] == {"cp_x_f32": "cp_x_host_f32"}
+    assert _lib.parse_header(dev + "int cp_x_pack_host(const float* a);\n")[3] == {}     # no type suffix, no device partner: not a twin
+    for twin in ("int cp_x_host_f32(const float* a, int n, float* out, int extra);\n",        # one parameter more
+                 "int cp_x_host_f32(const float* a, int n, double* out);\n",                  # another pointee
+                 "int cp_x_host_f32(const float* a, int n, float* out, void* stream);\n"):    # the stream kept
+        with pytest.raises(_lib.CasaposeHipError, match="cp_x_host_f32"):
+            _lib.parse_header(dev + twin)

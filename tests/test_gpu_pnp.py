@@ -85,6 +85,32 @@ def test_other_point_counts(device, name):
     T.assert_within_gates(poses, ref.poses, ref, "device against pnp.pnp, n = %d" % n)
 
 
+def test_one_call_path_for_the_kernel_and_its_twin(device):
+    """twin.call refuses a device tensor for the host twin in Python (nothing is launched, the outputs stay as they were); solve and solve_host
+    share one argument list and agree at b = 1, oc = 1, n = 5 (one hypothesis)"""
+    import torch
+
+    from casapose_amd import _lib, twin
+
+    cases, ref = T.fixture_set("n5")[:1], T.host_reference("n5")
+    xy, x3 = T.batch_of(cases, 1, 1)
+    solver = DevicePnP(device, 5)
+    d = {k: twin.array(a, t, solver.device) for k, (a, t) in dict(xy=(xy, np.float32), x3=(x3, np.float32), K=(T.K32, np.float32),
+                                                                  mask=(np.ones((1, 1), np.int32), np.int32)).items()}
+    out = twin.alloc(dict(poses=((1, 1, 3, 4), np.float32), info=((1, 1, 4), np.int32), cost=((1, 1, 2), np.float32)), solver.device, zero=True)
+    with pytest.raises(_lib.CasaposeHipError, match=r"cp_pnp_host_f64, argument 0 \(float\*\): a CUDA tensor for a host twin"):
+        twin.call("cp_pnp_f64", d["xy"], d["x3"], d["K"], 0, None, d["mask"], solver.table_host, 1, 1, 5, 1, 12.0, out["poses"], out["info"],
+                  out["cost"], host=True)
+    torch.cuda.synchronize()
+    assert not any(bool(v.any()) for v in out.values())
+    poses, info, cost, twin_info = solve_both(device, cases, 1, 1, T.K32, np.ones((1, 1), np.int32))
+    compare_info(info, twin_info, "n = 5, one pair")
+    assert info[0, 0] == 0 and info[0, 1] == 0 and info[0, 2] == 5
+    T.assert_within_gates(poses, ref.poses[:1], ref, "device against pnp.pnp, n = 5, one pair")
+    host = DevicePnP(None, 5).solve_host(xy, x3, T.K32, np.ones((1, 1), np.int32))
+    T.assert_within_gates(host.reshape(1, 3, 4), ref.poses[:1], ref, "twin against pnp.pnp, n = 5, one pair")
+
+
 @pytest.mark.parametrize("name", ["n10_outliers", "n11_outliers"])
 def test_consensus_with_other_point_counts(device, name):
     cases = T.fixture_set(name)
