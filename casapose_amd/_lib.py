@@ -124,6 +124,13 @@ class AugImage(C.Structure):
     ]
 
 
+class RansacState(C.Structure):
+    """cp_ransac_state of include/casapose_hip.h, field for field (tests/test_capi_symbols.py parses the header and compares): the RANSAC voter's
+    per-(image, object) record inside its workspace, found through cp_ransac_workspace_layout."""
+    _fields_ = [("tn", C.c_int), ("done", C.c_int), ("rounds", C.c_int), ("hyp_num", C.c_float), ("win_ratio", C.c_float * 9),
+                ("win_pts", (C.c_float * 2) * 9)]
+
+
 PLANES_F16X2 = 0x12  # CP_PLANES_F16X2: the fp16 two-way split (three products, fp32-level accuracy)
 
 SRC_DIRECT, SRC_NEAREST_SEL, SRC_BILINEAR_X2, SRC_ZERO_INSERT_X2 = 0, 1, 2, 3

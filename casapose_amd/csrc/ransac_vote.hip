@@ -28,14 +28,11 @@ namespace {
 constexpr int KP = 9;
 constexpr int HB = 16;  // granularity of the hypotheses per round (a voting block takes 16 or, when the count allows, 64 of them)
 
-struct ObjState {        // one per (image, object)
-    int tn;              // pixels (after min_num gate: 0 if skipped)
-    int done;            // stopping rule reached
-    int rounds;
-    float hyp_num;
-    float win_ratio[KP];
-    float win_pts[KP][2];
-};
+// one per (image, object): the public record of include/casapose_hip.h (cp_ransac_workspace_layout tells a caller where to read it)
+//   tn: pixels (after min_num gate: 0 if skipped); done: stopping rule reached
+using ObjState = cp_ransac_state;
+static_assert(sizeof(ObjState::win_ratio) == KP * sizeof(float) && sizeof(ObjState::win_pts) == KP * 2 * sizeof(float),
+              "cp_ransac_state is declared for KP keypoints");
 
 // counter-based random numbers (splitmix64 finaliser of seed + counter * golden ratio): 64 well-mixed bits per (seed, counter), no state
 __device__ __forceinline__ unsigned long long mix64(unsigned long long seed, unsigned long long ctr) {
@@ -491,6 +488,17 @@ Workspace carve(void* base, int batch, int h, int w, int objects, int hyp) {
 extern "C" size_t cp_ransac_workspace_bytes(int batch, int h, int w, int objects, int kp, int hyp) {
     (void)kp;
     return carve(nullptr, batch, h, w, objects, hyp).bytes;
+}
+
+extern "C" int cp_ransac_workspace_layout(int batch, int h, int w, int objects, int kp, int hyp, size_t* offsets, size_t* state_bytes) {
+    CP_REQUIRE(offsets, "cp_ransac_workspace_layout: null pointer");
+    CP_REQUIRE(kp == KP, "cp_ransac_workspace_layout: built for %d keypoints (got %d)", KP, kp);
+    CP_REQUIRE(batch > 0 && h > 0 && w > 0 && objects > 0 && objects < 255 && hyp > 0, "cp_ransac_workspace_layout: bad sizes");
+    const Workspace ws = carve(nullptr, batch, h, w, objects, hyp);   // the voter's own carve from base 0: the pointers are the offsets
+    const void* part[7] = {ws.rowcnt, ws.pixlist, ws.st, ws.hyp_pts, ws.counts, ws.sums, ws.thr};
+    for (int i = 0; i < 7; ++i) offsets[i] = (size_t) reinterpret_cast<uintptr_t>(part[i]);
+    if (state_bytes) *state_bytes = sizeof(ObjState);
+    return 0;
 }
 
 namespace {

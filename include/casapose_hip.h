@@ -357,6 +357,30 @@ int cp_ransac_vote_seeded_f32(const uint8_t* labels, const float* vertex, int ld
                               int32_t* rounds_out, void* stream);
 size_t cp_ransac_workspace_bytes(int batch, int h, int w, int objects, int kp, int hyp);
 
+/* The voter's per-(image, object) state record as it lies in the workspace (csrc/ransac_vote.hip uses this very struct). */
+typedef struct cp_ransac_state {
+    int tn;                 /* pixels the object votes with (after the min_num gate and the seeded entry's thinning); 0 = skipped */
+    int done;               /* 1: stopping rule or max_iter reached, or skipped */
+    int rounds;             /* rounds voted */
+    float hyp_num;          /* hypotheses drawn so far (rounds * hyp) */
+    float win_ratio[9];     /* best inlier ratio so far per keypoint */
+    float win_pts[9][2];    /* the hypothesis (x, y) that reached it; (0, 0) while no hypothesis had an inlier */
+} cp_ransac_state;
+/* Where the voter keeps its intermediate products inside the workspace, so that each stage can be read back and checked on its own.
+ * Host only; the same carving the voter itself applies.  offsets[7] receives the byte offsets, from a 256-byte aligned workspace base, of
+ *   [0] rowcnt   int32  [n][objects][h]           exclusive row starts of every object's pixel list
+ *   [1] pixlist  int32  [n][objects][h*w]         the first st.tn entries: the object's pixels (y*w + x) in raster order
+ *   [2] st       cp_ransac_state [n][objects]
+ *   [3] hyp_pts  float  [n][objects][hyp][kp][2]  the hypotheses (x, y) of the last round voted; (0, 0) where |det| <= 1e-6
+ *   [4] counts   int32  [n][objects][hyp][kp]     their inlier counts
+ *   [5] sums     double [n][objects][kp][5]       a00, a01, a11, b0, b1 of the refinement's normal equations over the winners' inliers
+ *   [6] thr      uint32 [n][objects]              cp_ransac_vote_seeded_f32 only: a pixel is kept if its 32-bit draw is below thr
+ *                                                 (0xffffffff: all kept, 0: object below min_num)
+ * and *state_bytes (optional) sizeof(cp_ransac_state).  What a finished call leaves behind: st, pixlist and sums are final after any call;
+ * hyp_pts and counts of an object are those of the last round it voted, so after a call with max_iter = 1 they are round 1's.  Objects that
+ * are skipped (st.tn = 0) leave their hyp_pts, counts and pixlist entries unwritten. */
+int cp_ransac_workspace_layout(int batch, int h, int w, int objects, int kp, int hyp, size_t* offsets /*[7]*/, size_t* state_bytes);
+
 /* GuidedBilinearUpsampling (_normalization_layers.py:569-664; casapose_c_gcu4_bilat): mask[n,Y,X] bit j = the low-resolution label of
  * tap j in {(y,x),(y,x+1),(y+1,x),(y+1,x+1)} (zero padded bottom/right) equals labels_hi[n,Y,X]; the upsampling blends the four taps
  * with the fixed sub-pixel weights after replacing non-matching taps by the mean of the matching ones (0 if none), which is the

@@ -88,6 +88,52 @@ def test_descriptor_structs_match_the_header_field_for_field(lib):
     assert _lib.ConvDesc().struct_size == C.sizeof(_lib.ConvDesc)
 
 
+def test_ransac_state_record_matches_the_header(lib):
+    """cp_ransac_state (the voter's per-object record, read back by the stage tests) is mirrored by _lib.RansacState field for field, and the
+    library was compiled with the same size."""
+    from casapose_amd import _lib
+
+    text = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "casapose_hip.h")).read(), flags=re.S)
+    body = re.search(r"typedef struct cp_ransac_state \{(.*?)\} cp_ransac_state;", text, flags=re.S).group(1)
+    header = [re.fullmatch(r"(int|float) (\w+)((?:\[\d+\])*)", " ".join(d.split())).groups() for d in body.split(";") if d.strip()]
+    assert header == [("int", "tn", ""), ("int", "done", ""), ("int", "rounds", ""), ("float", "hyp_num", ""), ("float", "win_ratio", "[9]"),
+                      ("float", "win_pts", "[9][2]")]
+
+    def spell(t, dims=""):
+        if isinstance(t, type) and issubclass(t, C.Array):
+            return spell(t._type_, dims + "[%d]" % t._length_)
+        return {C.c_int: "int", C.c_float: "float"}[t], dims
+
+    assert [(spell(t)[0], n, spell(t)[1]) for n, t in _lib.RansacState._fields_] == header
+    size = C.c_size_t()
+    assert lib.cp_ransac_workspace_layout(1, 8, 8, 1, 9, 16, (C.c_size_t * 7)(), C.byref(size)) == 0
+    assert size.value == C.sizeof(_lib.RansacState) == 4 * (4 + 9 + 18)
+
+
+def test_ransac_workspace_layout_is_the_voters_own_carving(lib):
+    """cp_ransac_workspace_layout (host only): seven parts in the documented order, each 256-byte aligned and large enough for its array, and
+    cp_ransac_workspace_bytes still what it was -- the end of the last part plus 256 bytes of alignment slack (known answers worked out by hand)."""
+    up = lambda n: (n + 255) // 256 * 256   # noqa: E731
+    known = {(2, 72, 100, 4, 9, 16): 251168, (2, 72, 100, 4, 9, 48): 278816, (2, 72, 100, 4, 9, 64): 292640, (1, 12, 16, 1, 9, 16): 4356,
+             (1, 12, 16, 1, 9, 128): 16132, (1, 60, 80, 8, 9, 128): 270880}
+    for (b, h, w, objects, kp, hyp), total in known.items():
+        offs = (C.c_size_t * 7)()
+        assert lib.cp_ransac_workspace_layout(b, h, w, objects, kp, hyp, offs, None) == 0
+        no = b * objects
+        sizes = [no * h * 4, no * h * w * 4, no * 124, no * hyp * 9 * 2 * 4, no * hyp * 9 * 4, no * 9 * 5 * 8, no * 4]    # rowcnt .. thr
+        want, p = [], 0
+        for i, n in enumerate(sizes):
+            if i == 6:
+                p = up(p) + 4           # the 4-byte `active objects` word sits between sums and thr
+            p = up(p)
+            want.append(p)
+            p += n
+        assert list(offs) == want, (list(offs), want)
+        assert lib.cp_ransac_workspace_bytes(b, h, w, objects, kp, hyp) == p + 256 == total, (b, h, w, objects, hyp, p + 256)
+    assert lib.cp_ransac_workspace_layout(2, 8, 8, 1, 9, 16, None, None) == -1
+    assert lib.cp_ransac_workspace_layout(2, 8, 8, 1, 8, 16, (C.c_size_t * 7)(), None) == -1 and b"keypoints" in lib.cp_last_error()
+
+
 def test_descriptor_of_another_abi_revision_is_refused(lib):
     """A caller built against a header with a shorter (or longer) cp_conv_desc is refused by size in every entry point that takes one."""
     from casapose_amd._lib import ConvDesc
@@ -267,6 +313,7 @@ def _known_signatures():
         "cp_last_error": (C.c_char_p, "char", []),
         "cp_bpnp_loss_workspace_bytes": (_Z, None, [i, i, i]),
         "cp_conv_stem_split_weight_floats": (_I, None, []),
+        "cp_ransac_workspace_layout": (_I, None, [i, i, i, i, i, i, _p("size_t"), _p("size_t")]),
     }
 
 
