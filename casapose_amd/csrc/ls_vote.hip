@@ -32,6 +32,105 @@ __device__ __forceinline__ float softplus_fast(float x) {
     return fmaxf(x, 0.f) + (__logf(u) + (t - (u - 1.0f)) * __frcp_rn(u));
 }
 
+// ---- what the two forward kernels share ----
+
+// the strip of this wave: strip id -> (image, strip row, strip column); all 4 waves of a block work on ONE image.  A kernel branches on find()
+// and calls decode() inside the branch, so a wave without a strip does none of the divisions
+struct LsStrip {
+    int img, sidx;          // every wave: the block's image (its commit needs it) and the wave's strip id
+    int x0, y0, x, ncols;   // a wave with a strip, after decode(): the strip's corner, the lane's column, the columns inside the image
+
+    // tells whether the wave has a strip
+    __device__ __forceinline__ bool find(int wave, int strips_x, int strips_y) {
+        const int strips_per_img = strips_x * strips_y;
+        const int blocks_per_img = (strips_per_img + WAVES - 1) / WAVES;
+        img = blockIdx.x / blocks_per_img;
+        sidx = (blockIdx.x % blocks_per_img) * WAVES + wave;
+        return sidx < strips_per_img;
+    }
+    __device__ __forceinline__ void decode(int lane, int strips_x, int W) {
+        const int sy = sidx / strips_x, sx = sidx % strips_x;
+        x0 = sx * 64, y0 = sy * ROWS;
+        x = x0 + lane;
+        ncols = min(64, W - x0);
+    }
+    // the lane's column centre; divide like the reference: (v + 0.5) / H in fp32
+    __device__ __forceinline__ float cx(int H) const { return ((float)x + 0.5f) / (float)H; }
+};
+
+// a lane's private sums of the run of equal labels it is in
+template <int KP>
+struct LsAcc {
+    double a[KP][5] = {};
+    int cur = 0;
+    double* const table;
+    __device__ __forceinline__ explicit LsAcc(double* acc_lds) : table(acc_lds) {}
+    __device__ __forceinline__ void flush() {
+        if (cur > 0) {
+            double* dst = table + (size_t)(cur - 1) * KP * 5;
+#pragma unroll
+            for (int j = 0; j < KP; ++j)
+#pragma unroll
+                for (int c = 0; c < 5; ++c) {
+                    atomicAdd(dst + j * 5 + c, a[j][c]);
+                    a[j][c] = 0.0;
+                }
+        }
+    }
+    __device__ __forceinline__ void enter(int lab) {
+        if (lab != cur) {
+            flush();
+            cur = lab;
+        }
+    }
+};
+
+// the block's LDS table [objects][KP][5]
+__device__ __forceinline__ void ls_table_zero(double* acc_lds, int nacc) {
+    for (int i = threadIdx.x; i < nacc; i += blockDim.x) acc_lds[i] = 0.0;
+    __syncthreads();
+}
+
+__device__ __forceinline__ void ls_table_commit(const double* acc_lds, int nacc, double* __restrict__ gdst) {
+    __syncthreads();
+    for (int i = threadIdx.x; i < nacc; i += blockDim.x) {
+        double v = acc_lds[i];
+        if (v != 0.0) atomicAdd(gdst + i, v);
+    }
+}
+
+// the five terms of one keypoint of one pixel: R = w (I - n n^T) and R c
+__device__ __forceinline__ void ls_add_terms(double (&a)[5], float ny, float nx, float w, float cy, float cx) {
+    const float r00 = (1.0f - ny * ny) * w;
+    const float r01 = (0.0f - ny * nx) * w;
+    const float r11 = (1.0f - nx * nx) * w;
+    const float q0 = r00 * cy + r01 * cx;  // (:103-105)
+    const float q1 = r01 * cy + r11 * cx;
+    a[0] += (double)r00;
+    a[1] += (double)r01;
+    a[2] += (double)r11;
+    a[3] += (double)q0;
+    a[4] += (double)q1;
+}
+
+// The two arithmetic choices.  Exact (generic kernel): libm weights and d / sqrt(d.d).  Fast (36-float kernel): softplus_fast and
+// d * rsqrt(d.d), one reciprocal square root for both components -- the libm calls cost as much as the whole memory stream.
+__device__ __forceinline__ float ls_weight_exact(float cf, int sigmoid) {
+    return sigmoid ? 1.0f / (1.0f + expf(-cf))                    // sigmoid_weights=True (:32-33, sigmoid_scale = 1)
+                   : fmaxf(cf, 0.f) + log1pf(expf(-fabsf(cf)));   // softplus (:35)
+}
+
+__device__ __forceinline__ float2 ls_normal_exact(float dy, float dx) {
+    const float nrm = sqrtf(dy * dy + dx * dx);
+    return make_float2((nrm > 0.f) ? dy / nrm : 0.f, (nrm > 0.f) ? dx / nrm : 0.f);  // divide_no_nan (:90)
+}
+
+__device__ __forceinline__ float2 ls_normal_fast(float dy, float dx) {
+    const float n2 = dy * dy + dx * dx;
+    const float inv = (n2 > 0.f) ? __frsqrt_rn(n2) : 0.f;  // divide_no_nan (:90)
+    return make_float2(dy * inv, dx * inv);
+}
+
 template <int KP>
 __global__ __launch_bounds__(256) void ls_accumulate_kernel(const float* __restrict__ field, int ld, int seg_off,
                                                             int dir_off, int conf_off, const uint8_t* __restrict__ labels,
@@ -44,45 +143,16 @@ __global__ __launch_bounds__(256) void ls_accumulate_kernel(const float* __restr
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int nacc = objects * KP * 5;
-    for (int i = tid; i < nacc; i += blockDim.x) acc_lds[i] = 0.0;
-    __syncthreads();
+    ls_table_zero(acc_lds, nacc);
 
-    // strip id -> (image, strip row, strip column); all 4 waves of a block work on ONE image
-    const int strips_per_img = strips_x * strips_y;
-    const int blocks_per_img = (strips_per_img + WAVES - 1) / WAVES;
-    const int img = blockIdx.x / blocks_per_img;
-    const int sidx = (blockIdx.x % blocks_per_img) * WAVES + wave;
     float* wstage = stage + (size_t)wave * 64 * ld;
-
-    if (sidx < strips_per_img) {
-        const int sy = sidx / strips_x, sx = sidx % strips_x;
-        const int x0 = sx * 64, y0 = sy * ROWS;
-        const int x = x0 + lane;
-        const int ncols = min(64, W - x0);
-        const float invH = 1.0f;  // divide like the reference: (v + 0.5) / H in fp32
-        (void)invH;
-        const float cx = ((float)x + 0.5f) / (float)H;
+    LsStrip s;
+    if (s.find(wave, strips_x, strips_y)) {
+        s.decode(lane, strips_x, W);
+        const int img = s.img, x0 = s.x0, y0 = s.y0, x = s.x, ncols = s.ncols;
+        const float cx = s.cx(H);
         const int classes = objects + 1;
-
-        double a[KP][5];
-#pragma unroll
-        for (int j = 0; j < KP; ++j)
-#pragma unroll
-            for (int c = 0; c < 5; ++c) a[j][c] = 0.0;
-        int cur = 0;
-
-        auto flush = [&]() {
-            if (cur > 0) {
-                double* dst = acc_lds + (size_t)(cur - 1) * KP * 5;
-#pragma unroll
-                for (int j = 0; j < KP; ++j)
-#pragma unroll
-                    for (int c = 0; c < 5; ++c) {
-                        atomicAdd(dst + j * 5 + c, a[j][c]);
-                        a[j][c] = 0.0;
-                    }
-            }
-        };
+        LsAcc<KP> acc(acc_lds);
 
         const int y_end = min(y0 + ROWS, H);
         // with given labels a row segment without a non-zero label contributes nothing: its records are not read.  The strip's labels are
@@ -118,51 +188,22 @@ __global__ __launch_bounds__(256) void ls_accumulate_kernel(const float* __restr
                     }
                 }
             }
-            if (lab != cur) {
-                flush();
-                cur = lab;
-            }
-#ifdef LS_NOCOMPUTE
-            if (lab > 250) {
-#else
+            acc.enter(lab);
             if (lab > 0) {
-#endif
                 const float cy = ((float)y + 0.5f) / (float)H;
 #pragma unroll
                 for (int j = 0; j < KP; ++j) {
-                    float dy = px[dir_off + 2 * j], dx = px[dir_off + 2 * j + 1];
-                    float cf = px[conf_off + j];
-#ifdef LS_NOSOFTPLUS
-                    float w = fmaxf(cf, 0.f);
-#else
-                    float w = sigmoid ? 1.0f / (1.0f + expf(-cf))                    // sigmoid_weights=True (:32-33, sigmoid_scale = 1)
-                                      : fmaxf(cf, 0.f) + log1pf(expf(-fabsf(cf)));   // softplus (:35)
-#endif
-                    float nrm = sqrtf(dy * dy + dx * dx);
-                    float ny = (nrm > 0.f) ? dy / nrm : 0.f;  // divide_no_nan (:90)
-                    float nx = (nrm > 0.f) ? dx / nrm : 0.f;
-                    float r00 = (1.0f - ny * ny) * w;
-                    float r01 = (0.0f - ny * nx) * w;
-                    float r11 = (1.0f - nx * nx) * w;
-                    float q0 = r00 * cy + r01 * cx;  // (:103-105)
-                    float q1 = r01 * cy + r11 * cx;
-                    a[j][0] += (double)r00;
-                    a[j][1] += (double)r01;
-                    a[j][2] += (double)r11;
-                    a[j][3] += (double)q0;
-                    a[j][4] += (double)q1;
+                    const float dy = px[dir_off + 2 * j], dx = px[dir_off + 2 * j + 1];
+                    const float w = ls_weight_exact(px[conf_off + j], sigmoid);
+                    const float2 n = ls_normal_exact(dy, dx);
+                    ls_add_terms(acc.a[j], n.x, n.y, w, cy, cx);
                 }
             }
             __builtin_amdgcn_wave_barrier();  // all lanes done reading before the next row overwrites
         }
-        flush();
+        acc.flush();
     }
-    __syncthreads();
-    double* gdst = sums + (size_t)img * nacc;
-    for (int i = tid; i < nacc; i += blockDim.x) {
-        double v = acc_lds[i];
-        if (v != 0.0) atomicAdd(gdst + i, v);
-    }
+    ls_table_commit(acc_lds, nacc, sums + (size_t)s.img * nacc);
 }
 
 // Fast path for the production record [9 logits | 18 directions | 9 confidences] (ld = 36, 8 objects, 9 keypoints): same strip
@@ -187,23 +228,16 @@ __global__ __launch_bounds__(256) void ls_accumulate36_kernel(const float* __res
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     constexpr int nacc = OBJ * KP * 5;
-    for (int i = tid; i < nacc; i += blockDim.x) acc_lds[i] = 0.0;
-    __syncthreads();
+    ls_table_zero(acc_lds, nacc);
 
-    const int strips_per_img = strips_x * strips_y;
-    const int blocks_per_img = (strips_per_img + WAVES - 1) / WAVES;
-    const int img = blockIdx.x / blocks_per_img;
-    const int sidx = (blockIdx.x % blocks_per_img) * WAVES + wave;
     float4* wstage = stage + (size_t)wave * 64 * NV;
-
-    if (sidx < strips_per_img) {
-        const int sy = sidx / strips_x, sx = sidx % strips_x;
-        const int x0 = sx * 64, y0 = sy * ROWS;
-        const int x = x0 + lane;
-        const int ncols = min(64, W - x0);
+    LsStrip s;
+    if (s.find(wave, strips_x, strips_y)) {
+        s.decode(lane, strips_x, W);
+        const int img = s.img, x0 = s.x0, y0 = s.y0, ncols = s.ncols;
         const int nvec = ncols * NV;
         const int nrows = min(ROWS, H - y0);
-        const float cx = ((float)x + 0.5f) / (float)H;
+        const float cx = s.cx(H);
 
         // ---- the strip's labels and its row mask, before any record is requested ----
         // lw[k] of lane l holds the four labels of row 4k + (l >> 4), columns 4 (l & 15) .. + 3 (a label outside the image reads as 0).
@@ -237,25 +271,7 @@ __global__ __launch_bounds__(256) void ls_accumulate36_kernel(const float* __res
             }
         }
 
-        double a[KP][5];
-#pragma unroll
-        for (int j = 0; j < KP; ++j)
-#pragma unroll
-            for (int c = 0; c < 5; ++c) a[j][c] = 0.0;
-        int cur = 0;
-        auto flush = [&]() {
-            if (cur > 0) {
-                double* dst = acc_lds + (size_t)(cur - 1) * KP * 5;
-#pragma unroll
-                for (int j = 0; j < KP; ++j)
-#pragma unroll
-                    for (int c = 0; c < 5; ++c) {
-                        atomicAdd(dst + j * 5 + c, a[j][c]);
-                        a[j][c] = 0.0;
-                    }
-            }
-        };
-
+        LsAcc<KP> acc(acc_lds);
         float4 pre[NV];
         auto issue = [&](int ry) {
             const float4* g = reinterpret_cast<const float4*>(field + (((size_t)img * H + y0 + ry) * W + x0) * LD);
@@ -300,10 +316,7 @@ __global__ __launch_bounds__(256) void ls_accumulate36_kernel(const float* __res
             int lab = 0;
             if (LAB) {
                 lab = label_of(ry);
-                if (ry != prev + 1) {  // rows in between were skipped: every lane's label was 0 there, which ends its run as before
-                    flush();
-                    cur = 0;
-                }
+                if (ry != prev + 1) acc.enter(0);  // rows in between were skipped: every lane's label was 0 there, which ends its run as before
             } else {
                 float best = r[0];
 #pragma unroll
@@ -311,51 +324,29 @@ __global__ __launch_bounds__(256) void ls_accumulate36_kernel(const float* __res
                     if (r[k] > best) { best = r[k]; lab = k; }
                 if (lane >= ncols) lab = 0;
             }
-            if (lab != cur) {
-                flush();
-                cur = lab;
-            }
-#ifdef LS_NOCOMPUTE
-            if (lab > 250) {
-#else
+            acc.enter(lab);
             if (lab > 0) {
-#endif
                 const float cy = ((float)(y0 + ry) + 0.5f) / (float)H;
 #pragma unroll
                 for (int j = 0; j < KP; ++j) {
-                    const float dy = r[9 + 2 * j], dx = r[9 + 2 * j + 1];
-                    const float cf = r[27 + j];
-                    // softplus (:35) = max(x,0) + log1p(exp(-|x|)) on the hardware exp2 / log2 units: t = exp(-|x|) in (0,1], and
-                    // log1p(t) = log(u) + (t - (u - 1)) / u with u = fl(1 + t) restores the bits the addition drops (error ~1e-7 of w;
-                    // the libm calls of the generic kernel cost as much as the whole memory stream)
-                    const float w = softplus_fast(cf);
-                    const float n2 = dy * dy + dx * dx;
-                    const float inv = (n2 > 0.f) ? __frsqrt_rn(n2) : 0.f;  // divide_no_nan (:90); one reciprocal square root for both components
-                    const float ny = dy * inv, nx = dx * inv;
-                    const float r00 = (1.0f - ny * ny) * w;
-                    const float r01 = (0.0f - ny * nx) * w;
-                    const float r11 = (1.0f - nx * nx) * w;
-                    const float q0 = r00 * cy + r01 * cx;  // (:103-105)
-                    const float q1 = r01 * cy + r11 * cx;
-                    a[j][0] += (double)r00;
-                    a[j][1] += (double)r01;
-                    a[j][2] += (double)r11;
-                    a[j][3] += (double)q0;
-                    a[j][4] += (double)q1;
+                    const float w = softplus_fast(r[27 + j]);  // softplus (:35)
+                    const float2 n = ls_normal_fast(r[9 + 2 * j], r[9 + 2 * j + 1]);
+                    ls_add_terms(acc.a[j], n.x, n.y, w, cy, cx);
                 }
             }
             __builtin_amdgcn_wave_barrier();  // all lanes done reading before the next row overwrites
             prev = ry;
             ry = nxt;
         }
-        flush();
+        acc.flush();
     }
-    __syncthreads();
-    double* gdst = sums + (size_t)img * nacc;
-    for (int i = tid; i < nacc; i += blockDim.x) {
-        double v = acc_lds[i];
-        if (v != 0.0) atomicAdd(gdst + i, v);
-    }
+    ls_table_commit(acc_lds, nacc, sums + (size_t)s.img * nacc);
+}
+
+// x = [[a,b],[b,c]]^-1 t for a regular symmetric system, det = a c - b^2 (each kernel keeps its own rank test)
+__device__ __forceinline__ void solve_sym2x2(double a, double b, double c, double det, double t0, double t1, double& x0, double& x1) {
+    x0 = (c * t0 - b * t1) / det;
+    x1 = (a * t1 - b * t0) / det;
 }
 
 // p = pinv([[S00,S01],[S01,S11]]) [T0,T1]^T * H   (voting_layers_2d.py:116-122);
@@ -373,9 +364,7 @@ __global__ void ls_solve_kernel(const double* __restrict__ sums, int total, int 
     double smax = fmax(fabs(l1), fabs(l2));
     if (smax > 0.0) {
         if (fabs(l2) > rcond * smax && fabs(l1) > rcond * smax) {
-            double det = a * c - b * b;
-            p0 = (c * t0 - b * t1) / det;
-            p1 = (a * t1 - b * t0) / det;
+            solve_sym2x2(a, b, c, a * c - b * b, t0, t1, p0, p1);
         } else {
             // rank one: keep only the dominant eigen-pair
             double lam = (fabs(l1) >= fabs(l2)) ? l1 : l2;
@@ -413,12 +402,43 @@ __global__ void ls_bwd_prepare_kernel(const double* __restrict__ sums, const flo
     const double tr = a + c;
     double p0 = 0, p1 = 0, u0 = 0, u1 = 0;
     if (tr > 0.0 && fabs(det) > 1e-12 * tr * tr) {  // regular system; a degenerate one passes no gradient
-        p0 = (c * t0 - b * t1) / det;
-        p1 = (a * t1 - b * t0) / det;
-        u0 = (c * g0 - b * g1) / det;
-        u1 = (a * g1 - b * g0) / det;
+        solve_sym2x2(a, b, c, det, t0, t1, p0, p1);
+        solve_sym2x2(a, b, c, det, g0, g1, u0, u1);
     }
     pu[4 * i] = (float)p0; pu[4 * i + 1] = (float)p1; pu[4 * i + 2] = (float)u0; pu[4 * i + 3] = (float)u1;
+}
+
+// One keypoint of one pixel: the gradient of its direction pair and confidence.  The kernels differ only in how values move, so they hand
+// in readers: dir() -> (dy, dx) and entry() -> the keypoint's (p0, p1, u0, u1) are read for a labelled pixel only, coef() -> the
+// regulariser's coefficient only where it applies (reg).
+struct LsGrad { float dy, dx, cf; };
+template <class Dir, class Entry, class Coef>
+__device__ __forceinline__ LsGrad ls_bwd_keypoint(float cf, int lab, bool reg, float cy, float cx, Dir dir, Entry entry, Coef coef) {
+    const float sg = 1.f / (1.f + __expf(-cf));
+    float gdy = 0.f, gdx = 0.f, gcf = 0.f;
+    if (lab > 0) {
+        const float2 d = dir();
+        const float dy = d.x, dx = d.y;
+        const float w = softplus_fast(cf);
+        const float nrm = sqrtf(dy * dy + dx * dx);
+        const float4 pu = entry();
+        const float p0 = pu.x, p1 = pu.y, u0 = pu.z, u1 = pu.w;
+        const float e0 = cy - p0, e1 = cx - p1;
+        if (nrm > 0.f) {
+            const float inr = 1.f / nrm;
+            const float ny = dy * inr, nx = dx * inr;
+            const float un = u0 * ny + u1 * nx, en = e0 * ny + e1 * nx, ue = u0 * e0 + u1 * e1;
+            gcf = (ue - un * en) * sg;
+            const float ln0 = -w * (u0 * en + e0 * un), ln1 = -w * (u1 * en + e1 * un);
+            const float nl = ny * ln0 + nx * ln1;
+            gdy = (ln0 - ny * nl) * inr;
+            gdx = (ln1 - nx * nl) * inr;
+        } else {
+            gcf = (u0 * e0 + u1 * e1) * sg;  // n = 0: R = w I
+        }
+    }
+    if (reg) gcf += coef() * sg;
+    return {gdy, gdx, gcf};
 }
 
 template <int KP>
@@ -444,39 +464,21 @@ __global__ void ls_bwd_kernel(const float* __restrict__ field, int ld, int dir_o
         const float cy = ((float)y + 0.5f) / (float)H, cx = ((float)x + 0.5f) / (float)H;
         const float* px = field + i * ld;
         const float* tab = pu + ((size_t)b * objects + (lab > 0 ? lab - 1 : 0)) * KP * 4;
+        const bool reg = rlab > 0 && conf_coef;
 #pragma unroll
         for (int j = 0; j < KP; ++j) {
-            const float cf = px[conf_off + j];
-            const float sg = 1.f / (1.f + __expf(-cf));
-            float gdy = 0.f, gdx = 0.f, gcf = 0.f;
-            if (lab > 0) {
-                const float dy = px[dir_off + 2 * j], dx = px[dir_off + 2 * j + 1];
-                const float w = softplus_fast(cf);
-                const float nrm = sqrtf(dy * dy + dx * dx);
-                const float p0 = tab[4 * j], p1 = tab[4 * j + 1], u0 = tab[4 * j + 2], u1 = tab[4 * j + 3];
-                const float e0 = cy - p0, e1 = cx - p1;
-                if (nrm > 0.f) {
-                    const float inr = 1.f / nrm;
-                    const float ny = dy * inr, nx = dx * inr;
-                    const float un = u0 * ny + u1 * nx, en = e0 * ny + e1 * nx, ue = u0 * e0 + u1 * e1;
-                    gcf = (ue - un * en) * sg;
-                    const float ln0 = -w * (u0 * en + e0 * un), ln1 = -w * (u1 * en + e1 * un);
-                    const float nl = ny * ln0 + nx * ln1;
-                    gdy = (ln0 - ny * nl) * inr;
-                    gdx = (ln1 - nx * nl) * inr;
-                } else {
-                    gcf = (u0 * e0 + u1 * e1) * sg;  // n = 0: R = w I
-                }
-            }
-            if (rlab > 0 && conf_coef) gcf += conf_coef[b * KP + j] * sg;
+            const LsGrad d = ls_bwd_keypoint(px[conf_off + j], lab, reg, cy, cx,
+                                             [&] { return make_float2(px[dir_off + 2 * j], px[dir_off + 2 * j + 1]); },
+                                             [&] { return make_float4(tab[4 * j], tab[4 * j + 1], tab[4 * j + 2], tab[4 * j + 3]); },
+                                             [&] { return conf_coef[b * KP + j]; });
             if (accumulate) {
-                g[ddir_off + 2 * j] += gdy;
-                g[ddir_off + 2 * j + 1] += gdx;
-                g[dconf_off + j] += gcf;
+                g[ddir_off + 2 * j] += d.dy;
+                g[ddir_off + 2 * j + 1] += d.dx;
+                g[dconf_off + j] += d.cf;
             } else {
-                g[ddir_off + 2 * j] = gdy;
-                g[ddir_off + 2 * j + 1] = gdx;
-                g[dconf_off + j] = gcf;
+                g[ddir_off + 2 * j] = d.dy;
+                g[ddir_off + 2 * j + 1] = d.dx;
+                g[dconf_off + j] = d.cf;
             }
         }
     }
@@ -520,35 +522,16 @@ __global__ void ls_bwd36_kernel(const float* __restrict__ field, const uint8_t* 
             out[4 * q] = v.x; out[4 * q + 1] = v.y; out[4 * q + 2] = v.z; out[4 * q + 3] = v.w;
         }
         const float* tab = pu + ((size_t)b * objects + (lab > 0 ? lab - 1 : 0)) * KP * 4;
+        const bool reg = rlab > 0 && conf_coef;
 #pragma unroll
         for (int j = 0; j < KP; ++j) {
-            const float cf = rec[27 + j];
-            const float sg = 1.f / (1.f + __expf(-cf));
-            float gdy = 0.f, gdx = 0.f, gcf = 0.f;
-            if (lab > 0) {
-                const float dy = rec[9 + 2 * j], dx = rec[9 + 2 * j + 1];
-                const float w = softplus_fast(cf);
-                const float nrm = sqrtf(dy * dy + dx * dx);
-                const float4 pv = *reinterpret_cast<const float4*>(tab + 4 * j);
-                const float p0 = pv.x, p1 = pv.y, u0 = pv.z, u1 = pv.w;
-                const float e0 = cy - p0, e1 = cx - p1;
-                if (nrm > 0.f) {
-                    const float inr = 1.f / nrm;
-                    const float ny = dy * inr, nx = dx * inr;
-                    const float un = u0 * ny + u1 * nx, en = e0 * ny + e1 * nx, ue = u0 * e0 + u1 * e1;
-                    gcf = (ue - un * en) * sg;
-                    const float ln0 = -w * (u0 * en + e0 * un), ln1 = -w * (u1 * en + e1 * un);
-                    const float nl = ny * ln0 + nx * ln1;
-                    gdy = (ln0 - ny * nl) * inr;
-                    gdx = (ln1 - nx * nl) * inr;
-                } else {
-                    gcf = (u0 * e0 + u1 * e1) * sg;  // n = 0: R = w I
-                }
-            }
-            if (rlab > 0 && conf_coef) gcf += conf_coef[b * KP + j] * sg;
-            out[2 * j] += gdy;
-            out[2 * j + 1] += gdx;
-            out[18 + j] += gcf;
+            const LsGrad d = ls_bwd_keypoint(rec[27 + j], lab, reg, cy, cx,
+                                             [&] { return make_float2(rec[9 + 2 * j], rec[9 + 2 * j + 1]); },
+                                             [&] { return *reinterpret_cast<const float4*>(tab + 4 * j); },
+                                             [&] { return conf_coef[b * KP + j]; });
+            out[2 * j] += d.dy;
+            out[2 * j + 1] += d.dx;
+            out[18 + j] += d.cf;
         }
 #pragma unroll
         for (int q = 0; q < 7; ++q) g4[q] = make_float4(out[4 * q], out[4 * q + 1], out[4 * q + 2], out[4 * q + 3]);
@@ -648,14 +631,15 @@ __global__ void kp_reproj_loss_kernel(const float* __restrict__ coords_yx, const
     if (threadIdx.x == 0) *loss_out = na > 0.0 ? red[0] / ((double)kp * na) : 0.0;
 }
 
+// the production record [9 logits | 18 directions | 9 confidences], which has kernels of its own; CP_LS_GENERIC (read on every call)
+// sends it to the generic ones
+bool is_record36(int ld, int dir_off, int conf_off) { return ld == 36 && dir_off == 9 && conf_off == 27 && !getenv("CP_LS_GENERIC"); }
+
 }  // namespace
 
 extern "C" size_t cp_ls_vote_workspace_bytes(int batch, int objects, int kp) {
     return (size_t)batch * objects * kp * 5 * sizeof(double);
 }
-
-extern "C" int cp_ls_vote_w_f32(const float* field, int ld, int seg_off, int dir_off, int conf_off, const uint8_t* labels, int batch, int h, int w,
-                                int objects, int kp, int sigmoid_weights, double* sums_ws, float* keypoints, void* stream);
 
 extern "C" int cp_ls_vote_f32(const float* field, int ld, int seg_off, int dir_off, int conf_off, const uint8_t* labels,
                               int batch, int h, int w, int objects, int kp, double* sums_ws, float* keypoints,
@@ -679,7 +663,7 @@ extern "C" int cp_ls_vote_w_f32(const float* field, int ld, int seg_off, int dir
     int strips_x = (w + 63) / 64, strips_y = (h + ROWS - 1) / ROWS;
     int blocks_per_img = (strips_x * strips_y + WAVES - 1) / WAVES;
     size_t lds = sizeof(double) * objects * kp * 5 + sizeof(float) * WAVES * 64 * ld;
-    if (!sigmoid_weights && ld == 36 && seg_off == 0 && dir_off == 9 && conf_off == 27 && objects == 8 && !getenv("CP_LS_GENERIC")) {  // the production record
+    if (!sigmoid_weights && seg_off == 0 && objects == 8 && is_record36(ld, dir_off, conf_off)) {
         if (labels)
             CP_LAUNCH(ls_accumulate36_kernel<true>, dim3(batch * blocks_per_img), dim3(256), lds, st, field, labels, batch, h, w, sums_ws, strips_x, strips_y);
         else
@@ -692,7 +676,6 @@ extern "C" int cp_ls_vote_w_f32(const float* field, int ld, int seg_off, int dir
     CP_LAUNCH(ls_solve_kernel, dim3((total + 255) / 256), dim3(256), 0, st, sums_ws, total, h, keypoints);
     return cp::check_launch("cp_ls_vote_f32");
 }
-
 
 extern "C" int cp_ls_vote_bwd_f32(const float* field, int ld, int dir_off, int conf_off, const uint8_t* labels, int batch, int h, int w,
                                   int objects, int kp, const double* sums_ws, const float* dkeypoints, float* pu_ws,
@@ -711,9 +694,9 @@ extern "C" int cp_ls_vote_bwd_f32(const float* field, int ld, int dir_off, int c
     const long long px = (long long)batch * h * w;
     long long blocks = (px + 255) / 256;
     if (blocks > 256 * 16) blocks = 256 * 16;
-    const bool rec36 = ld == 36 && dir_off == 9 && conf_off == 27 && dld % 4 == 0 && ddir_off % 4 == 0 && dconf_off == ddir_off + 18 && ddir_off + 28 <= dld &&
-                       (((uintptr_t)field | (uintptr_t)dfield | (uintptr_t)pu_ws) & 15) == 0 && !getenv("CP_LS_GENERIC");
-    if (rec36)   // the production record; in overwrite mode the float behind the 27 gradient values (padding of the row) is zeroed with them
+    const bool rec36 = is_record36(ld, dir_off, conf_off) && dld % 4 == 0 && ddir_off % 4 == 0 && dconf_off == ddir_off + 18 && ddir_off + 28 <= dld &&
+                       (((uintptr_t)field | (uintptr_t)dfield | (uintptr_t)pu_ws) & 15) == 0;
+    if (rec36)   // in overwrite mode the float behind the 27 gradient values (padding of the row) is zeroed with them
         CP_LAUNCH(ls_bwd36_kernel, dim3((unsigned)blocks), dim3(256), 0, st, field, labels, batch, h, w, objects, pu_ws, reg_labels, conf_coef, dfield, dld,
                   ddir_off, accumulate);
     else
