@@ -822,6 +822,36 @@ int cp_pose_eval_est_tile(void);
 int cp_pose_eval_f32(const float* points, const int32_t* counts, const int32_t* symmetric, int objects, int vmax, const float* pairs, int batch,
                      float allowed_error_2d, void* workspace, float* records, float* point_err2, float* point_err3, void* stream);
 
+/* ---- BOP pose errors with object symmetries (csrc/bop_errors.hip, csrc/bop_math.h) -------------------------------------------------------
+ * For every pair of an estimated pose P^ and a ground-truth pose P_ of one object, over the object's symmetry transforms S and the vertices x of
+ * its evaluation mesh:  e_MSSD = min_S max_x |P^ x - P_ S x| (millimetres),  e_MSPD = min_S max_x |proj_K(P^ x) - proj_K(P_ S x)| (pixels), with
+ * the projection of cp_pose_eval_f32 (a general 3x3 K, pixel 0 where the projective z is exactly 0).  Everything is device memory and fp32 unless
+ * noted.
+ *   points        [objects][vmax][3]  evaluation meshes; rows counts[o] .. vmax-1 are never read
+ *   counts        int32 [objects]     vertices per mesh, clamped to [0, vmax] in the kernel; an object without vertices gives +inf
+ *   syms          [objects][smax][12] symmetry transforms, row-major 3x4 [R|t], the identity included by the caller; rows sym_counts[o] ..
+ *                                     smax-1 are never read
+ *   sym_counts    int32 [objects]     transforms per object, clamped to [0, smax]
+ *   pairs         [npairs][36]        the record of cp_pose_eval_f32: estimated pose (12, row-major 3x4), ground-truth pose (12), K (9,
+ *                                     row-major); the last three floats are not read
+ *   object_index  int32 [npairs]      the object of each pair; an index outside [0, objects) gives +inf
+ *   errors        [npairs][2]         (e_MSSD, e_MSPD).  (+inf, +inf) where the estimate is the zero pose: |sum of its 12 entries| < 1e-4, as
+ *                                     cp_pose_eval_f32 decides it, or a sum that is not finite
+ *   per_symmetry  optional [npairs][smax][2] (NULL in production): the two maxima under every symmetry; +inf at and beyond sym_counts[o] and for
+ *                                     pairs whose errors are +inf
+ *   workspace     cp_bop_errors_workspace_bytes(npairs, smax) bytes, 8-byte aligned (0 for non-positive arguments)
+ * P_ S is composed once per (pair, symmetry) in fp64 and rounded once to fp32; distances are direct coordinate differences; the maximum is taken
+ * over squared distances with one root per (pair, symmetry).  No atomics: two calls on the same input give bit-identical output.  vmax <= 2^24,
+ * smax <= 2^16, npairs * ceil(smax / cp_bop_errors_sym_group()) < 2^24 per call.  cp_bop_errors_tile(): the vertices a block takes per step;
+ * cp_bop_errors_sym_group(): the symmetries a block takes (tests place their sizes by both).  Added in ABI 302 without changing any earlier entry
+ * point. */
+size_t cp_bop_errors_workspace_bytes(int npairs, int smax);
+int cp_bop_errors_tile(void);
+int cp_bop_errors_sym_group(void);
+int cp_bop_errors_f32(const float* points, const int32_t* counts, int objects, int vmax, const float* syms, const int32_t* sym_counts, int smax,
+                      const float* pairs, const int32_t* object_index, int npairs, void* workspace, float* errors, float* per_symmetry,
+                      void* stream);
+
 /* ---- device PnP (csrc/pnp.hip, csrc/pnp_math.h) -----------------------------------------------------------------------------------
  * Voted keypoints -> [3,4] poses for every (image, object) pair of a batch: casapose_amd/pose_estimation/pnp.py restated in fp64.  One block per
  * pair, one thread per hypothesis: EPnP on a 5-point set, inliers at <= reprojection_error over all n points; the consensus is the hypothesis
