@@ -11,8 +11,9 @@ targets, matching and recall are small and run on the host in NumPy.  There is n
 
 An estimate is correct for MSSD at theta when e_MSSD < theta * diameter, theta in 0.05 .. 0.50, and for MSPD at theta when e_MSPD < theta * r,
 theta in 5 .. 50 and r = image_width / 640.  Recall at theta is matched targets / all targets; AR_MSSD and AR_MSPD are the means of recall over
-their ten thresholds.  VSD needs the sensor's depth images, which the converted layout does not carry, so BOP's three-term AR is not computed:
-the mean of the two terms is reported as AR_MSSD_MSPD.
+their ten thresholds.  The mean of the two terms is reported as AR_MSSD_MSPD.  VSD, the third term of BOP's AR, needs the sensor's depth images and
+a renderer: `score(..., vsd=...)` hands the same pairs to pose_estimation/bop_vsd.py and then also reports AR_VSD and AR = (AR_VSD + AR_MSSD +
+AR_MSPD) / 3; without it no value is called AR.
 """
 from __future__ import annotations
 
@@ -284,12 +285,15 @@ def match_and_recall(groups: Iterable[Tuple[int, int, np.ndarray, np.ndarray]], 
 
 
 def score(results: Dict[str, np.ndarray], gts: Dict[Tuple[int, int], List[dict]], cameras: Dict[Tuple[int, int], np.ndarray], scorer,
-          object_ids: Sequence[int], diameters: Dict[int, float], targets: Optional[Iterable[dict]] = None, image_width: float = 640.0) -> dict:
+          object_ids: Sequence[int], diameters: Dict[int, float], targets: Optional[Iterable[dict]] = None, image_width: float = 640.0,
+          vsd=None) -> dict:
     """Scores of a result file (`read_bop_results`) against the ground truth.  gts and cameras are keyed by (scene_id, im_id): the instance
     lists and camera matrices load_json_info gives per scene.  scorer.errors(est, gt, K, object_index) is a DeviceBopScorer whose mesh o is
     object object_ids[o].  Per (scene, image, object) with targets: the estimates are sorted by score descending with ties in file order, rows
     that are "no estimate" dropped, the first inst_count kept, and every kept estimate is paired with every candidate instance; all pairs go to
-    the device in one call."""
+    the device in one call.  vsd (a bop_vsd.BopVsd, or anything with its `errors` and `taus`): the same pairs in the same order, with their
+    (scene_id, im_id) and diameters, also go to vsd.errors -> [pairs, ntau], and the result gains "AR_VSD", "recall_vsd" ([tau][theta]) and
+    "AR", over all objects and per object; without it the result is what it was before VSD existed."""
     wanted = select_targets(gts, targets)
     index_of = {int(o): i for i, o in enumerate(object_ids)}
     rows: Dict[Tuple[int, int, int], List[int]] = {}
@@ -298,7 +302,7 @@ def score(results: Dict[str, np.ndarray], gts: Dict[Tuple[int, int], List[dict]]
         key = (int(results["scene_id"][i]), int(results["im_id"][i]), int(results["obj_id"][i]))
         if real[i] and key in wanted:
             rows.setdefault(key, []).append(i)
-    est, gt, cams, obj_index, shapes = [], [], [], [], []
+    est, gt, cams, obj_index, shapes, image_keys = [], [], [], [], [], []
     for key, (count, cand) in wanted.items():
         if key[2] not in index_of:
             raise KeyError("object %d has targets but no evaluation mesh" % key[2])
@@ -312,6 +316,7 @@ def score(results: Dict[str, np.ndarray], gts: Dict[Tuple[int, int], List[dict]]
                 gt.append(np.hstack([np.asarray(g["R"], np.float64).reshape(3, 3), np.asarray(g["t"], np.float64).reshape(3, 1)]))
                 cams.append(np.asarray(cameras[key[:2]], np.float64).reshape(3, 3))
                 obj_index.append(index_of[key[2]])
+                image_keys.append(key[:2])
     if est:
         mssd, mspd = scorer.errors(np.stack(est), np.stack(gt), np.stack(cams), np.asarray(obj_index))
     else:
@@ -322,6 +327,17 @@ def score(results: Dict[str, np.ndarray], gts: Dict[Tuple[int, int], List[dict]]
         at += e * g
     out = match_and_recall(groups, diameters, image_width)
     out["pairs"] = int(at)
+    if vsd is not None:
+        from .bop_vsd import add_vsd_scores, match_and_recall_vsd
+
+        pair_diameters = [float(diameters[object_ids[o]]) for o in obj_index]
+        e = np.asarray(vsd.errors(np.stack(est), np.stack(gt), np.stack(cams), np.asarray(obj_index), image_keys, pair_diameters) if est
+                       else np.zeros((0, len(vsd.taus))), np.float64)
+        vsd_groups, at = [], 0
+        for key, count, ne, ng in shapes:
+            vsd_groups.append((key[2], count, e[at:at + ne * ng].reshape(ne, ng, e.shape[1])))
+            at += ne * ng
+        add_vsd_scores(out, match_and_recall_vsd(vsd_groups), vsd.taus)
     return out
 
 

@@ -957,8 +957,10 @@ int cp_render_scenes_host_f32(const double* records, int b, int oc, int H, int W
  * vertex at Z < near, with a face index outside its object's vertices or projecting beyond 2^20 pixels is dropped whole and counted in
  * dropped_triangles; an instance whose object index or label is out of range renders nothing.  Integer atomics only: two calls with the same
  * inputs give the same bytes.  1 <= frames <= 65535, 1 <= instances_max <= 256, H, W <= 16384, 0 < near <= far, 0 <= sample_offset <= 1.
- * cp_render_masks_workspace_bytes returns 0 for sizes outside these limits.  cp_render_masks_host_u8 runs the same code serially on host
- * pointers and launches nothing: it works without a GPU.  Added in ABI 302 without changing any earlier entry point. */
+ * cp_render_masks_workspace_bytes returns 0 for sizes outside these limits.  After the call plane [frame][instance] of the workspace holds,
+ * per pixel, the bit pattern of the instance's own nearest fp32 depth (whether or not another instance occludes it there) or 0xffffffff where
+ * the instance was not hit; cp_vsd_counts_i32 reads the planes and the records' bbox_obj.  cp_render_masks_host_u8 runs the same code serially
+ * on host pointers and launches nothing: it works without a GPU.  Added in ABI 302 without changing any earlier entry point. */
 size_t cp_render_masks_workspace_bytes(int frames, int instances_max, int H, int W);
 int cp_render_masks_u8(const float* verts, const int32_t* vert_counts, int Vmax, const int32_t* faces, const int32_t* face_counts, int Tmax,
                        int objects, const double* cams, const int32_t* inst_counts, const int32_t* inst_obj, const int32_t* inst_label,
@@ -968,6 +970,30 @@ int cp_render_masks_host_u8(const float* verts, const int32_t* vert_counts, int 
                             int objects, const double* cams, const int32_t* inst_counts, const int32_t* inst_obj, const int32_t* inst_label,
                             const double* poses, int frames, int instances_max, int H, int W, double near, double far, double sample_offset,
                             uint8_t* label, int32_t* records, void* workspace, size_t workspace_bytes);
+
+/* ---- BOP's Visible Surface Discrepancy (csrc/vsd.hip, csrc/vsd_math.h) -------------------------------------------------------------------
+ * For every pair of a rendered estimate and a rendered ground-truth instance of one image, the integers BOP's VSD error is made of: the pixels
+ * of the visible union, of the visible intersection and, per tau, the intersection pixels whose cost |d_g - d_e| / diameter reaches tau (BOP19
+ * visibility with tolerance delta against the sensor's depth image; distances from the camera centre in fp64; the rules are listed in
+ * csrc/vsd_math.h).  The error e_k = (counts[2 + k] + counts[0] - counts[1]) / counts[0] is the caller's (pose_estimation/bop_vsd.py).
+ * Everything is device memory.
+ *   planes     uint32 [nplanes][H][W]   the workspace of cp_render_masks_u8 after the call, nplanes = frames * instances_max
+ *   records    int32 [nplanes][11]      its records; words 2-5 (bbox_obj: x, y, w, h) bound the pixels a plane is read at
+ *   depth      fp32 [images][H][W]      sensor depth in millimetres; a value that is not > 0 (0, negative, NaN) is missing
+ *   cams       fp64 [images][4]         fx, fy, cx, cy; pixel centres at integer coordinates
+ *   pairs      int32 [npairs][4]        (image, estimate plane, ground-truth plane, unused)
+ *   diameters  fp64 [npairs]            the object's diameter, which normalises the cost
+ *   taus       fp64 [ntau]              1 <= ntau <= 32, in any order
+ *   split      blocks per pair, 1 .. 64: a speed setting, the counts do not depend on it
+ *   counts     int32 [npairs][2 + ntau] zeroed inside the call: union, intersection, then one count per tau
+ * A pair walks the union of its two planes' boxes clipped to the image and nothing else.  A pair whose image or plane index is out of range,
+ * whose diameter is not > 0 or whose two boxes are empty leaves zeros.  Integer atomics only: two calls with the same inputs give the same
+ * bytes.  H, W <= 16384, npairs * split < 2^31, delta >= 0.  cp_vsd_tile(): the pixels a block takes per step (tests place their sizes by it).
+ * There is no host twin: the arithmetic's host coverage is csrc/vsd_selftest.cpp.  Added in ABI 302 without changing any earlier entry point. */
+int cp_vsd_tile(void);
+int cp_vsd_counts_i32(const uint32_t* planes, const int32_t* records, int nplanes, int H, int W, const float* depth, const double* cams, int images,
+                      const int32_t* pairs, const double* diameters, int npairs, double delta, const double* taus, int ntau, int split,
+                      int32_t* counts, void* stream);
 
 /* ---- keypoints and models_info of a mesh set (csrc/models.hip, csrc/model_math.h) --------------------------------------------------------
  * What the dataset converter needs per object and BOP archives do not hold (data_handler/model_prep.py): the axis-aligned box, the squared
