@@ -24,6 +24,13 @@ inline int grid_for(long long n) {
     return (int)(b < 1 ? 1 : (b > 256 * 16 ? 256 * 16 : b));
 }
 
+// THE label read of all five passes: a value above `objects` is background (it has no histogram record; callers in this tree pass arg-max labels,
+// which are in range, but the C ABI is public)
+__device__ __forceinline__ int label_at(const uint8_t* __restrict__ lab, long long i, int objects) {
+    const int l = lab[i];
+    return l > objects ? 0 : l;
+}
+
 __device__ __forceinline__ int find_root(const int* parent, int x) {
     int p = parent[x];
     while (p != x) {
@@ -51,7 +58,7 @@ __device__ __forceinline__ void unite(int* parent, int a, int b) {
 // root; tile-local roots (the only pixels that can end up as component roots) get their size counter zeroed here.
 constexpr int TW = 64, TH = 16;
 __global__ __launch_bounds__(256) void ccl_local(const uint8_t* __restrict__ lab, int* __restrict__ parent, int* __restrict__ count, int H, int W,
-                                                 int tiles_x, int tiles_y) {
+                                                 int tiles_x, int tiles_y, int objects) {
     __shared__ uint8_t sl[TH][TW];
     __shared__ int sp[TH * TW];
     __shared__ unsigned long long same_left[TH];
@@ -63,7 +70,7 @@ __global__ __launch_bounds__(256) void ccl_local(const uint8_t* __restrict__ lab
 #pragma unroll
     for (int r = 0; r < TH / 4; ++r) {
         const int ly = wave * (TH / 4) + r, y = y0 + ly, x = x0 + lane;
-        const int l = (y < H && x < W) ? lab[img + (size_t)y * W + x] : 0;
+        const int l = (y < H && x < W) ? label_at(lab, (long long)(img + (size_t)y * W + x), objects) : 0;
         const int left = __shfl_up(l, 1);
         const bool sl_ = lane > 0 && l != 0 && l == left;
         const unsigned long long SL = __ballot(sl_), FG = __ballot(l != 0);
@@ -102,7 +109,8 @@ __global__ __launch_bounds__(256) void ccl_local(const uint8_t* __restrict__ lab
 }
 
 // Pass 2: stitch the tiles along their borders -- one thread per border pixel (6 % of the image), one global union per overlap segment
-__global__ void ccl_border(const uint8_t* __restrict__ lab, int* __restrict__ parent, int B, int H, int W, int tiles_x, int tiles_y) {
+__global__ void ccl_border(const uint8_t* __restrict__ lab, int* __restrict__ parent, int B, int H, int W, int tiles_x, int tiles_y,
+                           int objects) {
     const long long nh = (long long)B * (tiles_y - 1) * W, nv = (long long)B * H * (tiles_x - 1);
     for (long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x; i < nh + nv; i += (long long)gridDim.x * blockDim.x) {
         if (i < nh) {   // first row of a tile against the last row of the tile above
@@ -110,8 +118,8 @@ __global__ void ccl_border(const uint8_t* __restrict__ lab, int* __restrict__ pa
             const long long q = i / W;
             const int y = ((int)(q % (tiles_y - 1)) + 1) * TH, n = (int)(q / (tiles_y - 1));
             const long long g = ((long long)n * H + y) * W + x;
-            const int l = lab[g];
-            if (!l || lab[g - W] != l) continue;
+            const int l = label_at(lab, g, objects);
+            if (!l || lab[g - W] != l) continue;   // l is a valid label: a raw neighbour that equals it is valid too
             // the segment's first pixel does it -- inside one tile column only: there both rows' left links are tile-local and already made
             if ((x % TW) != 0 && lab[g - 1] == l && lab[g - W - 1] == l) continue;
             unite(parent, (int)g, (int)(g - W));
@@ -121,7 +129,7 @@ __global__ void ccl_border(const uint8_t* __restrict__ lab, int* __restrict__ pa
             const long long q = k / H;
             const int x = ((int)(q % (tiles_x - 1)) + 1) * TW, n = (int)(q / (tiles_x - 1));
             const long long g = ((long long)n * H + y) * W + x;
-            const int l = lab[g];
+            const int l = label_at(lab, g, objects);
             if (!l || lab[g - 1] != l) continue;
             if ((y % TH) != 0 && lab[g - W] == l && lab[g - W - 1] == l) continue;
             unite(parent, (int)g, (int)(g - 1));
@@ -131,7 +139,7 @@ __global__ void ccl_border(const uint8_t* __restrict__ lab, int* __restrict__ pa
 
 // Pass 3: flatten, component sizes, and the list of component roots per image (what the selection pass walks instead of the image)
 __global__ void ccl_flatten_count(const uint8_t* __restrict__ lab, int* __restrict__ parent, int* __restrict__ count, int* __restrict__ nroots,
-                                  int* __restrict__ roots, long long hw, long long total) {
+                                  int* __restrict__ roots, long long hw, long long total, int objects) {
     // Sizes: one atomic per (wave, distinct root) instead of one per pixel -- a large component
     // would otherwise serialise hundreds of thousands of atomics on one address.
     const long long stride = (long long)gridDim.x * blockDim.x;
@@ -142,7 +150,7 @@ __global__ void ccl_flatten_count(const uint8_t* __restrict__ lab, int* __restri
         const long long i = it * stride + blockIdx.x * (long long)blockDim.x + threadIdx.x;
         int r = -1;
         bool is_root = false;
-        if (i < total && lab[i]) {
+        if (i < total && label_at(lab, i, objects)) {
             r = find_root(parent, (int)i);
             parent[i] = r;
             is_root = r == (int)i;
@@ -209,7 +217,7 @@ __global__ __launch_bounds__(256) void ccl_select(const uint8_t* __restrict__ la
     __syncthreads();
     for (int k = threadIdx.x; k < nr; k += 256) {
         const int i = list[k];
-        atomicAdd(&fg[lab[i] - 1], (unsigned)count[i]);
+        atomicAdd(&fg[label_at(lab, i, objects) - 1], (unsigned)count[i]);   // a root is a labelled pixel: never 0
     }
     __syncthreads();
     for (int pass = 0; pass <= rank; ++pass) {
@@ -218,7 +226,7 @@ __global__ __launch_bounds__(256) void ccl_select(const uint8_t* __restrict__ la
             int o;
             if (k < nr) {
                 const int i = list[k];
-                o = lab[i] - 1;
+                o = label_at(lab, i, objects) - 1;
                 key = comp_key(count[i], min_size, 0xFFFFFFFEu - (unsigned)((long long)i - n * hw));
             } else {   // bin 0 of object o: every pixel that is not the object
                 o = k - nr;
@@ -237,7 +245,7 @@ __global__ __launch_bounds__(256) void ccl_select(const uint8_t* __restrict__ la
 __global__ void ccl_write(const uint8_t* __restrict__ lab, const int* __restrict__ parent, const unsigned long long* __restrict__ stats,
                           int objects, long long hw, long long total, uint8_t* __restrict__ out) {
     for (long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x; i < total; i += (long long)gridDim.x * blockDim.x) {
-        const int l = lab[i];
+        const int l = label_at(lab, i, objects);
         uint8_t o = 0;
         if (l) {
             const unsigned long long second = stats[((i / hw) * objects + (l - 1)) * 3 + 2];
@@ -255,9 +263,39 @@ __global__ void ccl_write(const uint8_t* __restrict__ lab, const int* __restrict
 
 }  // namespace
 
-extern "C" size_t cp_ccl_workspace_bytes(int batch, int h, int w, int objects) {
-    size_t px = (size_t)batch * h * w;   // parent, size counters, root lists (hw slots per image), roots per image, 3 words per (image, object)
-    return px * sizeof(int) * 3 + ((size_t)batch * sizeof(int) + 63) / 64 * 64 + (size_t)batch * objects * 3 * sizeof(unsigned long long) + 128;
+namespace {
+// THE carve of the caller's workspace: cp_ccl_workspace_bytes, cp_ccl_workspace_layout and cp_ccl_filter_labels all take it from here.
+// Offsets from a 64-byte aligned base: parent, size counters and root lists (hw slots per image) are packed int32 arrays, the roots-per-image
+// counters and the 3 words per (image, object) start on 64-byte boundaries.  `bytes` ends with 64 bytes of slack: cp_ccl_filter_labels rounds a
+// base that is not 64-byte aligned up to the next boundary.  (Rounding 12 px up to 64 is what offsets cost over the absolute
+// addresses the filter used to align; it is paid from the slack, which was 128 bytes, so the total is never above px * 12 + up64(4 * batch) +
+// stats + 128, the size before the carve was shared.)
+struct CclWs {
+    size_t off[5];   // parent, count, roots, nroots, stats
+    size_t bytes;
+};
+inline CclWs ccl_carve(int batch, int h, int w, int objects) {
+    const size_t px = (size_t)batch * h * w;
+    auto up64 = [](size_t n) { return (n + 63) / 64 * 64; };
+    CclWs ws;
+    ws.off[0] = 0;
+    ws.off[1] = px * sizeof(int);
+    ws.off[2] = 2 * px * sizeof(int);
+    ws.off[3] = up64(3 * px * sizeof(int));
+    ws.off[4] = up64(ws.off[3] + (size_t)batch * sizeof(int));
+    ws.bytes = ws.off[4] + (size_t)batch * objects * 3 * sizeof(unsigned long long) + 64;
+    return ws;
+}
+}  // namespace
+
+extern "C" size_t cp_ccl_workspace_bytes(int batch, int h, int w, int objects) { return ccl_carve(batch, h, w, objects).bytes; }
+
+extern "C" int cp_ccl_workspace_layout(int batch, int h, int w, int objects, size_t* offsets) {
+    CP_REQUIRE(offsets, "cp_ccl_workspace_layout: null pointer");
+    CP_REQUIRE(batch > 0 && h > 0 && w > 0 && objects > 0 && objects < 255, "cp_ccl_workspace_layout: bad sizes");
+    const CclWs ws = ccl_carve(batch, h, w, objects);
+    for (int i = 0; i < 5; ++i) offsets[i] = ws.off[i];
+    return 0;
 }
 
 extern "C" int cp_ccl_filter_labels(const uint8_t* labels_in, int batch, int h, int w, int objects, int min_size, int rank, void* ws,
@@ -268,20 +306,20 @@ extern "C" int cp_ccl_filter_labels(const uint8_t* labels_in, int batch, int h, 
     const long long hw = (long long)h * w, total = hw * batch;
     CP_REQUIRE(total < (1LL << 31) && hw < 0xFFFFFFF0LL, "cp_ccl_filter_labels: too many pixels for 32-bit component ids");
     hipStream_t st = (hipStream_t)stream;
-    int* parent = reinterpret_cast<int*>(ws);
-    int* count = parent + total;
-    int* roots = count + total;
-    uintptr_t np = (reinterpret_cast<uintptr_t>(roots + total) + 63) & ~(uintptr_t)63;
-    int* nroots = reinterpret_cast<int*>(np);
-    uintptr_t sp = (np + (size_t)batch * sizeof(int) + 63) & ~(uintptr_t)63;
-    unsigned long long* stats = reinterpret_cast<unsigned long long*>(sp);
+    const CclWs lay = ccl_carve(batch, h, w, objects);
+    const uintptr_t base = (reinterpret_cast<uintptr_t>(ws) + 63) & ~(uintptr_t)63;
+    int* parent = reinterpret_cast<int*>(base + lay.off[0]);
+    int* count = reinterpret_cast<int*>(base + lay.off[1]);
+    int* roots = reinterpret_cast<int*>(base + lay.off[2]);
+    int* nroots = reinterpret_cast<int*>(base + lay.off[3]);
+    unsigned long long* stats = reinterpret_cast<unsigned long long*>(base + lay.off[4]);
     const int g = grid_for(total);
     if (hipMemsetAsync(nroots, 0, sizeof(int) * (size_t)batch, st) != hipSuccess) return cp::check_launch("cp_ccl_filter_labels memset");
     const int tiles_x = (w + TW - 1) / TW, tiles_y = (h + TH - 1) / TH;
-    CP_LAUNCH(ccl_local, dim3(batch * tiles_x * tiles_y), dim3(256), 0, st, labels_in, parent, count, h, w, tiles_x, tiles_y);
+    CP_LAUNCH(ccl_local, dim3(batch * tiles_x * tiles_y), dim3(256), 0, st, labels_in, parent, count, h, w, tiles_x, tiles_y, objects);
     const long long nb = (long long)batch * (tiles_y - 1) * w + (long long)batch * h * (tiles_x - 1);
-    if (nb > 0) CP_LAUNCH(ccl_border, dim3(grid_for(nb)), dim3(THREADS), 0, st, labels_in, parent, batch, h, w, tiles_x, tiles_y);
-    CP_LAUNCH(ccl_flatten_count, dim3(g), dim3(THREADS), 0, st, labels_in, parent, count, nroots, roots, hw, total);
+    if (nb > 0) CP_LAUNCH(ccl_border, dim3(grid_for(nb)), dim3(THREADS), 0, st, labels_in, parent, batch, h, w, tiles_x, tiles_y, objects);
+    CP_LAUNCH(ccl_flatten_count, dim3(g), dim3(THREADS), 0, st, labels_in, parent, count, nroots, roots, hw, total, objects);
     CP_LAUNCH(ccl_select, dim3(batch), dim3(256), 0, st, labels_in, count, nroots, roots, stats, objects, hw, min_size, rank);
     CP_LAUNCH(ccl_write, dim3(g), dim3(THREADS), 0, st, labels_in, parent, stats, objects, hw, total, labels_out);
     return cp::check_launch("cp_ccl_filter_labels");

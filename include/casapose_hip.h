@@ -325,10 +325,29 @@ size_t cp_ls_vote_workspace_bytes(int batch, int objects, int kp);
  * 4-connectivity, keep the largest component of each object if it has >= min_size pixels):
  * labels_in uint8 [n,h,w] -> labels_out (pixels outside the kept component become 0).
  * rank 1 = the reference's default: the histogram entry that ranks SECOND in top_k order (the first is assumed to be bin 0, "everything
- * else"); rank 2 = output_second_largest_component (:58-59,71-73: three bins, the THIRD entry).  ws: int32 workspace of cp_ccl_workspace_bytes. */
+ * else"); rank 2 = output_second_largest_component (:58-59,71-73: three bins, the THIRD entry).  ws: int32 workspace of cp_ccl_workspace_bytes;
+ * it needs no initialisation.  A label value above `objects` is background: it joins no component, has no histogram and gives 0 in labels_out. */
 int cp_ccl_filter_labels(const uint8_t* labels_in, int batch, int h, int w, int objects, int min_size, int rank, void* ws,
                          uint8_t* labels_out, void* stream);
 size_t cp_ccl_workspace_bytes(int batch, int h, int w, int objects);
+
+/* Where cp_ccl_filter_labels keeps its intermediate products inside the caller's workspace (for tests and diagnostics).  Host only; the same
+ * carving the filter itself applies.  offsets[5] receives the byte offsets, from a 64-byte aligned workspace base (a base that is not is rounded
+ * up to the next 64-byte boundary by the filter; cp_ccl_workspace_bytes includes that slack), of
+ *   [0] parent  int32  [n*h*w]           after the call, for every pixel with a label in 1..objects: the image-global raster index
+ *                                        (n*h*w + y*w + x) of the first pixel in raster order of its component; -1 for background
+ *   [1] count   int32  [n*h*w]           count[r] = the component's size at root indices r only (r = a value of parent); other entries unspecified
+ *   [2] roots   int32  [n][h*w]          roots[n*h*w + 0 .. nroots[n]): the roots of image n, in any order; the rest unspecified
+ *   [3] nroots  int32  [n]               the number of components of image n (all objects together); 64-byte aligned
+ *   [4] stats   uint64 [n][objects][3]   slot 2: the selected histogram entry of (image, object) as (thresholded count << 32) | tie, where the
+ *                                        thresholded count is 0 below min_size, tie = 0xFFFFFFFF for bin 0 ("every pixel that is not the object") and
+ *                                        0xFFFFFFFE - (root - n*h*w) for a component; 0 when the histogram has no such entry (fewer than rank + 1
+ *                                        bins; the reference pads with empty bins there and keeps nothing).  An object without pixels has the
+ *                                        one-entry histogram {bin 0 = h*w}: its slot 2 is 0 for either rank.  Slots 0 and 1 are not written.
+ *                                        64-byte aligned
+ * in this order, without overlap, the last one ending inside cp_ccl_workspace_bytes.  Returns -1 for a null pointer or sizes
+ * cp_ccl_filter_labels refuses. */
+int cp_ccl_workspace_layout(int batch, int h, int w, int objects, size_t* offsets /*[5]*/);
 
 /* ransac_voting_layer_all_masks (casapose/pose_estimation/ransac_voting.py:276-368,447-484).
  * One call votes all (image, object) pairs.  labels: uint8 [n,h,w] hard object map

@@ -134,6 +134,27 @@ def test_ransac_workspace_layout_is_the_voters_own_carving(lib):
     assert lib.cp_ransac_workspace_layout(2, 8, 8, 1, 8, 16, (C.c_size_t * 7)(), None) == -1 and b"keypoints" in lib.cp_last_error()
 
 
+def test_ccl_workspace_layout_is_the_filters_own_carving(lib):
+    """cp_ccl_workspace_layout (host only): five parts in the documented order -- parent, count, roots packed int32 arrays, nroots and stats on
+    64-byte boundaries --, none overlapping the next, the last ending inside cp_ccl_workspace_bytes with the 64 bytes of slack for a base that
+    the filter has to round up; known totals worked out by hand; a null pointer or bad sizes give -1."""
+    up = lambda n: (n + 63) // 64 * 64   # noqa: E731
+    known = {(2, 70, 200, 4): 336320, (1, 1, 1, 1): 216, (3, 601, 599, 3): 12960344, (2, 32, 64, 254): 61472, (16, 480, 640, 8): 58985600}
+    for (b, h, w, objects), total in known.items():
+        offs = (C.c_size_t * 5)()
+        assert lib.cp_ccl_workspace_layout(b, h, w, objects, offs) == 0
+        px = b * h * w
+        sizes = [4 * px, 4 * px, 4 * px, 4 * b, 8 * b * objects * 3]        # parent .. stats
+        assert list(offs)[:3] == [0, 4 * px, 8 * px] and offs[3] == up(12 * px) and offs[4] == up(offs[3] + 4 * b)
+        assert all(offs[i] + sizes[i] <= offs[i + 1] for i in range(4))
+        assert lib.cp_ccl_workspace_bytes(b, h, w, objects) == offs[4] + sizes[4] + 64 == total, (b, h, w, objects, offs[4] + sizes[4] + 64)
+        # never above what the size function returned before the carve was shared: the packed arrays, both roundings, 128 bytes of slack
+        assert total <= 12 * px + up(4 * b) + sizes[4] + 128
+    assert lib.cp_ccl_workspace_layout(2, 8, 8, 1, None) == -1 and b"null pointer" in lib.cp_last_error()
+    for bad in ((0, 8, 8, 1), (2, 0, 8, 1), (2, 8, 0, 1), (2, 8, 8, 0), (2, 8, 8, 255)):
+        assert lib.cp_ccl_workspace_layout(*bad, (C.c_size_t * 5)()) == -1 and b"bad sizes" in lib.cp_last_error(), bad
+
+
 def test_descriptor_of_another_abi_revision_is_refused(lib):
     """A caller built against a header with a shorter (or longer) cp_conv_desc is refused by size in every entry point that takes one."""
     from casapose_amd._lib import ConvDesc
@@ -314,6 +335,7 @@ def _known_signatures():
         "cp_bpnp_loss_workspace_bytes": (_Z, None, [i, i, i]),
         "cp_conv_stem_split_weight_floats": (_I, None, []),
         "cp_ransac_workspace_layout": (_I, None, [i, i, i, i, i, i, _p("size_t"), _p("size_t")]),
+        "cp_ccl_workspace_layout": (_I, None, [i, i, i, i, _p("size_t")]),
     }
 
 
