@@ -210,7 +210,17 @@ if _m is None:
     raise CasaposeHipError("%s does not define CP_ABI_VERSION" % HEADER_PATH)
 ABI_VERSION = int(_m.group(1))
 # every symbol the header declares: (name, restype, argtypes); what each pointer points to; the kernels that have a host twin
-SYMBOLS, POINTEES, RETURN_POINTEES, TWINS = parse_header(_header)
+SYMBOLS, POINTEES, RETURN_POINTEES, _PAIRS = parse_header(_header)
+# cp_pnp_weighted_f64 takes cp_pnp_f64's arguments plus the weights: the pair is listed as that kernel's variant, and TWINS keeps one row per
+# kernel.  host_twin() reads both.
+TWIN_VARIANTS = {d: _PAIRS[d] for d in ("cp_pnp_weighted_f64",)}
+TWINS = {d: h for d, h in _PAIRS.items() if d not in TWIN_VARIANTS}
+
+
+def host_twin(name: str) -> Optional[str]:
+    """the host twin of the device entry point `name` (a kernel's, or a weighted variant's), or None"""
+    return TWINS.get(name) or TWIN_VARIANTS.get(name)
+
 
 _lib: Optional[C.CDLL] = None
 

@@ -49,6 +49,10 @@ __global__ void __launch_bounds__(THREADS) pnp_kernel(const float* __restrict__ 
     }
 }
 
+}  // namespace
+
+namespace cp_pnp {
+// declared in pnp_consensus.h; pnp_weighted.hip applies the same rules
 int check_arguments(const char* fn, const void* points_xy, const void* points_3d, const void* K, const void* solve, const void* table, int b, int oc,
                     int n, int H, float reprojection_error, const void* poses, const void* info, const void* cost) {
     CP_REQUIRE(points_xy && points_3d && K && solve && table && poses && info && cost, "%s: null pointer", fn);
@@ -60,8 +64,7 @@ int check_arguments(const char* fn, const void* points_xy, const void* points_3d
     CP_REQUIRE(reprojection_error > 0.f, "%s: reprojection_error must be positive (got %g)", fn, (double)reprojection_error);   // false for NaN
     return CP_OK;
 }
-
-}  // namespace
+}  // namespace cp_pnp
 
 extern "C" int cp_pnp_f64(const float* points_xy, const float* points_3d, const float* K, int k_per_image, const double* affine, const int32_t* solve,
                           const uint8_t* table, int b, int oc, int n, int H, float reprojection_error, float* poses, int32_t* info, float* cost,

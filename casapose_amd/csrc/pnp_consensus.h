@@ -9,6 +9,10 @@ namespace cp_pnp {
 
 constexpr int CONSENSUS_THREADS = MAX_HYPOTHESES;
 
+// the argument rules of cp_pnp_f64, cp_pnp_weighted_f64 and their twins (defined in pnp.hip, host only)
+int check_arguments(const char* fn, const void* points_xy, const void* points_3d, const void* K, const void* solve, const void* table, int b, int oc,
+                    int n, int H, float reprojection_error, const void* poses, const void* info, const void* cost);
+
 struct Consensus {   // LDS of one block
     int status;
     int count[CONSENSUS_THREADS], index[CONSENSUS_THREADS];

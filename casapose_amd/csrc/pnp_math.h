@@ -10,6 +10,7 @@
 // from pnp.py.  The final pose does not: it is the LM optimum of the all-point reprojection error reached from the consensus pose.
 #pragma once
 #include <math.h>
+#include <stddef.h>
 #include <stdint.h>
 
 #if defined(__HIPCC__)
@@ -510,11 +511,73 @@ PNP_HD double residual_normal(const Problem& P, const double* p, double* A, doub
     return cost;
 }
 
+// ---- uncertainty-weighted LM (cp_pnp_weighted_f64): per point the lower Cholesky factor L of its 2x2 keypoint covariance -----------------
+struct Whitening {
+    double l00[MAX_POINTS], l10[MAX_POINTS], l11[MAX_POINTS];
+};
+
+// point i's factor from cov3 = (sxx, sxy, syy) in the pixels of points_xy: Sigma = cov + floor I, through the linear part M = [[a0, a1], [a3, a4]]
+// of the crop->image affine Sigma' = M Sigma M^T, then Sigma' = L L^T.  false: Sigma' is non-finite or has no positive pivots
+PNP_HD bool load_whitening(Whitening& W, int i, const float* cov3, double floor, const double* affine) {
+    double s00 = (double)cov3[0] + floor, s01 = (double)cov3[1], s11 = (double)cov3[2] + floor;
+    if (affine) {
+        const double a = affine[0], b = affine[1], c = affine[3], d = affine[4];
+        const double t00 = a * s00 + b * s01, t01 = a * s01 + b * s11, t10 = c * s00 + d * s01, t11 = c * s01 + d * s11;   // M Sigma
+        s00 = t00 * a + t01 * b;
+        s01 = t00 * c + t01 * d;
+        s11 = t10 * c + t11 * d;
+    }
+    W.l00[i] = W.l11[i] = 1.0;
+    W.l10[i] = 0.0;
+    if (!(finite(s00) && finite(s01) && finite(s11)) || !(s00 > 0.0)) return false;
+    const double l00 = sqrt(s00), l10 = s01 / l00, piv = s11 - l10 * l10;
+    if (!(piv > 0.0) || !finite(l10) || !finite(piv)) return false;
+    W.l00[i] = l00;
+    W.l10[i] = l10;
+    W.l11[i] = sqrt(piv);
+    return true;
+}
+
+// residual_normal with every point's residual and Jacobian rows whitened by L^-1: cost = the Mahalanobis reprojection error
+PNP_HD double residual_normal_weighted(const Problem& P, const Whitening& W, const double* p, double* A, double* g) {
+    double R[9], Jl[9];
+    rotation_and_left_jacobian(p, R, Jl);
+    for (int i = 0; i < 36; ++i) A[i] = 0.0;
+    for (int i = 0; i < 6; ++i) g[i] = 0.0;
+    double cost = 0.0;
+#pragma unroll 1
+    for (int i = 0; i < P.n; ++i) {
+        double ru, rv, ju[6], jv[6];
+        point_residual(P, p, R, Jl, i, ru, rv, ju, jv);
+        const double l00 = W.l00[i], l10 = W.l10[i], l11 = W.l11[i];
+        ru = ru / l00;
+        rv = (rv - l10 * ru) / l11;
+        for (int a = 0; a < 6; ++a) {
+            ju[a] = ju[a] / l00;
+            jv[a] = (jv[a] - l10 * ju[a]) / l11;
+        }
+        cost += ru * ru + rv * rv;
+        for (int a = 0; a < 6; ++a) {
+            g[a] += ju[a] * ru + jv[a] * rv;
+            for (int b = 0; b < 6; ++b) A[a * 6 + b] += ju[a] * ju[b] + jv[a] * jv[b];
+        }
+    }
+    return cost;
+}
+
 // lam 1e-3, x0.1 on success, x10 on failure, <= 10 tries per iteration, at most max_iters iterations (pnp.pnp: 20), relative stop eps
 // (pnp.pnp: 1e-10).  p = (rvec, t) in and out; returns the iterations entered; cost[0] = the squared error at the start, cost[1] at the end.
-PNP_HD int refine_lm(const Problem& P, double* p, double* cost2, int max_iters = LM_ITERS, double eps = LM_EPS) {
+// WEIGHTED: the same schedule on residual_normal_weighted (W may be null otherwise); the unweighted instantiation never touches W.
+template <bool WEIGHTED>
+PNP_HD double lm_residual(const Problem& P, const Whitening* W, const double* p, double* A, double* g) {
+    if constexpr (WEIGHTED) return residual_normal_weighted(P, *W, p, A, g);
+    else return residual_normal(P, p, A, g);
+}
+
+template <bool WEIGHTED>
+PNP_HD int refine_lm_t(const Problem& P, const Whitening* W, double* p, double* cost2, int max_iters, double eps) {
     double A[36], g[6], A2[36], g2[6], B[36], rhs[6], step[6], q[6];
-    double lam = 1e-3, cost = residual_normal(P, p, A, g);
+    double lam = 1e-3, cost = lm_residual<WEIGHTED>(P, W, p, A, g);
     cost2[0] = cost;
     int iters = 0;
 #pragma unroll 1
@@ -533,7 +596,7 @@ PNP_HD int refine_lm(const Problem& P, double* p, double* cost2, int max_iters =
                 continue;
             }
             for (int i = 0; i < 6; ++i) q[i] = p[i] + step[i];
-            const double c2 = residual_normal(P, q, A2, g2);
+            const double c2 = lm_residual<WEIGHTED>(P, W, q, A2, g2);
             if (finite(c2) && c2 < cost) {
                 for (int i = 0; i < 6; ++i) { p[i] = q[i]; g[i] = g2[i]; }
                 for (int i = 0; i < 36; ++i) A[i] = A2[i];
@@ -549,6 +612,10 @@ PNP_HD int refine_lm(const Problem& P, double* p, double* cost2, int max_iters =
     }
     cost2[1] = cost;
     return iters;
+}
+
+PNP_HD int refine_lm(const Problem& P, double* p, double* cost2, int max_iters = LM_ITERS, double eps = LM_EPS) {
+    return refine_lm_t<false>(P, nullptr, p, cost2, max_iters, eps);
 }
 
 // ---- one pair: load, hypotheses, consensus, final solve ---------------------------------------------------------------------------------
@@ -634,7 +701,9 @@ PNP_HD void zero_outputs(int status, float* pose, int32_t* info, float* cost) {
 
 // EPnP on the consensus set (all points when it has fewer than 5, as pnp.pnp_rvec_t), then LM over all points: p = (rvec, t) in fp64,
 // c2 = the squared error before and after LM.  false: no finite pose
-PNP_HD bool consensus_pose(const Problem& P, const Score& sc, double* p, double* c2, int& iters) {
+// WEIGHTED: the final LM minimises the Mahalanobis error under W; the consensus set and both EPnP calls are the unweighted ones
+template <bool WEIGHTED>
+PNP_HD bool consensus_pose_t(const Problem& P, const Whitening* W, const Score& sc, double* p, double* c2, int& iters) {
     uint8_t idx[MAX_POINTS];
     int m = 0;
     if (sc.count >= SET_POINTS)
@@ -649,17 +718,22 @@ PNP_HD bool consensus_pose(const Problem& P, const Score& sc, double* p, double*
     if (!ok) return false;
     rodrigues_inverse(q.R, p);
     for (int d = 0; d < 3; ++d) p[3 + d] = q.t[d];
-    iters = refine_lm(P, p, c2);
+    iters = refine_lm_t<WEIGHTED>(P, W, p, c2, LM_ITERS, LM_EPS);
     bool fin = finite(c2[0]) && finite(c2[1]);
     for (int i = 0; i < 6; ++i) fin = fin && finite(p[i]);
     return fin;
 }
 
+PNP_HD bool consensus_pose(const Problem& P, const Score& sc, double* p, double* c2, int& iters) {
+    return consensus_pose_t<false>(P, nullptr, sc, p, c2, iters);
+}
+
 // consensus_pose, then pnp.pnp's ending: (rvec, t) rounded to fp32, the pose negated when t_z < 0, a non-finite result replaced by the zero pose
-PNP_HD void finish_pair(const Problem& P, int winner, const Score& sc, float* pose, int32_t* info, float* cost) {
+template <bool WEIGHTED>
+PNP_HD void finish_pair_t(const Problem& P, const Whitening* W, int winner, const Score& sc, float* pose, int32_t* info, float* cost) {
     double p[6], c2[2], R[9];
     int iters = 0;
-    if (!consensus_pose(P, sc, p, c2, iters)) {
+    if (!consensus_pose_t<WEIGHTED>(P, W, sc, p, c2, iters)) {
         zero_outputs(NO_SOLUTION, pose, info, cost);
         return;
     }
@@ -673,6 +747,10 @@ PNP_HD void finish_pair(const Problem& P, int winner, const Score& sc, float* po
     info[0] = OK; info[1] = winner; info[2] = sc.count < 0 ? 0 : sc.count; info[3] = iters;
     cost[0] = (float)c2[0];
     cost[1] = (float)c2[1];
+}
+
+PNP_HD void finish_pair(const Problem& P, int winner, const Score& sc, float* pose, int32_t* info, float* cost) {
+    finish_pair_t<false>(P, nullptr, winner, sc, pose, info, cost);
 }
 
 // the consensus over the H hypotheses of the table, serially: what the kernels' blocks find with one thread per hypothesis
@@ -704,6 +782,53 @@ PNP_HD void solve_pair_serial(const float* xy, const float* xyz, const float* K,
     Score best;
     const int winner = consensus_serial(P, table, H, reprojection_error, best);
     finish_pair(P, winner, best, pose, info, cost);
+}
+
+// solve_pair_serial with the final LM weighted by the keypoint covariances cov [n][3]; *weighted = 1 when every point's covariance was usable,
+// otherwise 0 and the pair is solved exactly as solve_pair_serial solves it
+PNP_HD void solve_pair_weighted_serial(const float* xy, const float* xyz, const float* K, const double* affine, const float* cov, double cov_floor,
+                                       int n, const uint8_t* table, int H, double reprojection_error, float* pose, int32_t* info, float* cost,
+                                       int32_t* weighted) {
+    Problem P;
+    Whitening W;
+    P.n = n;
+    for (int i = 0; i < 9; ++i) P.K[i] = (double)K[i];
+    bool usable = true;
+    for (int i = 0; i < n; ++i) {
+        load_point(P, i, xy, xyz, affine);
+        usable = load_whitening(W, i, cov + 3 * i, cov_floor, affine) && usable;
+    }
+    *weighted = 0;
+    const int status = check_problem(P);
+    if (status != OK) {
+        zero_outputs(status, pose, info, cost);
+        return;
+    }
+    Score best;
+    const int winner = consensus_serial(P, table, H, reprojection_error, best);
+    if (usable) finish_pair_t<true>(P, &W, winner, best, pose, info, cost);
+    else finish_pair_t<false>(P, nullptr, winner, best, pose, info, cost);
+    *weighted = usable ? 1 : 0;
+}
+
+// every pair of a batch, serially: the body of cp_pnp_weighted_host_f64 (pnp.hip) after its argument checks, and what wpnp_selftest.cpp runs
+PNP_HD void solve_batch_weighted_serial(const float* points_xy, const float* points_3d, const float* K, int k_per_image, const double* affine,
+                                        const int32_t* solve, const uint8_t* table, int b, int oc, int n, int H, double reprojection_error,
+                                        const float* cov, double cov_floor, float* poses, int32_t* info, float* cost, int32_t* weighted) {
+    for (int pair = 0; pair < b * oc; ++pair) {
+        float* pose = poses + (size_t)pair * 12;
+        int32_t* inf = info + (size_t)pair * 4;
+        float* cst = cost + (size_t)pair * 2;
+        if (solve[pair] == 0) {
+            zero_outputs(SKIPPED, pose, inf, cst);
+            weighted[pair] = 0;
+            continue;
+        }
+        const int image = pair / oc;
+        solve_pair_weighted_serial(points_xy + (size_t)pair * n * 2, points_3d + (size_t)pair * n * 3, K + (k_per_image ? (size_t)image * 9 : 0),
+                                   affine ? affine + (size_t)image * 6 : nullptr, cov + (size_t)pair * n * 3, cov_floor, n, table, H,
+                                   reprojection_error, pose, inf, cst, weighted + pair);
+    }
 }
 
 }  // namespace cp_pnp

@@ -502,6 +502,38 @@ extern "C" int cp_ransac_workspace_layout(int batch, int h, int w, int objects, 
 }
 
 namespace {
+// The compaction both entry families start with: row counts, for the seeded entries the thinning thresholds and the thinned row counts, the row
+// scan -- which writes a fresh state per pair, done = (tn == 0) -- and the pixel lists.  The min_num gate belongs to the un-thinned count: the
+// seeded path applies it in thin_threshold_kernel and scans with a gate of one pixel.
+int compact_objects(const uint8_t* labels, int batch, int h, int w, int objects, bool seeded, unsigned long long seed, int min_num, int max_num,
+                    const Workspace& ws, hipStream_t st) {
+    const int no = batch * objects, rows = batch * h;
+    const unsigned* thr = nullptr;
+    CP_LAUNCH(rowcount_kernel, dim3((rows + 3) / 4), dim3(256), 0, st, labels, batch, h, w, objects, ws.rowcnt, thr, seed);
+    if (seeded) {
+        CP_LAUNCH(thin_threshold_kernel, dim3((no + 3) / 4), dim3(256), 0, st, ws.rowcnt, h, no, min_num, max_num, ws.thr);
+        thr = ws.thr;
+        CP_LAUNCH(rowcount_kernel, dim3((rows + 3) / 4), dim3(256), 0, st, labels, batch, h, w, objects, ws.rowcnt, thr, seed);
+    }
+    CP_LAUNCH(rowscan_kernel, dim3((no + 3) / 4), dim3(256), 0, st, ws.rowcnt, h, no, seeded ? 1 : min_num, ws.st);
+    CP_LAUNCH(compact_kernel, dim3((rows + 3) / 4), dim3(256), 0, st, labels, batch, h, w, objects, ws.rowcnt, ws.pixlist, h * w, thr, seed);
+    return CP_OK;
+}
+
+constexpr int PX_CHUNKS = 8;   // pixel chunks per (pair, hypothesis block) of vote_kernel and per pair of refine_accumulate_kernel
+
+// one round's inlier counts of ws.hyp_pts into ws.counts: vote_kernel<64> when hyp allows, else <16>
+int launch_vote(const float* vertex, int ld, int dir_off, int h, int w, int objects, int no, int hyp, float inlier_thresh, const Workspace& ws,
+                hipStream_t st) {
+    if (hyp % 64 == 0)
+        CP_LAUNCH(vote_kernel<64>, dim3(hyp / 64, PX_CHUNKS, no), dim3(256), 0, st, vertex, ld, dir_off, h, w, objects, ws.pixlist, h * w, ws.hyp_pts, hyp,
+                  ws.st, ws.counts, inlier_thresh, PX_CHUNKS);
+    else
+        CP_LAUNCH(vote_kernel<HB>, dim3(hyp / HB, PX_CHUNKS, no), dim3(256), 0, st, vertex, ld, dir_off, h, w, objects, ws.pixlist, h * w, ws.hyp_pts, hyp,
+                  ws.st, ws.counts, inlier_thresh, PX_CHUNKS);
+    return CP_OK;
+}
+
 int ransac_vote(const uint8_t* labels, const float* vertex, int ld, int dir_off, int batch, int h, int w, int objects, int kp, const int32_t* idx,
                 bool seeded, unsigned long long seed, int hyp, float inlier_thresh, float confidence, int max_iter, int min_num, int max_num, void* wsp,
                 float* out, int32_t* rounds_out, void* stream);
@@ -539,29 +571,15 @@ int ransac_vote(const uint8_t* labels, const float* vertex, int ld, int dir_off,
     Workspace ws = carve(wsp, batch, h, w, objects, hyp);
     const int no = batch * objects;
     const int list_stride = h * w;
-    const int rows = batch * h;
     (void)hipMemsetAsync(ws.sums, 0, (size_t)no * KP * 5 * sizeof(double), st);
-    const unsigned* thr = nullptr;
-    CP_LAUNCH(rowcount_kernel, dim3((rows + 3) / 4), dim3(256), 0, st, labels, batch, h, w, objects, ws.rowcnt, thr, seed);
-    if (seeded) {
-        CP_LAUNCH(thin_threshold_kernel, dim3((no + 3) / 4), dim3(256), 0, st, ws.rowcnt, h, no, min_num, max_num, ws.thr);
-        thr = ws.thr;
-        CP_LAUNCH(rowcount_kernel, dim3((rows + 3) / 4), dim3(256), 0, st, labels, batch, h, w, objects, ws.rowcnt, thr, seed);
-    }
-    CP_LAUNCH(rowscan_kernel, dim3((no + 3) / 4), dim3(256), 0, st, ws.rowcnt, h, no, seeded ? 1 : min_num, ws.st);   // (seeded: gated before the thinning, above)
-    CP_LAUNCH(compact_kernel, dim3((rows + 3) / 4), dim3(256), 0, st, labels, batch, h, w, objects, ws.rowcnt, ws.pixlist, list_stride, thr, seed);
-    const int px_chunks = 8;
+    if (int rc = compact_objects(labels, batch, h, w, objects, seeded, seed, min_num, max_num, ws, st)) return rc;
+    const int px_chunks = PX_CHUNKS;
     const long long nhyp = (long long)no * hyp * KP;
     for (int r = 0; r < max_iter; ++r) {
         const int32_t* draws = idx ? idx + (size_t)r * nhyp * 2 : nullptr;
         CP_LAUNCH(hypgen_kernel, dim3((unsigned)((nhyp + 255) / 256)), dim3(256), 0, st, vertex, ld, dir_off, h, w, objects, ws.pixlist,
                   list_stride, draws, hyp, ws.st, ws.hyp_pts, no, ws.counts, seed, r);
-        if (hyp % 64 == 0)
-            CP_LAUNCH(vote_kernel<64>, dim3(hyp / 64, px_chunks, no), dim3(256), 0, st, vertex, ld, dir_off, h, w, objects, ws.pixlist, list_stride,
-                      ws.hyp_pts, hyp, ws.st, ws.counts, inlier_thresh, px_chunks);
-        else
-            CP_LAUNCH(vote_kernel<HB>, dim3(hyp / HB, px_chunks, no), dim3(256), 0, st, vertex, ld, dir_off, h, w, objects, ws.pixlist, list_stride,
-                      ws.hyp_pts, hyp, ws.st, ws.counts, inlier_thresh, px_chunks);
+        if (int rc = launch_vote(vertex, ld, dir_off, h, w, objects, no, hyp, inlier_thresh, ws, st)) return rc;
         CP_LAUNCH(update_kernel, dim3((no + 3) / 4), dim3(256), 0, st, ws.counts, ws.hyp_pts, hyp, ws.st, no, confidence, max_iter);
         // The stopping rule lives on the device; the remaining rounds of finished objects are empty launches (4 per round, ~25 us).  After
         // rounds 1, 2, 4, 8, 16 the host asks how many objects are still voting (one 4-byte copy + stream synchronisation, ~20 us) and stops
@@ -581,3 +599,111 @@ int ransac_vote(const uint8_t* labels, const float* vertex, int ld, int dir_off,
     return cp::check_launch("cp_ransac_vote_f32");
 }
 }  // namespace
+
+// ---- keypoint covariances from the voting distribution (cp_kp_cov_f32, cp_kp_cov_seeded_f32) -------------------------------------------------
+// One round of the voter's own compaction, hypgen_kernel and vote_kernel, then the weighted second moments of the hypotheses about a given
+// mean, with the inlier counts as weights.
+namespace {
+
+constexpr unsigned long long COV_KEY = 0x6B70636F76617221ull;   // the seeded draws' key, mix64(seed ^ COV_KEY, .): another key than the voting rounds', as the thinning has
+
+// One wave per (image, object, keypoint); lane l walks hypotheses l, l + 64, ... and accumulates c (h - mean)(h - mean)^T in fp64, the lanes are
+// summed by an xor shuffle tree (a fixed order: two calls give the same bits), lane 0 divides and rounds to fp32 once.
+__global__ __launch_bounds__(256) void kp_cov_kernel(const float* __restrict__ hyp_pts, const int* __restrict__ counts, const ObjState* __restrict__ st,
+                                                     const float* __restrict__ mean, int hyp, int n_wave_total, float* __restrict__ cov,
+                                                     int32_t* __restrict__ wsum) {
+    const int wv = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);   // = io * KP + v
+    const int lane = threadIdx.x & 63;
+    if (wv >= n_wave_total) return;   // wave-uniform
+    const int io = wv / KP, v = wv - io * KP;
+    const float mxf = mean[(size_t)wv * 2], myf = mean[(size_t)wv * 2 + 1];
+    double sxx = 0.0, sxy = 0.0, syy = 0.0;
+    long long wt = 0;
+    if (st[io].tn != 0 && fabsf(mxf) <= 3.4028234e38f && fabsf(myf) <= 3.4028234e38f) {   // (false for a NaN mean)
+        const double mx = (double)mxf, my = (double)myf;
+        for (int h = lane; h < hyp; h += 64) {
+            const size_t i = ((size_t)io * hyp + h) * KP + v;
+            const int c = counts[i];
+            if (c <= 0) continue;   // skipped, not multiplied: a hypothesis without inliers may be non-finite
+            const double dx = (double)hyp_pts[2 * i] - mx, dy = (double)hyp_pts[2 * i + 1] - my;
+            const double cd = (double)c;
+            sxx += cd * (dx * dx);
+            sxy += cd * (dx * dy);
+            syy += cd * (dy * dy);
+            wt += c;
+        }
+    }
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) {
+        sxx += __shfl_xor(sxx, off);
+        sxy += __shfl_xor(sxy, off);
+        syy += __shfl_xor(syy, off);
+        wt += __shfl_xor(wt, off);
+    }
+    if (lane != 0) return;
+    const double inv = wt > 0 ? 1.0 / (double)wt : 0.0;
+    cov[(size_t)wv * 3 + 0] = wt > 0 ? (float)(sxx * inv) : 0.f;
+    cov[(size_t)wv * 3 + 1] = wt > 0 ? (float)(sxy * inv) : 0.f;
+    cov[(size_t)wv * 3 + 2] = wt > 0 ? (float)(syy * inv) : 0.f;
+    wsum[wv] = (int32_t)(wt > 0x7fffffffLL ? 0x7fffffffLL : wt);
+}
+
+int kp_cov(const char* fn, const uint8_t* labels, const float* vertex, int ld, int dir_off, int batch, int h, int w, int objects, int kp,
+           const float* mean, const int32_t* draws, bool seeded, unsigned long long seed, int hyp, float inlier_thresh, int min_num, int max_num,
+           void* wsp, float* cov, int32_t* wsum, void* stream) {
+    CP_REQUIRE(labels && vertex && mean && wsp && cov && wsum, "%s: null pointer", fn);
+    CP_REQUIRE(kp == KP, "%s: built for %d keypoints (got %d)", fn, KP, kp);
+    CP_REQUIRE(batch > 0 && h > 0 && w > 0 && objects > 0 && objects < 255, "%s: bad sizes", fn);
+    CP_REQUIRE(hyp > 0 && hyp % HB == 0, "%s: the number of hypotheses must be a multiple of %d", fn, HB);
+    CP_REQUIRE(dir_off >= 0 && dir_off + 2 * kp <= ld, "%s: bad channel offsets", fn);
+    CP_REQUIRE((long long)h * w < (1LL << 31), "%s: image too large", fn);
+    CP_REQUIRE(max_num >= 1, "%s: max_num must be positive", fn);
+    const long long px = (long long)h * w < (long long)max_num ? (long long)h * w : (long long)max_num;
+    CP_REQUIRE((long long)hyp * px < (1LL << 31), "%s: hyp * min(max_num, h*w) must stay below 2^31 (hyp %d, %lld pixels)", fn, hyp, px);
+    hipStream_t st = (hipStream_t)stream;
+    Workspace ws = carve(wsp, batch, h, w, objects, hyp);
+    const int no = batch * objects, list_stride = h * w;
+    // the voter's own compaction, with its thinning for this seed (the same pixels vote) and a fresh state per pair: done = (tn == 0), so that
+    // hypgen_kernel and vote_kernel run for every pair that has pixels
+    if (int rc = compact_objects(labels, batch, h, w, objects, seeded, seed, min_num, max_num, ws, st)) return rc;
+    const long long nhyp = (long long)no * hyp * KP;
+    CP_LAUNCH(hypgen_kernel, dim3((unsigned)((nhyp + 255) / 256)), dim3(256), 0, st, vertex, ld, dir_off, h, w, objects, ws.pixlist, list_stride,
+              draws, hyp, ws.st, ws.hyp_pts, no, ws.counts, seed ^ COV_KEY, 0);
+    if (int rc = launch_vote(vertex, ld, dir_off, h, w, objects, no, hyp, inlier_thresh, ws, st)) return rc;
+    const int waves = no * KP;
+    CP_LAUNCH(kp_cov_kernel, dim3((waves + 3) / 4), dim3(256), 0, st, ws.hyp_pts, ws.counts, ws.st, mean, hyp, waves, cov, wsum);
+    return cp::check_launch(fn);
+}
+
+}  // namespace
+
+extern "C" size_t cp_kp_cov_workspace_bytes(int batch, int h, int w, int objects, int kp, int hyp) {
+    (void)kp;
+    return carve(nullptr, batch, h, w, objects, hyp).bytes;
+}
+
+extern "C" int cp_kp_cov_workspace_layout(int batch, int h, int w, int objects, int kp, int hyp, size_t* offsets, size_t* state_bytes) {
+    CP_REQUIRE(offsets, "cp_kp_cov_workspace_layout: null pointer");
+    CP_REQUIRE(kp == KP, "cp_kp_cov_workspace_layout: built for %d keypoints (got %d)", KP, kp);
+    CP_REQUIRE(batch > 0 && h > 0 && w > 0 && objects > 0 && objects < 255 && hyp > 0, "cp_kp_cov_workspace_layout: bad sizes");
+    const Workspace ws = carve(nullptr, batch, h, w, objects, hyp);   // the op's own carve from base 0: the pointers are the offsets
+    const void* part[4] = {ws.pixlist, ws.st, ws.hyp_pts, ws.counts};
+    for (int i = 0; i < 4; ++i) offsets[i] = (size_t) reinterpret_cast<uintptr_t>(part[i]);
+    if (state_bytes) *state_bytes = sizeof(ObjState);
+    return 0;
+}
+
+extern "C" int cp_kp_cov_f32(const uint8_t* labels, const float* vertex, int ld, int dir_off, int batch, int h, int w, int objects, int kp,
+                             const float* mean, const int32_t* draws, int hyp, float inlier_thresh, int min_num, int max_num, void* wsp, float* cov,
+                             int32_t* wsum, void* stream) {
+    CP_REQUIRE(draws, "cp_kp_cov_f32: null pointer");
+    return kp_cov("cp_kp_cov_f32", labels, vertex, ld, dir_off, batch, h, w, objects, kp, mean, draws, false, 0ull, hyp, inlier_thresh, min_num, max_num,
+                  wsp, cov, wsum, stream);
+}
+
+extern "C" int cp_kp_cov_seeded_f32(const uint8_t* labels, const float* vertex, int ld, int dir_off, int batch, int h, int w, int objects, int kp,
+                                    const float* mean, unsigned long long seed, int hyp, float inlier_thresh, int min_num, int max_num, void* wsp,
+                                    float* cov, int32_t* wsum, void* stream) {
+    return kp_cov("cp_kp_cov_seeded_f32", labels, vertex, ld, dir_off, batch, h, w, objects, kp, mean, nullptr, true, seed, hyp, inlier_thresh, min_num,
+                  max_num, wsp, cov, wsum, stream);
+}

@@ -62,6 +62,7 @@ class DevicePnP:
         self.last_info: Optional[np.ndarray] = None
         self.last_cost: Optional[np.ndarray] = None
         self.last_poses = None
+        self.last_weighted: Optional[np.ndarray] = None   # int32 [b,oc] of the last call with cov: 1 where the LM was weighted; None without cov
 
     def _shapes(self, points_xy, points_3d, K, solve_mask, affine):
         if points_xy.ndim != 4 or points_xy.shape[2] != self.n_points or points_xy.shape[3] != 2:
@@ -77,44 +78,63 @@ class DevicePnP:
             raise ValueError("affine must be [%d, 6] (got %s)" % (b, tuple(affine.shape)))
         return b, oc
 
-    def _call(self, xy, x3, K, mask, affine, poses, info, cost, host: bool) -> None:
-        """cp_pnp_f64 on the current stream, or its host twin: the one argument list of both"""
+    def _call(self, xy, x3, K, mask, affine, poses, info, cost, host: bool, cov=None, cov_floor: float = 0.0, weighted=None) -> None:
+        """cp_pnp_f64 on the current stream, or with cov cp_pnp_weighted_f64; host: their twins.  One argument list per entry point."""
         b, oc = int(xy.shape[0]), int(xy.shape[1])
-        twin.call("cp_pnp_f64", xy, x3, K, int(K.ndim == 3), affine, mask, self.table_host if host else self.table, b, oc, self.n_points,
-                  self.hypotheses, self.reprojection_error, poses, info, cost, host=host,
-                  stream=None if host else torch.cuda.current_stream(self.device).cuda_stream)
+        head = (xy, x3, K, int(K.ndim == 3), affine, mask, self.table_host if host else self.table, b, oc, self.n_points, self.hypotheses,
+                self.reprojection_error)
+        stream = None if host else torch.cuda.current_stream(self.device).cuda_stream
+        if cov is None:
+            twin.call("cp_pnp_f64", *head, poses, info, cost, host=host, stream=stream)
+        else:
+            twin.call("cp_pnp_weighted_f64", *head, cov, float(cov_floor), poses, info, cost, weighted, host=host, stream=stream)
 
     def launch(self, xy, x3, K, mask, affine, poses, info, cost) -> None:
         """cp_pnp_f64 on the current stream over contiguous device tensors of the right types."""
         self._call(xy, x3, K, mask, affine, poses, info, cost, host=False)
 
-    def _solve(self, points_xy, points_3d, K, solve_mask, affine, host: bool) -> dict:
-        """the inputs converted and the outputs made where the call runs (this device, or NumPy arrays for the twin) -> poses, info, cost"""
+    def _solve(self, points_xy, points_3d, K, solve_mask, affine, host: bool, cov=None, cov_floor: float = 1.0 / 12.0) -> dict:
+        """the inputs converted and the outputs made where the call runs (this device, or NumPy arrays for the twin) -> poses, info, cost and,
+        with cov, weighted"""
         dev = None if host else self.device
         xy, x3, Kc = (twin.array(a, np.float32, dev) for a in (points_xy, points_3d, K))
         mask = twin.array(solve_mask, np.int32, dev)
         aff = None if affine is None else twin.array(affine, np.float64, dev)
         b, oc = self._shapes(xy, x3, Kc, mask, aff)
-        out = twin.alloc(dict(poses=((b, oc, 3, 4), np.float32), info=((b, oc, 4), np.int32), cost=((b, oc, 2), np.float32)), dev)
-        self._call(xy, x3, Kc, mask, aff, out["poses"], out["info"], out["cost"], host)
+        spec = dict(poses=((b, oc, 3, 4), np.float32), info=((b, oc, 4), np.int32), cost=((b, oc, 2), np.float32))
+        if cov is None:
+            out = twin.alloc(spec, dev)
+            self._call(xy, x3, Kc, mask, aff, out["poses"], out["info"], out["cost"], host)
+            return out
+        cv = twin.array(cov, np.float32, dev)   # a device tensor stays where it is
+        if tuple(cv.shape) != (b, oc, self.n_points, 3):
+            raise ValueError("cov must be [%d, %d, %d, 3] (got %s)" % (b, oc, self.n_points, tuple(cv.shape)))
+        out = twin.alloc(dict(spec, weighted=((b, oc), np.int32)), dev)
+        self._call(xy, x3, Kc, mask, aff, out["poses"], out["info"], out["cost"], host, cv, cov_floor, out["weighted"])
         return out
 
-    def solve(self, points_xy, points_3d, K, solve_mask, affine=None):
+    def solve(self, points_xy, points_3d, K, solve_mask, affine=None, cov=None, cov_floor: float = 1.0 / 12.0):
         """points_xy [b,oc,n,2] (x,y), points_3d [b,oc,n,3], K [3,3] or [b,3,3], solve_mask [b,oc] (0: the zero pose), affine None or [b,6]
         (affine_from_offsets): device tensors, or host arrays that are uploaded.  -> poses, a device tensor [b,oc,3,4].  `last_info` int32
-        [b,oc,4] (status, winning hypothesis, inlier count, LM iterations) and `last_cost` float32 [b,oc,2] are downloaded with it."""
+        [b,oc,4] (status, winning hypothesis, inlier count, LM iterations) and `last_cost` float32 [b,oc,2] are downloaded with it.
+        cov: keypoint covariances [b,oc,n,3] = (sxx, sxy, syy) in the pixels of points_xy (keypoint_covariance's output, used where it lies);
+        the final LM then minimises the Mahalanobis error (cp_pnp_weighted_f64) and `last_weighted` int32 [b,oc] says where.  cov_floor is
+        added to sxx and syy first: by default 1/12 px^2, the variance of a position known only to one pixel of the field's grid.  cov=None is
+        the unweighted call."""
         if self.device is None:
             raise _lib.CasaposeHipError("this DevicePnP was built without a device: only solve_host is available")
         with torch.cuda.device(self.device):
-            out = self._solve(points_xy, points_3d, K, solve_mask, affine, host=False)
+            out = self._solve(points_xy, points_3d, K, solve_mask, affine, host=False, cov=cov, cov_floor=cov_floor)
             self.last_info, self.last_cost = out["info"].cpu().numpy(), out["cost"].cpu().numpy()   # the copies synchronise
+            self.last_weighted = out["weighted"].cpu().numpy() if cov is not None else None
         self.last_poses = out["poses"]
         return self.last_poses
 
-    def solve_host(self, points_xy, points_3d, K, solve_mask, affine=None) -> np.ndarray:
+    def solve_host(self, points_xy, points_3d, K, solve_mask, affine=None, cov=None, cov_floor: float = 1.0 / 12.0) -> np.ndarray:
         """The host twin of solve() on NumPy arrays: the same code, serially, without a GPU.  -> poses float32 [b,oc,3,4]."""
-        out = self._solve(points_xy, points_3d, K, solve_mask, affine, host=True)
+        out = self._solve(points_xy, points_3d, K, solve_mask, affine, host=True, cov=cov, cov_floor=cov_floor)
         self.last_info, self.last_cost, self.last_poses = out["info"], out["cost"], out["poses"]
+        self.last_weighted = out.get("weighted")
         return self.last_poses
 
 
@@ -124,8 +144,8 @@ class HostTwinPnP(DevicePnP):
     def __init__(self, n_points: int, reprojection_error: float = 12.0):
         super().__init__(None, n_points, reprojection_error)
 
-    def solve(self, points_xy, points_3d, K, solve_mask, affine=None):
-        return torch.from_numpy(self.solve_host(points_xy, points_3d, K, solve_mask, affine))
+    def solve(self, points_xy, points_3d, K, solve_mask, affine=None, cov=None, cov_floor: float = 1.0 / 12.0):
+        return torch.from_numpy(self.solve_host(points_xy, points_3d, K, solve_mask, affine, cov=cov, cov_floor=cov_floor))
 
 
 _from_environment = None   # (n_points, device, solver) of the last solver_from_environment call

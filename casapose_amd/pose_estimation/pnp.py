@@ -232,13 +232,54 @@ def _residual_and_jacobian(X, x, K, rvec, t):
     return r, J
 
 
-def refine_lm(points_3d, points_2d, K, rvec, t, iters: int = 20, eps: float = 1e-10):
+COV_FLOOR = 1.0 / 12.0   # px^2: the variance of a position known only to one pixel of the field's grid; the callers' default floor (DevicePnP.solve)
+
+
+def covariance_matrices(cov, n: int) -> np.ndarray:
+    """cov as fp64 [n,2,2]: given as [n,2,2], or as [n,3] = (sxx, sxy, syy) per point (keypoint_covariance's layout)."""
+    c = np.asarray(cov, np.float64)
+    if c.shape == (n, 3):
+        c = np.stack([np.stack([c[:, 0], c[:, 1]], -1), np.stack([c[:, 1], c[:, 2]], -1)], -2)
+    if c.shape != (n, 2, 2):
+        raise ValueError("cov must be [%d, 2, 2] or [%d, 3] (got %s)" % (n, n, np.shape(cov)))
+    return c
+
+
+def whitening_factors(cov, n: int) -> Optional[np.ndarray]:
+    """The inverses [n,2,2] of the lower Cholesky factors of the covariances, or None when one of them is non-finite or not positive
+    definite: the solve is then the unweighted one, as in cp_pnp_weighted_f64."""
+    c = covariance_matrices(cov, n)
+    if not np.isfinite(c).all():
+        return None
+    try:
+        L = np.linalg.cholesky(c)
+    except np.linalg.LinAlgError:
+        return None
+    if not (np.isfinite(L).all() and (L[:, 0, 0] > 0).all() and (L[:, 1, 1] > 0).all()):
+        return None
+    return np.linalg.inv(L)
+
+
+def _whitened(r, J, Li):
+    n = Li.shape[0]
+    return np.einsum("nab,nb->na", Li, r.reshape(n, 2)).reshape(-1), np.einsum("nab,nbc->nac", Li, J.reshape(n, 2, 6)).reshape(2 * n, 6)
+
+
+def refine_lm(points_3d, points_2d, K, rvec, t, iters: int = 20, eps: float = 1e-10, cov=None):
+    """cov (fp64 [n,2,2] or [n,3], image pixels): the residual and Jacobian rows of every point are whitened by the inverse Cholesky factor of its
+    covariance, so that the Mahalanobis reprojection error is minimised; an unusable covariance set (whitening_factors) is ignored."""
     X = np.asarray(points_3d, np.float64).reshape(-1, 3)
     x = np.asarray(points_2d, np.float64).reshape(-1, 2)
     K = np.asarray(K, np.float64)
     p = np.concatenate([np.asarray(rvec, np.float64).reshape(3), np.asarray(t, np.float64).reshape(3)])
+    Li = None if cov is None else whitening_factors(cov, X.shape[0])
+    if Li is None:
+        resid = _residual_and_jacobian
+    else:
+        def resid(X, x, K, rvec, t):
+            return _whitened(*_residual_and_jacobian(X, x, K, rvec, t), Li)
     lam = 1e-3
-    r, J = _residual_and_jacobian(X, x, K, p[:3], p[3:])
+    r, J = resid(X, x, K, p[:3], p[3:])
     cost = r @ r
     for _ in range(iters):
         A = J.T @ J
@@ -251,7 +292,7 @@ def refine_lm(points_3d, points_2d, K, rvec, t, iters: int = 20, eps: float = 1e
                 lam *= 10.0
                 continue
             q = p + step
-            r2, J2 = _residual_and_jacobian(X, x, K, q[:3], q[3:])
+            r2, J2 = resid(X, x, K, q[:3], q[3:])
             c2 = r2 @ r2
             if np.isfinite(c2) and c2 < cost:
                 p, r, J, lam = q, r2, J2, max(lam * 0.1, 1e-12)
@@ -308,9 +349,9 @@ def solve_pnp_ransac(points_3d, points_2d, K, reprojection_error: float = 12.0, 
     return True, rodrigues_inverse(R), t, best_inl
 
 
-def pnp_rvec_t(points_3d, points_2d, camera_matrix, init_pose=None, rng=None) -> np.ndarray:
+def pnp_rvec_t(points_3d, points_2d, camera_matrix, init_pose=None, rng=None, cov=None) -> np.ndarray:
     """bpnp_layers.pnp (:86-117): RANSAC-EPnP (or the given initial pose) then iterative refinement over all points;
-    returns the 6-vector (rvec, t) as float32."""
+    returns the 6-vector (rvec, t) as float32.  cov: keypoint covariances for the refinement alone (refine_lm); RANSAC and EPnP stay unweighted."""
     X = np.asarray(points_3d, np.float64).reshape(-1, 3)
     x = np.asarray(points_2d, np.float64).reshape(-1, 2)
     if init_pose is None:
@@ -323,19 +364,19 @@ def pnp_rvec_t(points_3d, points_2d, camera_matrix, init_pose=None, rng=None) ->
                 return np.full(6, np.nan, np.float32)
     else:
         rvec, t = np.asarray(init_pose[:3], np.float64), np.asarray(init_pose[3:6], np.float64)
-    rvec, t = refine_lm(X, x, camera_matrix, rvec, t)
+    rvec, t = refine_lm(X, x, camera_matrix, rvec, t, cov=cov)
     return np.concatenate([rvec, t]).astype(np.float32)
 
 
-def pnp(points_3d, points_2d, camera_matrix, rng=None) -> np.ndarray:
+def pnp(points_3d, points_2d, camera_matrix, rng=None, cov=None) -> np.ndarray:
     """ransac_voting.pnp (:13-57): [3,4] float32 pose; zeros if the 2-D points are all zero (object absent, :17-18) or the
-    solve fails (:48-49); the pose is negated when t_z < 0 (:53-55)."""
+    solve fails (:48-49); the pose is negated when t_z < 0 (:53-55).  cov: see pnp_rvec_t."""
     x = np.asarray(points_2d, np.float64).reshape(-1, 2)
     X = np.asarray(points_3d, np.float64).reshape(-1, 3)
     assert X.shape[0] == x.shape[0], "points 3D and points 2D must have same number of vertices"
     if abs(x.sum()) < 1e-4:
         return np.zeros((3, 4), np.float32)
-    p = pnp_rvec_t(X, x, camera_matrix, rng=rng)
+    p = pnp_rvec_t(X, x, camera_matrix, rng=rng, cov=cov)
     if not np.all(np.isfinite(p)):
         return np.zeros((3, 4), np.float32)
     R, t = rodrigues(p[:3]), p[3:].astype(np.float64)

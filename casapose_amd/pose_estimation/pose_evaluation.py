@@ -38,6 +38,17 @@ def transform_points_back(points_xy: np.ndarray, offsets: np.ndarray) -> np.ndar
     return np.stack([a * p[:, 0] + b * p[:, 1] + c, -b * p[:, 0] + a * p[:, 1] + d], axis=1)
 
 
+def transform_cov_back(cov, offsets: np.ndarray) -> np.ndarray:
+    """Keypoint covariances [n,3] = (sxx, sxy, syy) or [n,2,2] in crop pixels -> fp64 [n,2,2] in original image pixels: M cov M^T with M the
+    linear part of transform_points_back (a rotation by -angle over the scale)."""
+    o = _np(offsets).reshape(10)
+    ar = -o[6] * (np.pi / 180.0)
+    M = np.array([[np.cos(ar), np.sin(ar)], [-np.sin(ar), np.cos(ar)]]) / o[7]
+    c = _np(cov)
+    c = c.reshape(-1, 2, 2) if c.shape[-2:] == (2, 2) else c.reshape(-1, 3)
+    return M @ _pnp.covariance_matrices(c, c.shape[0]) @ M.T
+
+
 def project(xyz: np.ndarray, K: np.ndarray, RT: np.ndarray) -> Tuple[np.ndarray, np.ndarray]:
     """project_tf (ransac_voting.py:173-182): -> (pixels [n,2] with divide_no_nan, camera-frame points [n,3])."""
     cam = xyz @ RT[:, :3].T + RT[:, 3:].T
@@ -46,20 +57,22 @@ def project(xyz: np.ndarray, K: np.ndarray, RT: np.ndarray) -> Tuple[np.ndarray,
     return np.where(z != 0, pix[:, :2] / np.where(z != 0, z, 1.0), 0.0), cam
 
 
-def _solved_poses(solver, points_xy, points_3d, cams, mask, affine) -> np.ndarray:
+def _solved_poses(solver, points_xy, points_3d, cams, mask, affine, cov=None) -> np.ndarray:
     """One solver call for the batch -> float32 [b,oc,3,4] on the host.  A pair that was asked for and came back without a pose (a non-finite or
     degenerate keypoint set) has the zero pose, like the host path's failed solve (ransac_voting.py:48-49)."""
-    poses = solver.solve(points_xy, points_3d, cams, mask, affine=affine)
+    # cov (a device tensor from keypoint_covariance) goes to the solver as it is: no host copy between the voter and the solve
+    poses = solver.solve(points_xy, points_3d, cams, mask, affine=affine, cov=cov)
     poses = poses.detach().cpu().numpy() if hasattr(poses, "detach") else np.asarray(poses)
     return poses.astype(np.float32, copy=False).reshape(mask.shape[0], mask.shape[1], 3, 4)
 
 
-def estimate_poses(points, keypoints, camera_matrixes, valid_points_filter, offsets, rng=None, solver=None):
+def estimate_poses(points, keypoints, camera_matrixes, valid_points_filter, offsets, rng=None, solver=None, cov=None):
     """points [b,oc,vn,2] (x,y) crop pixels; keypoints [b,oc,ic,vn,3]; camera_matrixes [b,3,3]; valid_points_filter [b,oc];
     offsets [b,10]  ->  (poses [b,oc,3,4], false_positive [oc]).  A point set summing to |.| < 0.01 means "object not
     voted" and yields the zero pose (map_offsets / map_pnp, :488-515); a non-empty vote for an object that is not in the
     ground truth counts as a false positive (:518-523).  solver: a DevicePnP solves the voted pairs in one call instead of the loop
-    over pnp.pnp; the zero poses and the false-positive counts follow the same rules."""
+    over pnp.pnp; the zero poses and the false-positive counts follow the same rules.  cov: keypoint covariances [b,oc,vn,3] in crop pixels
+    (keypoint_covariance) weight the final LM of whichever PnP runs."""
     pts = _np(points)
     kp3 = _np(keypoints)
     cams = _np(camera_matrixes)
@@ -72,7 +85,8 @@ def estimate_poses(points, keypoints, camera_matrixes, valid_points_filter, offs
         sums = pts.sum(axis=(2, 3))
         false_pos = ((valid.reshape(b, oc) == 0) & (sums > 0)).sum(axis=0).astype(np.float32)
         mask = (np.abs(sums) >= 0.01).astype(np.int32)
-        return _solved_poses(solver, pts, kp3[:, :, 0], cams, mask, affine_from_offsets(offs)), false_pos
+        return _solved_poses(solver, pts, kp3[:, :, 0], cams, mask, affine_from_offsets(offs), cov), false_pos
+    cov = None if cov is None else _np(cov) + np.array([_pnp.COV_FLOOR, 0.0, _pnp.COV_FLOOR])
     poses = np.zeros((b, oc, 3, 4), np.float32)
     false_pos = np.zeros(oc, np.float32)
     for n in range(b):
@@ -84,7 +98,7 @@ def estimate_poses(points, keypoints, camera_matrixes, valid_points_filter, offs
                 continue
             p_img = transform_points_back(p, offs[n])
             cam = cams[n] if cams.ndim == 3 else cams
-            poses[n, o] = _pnp.pnp(kp3[n, o, 0], p_img, cam, rng=rng)
+            poses[n, o] = _pnp.pnp(kp3[n, o, 0], p_img, cam, rng=rng, cov=None if cov is None else transform_cov_back(cov[n, o], offs[n]))
     return poses, false_pos
 
 
@@ -199,6 +213,11 @@ def estimate_and_evaluate_poses(output_seg, target_seg, output_vertex, poses_gt,
     b, oc, ic = G.shape[0], G.shape[1], G.shape[2]
     h, w = output_seg.shape[1], output_seg.shape[2]
     avail = _objects_available(target_seg, min_num)
+    from .keypoint_covariance import uncertainty_pnp_enabled
+
+    cov, uncertainty = None, uncertainty_pnp_enabled()   # CASAPOSE_UNCERTAINTY_PNP=1
+    if uncertainty and points_estimated is not None:
+        raise ValueError("estimate_and_evaluate_poses: CASAPOSE_UNCERTAINTY_PNP=1 needs a vector field to vote on, but the keypoints were given")
     if points_estimated is None:
         lab = torch.argmax(output_seg, dim=3)
         onehot = torch.nn.functional.one_hot(lab, output_seg.shape[3])[..., 1:].to(torch.float32)
@@ -211,10 +230,13 @@ def estimate_and_evaluate_poses(output_seg, target_seg, output_vertex, poses_gt,
             idx = torch.clamp(lab - 1, min=0)[..., None, None].expand(b, h, w, 1, vc * 2)
             output_vertex = torch.where((lab == 0)[..., None], torch.zeros((), dtype=sl.dtype, device=sl.device), torch.gather(sl, 3, idx)[:, :, :, 0])
         vert = output_vertex.reshape(b, h, w, -1, 2).contiguous()
-        points_estimated = ransac_voting_layer_all_masks(onehot, vert, 512, inlier_thresh=0.99, max_iter=20, min_num=min_num, max_num=30000, **kw)
+        points_estimated = ransac_voting_layer_all_masks(onehot, vert, 512, inlier_thresh=0.99, max_iter=20, min_num=min_num, max_num=30000,
+                                                         return_covariance=uncertainty, **kw)
+        if uncertainty:
+            points_estimated, cov = points_estimated
     else:
         points_estimated = _np(points_estimated) * np.array([[[[h, w]]]], np.float64)
-    poses, false_positive_mask = estimate_poses(points_estimated, object_points_3d, camera_data, avail, offsets, solver=solver)
+    poses, false_positive_mask = estimate_poses(points_estimated, object_points_3d, camera_data, avail, offsets, solver=solver, cov=cov)
     if evaluator is not None:
         e2, e3, v2, v3, miss, vcount, fp = evaluator.evaluate(poses, G, camera_data, diameters, avail, 5.0)
     else:
@@ -223,12 +245,27 @@ def estimate_and_evaluate_poses(output_seg, target_seg, output_vertex, poses_gt,
     return [v2, v3, vcount, false_positive_mask, e2, e3, miss, fp], poses, points_estimated
 
 
-def poses_pnp(points_estimated, seg_estimated, object_points_3d, camera_data, no_objects: int, min_num: int = 20, rng=None, solver=None):
+def poses_pnp(points_estimated, seg_estimated, object_points_3d, camera_data, no_objects: int, min_num: int = 20, rng=None, solver=None, cov=None):
     """pose_evaluation.py:164-217: voted keypoints [b,oc,vc,2] in (y,x) -> poses [b,oc,1,3,4]; objects with <= min_num
     estimated pixels get the zero pose; the pose is negated when t_z < 0.  solver: a DevicePnP solves the batch in one call; None asks
-    device_pnp.solver_from_environment (CASAPOSE_DEVICE_PNP=1, a segmentation on a GPU), and without one the host loop below runs."""
+    device_pnp.solver_from_environment (CASAPOSE_DEVICE_PNP=1, a segmentation on a GPU), and without one the host loop below runs.  cov: keypoint
+    covariances [b,oc,vc,3] = (sxx, sxy, syy) in (x,y) pixels (keypoint_covariance) weight the final LM of whichever PnP runs; with
+    CASAPOSE_UNCERTAINTY_PNP=1 and no cov they are voted here when points_estimated is the tensor a CoordLSVotingWeighted just returned."""
     import torch
 
+    from .keypoint_covariance import uncertainty_pnp_enabled
+
+    if cov is None and uncertainty_pnp_enabled():
+        # a caller that holds only the keypoints (util_scripts/test_minimal.py): when they are the very tensor an LS voter just returned, the
+        # voter still has the labels and the field it voted with
+        from .keypoint_covariance import keypoint_covariance
+        from .voting_layers_2d import voter_of
+
+        voter = voter_of(points_estimated)
+        if voter is None:
+            raise ValueError("poses_pnp: CASAPOSE_UNCERTAINTY_PNP=1 needs cov= (keypoint_covariance of the voter's labels, the vector field and the "
+                             "voted keypoints), or the keypoints tensor as CoordLSVotingWeighted returned it: this call has no vector field to vote on")
+        cov = keypoint_covariance(voter.last_labels, voter.last_field, points_estimated.flip(-1))
     if solver is None and hasattr(seg_estimated, "detach") and seg_estimated.is_cuda:
         from .device_pnp import solver_from_environment
 
@@ -242,17 +279,20 @@ def poses_pnp(points_estimated, seg_estimated, object_points_3d, camera_data, no
     cam = cam[0] if cam.ndim == 3 else cam
     if solver is not None:
         mask = np.array([[int((lab[n] == o + 1).sum()) > min_num for o in range(oc)] for n in range(b)], np.int32)
-        poses = _solved_poses(solver, np.ascontiguousarray(pts[:, :oc]), kp3.reshape(b, -1, pts.shape[2], 3)[:, :oc], cam, mask, None)
+        if cov is not None:
+            cov = cov[:, :oc].contiguous() if hasattr(cov, "detach") else np.ascontiguousarray(_np(cov)[:, :oc])
+        poses = _solved_poses(solver, np.ascontiguousarray(pts[:, :oc]), kp3.reshape(b, -1, pts.shape[2], 3)[:, :oc], cam, mask, None, cov)
         bad = np.argwhere((mask != 0) & np.isin(np.asarray(solver.last_info)[..., 0], (2, 4)))   # a degenerate keypoint set (3) is the zero pose
         if len(bad):
             raise FloatingPointError("poses_pnp: non-finite pose for image %d object %d" % (bad[0][0], bad[0][1]))
         return poses[:, :, None]
     out = np.zeros((b, oc, 1, 3, 4), np.float32)
+    cov = None if cov is None else _np(cov) + np.array([_pnp.COV_FLOOR, 0.0, _pnp.COV_FLOOR])
     for n in range(b):
         for o in range(oc):
             if int((lab[n] == o + 1).sum()) <= min_num:
                 continue
-            p6 = _pnp.pnp_rvec_t(kp3[n, o].reshape(-1, 3), pts[n, o], cam, rng=rng)
+            p6 = _pnp.pnp_rvec_t(kp3[n, o].reshape(-1, 3), pts[n, o], cam, rng=rng, cov=None if cov is None else cov[n, o])
             if not np.all(np.isfinite(p6)):
                 raise FloatingPointError("poses_pnp: non-finite pose for image %d object %d" % (n, o))
             R, t = _pnp.rodrigues(p6[:3]), p6[3:].astype(np.float64)

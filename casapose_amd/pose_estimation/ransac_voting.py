@@ -40,7 +40,7 @@ def _device_generator_seed(generator: torch.Generator) -> int:
 def ransac_voting_layer_all_masks(mask: torch.Tensor, vertex: torch.Tensor, round_hyp_num: int, inlier_thresh: float = 0.99,
                                   confidence: float = 0.99, max_iter: int = 20, min_num: int = 5, max_num: int = 30000,
                                   draws: Optional[torch.Tensor] = None, generator: Optional[torch.Generator] = None,
-                                  return_rounds: bool = False):
+                                  return_rounds: bool = False, return_covariance: bool = False):
     """mask [b,h,w,oc] one-hot object masks (no background channel), vertex [b,h,w,vn,2] or
     [b,h,w,vn*2] in (dy,dx) order.  Returns [b,oc,vn,2] keypoints in (x,y).
 
@@ -51,7 +51,8 @@ def ransac_voting_layer_all_masks(mask: torch.Tensor, vertex: torch.Tensor, roun
     synchronise the stream: ADVICE round 4); no draw tensor exists.  The random stream of a given seed differs from round 3's torch.randint
     draws (INTEGRATION.md, section on the voters).  `draws` (int32 [max_iter,b,oc,round_hyp_num,vn,2],
     values in [0,2^31)) replaces the pixel-pair draws of :319-321 -- tests inject them; on that path the thinning is done here with torch (it needs
-    the counts on the host)."""
+    the counts on the host).  return_covariance: the keypoint covariances float32 [b,oc,vn,3] about the voted points are returned as the last element
+    (keypoint_covariance.py: one more round of hypotheses over the same labels, with a seed of its own from the same generator)."""
     if not mask.is_cuda:
         raise _lib.CasaposeHipError("ransac_voting_layer_all_masks needs CUDA (ROCm) tensors; there is no CPU fallback")
     lib = _lib.load()
@@ -74,7 +75,7 @@ def ransac_voting_layer_all_masks(mask: torch.Tensor, vertex: torch.Tensor, roun
         check(lib.cp_ransac_vote_seeded_f32(labels.data_ptr(), vert.data_ptr(), vert.shape[3], 0, b, h, w, oc, vn, seed, round_hyp_num, float(inlier_thresh),
                                             float(confidence), int(max_iter), int(min_num), int(max_num), ws.data_ptr(), out.data_ptr(), rounds.data_ptr(), stream),
               "cp_ransac_vote_seeded_f32")
-        return (out, rounds) if return_rounds else out
+        return _results(out, rounds, return_rounds, return_covariance, labels, vert, round_hyp_num, inlier_thresh, min_num, max_num, generator)
     if int(counts.max()) > max_num:
         # random down-sampling of large masks (:295-301): keep a pixel with probability max_num / count
         keep_p = (max_num / counts.clamp(min=1).to(torch.float32)).clamp(max=1.0)  # [b,oc]
@@ -88,4 +89,14 @@ def ransac_voting_layer_all_masks(mask: torch.Tensor, vertex: torch.Tensor, roun
     check(lib.cp_ransac_vote_f32(labels.data_ptr(), vert.data_ptr(), vert.shape[3], 0, b, h, w, oc, vn, draws.data_ptr(), round_hyp_num,
                                  float(inlier_thresh), float(confidence), int(max_iter), int(min_num), int(max_num), ws.data_ptr(),
                                  out.data_ptr(), rounds.data_ptr(), stream), "cp_ransac_vote_f32")
-    return (out, rounds) if return_rounds else out
+    return _results(out, rounds, return_rounds, return_covariance, labels, vert, round_hyp_num, inlier_thresh, min_num, max_num, generator)
+
+
+def _results(out, rounds, return_rounds, return_covariance, labels, vert, hyp, inlier_thresh, min_num, max_num, generator):
+    """what ransac_voting_layer_all_masks returns: the keypoints, then the rounds and the covariance where they were asked for"""
+    res = [out] + ([rounds] if return_rounds else [])
+    if return_covariance:
+        from .keypoint_covariance import keypoint_covariance
+
+        res.append(keypoint_covariance(labels, vert, out, hyp=hyp, inlier_thresh=inlier_thresh, min_num=min_num, max_num=max_num, generator=generator))
+    return res[0] if len(res) == 1 else tuple(res)

@@ -4,12 +4,14 @@
 """
 from __future__ import annotations
 
+import weakref
 from typing import Optional, Sequence
 
 import torch
 
 from .. import _lib, ops
 from .._lib import check
+from .keypoint_covariance import uncertainty_pnp_enabled
 
 
 def _as_record(seg: torch.Tensor, direct: torch.Tensor, conf: torch.Tensor):
@@ -47,6 +49,19 @@ class CoordLSVotingWeighted:
         self.filter_estimates = filter_estimates
         self.sigmoid_weights = bool(sigmoid_weights)   # w = sigmoid(sigmoid_scale * conf), sigmoid_scale = 1 (voting_layers_2d.py:20,32-33); default softplus
         self.min_component = 50  # voting_layers_2d.py:66
+        self._voted = None   # the last call's filtered label map, or (record, objects, seg offset) of an unfiltered call
+        self.last_field: Optional[torch.Tensor] = None   # with CASAPOSE_UNCERTAINTY_PNP=1: the last call's merged field [b,h,w,2*kp] (dy,dx), a view
+
+    @property
+    def last_labels(self) -> Optional[torch.Tensor]:
+        """uint8 [b,h,w]: the label map the last call voted with -- the filtered map with filter_estimates, the arg-max map otherwise.
+        keypoint_covariance takes it over the pixels that voted.  With CASAPOSE_UNCERTAINTY_PNP=1 the arg-max map is made in the call
+        itself; otherwise the voter takes the arg-max inside its kernel and the map is made when it is first asked for, from the
+        segmentation the voter was given: ask before that tensor is overwritten."""
+        if isinstance(self._voted, tuple):
+            rec, objects, so = self._voted
+            self._voted = ops.argmax_labels(rec, classes=objects + 1, offset=so)
+        return self._voted
 
     def __call__(self, inp: Sequence[torch.Tensor], **kwargs) -> torch.Tensor:
         seg, direct, conf = inp
@@ -70,4 +85,21 @@ class CoordLSVotingWeighted:
             check(lib.cp_ccl_filter_labels(lab0.data_ptr(), b, h, w, objects, self.min_component, 2 if self.output_second_largest_component else 1, ws.data_ptr(),
                                            labels.data_ptr(), torch.cuda.current_stream(rec.device).cuda_stream),
                   "cp_ccl_filter_labels")
-        return ops.ls_vote(rec, so, do, co, objects, self.num_points, labels=labels, sigmoid_weights=self.sigmoid_weights)
+        self._voted = labels if labels is not None else (rec, objects, so)
+        out = ops.ls_vote(rec, so, do, co, objects, self.num_points, labels=labels, sigmoid_weights=self.sigmoid_weights)
+        if uncertainty_pnp_enabled():   # what a caller that only holds the keypoints (poses_pnp) needs to vote their covariance: voter_of()
+            global _last_vote
+            self.last_labels   # (made now: the record may be the network's output buffer)
+            self.last_field = rec[..., do:do + 2 * self.num_points]
+            _last_vote = (weakref.ref(out), self)
+        return out
+
+
+_last_vote = None   # (weak reference to the keypoints the last vote under CASAPOSE_UNCERTAINTY_PNP=1 returned, its voter)
+
+
+def voter_of(points) -> Optional[CoordLSVotingWeighted]:
+    """The voter whose last call, made under CASAPOSE_UNCERTAINTY_PNP=1, returned this very tensor; None for any other object."""
+    if _last_vote is not None and _last_vote[0]() is points:
+        return _last_vote[1]
+    return None

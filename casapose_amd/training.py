@@ -223,13 +223,15 @@ def train_step(net, batch: Dict[str, torch.Tensor], loss_factors, optimizer: Opt
     return [float(total), float(s[0]), float(s[1]), float(s[2]), kpv]
 
 
-def poses_from_coords(coords_yx, objects_available, batch, rng=None, solver=None) -> Tuple[np.ndarray, np.ndarray]:
+def poses_from_coords(coords_yx, objects_available, batch, rng=None, solver=None, cov=None) -> Tuple[np.ndarray, np.ndarray]:
     """The pose branch of keypoint_reprojection_loss (loss_functions.py:229,264-315): voted keypoints (y,x) in crop
     pixels -> (x,y) -> original image pixels (transform_points_back) -> host PnP -> pose negated if t_z < 0 -> zeroed for
     unavailable objects.  Returns (poses [B,oc,1,3,4], image-space points [B,oc,kp,2]) as float32 arrays.  solver: a DevicePnP
-    (pose_estimation/device_pnp.py) solves the available pairs in one call on the GPU instead of the host loop."""
+    (pose_estimation/device_pnp.py) solves the available pairs in one call on the GPU instead of the host loop.  cov: keypoint covariances
+    [B,oc,kp,3] = (sxx, sxy, syy) in crop pixels, x before y (keypoint_covariance), weight the final LM of whichever PnP runs; a device tensor
+    goes to the device solver as it is."""
     from .pose_estimation import pnp as _pnp
-    from .pose_estimation.pose_evaluation import transform_points_back
+    from .pose_estimation.pose_evaluation import transform_cov_back, transform_points_back
 
     c = _host(coords_yx)
     B, oc, kp, _ = c.shape
@@ -240,6 +242,7 @@ def poses_from_coords(coords_yx, objects_available, batch, rng=None, solver=None
     p3d = _host(batch["keypoints3d"]).reshape(B, oc, -1, 3)
     poses = np.zeros((B, oc, 1, 3, 4), np.float32)
     pts = np.zeros((B, oc, kp, 2), np.float32)
+    cov_host = None if cov is None or solver is not None else _host(cov).astype(np.float64) + np.array([_pnp.COV_FLOOR, 0.0, _pnp.COV_FLOOR])
     for n in range(B):
         for o in range(oc):
             xy = transform_points_back(c[n, o, :, ::-1], offs[n])
@@ -248,7 +251,7 @@ def poses_from_coords(coords_yx, objects_available, batch, rng=None, solver=None
             pts[n, o] = xy
             if solver is not None:
                 continue
-            p6 = _pnp.pnp_rvec_t(p3d[n, o], xy, cam, rng=rng)
+            p6 = _pnp.pnp_rvec_t(p3d[n, o], xy, cam, rng=rng, cov=None if cov_host is None else transform_cov_back(cov_host[n, o], offs[n]))
             if not np.all(np.isfinite(p6)):
                 raise FloatingPointError("PnP returned a non-finite pose (image %d, object %d)" % (n, o))  # tf.Assert, loss_functions.py:299-304
             R, t = _pnp.rodrigues(p6[:3]), p6[3:].astype(np.float64)
@@ -258,7 +261,7 @@ def poses_from_coords(coords_yx, objects_available, batch, rng=None, solver=None
         from .pose_estimation.device_pnp import affine_from_offsets
 
         mask = (avail != 0).astype(np.int32)
-        solved = solver.solve(np.ascontiguousarray(c[..., ::-1]), p3d, cam, mask, affine=affine_from_offsets(offs))
+        solved = solver.solve(np.ascontiguousarray(c[..., ::-1]), p3d, cam, mask, affine=affine_from_offsets(offs), cov=cov)
         bad = np.argwhere((mask != 0) & np.isin(np.asarray(solver.last_info)[..., 0], (2, 4)))   # a degenerate keypoint set (3) is the zero pose
         if len(bad):
             raise FloatingPointError("PnP returned a non-finite pose (image %d, object %d)" % (bad[0][0], bad[0][1]))
@@ -268,7 +271,8 @@ def poses_from_coords(coords_yx, objects_available, batch, rng=None, solver=None
 
 def test_step(net, batch, opt, loss_factors, evaluation_points=None, object_points_3d_count=None, evaluator=None):
     """One evaluation step of test_casapose.py (:268-384): inference forward, (component-filtered) LS keypoint voting or
-    RANSAC voting, PnP (on the host, or with CASAPOSE_DEVICE_PNP=1 on the GPU: device_pnp.solver_from_environment), losses and the eight per-object pose statistics (computed on the GPU with a DevicePoseEvaluator as `evaluator`, or,
+    RANSAC voting, PnP (on the host, or with CASAPOSE_DEVICE_PNP=1 on the GPU: device_pnp.solver_from_environment; with CASAPOSE_UNCERTAINTY_PNP=1
+    weighted by the keypoint covariances of keypoint_covariance.py), losses and the eight per-object pose statistics (computed on the GPU with a DevicePoseEvaluator as `evaluator`, or,
     with CASAPOSE_DEVICE_EVAL=1 and evaluation meshes, with the one device_evaluation.evaluator_from_environment keeps for them).
     Returns (losses [5 floats], pose_stats [8 arrays of oc], poses [B,oc,3,4], points, seconds)."""
     import time
@@ -301,11 +305,16 @@ def test_step(net, batch, opt, loss_factors, evaluation_points=None, object_poin
                                       filter_estimates=bool(getattr(opt, "confidence_filter_estimates", True)),
                                       output_second_largest_component=bool(getattr(opt, "confidence_choose_second", False)))
         coords = voter([seg if with_gt else o_seg, o_dirs, conf])
+    from .pose_estimation.keypoint_covariance import keypoint_covariance, uncertainty_pnp_enabled
+
+    cov = None
+    if coords is not None and uncertainty_pnp_enabled():   # CASAPOSE_UNCERTAINTY_PNP=1: the covariance about the LS-voted keypoints, over the pixels that voted
+        cov = keypoint_covariance(voter.last_labels, o_dirs, coords.flip(-1))
     losses = train_step(net, batch, loss_factors, None, opt, train=False, coords=coords, min_num=int(getattr(opt, "min_object_size_test", 1)),
                         min_num_gt=1, filter_with_gt=bool(getattr(opt, "filter_test_with_gt", False)))
     if coords is not None:
         plan, _ = net.training_plan(img.shape[0], img.shape[1], img.shape[2])
-        poses, pts = poses_from_coords(coords, plan.objects_available, batch, solver=solver)
+        poses, pts = poses_from_coords(coords, plan.objects_available, batch, solver=solver, cov=cov)
         stats, poses, pts = evaluate_pose_estimates(pts, poses, batch["poses_gt"], seg, batch["keypoints3d"], batch["cam_mat"], batch["diameters"],
                                                     evaluation_points=evaluation_points, object_points_3d_count=object_points_3d_count, min_num=1,
                                                     evaluator=evaluator)

@@ -1,6 +1,6 @@
 """One call path for a kernel and its host twin.
 
-A host twin (`cp_X_host_T` beside `cp_X_T` in include/casapose_hip.h; `_lib.TWINS` finds the pairs) runs a kernel's arithmetic serially on
+A host twin (`cp_X_host_T` beside `cp_X_T` in include/casapose_hip.h; `_lib.TWINS` finds the pairs, `_lib.TWIN_VARIANTS` their weighted variants) runs a kernel's arithmetic serially on
 host pointers and takes the kernel's arguments minus the trailing stream.  A wrapper therefore writes its argument list once and hands it to
 `call`; only where the arrays live differs: `array` converts an input and `alloc` makes a set of outputs, on a device or as NumPy arrays.
 
@@ -63,9 +63,9 @@ def call(name: str, *args, host: bool = False, stream: Optional[int] = None) -> 
     lib = _lib.load()
     if _lib.POINTEES.get(name, ())[-1:] != ("void",):
         raise _lib.CasaposeHipError("%s is no entry point of %s that ends in a stream" % (name, _lib.HEADER_PATH))
-    if host and name not in _lib.TWINS:
+    if host and _lib.host_twin(name) is None:
         raise _lib.CasaposeHipError("%s has no host twin" % name)
-    symbol = _lib.TWINS[name] if host else name
+    symbol = _lib.host_twin(name) if host else name
     if host != (stream is None):
         raise _lib.CasaposeHipError("%s: %s" % (symbol, "a host twin takes no stream" if host else "a device call needs a stream"))
     pointees = _lib.POINTEES[name][:-1]

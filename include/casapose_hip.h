@@ -400,6 +400,36 @@ typedef struct cp_ransac_state {
  * are skipped (st.tn = 0) leave their hyp_pts, counts and pixlist entries unwritten. */
 int cp_ransac_workspace_layout(int batch, int h, int w, int objects, int kp, int hyp, size_t* offsets /*[7]*/, size_t* state_bytes);
 
+/* Keypoint covariances from the voting distribution (PVNet's uncertainty, about a given mean): for every (image, object) pair and keypoint v,
+ * `hyp` two-ray hypotheses h_j are drawn and voted exactly as one round of the voter above draws and votes them (same compaction, same
+ * hypothesis and inlier kernels), c_j = the inlier count of h_j over the pair's pixels, and
+ *   wsum = sum_j c_j,    cov = sum_j c_j (h_j - mean)(h_j - mean)^T / wsum    as (sxx, sxy, syy) in px^2.
+ * A hypothesis with c_j = 0 is skipped (a non-finite hypothesis has no inliers and never reaches the sum).  The centred differences are
+ * accumulated in fp64 by one wave per (pair, keypoint) and reduced in a fixed order: no float atomics, two calls give the same bits; cov is
+ * rounded to fp32 once.  cov = 0 and wsum = 0 for a pair without pixels, a pair below min_num (counted before any thinning), wsum = 0, or a
+ * non-finite mean.  wsum saturates at 2^31 - 1.
+ *   labels, vertex, ld, dir_off, batch, h, w, objects, kp, hyp, inlier_thresh, min_num, max_num: as for cp_ransac_vote_f32
+ *   mean   fp32 [n][objects][kp][2]   (x, y) pixels in the voter's (x + 0.5, y + 0.5) convention: the voted keypoints of either voter
+ *   draws  int32 [n][objects][hyp][kp][2]   cp_kp_cov_f32: uniform in [0, 2^31), a draw d selects pixel d % tn (max_num is then signature parity)
+ *   seed   cp_kp_cov_seeded_f32: the draws come from the voter's counter-based generator under another key than the voting rounds' (seed ^ a
+ *          constant, as the thinning's), and objects above max_num pixels are thinned inside the compaction with the pixel decisions cp_ransac_vote_seeded_f32
+ *          makes for this seed: the covariance is taken over the pixels that voted
+ *   cov    fp32 [n][objects][kp][3];   wsum  int32 [n][objects][kp]
+ *   ws     cp_kp_cov_workspace_bytes(...) bytes, 256-byte aligned.  The call builds its own state records; a workspace a voting call used may be
+ *          reused, its contents are not.
+ * hyp must be a multiple of 16 and hyp * min(max_num, h*w) < 2^31.  cp_kp_cov_workspace_layout: offsets[4] = the byte offsets of
+ *   [0] pixlist  int32 [n][objects][h*w]   [1] st  cp_ransac_state [n][objects] (tn; done = (tn == 0))
+ *   [2] hyp_pts  float [n][objects][hyp][kp][2]   [3] counts  int32 [n][objects][hyp][kp]
+ * as after one voting round; pairs with tn = 0 leave theirs unwritten. */
+int cp_kp_cov_f32(const uint8_t* labels, const float* vertex, int ld, int dir_off, int batch, int h, int w, int objects, int kp,
+                  const float* mean, const int32_t* draws, int hyp, float inlier_thresh, int min_num, int max_num, void* ws, float* cov,
+                  int32_t* wsum, void* stream);
+int cp_kp_cov_seeded_f32(const uint8_t* labels, const float* vertex, int ld, int dir_off, int batch, int h, int w, int objects, int kp,
+                         const float* mean, unsigned long long seed, int hyp, float inlier_thresh, int min_num, int max_num, void* ws, float* cov,
+                         int32_t* wsum, void* stream);
+size_t cp_kp_cov_workspace_bytes(int batch, int h, int w, int objects, int kp, int hyp);
+int cp_kp_cov_workspace_layout(int batch, int h, int w, int objects, int kp, int hyp, size_t* offsets /*[4]*/, size_t* state_bytes);
+
 /* GuidedBilinearUpsampling (_normalization_layers.py:569-664; casapose_c_gcu4_bilat): mask[n,Y,X] bit j = the low-resolution label of
  * tap j in {(y,x),(y,x+1),(y+1,x),(y+1,x+1)} (zero padded bottom/right) equals labels_hi[n,Y,X]; the upsampling blends the four taps
  * with the fixed sub-pixel weights after replacing non-matching taps by the mean of the matching ones (0 if none), which is the
@@ -896,6 +926,23 @@ int cp_pnp_f64(const float* points_xy, const float* points_3d, const float* K, i
                const uint8_t* table, int b, int oc, int n, int H, float reprojection_error, float* poses, int32_t* info, float* cost, void* stream);
 int cp_pnp_host_f64(const float* points_xy, const float* points_3d, const float* K, int k_per_image, const double* affine, const int32_t* solve,
                     const uint8_t* table, int b, int oc, int n, int H, float reprojection_error, float* poses, int32_t* info, float* cost);
+/* Uncertainty-weighted PnP (csrc/pnp_weighted.hip): cp_pnp_f64 whose final LM minimises the Mahalanobis reprojection error.  The consensus stage and both EPnP calls
+ * are cp_pnp_f64's (plain pixel errors against reprojection_error); only the LM over all points differs, with the same damping schedule, trip
+ * counts and relative stop.
+ *   cov        fp32 [b*oc][n][3]   (sxx, sxy, syy) per keypoint in the pixel system of points_xy (cp_kp_cov_f32's output); never NULL -- callers
+ *                                  without covariances use cp_pnp_f64
+ *   cov_floor  added to sxx and syy before anything else (>= 0, finite)
+ *   weighted   int32 [b*oc]        1: solved with weights; 0: not solved (status != 0), or solved exactly as cp_pnp_f64 solves it
+ * Per point Sigma = cov + cov_floor I, with an affine Sigma' = M Sigma M^T for M = [[a0, a1], [a3, a4]], Sigma' = L L^T (lower Cholesky), and the
+ * residual (ru, rv) with its two Jacobian rows becomes ru' = ru / l00, rv' = (rv - l10 ru') / l11.  If any point of a pair has a non-finite
+ * Sigma' or one without positive pivots, the whole pair takes cp_pnp_f64's path and weighted = 0.  cost: the Mahalanobis cost before and after
+ * LM when weighted = 1.  Added in ABI 302 without changing any earlier entry point. */
+int cp_pnp_weighted_f64(const float* points_xy, const float* points_3d, const float* K, int k_per_image, const double* affine, const int32_t* solve,
+                        const uint8_t* table, int b, int oc, int n, int H, float reprojection_error, const float* cov, float cov_floor, float* poses,
+                        int32_t* info, float* cost, int32_t* weighted, void* stream);
+int cp_pnp_weighted_host_f64(const float* points_xy, const float* points_3d, const float* K, int k_per_image, const double* affine,
+                             const int32_t* solve, const uint8_t* table, int b, int oc, int n, int H, float reprojection_error, const float* cov,
+                             float cov_floor, float* poses, int32_t* info, float* cost, int32_t* weighted);
 
 /* ---- BPnP keypoint loss (csrc/bpnp.hip, csrc/bpnp_math.h) ----------------------------------------------------------------------------
  * keypoint_reprojection_loss with use_bpnp_reprojection_loss = 1 (loss_functions.py:264-323) and its gradient, on the device:
