@@ -214,12 +214,15 @@ SYMBOLS, POINTEES, RETURN_POINTEES, _PAIRS = parse_header(_header)
 # cp_pnp_weighted_f64 takes cp_pnp_f64's arguments plus the weights: the pair is listed as that kernel's variant, and TWINS keeps one row per
 # kernel.  host_twin() reads both.
 TWIN_VARIANTS = {d: _PAIRS[d] for d in ("cp_pnp_weighted_f64",)}
-TWINS = {d: h for d, h in _PAIRS.items() if d not in TWIN_VARIANTS}
+# cp_depth_icp_step_f64 has no inputs of its own: it reads the planes and rewrites the poses of cp_render_masks_u8, whose row TWINS holds.  Its
+# pair is listed as a step on that kernel's output.
+TWIN_STEPS = {d: _PAIRS[d] for d in ("cp_depth_icp_step_f64",)}
+TWINS = {d: h for d, h in _PAIRS.items() if d not in TWIN_VARIANTS and d not in TWIN_STEPS}
 
 
 def host_twin(name: str) -> Optional[str]:
-    """the host twin of the device entry point `name` (a kernel's, or a weighted variant's), or None"""
-    return TWINS.get(name) or TWIN_VARIANTS.get(name)
+    """the host twin of the device entry point `name` (a kernel's, a weighted variant's or a follow-up step's), or None"""
+    return TWINS.get(name) or TWIN_VARIANTS.get(name) or TWIN_STEPS.get(name)
 
 
 _lib: Optional[C.CDLL] = None

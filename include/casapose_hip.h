@@ -1061,6 +1061,43 @@ int cp_vsd_counts_i32(const uint32_t* planes, const int32_t* records, int nplane
                       const int32_t* pairs, const double* diameters, int npairs, double delta, const double* taus, int ntau, int split,
                       int32_t* counts, void* stream);
 
+/* ---- depth refinement: projective point-to-plane ICP (csrc/depth_icp.hip, csrc/icp_math.h) -----------------------------------------------
+ * One Gauss-Newton step per job = (image, rendered plane, gate): every pixel of the plane's bbox_obj, clipped to [1, W-2] x [1, H-2], whose
+ * rendered depth z and four neighbours are hit without a depth step of jump x gate or more and whose sensor depth d has d > 0 and |d - z| < gate
+ * gives a normal n from the central differences of the back-projected plane, a residual r = n . (q - p) and a Jacobian J = (p x n, n); the
+ * sums of J J^T, J r and r r are solved with relative damping by Cholesky for xi = (omega, v), and the pose becomes dR R, dR t + v with dR
+ * the rotation of the unit quaternion (1, omega / 2) / |.| (the rules are listed in csrc/icp_math.h).  Everything is device memory.
+ *   planes     uint32 [nplanes][H][W]   the workspace of cp_render_masks_u8 after the call, nplanes = frames * instances_max
+ *   records    int32 [nplanes][11]      its records; words 2-5 (bbox_obj: x, y, w, h) bound the pixels a plane is read at
+ *   depth      fp32 [images][H][W]      sensor depth in millimetres; a value that is not > 0 (0, negative, NaN) is missing
+ *   cams       fp64 [images][4]         fx, fy, cx, cy; pixel centres at integer coordinates
+ *   jobs       int32 [njobs][4]         (image, plane, unused, unused); with update = 1 no two jobs may name the same plane
+ *   gates      fp64 [njobs]             millimetres, > 0
+ *   jump       in gates, > 0            damping >= 0: times diag(A)         min_pixels >= 1
+ *   update     1: rewrite the poses of the jobs that solved; 0: stats and status only
+ *   split      blocks per job in the accumulation, 1 .. 64: a speed setting, no bit of the result depends on it
+ *   poses      fp64 [nplanes][12]       the poses the planes were rendered at -- the renderer's own `poses` argument -- rewritten in place,
+ *                                       so the next cp_render_masks_u8 on the same stream renders the refined poses
+ *   stats      fp64 [njobs][4]          pixels used, RMS residual before the update, |omega|, |v|
+ *   status     int32 [njobs]            0 solved; 1 fewer than min_pixels pixels; 2 a Cholesky pivot was not positive; 3 the job was
+ *                                       refused: image or plane index out of range or gate not > 0 (nothing is read for it, stats are zeros).
+ *                                       Every status but 0 leaves the pose as it is
+ *   workspace  cp_depth_icp_workspace_bytes(njobs, H, W) bytes, 8-byte aligned: per job one record of 29 fp64 words (28 sums, the count)
+ *              per tile of cp_depth_icp_tile() pixels of the largest clipped box; needs no initialisation
+ * The order of summation is fixed (lane sums, one 64-lane tree per tile, tiles in index order) and there are no floating-point atomics: two
+ * calls with the same inputs, any split and any workspace contents give the same bytes.  No pixel outside the clipped box grown by one pixel
+ * is addressed.  H, W <= 16384, njobs * split < 2^31.  cp_depth_icp_workspace_bytes returns 0 for sizes outside these limits.
+ * cp_depth_icp_step_host_f64 runs the same code serially on host pointers and launches nothing: it works without a GPU and gives the
+ * device's bytes.  Added in ABI 302 without changing any earlier entry point. */
+int cp_depth_icp_tile(void);
+size_t cp_depth_icp_workspace_bytes(int njobs, int H, int W);
+int cp_depth_icp_step_f64(const uint32_t* planes, const int32_t* records, int nplanes, int H, int W, const float* depth, const double* cams,
+                          int images, const int32_t* jobs, const double* gates, int njobs, double jump, double damping, int min_pixels, int update,
+                          int split, double* poses, double* stats, int32_t* status, void* workspace, size_t workspace_bytes, void* stream);
+int cp_depth_icp_step_host_f64(const uint32_t* planes, const int32_t* records, int nplanes, int H, int W, const float* depth, const double* cams,
+                               int images, const int32_t* jobs, const double* gates, int njobs, double jump, double damping, int min_pixels,
+                               int update, int split, double* poses, double* stats, int32_t* status, void* workspace, size_t workspace_bytes);
+
 /* ---- keypoints and models_info of a mesh set (csrc/models.hip, csrc/model_math.h) --------------------------------------------------------
  * What the dataset converter needs per object and BOP archives do not hold (data_handler/model_prep.py): the axis-aligned box, the squared
  * diameter (the largest squared distance over all vertex pairs) and no_points keypoints, the box centre followed by farthest-point samples of
