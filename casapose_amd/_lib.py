@@ -144,7 +144,7 @@ TILE_SPLIT3, TILE_BF16, TILE_F16X2 = 100, 101, 102
 HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "casapose_hip.h")
 _SCALARS = {"int": C.c_int, "long long": C.c_longlong, "int64_t": C.c_int64, "unsigned long long": C.c_ulonglong, "uint64_t": C.c_uint64,
             "float": C.c_float, "double": C.c_double, "size_t": C.c_size_t}
-_POINTEE_ONLY = ("void", "char", "int32_t", "uint8_t", "uint32_t", "cp_conv_desc", "cp_aug_image")
+_POINTEE_ONLY = ("void", "char", "int32_t", "uint8_t", "uint16_t", "uint32_t", "cp_conv_desc", "cp_aug_image")
 
 
 def _parse_type(decl: str, where: str, is_return: bool = False):
@@ -171,7 +171,7 @@ def parse_header(text: str):
     """Every function prototype of a header in the style of include/casapose_hip.h -> (symbols, pointees, return_pointees, twins):
     symbols [(name, restype, argtypes)] in declaration order; pointees {name: per argument, what a pointer points to ("float", "void",
     "uint8_t*", ...) or None for a scalar}; return_pointees {name: the same for the return value}; twins {X_T: X_host_T} for T in f32 / f64 /
-    u8 where both are declared -- X_host_T then must take X_T's parameters minus a trailing `void* stream`.  A statement that is no struct, enum
+    u8 / u16 where both are declared -- X_host_T then must take X_T's parameters minus a trailing `void* stream`.  A statement that is no struct, enum
     or readable prototype raises CasaposeHipError: nothing is skipped."""
     text = re.sub(r"/\*.*?\*/", " ", text, flags=re.S)
     text = re.sub(r"//[^\n]*|^[ \t]*#[^\n]*", " ", text, flags=re.M)
@@ -194,7 +194,7 @@ def parse_header(text: str):
         pointees[name] = tuple(p for _, p in parsed)
     twins, argtypes = {}, {n: a for n, _, a in symbols}
     for host in pointees:
-        m = re.fullmatch(r"(\w+)_host_(f32|f64|u8)", host)
+        m = re.fullmatch(r"(\w+)_host_(f32|f64|u8|u16)", host)
         device = m and "%s_%s" % m.groups()
         if device in pointees:
             if argtypes[device] != argtypes[host] + [C.c_void_p] or pointees[device] != pointees[host] + ("void",):
@@ -215,8 +215,9 @@ SYMBOLS, POINTEES, RETURN_POINTEES, _PAIRS = parse_header(_header)
 # kernel.  host_twin() reads both.
 TWIN_VARIANTS = {d: _PAIRS[d] for d in ("cp_pnp_weighted_f64",)}
 # cp_depth_icp_step_f64 has no inputs of its own: it reads the planes and rewrites the poses of cp_render_masks_u8, whose row TWINS holds.  Its
-# pair is listed as a step on that kernel's output.
-TWIN_STEPS = {d: _PAIRS[d] for d in ("cp_depth_icp_step_f64",)}
+# pair is listed as a step on that kernel's output.  cp_contour_step_f64 is the same kind of step, and cp_mask_edt_u16 is one on the label map
+# cp_ccl_filter_labels leaves behind.
+TWIN_STEPS = {d: _PAIRS[d] for d in ("cp_depth_icp_step_f64", "cp_contour_step_f64", "cp_mask_edt_u16")}
 TWINS = {d: h for d, h in _PAIRS.items() if d not in TWIN_VARIANTS and d not in TWIN_STEPS}
 
 

@@ -30,6 +30,7 @@ import glob
 import json
 import math
 import os
+import weakref
 from typing import Dict, Iterator, List, Optional, Sequence, Tuple
 
 import numpy as np
@@ -265,6 +266,8 @@ def load_split(path: str, ratio: float, rng: np.random.Generator) -> List[int]:
 
 # ------------------------------------------------------------------------------------------------
 class VectorfieldDataset:
+    last_instance = None   # weak reference to the dataset built last: names the meshes for pose_estimation/mask_refine.py (CASAPOSE_MASK_REFINE=1)
+
     def __init__(self, root, path_meshes, no_points=9, color_input=False, normal=(0.5, 0.5), test=False, objectsofinterest=(), save=False, noise=2,
                  data_size=None, random_translation=(25.0, 25.0), random_rotation=15.0, random_crop=True, contrast=0.2, brightness=0.2, hue=0.05,
                  saturation=0.2, use_train_split=False, use_validation_split=False, train_validation_split=0.9, output_folder="", use_imgaug=False,
@@ -287,6 +290,8 @@ class VectorfieldDataset:
         #                                               not depend on the number of replicas or on which of them reads it
         self.order_rng = np.random.default_rng([self.seed, 1])  # epoch permutations only: identical on every replica
         self.meshes = self.load_meshes(path_meshes)
+        self.last_offsets: Optional[np.ndarray] = None   # the offsets of the sample drawn last (draw_geometry)
+        VectorfieldDataset.last_instance = weakref.ref(self)
         self.imgs: List[Tuple[str, str, str, str, str]] = []
         self.class_labels: Dict[str, Dict[str, int]] = {}
         self.fixed_transformations: Dict[str, Dict[str, np.ndarray]] = {}
@@ -380,6 +385,7 @@ class VectorfieldDataset:
         dy = round(self.rng.normal(0, 2) * float(self.random_translation[1]))
         angle = round(self.rng.normal(0, 1) * float(self.random_rotation))
         offsets = np.array([h_crop, w_crop, out_h, out_w, dx, dy, angle, scale, width, height], np.float32)
+        self.last_offsets = offsets
         tm = np.array([[1, 0, dx], [0, 1, dy]], np.float64)
         rm = get_rotation_matrix_2D((width / 2, height / 2), angle)
         # output -> input map of the image warp (tfa.image.transform convention == PIL AFFINE)

@@ -18,6 +18,7 @@ import numpy as np
 
 from .bop_vsd import DEFAULT_FAR, DEFAULT_NEAR
 from .pose_evaluation import _np
+from .refine_common import ChunkedRefiner, result_info
 
 # info["status"]: 0-3 are the step's own (csrc/icp_math.h), 4 and 5 the loop's
 REFINED, FEW_PIXELS, SINGULAR, REFUSED, LOST_PIXELS, RMS_ROSE = range(6)
@@ -43,25 +44,13 @@ def keep_rule(status, stats, min_pixels: int) -> np.ndarray:
     return out
 
 
-class DeviceDepthRefiner:
+class DeviceDepthRefiner(ChunkedRefiner):
     """verts, faces: one [V, 3] and one [T, 3] array per object (object_index in `refine` indexes them), uploaded once.  `near`, `far`
     (millimetres) bound the rendered depths; `workspace_cap` bounds the bytes of depth planes plus step records of one chunk."""
 
     def __init__(self, verts: Sequence, faces: Sequence, device, near: float = DEFAULT_NEAR, far: float = DEFAULT_FAR,
                  workspace_cap: Optional[int] = None):
-        from .. import _lib
-        from ..data_handler.bop_converter import DEFAULT_WORKSPACE_CAP, MaskRenderer
-
-        if len(verts) != len(faces) or len(verts) < 1:
-            raise ValueError("verts and faces hold one array per object (got %d and %d)" % (len(verts), len(faces)))
-        self._lib_module, self._lib = _lib, _lib.load()
-        self.objects = len(verts)
-        self.workspace_cap = int(DEFAULT_WORKSPACE_CAP if workspace_cap is None else workspace_cap)
-        self.renderer = MaskRenderer(device, {i: (verts[i], faces[i]) for i in range(self.objects)}, self.workspace_cap)
-        self.device = self.renderer.device
-        self.near, self.far = float(near), float(far)
-        self.last_chunks = 0       # chunks of the last refine() call
-        self.last_renders = 0      # planes rendered by it, over all passes
+        super().__init__(verts, faces, device, near, far, workspace_cap)
 
     # ---- one chunk: frames of one image size ---------------------------------------------------------------------------------------------
     def prepare(self, frames: List[dict], depths: List[np.ndarray], cams: np.ndarray, jobs: np.ndarray, gates: np.ndarray, imax: int, H: int, W: int,
@@ -71,36 +60,13 @@ class DeviceDepthRefiner:
         the device or (host) as NumPy arrays.  Poses, stats and status share one buffer, so that `finish` is one copy."""
         from .. import twin
 
-        r = self.renderer
-        dev = None if host else self.device
-        packed = r.pack(frames, imax)
-        slots, njobs = len(frames) * imax, len(jobs)
-        n_pose, n_stats = slots * 12, passes * njobs * 4
-        host_buf = np.zeros(n_pose + n_stats + (passes * njobs + 1) // 2, np.float64)
-        host_buf[:n_pose] = packed["poses"].reshape(-1)
-        buf = twin.array(host_buf, np.float64, dev)
-        tail = buf[n_pose + n_stats:]
-        if dev is None:
-            stream, status = None, tail.view(np.int32)
-        else:
-            import torch
-
-            stream, status = torch.cuda.current_stream(dev).cuda_stream, tail.view(torch.int32)
-        d = {k: twin.array(a, a.dtype, dev) for k, a in packed.items() if k != "poses"}
-        d["poses"] = buf[:n_pose]          # the renderer's pose array is the one the step rewrites
-        size = int(self._lib.cp_render_masks_workspace_bytes(len(frames), imax, H, W))
-        icp_size = int(self._lib.cp_depth_icp_workspace_bytes(njobs, H, W))
-        work = twin.alloc(dict(planes=((size // 4,), np.uint32), icp=((icp_size // 8,), np.float64)), dev)
-        return dict(device=dev, stream=stream, mesh=(r.verts, r.vert_counts, r.faces, r.face_counts) if dev is None else r.d_mesh, packed=d,
-                    frames=len(frames), slots=slots, njobs=njobs, H=H, W=W, passes=passes, buf=buf, n_pose=n_pose, n_stats=n_stats,
-                    stats=buf[n_pose:n_pose + n_stats], status=status, planes=work["planes"], planes_bytes=size, icp=work["icp"], icp_bytes=icp_size,
-                    depth=twin.array(np.stack([np.asarray(a, np.float32) for a in depths]), np.float32, dev), images=len(depths),
-                    cams=twin.array(cams, np.float64, dev), jobs=twin.array(jobs, np.int32, dev), gates=twin.array(gates, np.float64, dev), records=None)
-
-    def render(self, c: dict) -> None:
-        """every slot of the chunk at its current pose: the planes and c["records"]"""
-        _, c["records"] = self.renderer._render(c["mesh"], c["packed"], c["frames"], c["H"], c["W"], self.near, self.far, 0.0, c["planes"],
-                                                c["planes_bytes"], c["device"], c["stream"])
+        c = self.buffers(frames, len(jobs), imax, H, W, passes, host)
+        dev = c["device"]
+        icp_size = int(self._lib.cp_depth_icp_workspace_bytes(len(jobs), H, W))
+        c.update(icp=twin.alloc(dict(icp=((icp_size // 8,), np.float64)), dev)["icp"], icp_bytes=icp_size,
+                 depth=twin.array(np.stack([np.asarray(a, np.float32) for a in depths]), np.float32, dev), images=len(depths),
+                 cams=twin.array(cams, np.float64, dev), jobs=twin.array(jobs, np.int32, dev), gates=twin.array(gates, np.float64, dev))
+        return c
 
     def step(self, c: dict, it: int, update: int, jump: float, damping: float, min_pixels: int, split: int = DEFAULT_SPLIT) -> None:
         """cp_depth_icp_step_f64 (or its host twin) over the chunk's last render; stats and status go to row `it`"""
@@ -110,13 +76,6 @@ class DeviceDepthRefiner:
         twin.call("cp_depth_icp_step_f64", c["planes"], c["records"], c["slots"], c["H"], c["W"], c["depth"], c["cams"], c["images"], c["jobs"], c["gates"],
                   n, float(jump), float(damping), int(min_pixels), int(update), int(split), c["packed"]["poses"], c["stats"][it * n * 4:(it + 1) * n * 4],
                   c["status"][it * n:(it + 1) * n], c["icp"], c["icp_bytes"], host=c["device"] is None, stream=c["stream"])
-
-    def finish(self, c: dict):
-        """the one copy back -> (poses [slots, 12], stats [passes, njobs, 4], status [passes, njobs])"""
-        back = c["buf"] if c["device"] is None else c["buf"].cpu().numpy()
-        n_pose, n_stats, passes, n = c["n_pose"], c["n_stats"], c["passes"], c["njobs"]
-        return (back[:n_pose].reshape(c["slots"], 12), back[n_pose:n_pose + n_stats].reshape(passes, n, 4),
-                back[n_pose + n_stats:].view(np.int32)[:passes * n].reshape(passes, n))
 
     # ---- all estimates ---------------------------------------------------------------------------------------------------------------------
     def refine(self, poses, K, object_index, image_index, depths: Sequence, diameters, iterations: int = 8, gate: float = 0.25, jump: float = 0.75,
@@ -170,8 +129,6 @@ class DeviceDepthRefiner:
         step_stats = np.zeros((passes, n, 4), np.float64)
         self.last_chunks = self.last_renders = 0
 
-        from ..data_handler.bop_converter import MAX_INSTANCES
-
         by_size: Dict[Tuple[int, int], Dict[int, List[int]]] = {}
         for p in range(n):
             shape = np.shape(depths[int(img[p])])
@@ -185,21 +142,9 @@ class DeviceDepthRefiner:
 
             on_device = torch.cuda.device(self.device)      # the launches go to the calling thread's current device
         for (H, W), members in by_size.items():
-            imax = min(MAX_INSTANCES, max(len(rows) for rows in members.values()))
-            frame_planes = int(self._lib.cp_render_masks_workspace_bytes(1, imax, H, W))
-            if frame_planes == 0:
-                raise ValueError("the renderer takes H, W in [1, 16384] (got %d x %d)" % (H, W))
-            one = frame_planes + int(self._lib.cp_depth_icp_workspace_bytes(imax, H, W))
-            if one > cap:
-                raise ValueError("one %d x %d frame with %d estimates needs %d bytes of depth planes and step records, the workspace cap is %d"
-                                 % (H, W, imax, one, cap))
-            step = max(1, min(cap // one, 65535))
-            frames = []      # (image, rows): up to imax estimates of one image
-            for m, rows in members.items():
-                for lo in range(0, len(rows), imax):
-                    frames.append((m, rows[lo:lo + imax]))
-            for lo in range(0, len(frames), step):
-                part = frames[lo:lo + step]
+            imax, chunks = self.frame_chunks(members, H, W, lambda slots: self._lib.cp_depth_icp_workspace_bytes(slots, H, W), cap,
+                                             "depth planes and step records")
+            for part in chunks:
                 local: Dict[int, int] = {}
                 for m, _ in part:
                     local.setdefault(m, len(local))
@@ -223,9 +168,7 @@ class DeviceDepthRefiner:
                 self.last_renders += passes * len(where)
         status = keep_rule(step_status, step_stats, int(min_pixels))
         out[status != REFINED] = est[status != REFINED]
-        info = dict(status=status, status_names=STATUS_NAMES, pixels_first=step_stats[0, :, 0].astype(np.int64),
-                    pixels_last=step_stats[-1, :, 0].astype(np.int64), rms_first=step_stats[0, :, 1].copy(), rms_last=step_stats[-1, :, 1].copy(),
-                    step_status=step_status, step_stats=step_stats)
+        info = result_info(step_status, step_stats, status, STATUS_NAMES)
         return out.reshape(n, 3, 4), info
 
 

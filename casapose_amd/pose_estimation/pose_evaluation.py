@@ -246,6 +246,19 @@ def estimate_and_evaluate_poses(output_seg, target_seg, output_vertex, poses_gt,
 
 
 def poses_pnp(points_estimated, seg_estimated, object_points_3d, camera_data, no_objects: int, min_num: int = 20, rng=None, solver=None, cov=None):
+    """`_poses_pnp`; with CASAPOSE_MASK_REFINE=1 its poses are then aligned with the label map of the voter that returned `points_estimated`
+    (mask_refine.refine_voted_poses; util_scripts/test_minimal.py calls this inside a frame's measured time)."""
+    from .refine_common import mask_refine_enabled
+
+    poses = _poses_pnp(points_estimated, seg_estimated, object_points_3d, camera_data, no_objects, min_num, rng, solver, cov)
+    if mask_refine_enabled():
+        from .mask_refine import refine_voted_poses
+
+        poses = refine_voted_poses(poses, points_estimated, camera_data, seg_estimated.device if hasattr(seg_estimated, "detach") else None)
+    return poses
+
+
+def _poses_pnp(points_estimated, seg_estimated, object_points_3d, camera_data, no_objects: int, min_num: int = 20, rng=None, solver=None, cov=None):
     """pose_evaluation.py:164-217: voted keypoints [b,oc,vc,2] in (y,x) -> poses [b,oc,1,3,4]; objects with <= min_num
     estimated pixels get the zero pose; the pose is negated when t_z < 0.  solver: a DevicePnP solves the batch in one call; None asks
     device_pnp.solver_from_environment (CASAPOSE_DEVICE_PNP=1, a segmentation on a GPU), and without one the host loop below runs.  cov: keypoint

@@ -12,6 +12,7 @@ import torch
 from .. import _lib, ops
 from .._lib import check
 from .keypoint_covariance import uncertainty_pnp_enabled
+from .refine_common import mask_refine_enabled
 
 
 def _as_record(seg: torch.Tensor, direct: torch.Tensor, conf: torch.Tensor):
@@ -87,19 +88,22 @@ class CoordLSVotingWeighted:
                   "cp_ccl_filter_labels")
         self._voted = labels if labels is not None else (rec, objects, so)
         out = ops.ls_vote(rec, so, do, co, objects, self.num_points, labels=labels, sigmoid_weights=self.sigmoid_weights)
-        if uncertainty_pnp_enabled():   # what a caller that only holds the keypoints (poses_pnp) needs to vote their covariance: voter_of()
+        uncertainty = uncertainty_pnp_enabled()
+        if uncertainty or mask_refine_enabled():   # what a caller that only holds the keypoints (poses_pnp) needs: voter_of()
             global _last_vote
             self.last_labels   # (made now: the record may be the network's output buffer)
-            self.last_field = rec[..., do:do + 2 * self.num_points]
+            if uncertainty:    # to vote the keypoints' covariance; the mask refinement (mask_refine.refine_voted_poses) needs the labels only
+                self.last_field = rec[..., do:do + 2 * self.num_points]
             _last_vote = (weakref.ref(out), self)
         return out
 
 
-_last_vote = None   # (weak reference to the keypoints the last vote under CASAPOSE_UNCERTAINTY_PNP=1 returned, its voter)
+_last_vote = None   # (weak reference to the keypoints the last vote under CASAPOSE_UNCERTAINTY_PNP=1 or CASAPOSE_MASK_REFINE=1 returned, its voter)
 
 
 def voter_of(points) -> Optional[CoordLSVotingWeighted]:
-    """The voter whose last call, made under CASAPOSE_UNCERTAINTY_PNP=1, returned this very tensor; None for any other object."""
+    """The voter whose last call, made under CASAPOSE_UNCERTAINTY_PNP=1 or CASAPOSE_MASK_REFINE=1, returned this very tensor; None for any other
+    object."""
     if _last_vote is not None and _last_vote[0]() is points:
         return _last_vote[1]
     return None

@@ -16,7 +16,7 @@ import torch
 from . import _lib
 
 # C pointee type of the header -> dtype name, which torch and NumPy share; void* takes any
-_DTYPES = {"float": "float32", "double": "float64", "int": "int32", "int32_t": "int32", "uint32_t": "uint32", "uint8_t": "uint8",
+_DTYPES = {"float": "float32", "double": "float64", "int": "int32", "int32_t": "int32", "uint32_t": "uint32", "uint16_t": "uint16", "uint8_t": "uint8",
            "long long": "int64", "int64_t": "int64"}
 
 

@@ -1098,6 +1098,52 @@ int cp_depth_icp_step_host_f64(const uint32_t* planes, const int32_t* records, i
                                int images, const int32_t* jobs, const double* gates, int njobs, double jump, double damping, int min_pixels,
                                int update, int split, double* poses, double* stats, int32_t* status, void* workspace, size_t workspace_bytes);
 
+/* ---- mask refinement: contour alignment against a label map (csrc/mask_contour.hip, csrc/contour_math.h) ---------------------------------
+ * cp_mask_edt_u16: per job = (image, label) the exact squared Euclidean distance, clamped just past the gate, to the object's trusted boundary.
+ * A seed is a pixel of the label with a 4-neighbour inside the image whose label is 0; a neighbour of another label (an occlusion edge) or
+ * outside the image makes no seed.  D2(p) = min(min over seeds |p - s|^2, gate^2 + 1); without seeds gate^2 + 1 everywhere.
+ *   labels     uint8 [images][H][W]     the filtered label map (cp_ccl_filter_labels), 0 = background
+ *   jobs       int32 [njobs][2]         (image, label)
+ *   gate       whole pixels, 1 .. 255
+ *   planes     uint16 [njobs][H][W]     every word of every accepted job's plane is written: needs no initialisation
+ *   status     int32 [njobs]            0 done; 3 refused: image outside [0, images) or label outside [1, 255] (nothing of the job's plane or
+ *                                       workspace is written)
+ *   workspace  cp_mask_edt_workspace_bytes(njobs, H, W) bytes, 2-byte aligned (the row pass: uint16 [njobs][H][W]); needs no initialisation
+ * Integers only and no atomics: the planes do not depend on the workspace's contents.  H, W <= 16384; cp_mask_edt_workspace_bytes returns 0
+ * outside these limits or where njobs x H x ceil(W / 256) or njobs x ceil(H / 32) x ceil(W / 64) blocks are more than 2^31 - 1.
+ * cp_contour_step_f64: one Gauss-Newton step per job = (image, rendered plane, field plane, gate) on the rendered silhouette.  A pixel of the
+ * plane's bbox_obj clipped to [1, W-2] x [1, H-2] is a contour pixel when it is hit and one of its four neighbours is not; it is used when its
+ * depth is > 0 and D2 at it and its four neighbours is <= gate^2.  e = ((D2(x+1,y) - D2(x-1,y)) / 4, (D2(x,y+1) - D2(x,y-1)) / 4), J = the
+ * projection's Jacobian at the back-projected pixel times [-[p]x | I]; A += (J^T e)(e^T J) / (e . e), b -= J^T e; the solve and the pose update are
+ * cp_depth_icp_step_f64's (the rules are listed in csrc/contour_math.h).  Everything is device memory.
+ *   planes, records, nplanes, cams, poses, damping, min_pixels, update, split   as cp_depth_icp_step_f64
+ *   fields     uint16 [nfields][H][W]   planes of cp_mask_edt_u16
+ *   sample_offset  the `sample_offset` the planes were rendered with, 0 .. 1: pixel (x, y) is back-projected from (x + o, y + o), o in whole
+ *                  256ths of a pixel as the rasteriser rounds it
+ *   jobs       int32 [njobs][4]         (image, plane, field, gate in pixels); with update = 1 no two jobs may name the same plane
+ *   stats      fp64 [njobs][4]          used pixels, RMS of |e| in pixels before the update, contour pixels, sum e . e
+ *   status     int32 [njobs]            0 solved; 1 fewer than min_pixels used pixels; 2 a Cholesky pivot was not positive; 3 refused: image,
+ *                                       plane or field index out of range or gate outside [1, 255] (nothing is read for it, stats are zeros).
+ *                                       Every status but 0 leaves the pose as it is
+ *   workspace  cp_contour_step_workspace_bytes(njobs, H, W) bytes, 8-byte aligned: per job one record of 30 fp64 words (28 sums, two counts)
+ *              per tile of cp_contour_tile() pixels of the largest clipped box; needs no initialisation
+ * The order of summation is cp_depth_icp_step_f64's and there are no atomics: two calls with the same inputs, any split and any workspace
+ * contents give the same bytes.  The host twins run the same code serially on host pointers and launch nothing: they work without a GPU and
+ * give the device's bytes.  Added in ABI 302 without changing any earlier entry point. */
+int cp_contour_tile(void);
+size_t cp_mask_edt_workspace_bytes(int njobs, int H, int W);
+size_t cp_contour_step_workspace_bytes(int njobs, int H, int W);
+int cp_mask_edt_u16(const uint8_t* labels, int images, int H, int W, const int32_t* jobs, int njobs, int gate, uint16_t* planes, int32_t* status,
+                    void* workspace, size_t workspace_bytes, void* stream);
+int cp_mask_edt_host_u16(const uint8_t* labels, int images, int H, int W, const int32_t* jobs, int njobs, int gate, uint16_t* planes, int32_t* status,
+                         void* workspace, size_t workspace_bytes);
+int cp_contour_step_f64(const uint32_t* planes, const int32_t* records, int nplanes, int H, int W, const uint16_t* fields, int nfields,
+                        const double* cams, int images, const int32_t* jobs, int njobs, double sample_offset, double damping, int min_pixels, int update,
+                        int split, double* poses, double* stats, int32_t* status, void* workspace, size_t workspace_bytes, void* stream);
+int cp_contour_step_host_f64(const uint32_t* planes, const int32_t* records, int nplanes, int H, int W, const uint16_t* fields, int nfields,
+                             const double* cams, int images, const int32_t* jobs, int njobs, double sample_offset, double damping, int min_pixels,
+                             int update, int split, double* poses, double* stats, int32_t* status, void* workspace, size_t workspace_bytes);
+
 /* ---- keypoints and models_info of a mesh set (csrc/models.hip, csrc/model_math.h) --------------------------------------------------------
  * What the dataset converter needs per object and BOP archives do not hold (data_handler/model_prep.py): the axis-aligned box, the squared
  * diameter (the largest squared distance over all vertex pairs) and no_points keypoints, the box centre followed by farthest-point samples of
