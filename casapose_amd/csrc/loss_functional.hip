@@ -232,6 +232,21 @@ __global__ __launch_bounds__(THREADS) void sep_main_kernel(const float* __restri
     }
 }
 
+// THE carve of cp_pose_loss_sep_f32's workspace: cp_pose_loss_sep_workspace_bytes, cp_pose_loss_sep_workspace_layout and the launcher all take
+// it from here.  Byte offsets from the workspace pointer: filtered label map | pixel counts [batch][seg_dim] (entry 0 of an image unused);
+// `bytes` ends with 256 spare bytes, as it always has.
+struct SepLossWs {
+    size_t off[2];   // fg, counts
+    size_t bytes;
+};
+inline SepLossWs sep_loss_carve(int batch, int h, int w, int seg_dim) {
+    SepLossWs ws;
+    ws.off[0] = 0;
+    ws.off[1] = ((size_t)batch * h * w + 255) & ~(size_t)255;
+    ws.bytes = ws.off[1] + (size_t)batch * seg_dim * sizeof(int) + 256;
+    return ws;
+}
+
 }  // namespace
 
 extern "C" int cp_vector_field_f32(const uint8_t* labels, const float* keypoints_yx, int batch, int h, int w, int objects, int instances, int kp,
@@ -275,8 +290,16 @@ extern "C" int cp_proxy_voting_f32(const float* pred, int pld, int kp, const uin
     return cp::check_launch("cp_proxy_voting_f32");
 }
 
-extern "C" size_t cp_pose_loss_sep_workspace_bytes(int batch, int h, int w, int seg_dim) {
-    return (((size_t)batch * h * w + 255) & ~(size_t)255) + (size_t)batch * seg_dim * sizeof(int) + 256;
+extern "C" size_t cp_pose_loss_sep_workspace_bytes(int batch, int h, int w, int seg_dim) { return sep_loss_carve(batch, h, w, seg_dim).bytes; }
+
+extern "C" int cp_pose_loss_sep_workspace_layout(int batch, int h, int w, int seg_dim, size_t* offsets) {
+    CP_REQUIRE(offsets, "cp_pose_loss_sep_workspace_layout: null pointer");
+    CP_REQUIRE(batch > 0 && h > 0 && w > 0 && (long long)batch * h * w < (1LL << 31) && seg_dim >= 2 && seg_dim <= 64,
+               "cp_pose_loss_sep_workspace_layout: bad shape");
+    const SepLossWs ws = sep_loss_carve(batch, h, w, seg_dim);
+    offsets[0] = ws.off[0];
+    offsets[1] = ws.off[1];
+    return 0;
 }
 
 extern "C" int cp_pose_loss_sep_f32(const float* out, int ld, int seg_dim, int kp, const uint8_t* labels_ce, const uint8_t* labels_fg,
@@ -289,8 +312,9 @@ extern "C" int cp_pose_loss_sep_f32(const float* out, int ld, int seg_dim, int k
     CP_REQUIRE(batch > 0 && h > 0 && w > 0 && (long long)batch * h * w < (1LL << 31), "cp_pose_loss_sep_f32: bad shape");
     hipStream_t st = (hipStream_t)stream;
     const int ppi = h * w;
-    uint8_t* fg = (uint8_t*)ws;
-    int* counts = (int*)((char*)ws + (((size_t)batch * ppi + 255) & ~(size_t)255));
+    const SepLossWs lay = sep_loss_carve(batch, h, w, seg_dim);
+    uint8_t* fg = (uint8_t*)ws + lay.off[0];
+    int* counts = (int*)((char*)ws + lay.off[1]);
     if (hipMemsetAsync(counts, 0, sizeof(int) * batch * seg_dim, st) != hipSuccess) return cp::check_launch("cp_pose_loss_sep_f32 memset");
     if (hipMemsetAsync(loss_sums, 0, sizeof(double) * 3, st) != hipSuccess) return cp::check_launch("cp_pose_loss_sep_f32 memset");
     const int gx = grid_x(ppi);

@@ -233,11 +233,36 @@ __global__ void proxy_filter_apply_kernel(uint8_t* __restrict__ fg, const uint8_
     }
 }
 
+// THE carve of the caller's workspace: cp_pose_loss_workspace_bytes, cp_pose_loss_workspace_layout and cp_pose_loss_f32 all take it from here.
+// Byte offsets from the workspace pointer: filtered label map | per-image counts | per-object proxy sums (fp64), counts, flags.  The three
+// per-object arrays are indexed [b * objects + o]; each has room for 64 objects per image, whatever `objects` is.  `bytes` ends with 256 spare
+// bytes, as it always has.
+struct LossWs {
+    size_t off[5];   // fg, count, objsum, objcnt, bad
+    size_t bytes;
+};
+inline LossWs loss_carve(int batch, int h, int w) {
+    auto up256 = [](size_t n) { return (n + 255) & ~(size_t)255; };
+    LossWs ws;
+    ws.off[0] = 0;
+    ws.off[1] = up256((size_t)batch * h * w);
+    ws.off[2] = ws.off[1] + up256(sizeof(int) * (size_t)batch);
+    ws.off[3] = ws.off[2] + (size_t)batch * 64 * sizeof(double);
+    ws.off[4] = ws.off[3] + (size_t)batch * 64 * sizeof(int);
+    ws.bytes = ws.off[4] + (size_t)batch * 64 + 256;
+    return ws;
+}
+
 }  // namespace
 
-extern "C" size_t cp_pose_loss_workspace_bytes(int batch, int h, int w) {
-    // filtered label map | per-image counts | per-object proxy sums (fp64), counts, flags (up to 64 objects)
-    return (((size_t)batch * h * w + 255) & ~(size_t)255) + (((sizeof(int) * (size_t)batch) + 255) & ~(size_t)255) + (size_t)batch * 64 * (8 + 4 + 1) + 256;
+extern "C" size_t cp_pose_loss_workspace_bytes(int batch, int h, int w) { return loss_carve(batch, h, w).bytes; }
+
+extern "C" int cp_pose_loss_workspace_layout(int batch, int h, int w, size_t* offsets) {
+    CP_REQUIRE(offsets, "cp_pose_loss_workspace_layout: null pointer");
+    CP_REQUIRE(batch > 0 && h > 0 && w > 0 && (long long)batch * h * w < (1LL << 31), "cp_pose_loss_workspace_layout: bad shape");
+    const LossWs ws = loss_carve(batch, h, w);
+    for (int i = 0; i < 5; ++i) offsets[i] = ws.off[i];
+    return 0;
 }
 
 extern "C" int cp_pose_loss_f32(const float* out, int ld, int seg_dim, int kp, const uint8_t* labels_ce, const uint8_t* labels_fg,
@@ -252,8 +277,9 @@ extern "C" int cp_pose_loss_f32(const float* out, int ld, int seg_dim, int kp, c
     CP_REQUIRE(batch > 0 && h > 0 && w > 0 && (long long)batch * h * w < (1LL << 31), "cp_pose_loss_f32: bad shape");
     hipStream_t st = (hipStream_t)stream;
     const int ppi = h * w;
-    uint8_t* fg = (uint8_t*)ws;
-    int* count = (int*)((char*)ws + (((size_t)batch * ppi + 255) & ~(size_t)255));
+    const LossWs lay = loss_carve(batch, h, w);
+    uint8_t* fg = (uint8_t*)ws + lay.off[0];
+    int* count = (int*)((char*)ws + lay.off[1]);
     if (hipMemsetAsync(count, 0, sizeof(int) * batch, st) != hipSuccess) return cp::check_launch("cp_pose_loss_f32 memset");
     if (hipMemsetAsync(loss_sums, 0, sizeof(double) * 3, st) != hipSuccess) return cp::check_launch("cp_pose_loss_f32 memset");
     int gx = (ppi + THREADS - 1) / THREADS;
@@ -261,11 +287,10 @@ extern "C" int cp_pose_loss_f32(const float* out, int ld, int seg_dim, int kp, c
     CP_LAUNCH(loss_prepare_kernel, dim3(gx, batch), dim3(THREADS), 0, st, out, ld, seg_dim, labels_fg, ppi, batch, filter_with_segmentation, fg, count);
     if (cp::check_launch("cp_pose_loss_f32 prepare") != CP_OK) return CP_ERR_LAUNCH;
     if (filter_high_proxy_errors || object_loss_values) {
-        char* base = (char*)count + (((sizeof(int) * (size_t)batch) + 255) & ~(size_t)255);
-        double* objsum = (double*)base;
-        int* objcnt = (int*)(base + (size_t)batch * 64 * 8);
-        uint8_t* bad = (uint8_t*)(base + (size_t)batch * 64 * 12);
-        if (hipMemsetAsync(base, 0, (size_t)batch * 64 * 13, st) != hipSuccess) return cp::check_launch("cp_pose_loss_f32 memset");
+        double* objsum = (double*)((char*)ws + lay.off[2]);
+        int* objcnt = (int*)((char*)ws + lay.off[3]);
+        uint8_t* bad = (uint8_t*)ws + lay.off[4];
+        if (hipMemsetAsync(objsum, 0, lay.off[4] + (size_t)batch * 64 - lay.off[2], st) != hipSuccess) return cp::check_launch("cp_pose_loss_f32 memset");
         CP_LAUNCH(proxy_object_sums_kernel, dim3(gx, batch), dim3(THREADS), objects * (sizeof(double) + sizeof(int)), st, out, ld, seg_dim, kp, fg, keypoints_yx,
                   objects, h, w, objsum, objcnt);
         // values are always reported against the segmentation-filtered mask; the foreground is only edited when the filter is on

@@ -703,6 +703,20 @@ int cp_pose_loss_f32(const float* out, int ld, int seg_dim, int kp, const uint8_
                      int filter_high_proxy_errors, float mask_w, float vertex_w, float proxy_w, void* ws, float* dout, int dld,
                      int vert_off, double* loss_sums, float* object_loss_values, void* stream);
 
+/* Where cp_pose_loss_f32 keeps its intermediate products inside the caller's workspace (for tests and diagnostics).  Host only; the same
+ * carving the loss itself applies.  offsets[5] receives the byte offsets, from the workspace pointer, of
+ *   [0] fg      uint8  [batch*h*w]        the foreground label map the vertex / proxy terms used: labels_fg after the segmentation filter and,
+ *                                         with filter_high_proxy_errors, after the removal of the flagged objects
+ *   [1] count   int32  [batch]            foreground pixels of each image in that map
+ *   [2] objsum  double [batch*objects]    per (image, object), index b*objects + o: the smooth-L1 proxy distances summed over the object's
+ *                                         pixels and keypoints, on the segmentation-filtered map
+ *   [3] objcnt  int32  [batch*objects]    the object's pixels in that map
+ *   [4] bad     uint8  [batch*objects]    1 where the reported value (0 below 20 pixels, else objsum / (kp*objcnt + 1e-3)) is not < 5
+ * in this order, without overlap, the last one ending inside cp_pose_loss_workspace_bytes.  [2]..[4] are written only when
+ * filter_high_proxy_errors or object_loss_values is given; each has room for 64 objects per image.  Returns -1 for a null pointer or a
+ * shape cp_pose_loss_f32 refuses. */
+int cp_pose_loss_workspace_layout(int batch, int h, int w, size_t* offsets /*[5]*/);
+
 /* compute_loss for the `pvnet` model with SEPARATED vector fields (train_casapose.py:57,97-125): the output holds seg_dim logits followed by
  * objects*2*kp direction channels, object o in [seg_dim + o*2kp, seg_dim + (o+1)*2kp).  vertex = sum over objects of smooth_l1_loss(slice,
  * target slice, one-hot of the object), proxy = sum over objects of proxy_voting_loss_v2(slice, the object's keypoints, one-hot of the object):
@@ -713,6 +727,10 @@ size_t cp_pose_loss_sep_workspace_bytes(int batch, int h, int w, int seg_dim);
 int cp_pose_loss_sep_f32(const float* out, int ld, int seg_dim, int kp, const uint8_t* labels_ce, const uint8_t* labels_fg,
                          const float* keypoints_yx, int objects, int batch, int h, int w, int filter_with_segmentation, float mask_w,
                          float vertex_w, float proxy_w, void* ws, float* dout, int dld, int vert_off, double* loss_sums, void* stream);
+
+/* The same for cp_pose_loss_sep_f32.  offsets[2]: [0] fg uint8 [batch*h*w], labels_fg after the segmentation filter; [1] counts int32
+ * [batch][seg_dim], the pixels of label l of image b in that map at b*seg_dim + l (entry 0 of an image stays 0).  Host only. */
+int cp_pose_loss_sep_workspace_layout(int batch, int h, int w, int seg_dim, size_t* offsets /*[2]*/);
 
 /* The reference's loss / target functions as stand-alone passes (values only; the training step differentiates the fused kernels above).
  * They back the importable casapose.utils.loss_functions / casapose.utils.image_utils modules.

@@ -155,6 +155,36 @@ def test_ccl_workspace_layout_is_the_filters_own_carving(lib):
         assert lib.cp_ccl_workspace_layout(*bad, (C.c_size_t * 5)()) == -1 and b"bad sizes" in lib.cp_last_error(), bad
 
 
+def test_pose_loss_workspace_layouts_are_the_losses_own_carving(lib):
+    """cp_pose_loss_workspace_layout / cp_pose_loss_sep_workspace_layout (host only): the parts in the documented order, aligned for their types,
+    none overlapping the next (the per-object arrays with room for 64 objects per image), the last ending inside *_workspace_bytes, whose totals are
+    what they were before the carve was shared -- label map and counts rounded up to 256 bytes, 256 spare bytes (known answers worked out by hand)."""
+    up = lambda n: (n + 255) // 256 * 256   # noqa: E731
+    known = {(2, 24, 32): 3712, (1, 5, 7): 1600, (2, 260, 508): 266368, (16, 480, 640): 4929024, (65, 1, 1): 55104}
+    for (b, h, w), total in known.items():
+        offs = (C.c_size_t * 5)()
+        assert lib.cp_pose_loss_workspace_layout(b, h, w, offs) == 0
+        px = b * h * w
+        sizes = [px, 4 * b, 8 * b * 64, 4 * b * 64, b * 64]                  # fg, count, objsum, objcnt, bad
+        assert list(offs) == [0, up(px), up(px) + up(4 * b), up(px) + up(4 * b) + 512 * b, up(px) + up(4 * b) + 768 * b]
+        assert all(offs[i] + sizes[i] <= offs[i + 1] for i in range(4)) and offs[1] % 4 == 0 and offs[2] % 8 == 0 and offs[3] % 4 == 0
+        assert lib.cp_pose_loss_workspace_bytes(b, h, w) == offs[4] + sizes[4] + 256 == total, (b, h, w, offs[4] + sizes[4] + 256)
+        assert total == up(px) + up(4 * b) + b * 64 * 13 + 256                # the expression the size function held before
+    assert lib.cp_pose_loss_workspace_layout(2, 8, 8, None) == -1 and b"null pointer" in lib.cp_last_error()
+    for bad in ((0, 8, 8), (2, 0, 8), (2, 8, 0), (2, 32768, 32768)):
+        assert lib.cp_pose_loss_workspace_layout(*bad, (C.c_size_t * 5)()) == -1 and b"bad shape" in lib.cp_last_error(), bad
+    known = {(2, 24, 32, 4): 1824, (1, 5, 7, 2): 520, (2, 516, 512, 3): 528664, (16, 480, 640, 9): 4916032}
+    for (b, h, w, k), total in known.items():
+        offs = (C.c_size_t * 2)()
+        assert lib.cp_pose_loss_sep_workspace_layout(b, h, w, k, offs) == 0
+        px = b * h * w
+        assert list(offs) == [0, up(px)]
+        assert lib.cp_pose_loss_sep_workspace_bytes(b, h, w, k) == offs[1] + 4 * b * k + 256 == total, (b, h, w, k, offs[1] + 4 * b * k + 256)
+    assert lib.cp_pose_loss_sep_workspace_layout(2, 8, 8, 3, None) == -1 and b"null pointer" in lib.cp_last_error()
+    for bad in ((0, 8, 8, 3), (2, 8, 8, 1), (2, 8, 8, 65), (2, 32768, 32768, 3)):
+        assert lib.cp_pose_loss_sep_workspace_layout(*bad, (C.c_size_t * 2)()) == -1 and b"bad shape" in lib.cp_last_error(), bad
+
+
 def test_descriptor_of_another_abi_revision_is_refused(lib):
     """A caller built against a header with a shorter (or longer) cp_conv_desc is refused by size in every entry point that takes one."""
     from casapose_amd._lib import ConvDesc
@@ -336,6 +366,8 @@ def _known_signatures():
         "cp_conv_stem_split_weight_floats": (_I, None, []),
         "cp_ransac_workspace_layout": (_I, None, [i, i, i, i, i, i, _p("size_t"), _p("size_t")]),
         "cp_ccl_workspace_layout": (_I, None, [i, i, i, i, _p("size_t")]),
+        "cp_pose_loss_workspace_layout": (_I, None, [i, i, i, _p("size_t")]),
+        "cp_pose_loss_sep_workspace_layout": (_I, None, [i, i, i, i, _p("size_t")]),
     }
 
 
