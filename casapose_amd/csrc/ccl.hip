@@ -324,3 +324,125 @@ extern "C" int cp_ccl_filter_labels(const uint8_t* labels_in, int batch, int h, 
     CP_LAUNCH(ccl_write, dim3(g), dim3(THREADS), 0, st, labels_in, parent, stats, objects, hw, total, labels_out);
     return cp::check_launch("cp_ccl_filter_labels");
 }
+
+// ---------------------------------------------------------------------------------------------------------------------------------------------
+// Several instances of one object: cp_ccl_instance_labels keeps the R = max_instances largest components of each object as separate slots
+// (voting_layers_2d.py:43-79 keeps one).  Passes 1-3 above are reused as they are; the selection and the write pass below replace ccl_select /
+// ccl_write.  The rule (include/casapose_hip.h states it once): a component of at least min_size pixels is eligible, the eligible components of
+// an object are ordered by (size descending, root ascending), instance r of object o gets slot (o-1)*R + r + 1, everything else slot 0.  There is
+// no "bin 0" here: the rest of the image does not compete, and an object without an eligible component keeps nothing.
+namespace {
+
+// key of an eligible component: (size << 32) | (0xFFFFFFFE - local root); larger key = earlier instance.  0 = no component.
+__device__ __forceinline__ unsigned long long inst_key(int cnt, long long root_local) {
+    return ((unsigned long long)(unsigned)cnt << 32) | (unsigned long long)(0xFFFFFFFEu - (unsigned)root_local);
+}
+
+constexpr int MAX_SLOTS = 254, MAX_INST = 16;
+
+// Selection (one block per image, over the root list): pass r takes, per object, the largest key below the winner of pass r - 1 -- the
+// pattern of ccl_select with R ranks.  Integer LDS maxima only: the result does not depend on the order of the list.
+__global__ __launch_bounds__(256) void ccl_instance_select(const uint8_t* __restrict__ lab, const int* __restrict__ count, const int* __restrict__ nroots,
+                                                           const int* __restrict__ roots, unsigned long long* __restrict__ keys, int32_t* __restrict__ inst,
+                                                           int objects, int R, long long hw, int min_size) {
+    __shared__ unsigned long long best[MAX_SLOTS];
+    const int n = blockIdx.x, nr = nroots[n], slots = objects * R;
+    const int* list = roots + (long long)n * hw;
+    for (int s = threadIdx.x; s < slots; s += 256) best[s] = 0ull;
+    __syncthreads();
+    for (int r = 0; r < R; ++r) {
+        for (int k = threadIdx.x; k < nr; k += 256) {
+            const int i = list[k], cnt = count[i];
+            if (cnt < min_size) continue;
+            const int o = label_at(lab, i, objects) - 1;   // a root is a labelled pixel: never 0
+            const unsigned long long key = inst_key(cnt, (long long)i - n * hw);
+            if (r == 0) atomicMax(&best[o * R], key);
+            else if (key < best[o * R + r - 1]) atomicMax(&best[o * R + r], key);   // an empty rank r - 1 (0) leaves every later rank empty
+        }
+        __syncthreads();
+    }
+    for (int s = threadIdx.x; s < slots; s += 256) {
+        const unsigned long long key = best[s];
+        const long long at = (long long)n * slots + s;
+        keys[at] = key;
+        inst[2 * at] = (int32_t)(key >> 32);
+        inst[2 * at + 1] = key ? (int32_t)(0xFFFFFFFEu - (unsigned)(key & 0xFFFFFFFFull)) : -1;
+    }
+}
+
+// Write: a labelled pixel's flattened parent against the (at most R) winners of its object
+__global__ void ccl_instance_write(const uint8_t* __restrict__ lab, const int* __restrict__ parent, const unsigned long long* __restrict__ keys,
+                                   int objects, int R, long long hw, long long total, uint8_t* __restrict__ out) {
+    for (long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x; i < total; i += (long long)gridDim.x * blockDim.x) {
+        const int l = label_at(lab, i, objects);
+        uint8_t slot = 0;
+        if (l) {
+            const long long n = i / hw;
+            const unsigned tie = 0xFFFFFFFEu - (unsigned)((long long)parent[i] - n * hw);
+            const unsigned long long* k = keys + (n * objects + (l - 1)) * R;
+            for (int r = 0; r < R; ++r) {
+                const unsigned long long key = k[r];
+                if (key == 0ull) break;
+                if ((unsigned)(key & 0xFFFFFFFFull) == tie) {
+                    slot = (uint8_t)((l - 1) * R + r + 1);
+                    break;
+                }
+            }
+        }
+        out[i] = slot;
+    }
+}
+
+// THE carve of cp_ccl_instance_labels' workspace: the first four regions are ccl_carve's (parent, count, roots, nroots: what passes 1-3 fill),
+// the fifth holds the winners' keys, uint64 [batch][objects][R], 64-byte aligned.  64 bytes of slack for a base that is not 64-byte aligned.
+struct CclInstWs {
+    size_t off[5];   // parent, count, roots, nroots, keys
+    size_t bytes;
+};
+inline CclInstWs ccl_instance_carve(int batch, int h, int w, int objects, int max_instances) {
+    const CclWs base = ccl_carve(batch, h, w, objects);
+    CclInstWs ws;
+    for (int i = 0; i < 5; ++i) ws.off[i] = base.off[i];
+    ws.bytes = ws.off[4] + (size_t)batch * objects * max_instances * sizeof(unsigned long long) + 64;
+    return ws;
+}
+
+inline bool ccl_instance_sizes_ok(int batch, int h, int w, int objects, int max_instances) {
+    return batch > 0 && h > 0 && w > 0 && objects > 0 && max_instances >= 1 && max_instances <= MAX_INST && objects * max_instances <= MAX_SLOTS;
+}
+
+}  // namespace
+
+extern "C" size_t cp_ccl_instance_workspace_bytes(int batch, int h, int w, int objects, int max_instances) {
+    if (!ccl_instance_sizes_ok(batch, h, w, objects, max_instances)) return 0;
+    return ccl_instance_carve(batch, h, w, objects, max_instances).bytes;
+}
+
+extern "C" int cp_ccl_instance_labels(const uint8_t* labels_in, int batch, int h, int w, int objects, int max_instances, int min_size, void* ws,
+                                      uint8_t* slots_out, int32_t* inst_out, void* stream) {
+    CP_REQUIRE(labels_in && slots_out && inst_out && ws, "cp_ccl_instance_labels: null pointer");
+    CP_REQUIRE(max_instances >= 1 && max_instances <= MAX_INST, "cp_ccl_instance_labels: max_instances must be in 1..%d (got %d)", MAX_INST, max_instances);
+    CP_REQUIRE(batch > 0 && h > 0 && w > 0 && objects > 0, "cp_ccl_instance_labels: bad sizes");
+    CP_REQUIRE(objects <= MAX_SLOTS && objects * max_instances <= MAX_SLOTS,
+               "cp_ccl_instance_labels: objects * max_instances must be at most %d: slot ids are bytes (got %d * %d)", MAX_SLOTS, objects, max_instances);
+    const long long hw = (long long)h * w, total = hw * batch;
+    CP_REQUIRE(total < (1LL << 31) && hw < 0xFFFFFFF0LL, "cp_ccl_instance_labels: too many pixels for 32-bit component ids");
+    hipStream_t st = (hipStream_t)stream;
+    const CclInstWs lay = ccl_instance_carve(batch, h, w, objects, max_instances);
+    const uintptr_t base = (reinterpret_cast<uintptr_t>(ws) + 63) & ~(uintptr_t)63;
+    int* parent = reinterpret_cast<int*>(base + lay.off[0]);
+    int* count = reinterpret_cast<int*>(base + lay.off[1]);
+    int* roots = reinterpret_cast<int*>(base + lay.off[2]);
+    int* nroots = reinterpret_cast<int*>(base + lay.off[3]);
+    unsigned long long* keys = reinterpret_cast<unsigned long long*>(base + lay.off[4]);
+    const int g = grid_for(total);
+    if (hipMemsetAsync(nroots, 0, sizeof(int) * (size_t)batch, st) != hipSuccess) return cp::check_launch("cp_ccl_instance_labels memset");
+    const int tiles_x = (w + TW - 1) / TW, tiles_y = (h + TH - 1) / TH;
+    CP_LAUNCH(ccl_local, dim3(batch * tiles_x * tiles_y), dim3(256), 0, st, labels_in, parent, count, h, w, tiles_x, tiles_y, objects);
+    const long long nb = (long long)batch * (tiles_y - 1) * w + (long long)batch * h * (tiles_x - 1);
+    if (nb > 0) CP_LAUNCH(ccl_border, dim3(grid_for(nb)), dim3(THREADS), 0, st, labels_in, parent, batch, h, w, tiles_x, tiles_y, objects);
+    CP_LAUNCH(ccl_flatten_count, dim3(g), dim3(THREADS), 0, st, labels_in, parent, count, nroots, roots, hw, total, objects);
+    CP_LAUNCH(ccl_instance_select, dim3(batch), dim3(256), 0, st, labels_in, count, nroots, roots, keys, inst_out, objects, max_instances, hw, min_size);
+    CP_LAUNCH(ccl_instance_write, dim3(g), dim3(THREADS), 0, st, labels_in, parent, keys, objects, max_instances, hw, total, slots_out);
+    return cp::check_launch("cp_ccl_instance_labels");
+}

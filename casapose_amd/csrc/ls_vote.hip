@@ -727,3 +727,167 @@ extern "C" int cp_kp_reproj_loss_f32(const float* coords_yx, const float* gt_xy,
               g_yx, loss_out);
     return cp::check_launch("cp_kp_reproj_loss_f32");
 }
+
+// ---------------------------------------------------------------------------------------------------------------------------------------------
+// Voting keyed by (object, instance): cp_ls_vote_slots_f32 takes the slot map of cp_ccl_instance_labels as its label map and keeps one row of
+// sums per slot.  The logits are not read.  The per-pixel arithmetic, the accumulators and the solve are the ones above.
+namespace {
+
+// ls_accumulate36_kernel<true> with a run-time number of table rows: the same strip walk (labels of the 64 x 16 strip first, row mask by ballot,
+// one row segment prefetched ahead, nine 16-byte LDS reads per pixel) over the production record, the LDS table [slots][9][5] in front of the
+// staging buffer.  A table of 254 slots is 91 KB, so what a block pays per table entry is kept away from the blocks that have nothing to add:
+// the labels are read BEFORE the table is zeroed, and a block whose four strips hold no label ends there (no zeroing, no commit scan).
+__global__ __launch_bounds__(256) void ls_accumulate36_slots_kernel(const float* __restrict__ field, const uint8_t* __restrict__ labels, int B, int H,
+                                                                    int W, int slots, double* __restrict__ sums, int strips_x, int strips_y) {
+    constexpr int KP = 9, LD = 36, NV = LD / 4;
+    extern __shared__ __attribute__((aligned(16))) char smem_raw[];
+    const int nacc = slots * KP * 5;
+    double* acc_lds = reinterpret_cast<double*>(smem_raw);                                            // [slots][KP][5]
+    float4* stage = reinterpret_cast<float4*>(smem_raw + (sizeof(double) * nacc + 15) / 16 * 16);       // [WAVES][64*NV]
+
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    float4* wstage = stage + (size_t)wave * 64 * NV;
+    LsStrip s;
+    const bool has = s.find(wave, strips_x, strips_y);
+    int nvec = 0;
+    float cx = 0.f;
+    // lw[k] of lane l holds the four labels of row 4k + (l >> 4), columns 4 (l & 15) .. + 3 (a label outside the image reads as 0)
+    unsigned lw[4] = {0u, 0u, 0u, 0u};
+    unsigned rowmask = 0;
+    if (has) {
+        s.decode(lane, strips_x, W);
+        const int ncols = s.ncols, nrows = min(ROWS, H - s.y0);
+        nvec = ncols * NV;
+        cx = s.cx(H);
+        const uint8_t* lb = labels + ((size_t)s.img * H + s.y0) * W + s.x0;
+        const int lr = lane >> 4, lc = (lane & 15) * 4;
+        const bool words = ((W & 3) == 0) && (((uintptr_t)labels & 3) == 0);  // every row segment starts on a 4-byte boundary
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            const int ry = 4 * k + lr;
+            if (ry < nrows) {
+                const uint8_t* p = lb + (size_t)ry * W + lc;
+                if (words) {
+                    if (lc < ncols) lw[k] = *reinterpret_cast<const unsigned*>(p);  // ncols % 4 == 0 here: the word is inside the row
+                } else {
+#pragma unroll
+                    for (int c = 0; c < 4; ++c)
+                        if (lc + c < ncols) lw[k] |= (unsigned)p[c] << (8 * c);
+                }
+            }
+        }
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            const unsigned long long bal = __builtin_amdgcn_ballot_w64(lw[k] != 0u);
+#pragma unroll
+            for (int j = 0; j < 4; ++j)
+                if ((bal >> (16 * j)) & 0xffffull) rowmask |= 1u << (4 * k + j);
+        }
+    }
+    if (!__syncthreads_or(rowmask != 0u)) return;   // block-uniform: nothing labelled in any of its strips
+    ls_table_zero(acc_lds, nacc);
+
+    if (rowmask) {   // wave-uniform
+        const int img = s.img, x0 = s.x0, y0 = s.y0;
+        LsAcc<KP> acc(acc_lds);
+        float4 pre[NV];
+        auto issue = [&](int ry) {
+            const float4* g = reinterpret_cast<const float4*>(field + (((size_t)img * H + y0 + ry) * W + x0) * LD);
+#pragma unroll
+            for (int i = 0; i < NV; ++i) {
+                const int v = lane + 64 * i;
+                pre[i] = (v < nvec) ? g[v] : make_float4(0.f, 0.f, 0.f, 0.f);
+            }
+        };
+        // this lane's label in row ry: byte (lane & 3) of the word that lane 16 (ry & 3) + (lane >> 2) holds in lw[ry >> 2]; a value above
+        // `slots` has no table row and is background
+        auto label_of = [&](int ry) {
+            const int k = ry >> 2;
+            const unsigned wsel = (k == 0) ? lw[0] : (k == 1) ? lw[1] : (k == 2) ? lw[2] : lw[3];
+            const unsigned wv = (unsigned)__shfl((int)wsel, ((ry & 3) << 4) + (lane >> 2));
+            const int l = (int)((wv >> (8 * (lane & 3))) & 0xffu);
+            return l > slots ? 0 : l;
+        };
+
+        unsigned todo = rowmask;
+        int ry = __builtin_ctz(todo), prev = -1;
+        todo &= todo - 1;
+        issue(ry);
+        while (ry >= 0) {
+#pragma unroll
+            for (int i = 0; i < NV; ++i) wstage[lane + 64 * i] = pre[i];
+            int nxt = -1;
+            if (todo) {
+                nxt = __builtin_ctz(todo);
+                todo &= todo - 1;
+                issue(nxt);  // in flight while this row is processed
+            }
+            __builtin_amdgcn_wave_barrier();
+            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // this wave's LDS writes have landed (the prefetch stays in flight)
+            float r[LD];
+#pragma unroll
+            for (int i = 0; i < NV; ++i) {
+                const float4 q = wstage[lane * NV + i];
+                r[4 * i] = q.x; r[4 * i + 1] = q.y; r[4 * i + 2] = q.z; r[4 * i + 3] = q.w;
+            }
+            if (ry != prev + 1) acc.enter(0);  // rows in between were skipped: every lane's label was 0 there, which ends its run
+            const int lab = label_of(ry);
+            acc.enter(lab);
+            if (lab > 0) {
+                const float cy = ((float)(y0 + ry) + 0.5f) / (float)H;
+#pragma unroll
+                for (int j = 0; j < KP; ++j) {
+                    const float w = softplus_fast(r[27 + j]);  // softplus (:35)
+                    const float2 n = ls_normal_fast(r[9 + 2 * j], r[9 + 2 * j + 1]);
+                    ls_add_terms(acc.a[j], n.x, n.y, w, cy, cx);
+                }
+            }
+            __builtin_amdgcn_wave_barrier();  // all lanes done reading before the next row overwrites
+            prev = ry;
+            ry = nxt;
+        }
+        acc.flush();
+    }
+    ls_table_commit(acc_lds, nacc, sums + (size_t)s.img * nacc);
+}
+
+constexpr int LS_MAX_LDS = 160 * 1024;   // per workgroup on gfx950
+
+}  // namespace
+
+extern "C" int cp_ls_vote_slots_f32(const float* field, int ld, int dir_off, int conf_off, const uint8_t* slot_map, int batch, int h, int w,
+                                    int slots, int kp, int sigmoid_weights, double* sums_ws, float* keypoints, void* stream) {
+    CP_REQUIRE(field && slot_map && sums_ws && keypoints, "cp_ls_vote_slots_f32: null pointer (the slot map is required)");
+    CP_REQUIRE(batch > 0 && h > 0 && w > 0 && slots > 0 && slots < 255, "cp_ls_vote_slots_f32: bad sizes (slots must be in 1..254)");
+    CP_REQUIRE(kp == MAXKP, "cp_ls_vote_slots_f32: built for %d keypoints (got %d)", MAXKP, kp);
+    CP_REQUIRE(ld % 4 == 0 && ld > 0 && ld <= 64 && ((uintptr_t)field & 15) == 0,
+               "cp_ls_vote_slots_f32: ld must be a multiple of 4 (<= 64) and field 16-byte aligned");
+    CP_REQUIRE(dir_off >= 0 && dir_off + 2 * kp <= ld && conf_off >= 0 && conf_off + kp <= ld,
+               "cp_ls_vote_slots_f32: channel offsets outside the pixel record");
+    hipStream_t st = (hipStream_t)stream;
+    const size_t nbytes = cp_ls_vote_workspace_bytes(batch, slots, kp);
+    if (hipMemsetAsync(sums_ws, 0, nbytes, st) != hipSuccess) return cp::check_launch("cp_ls_vote_slots_f32 memset");
+    const int strips_x = (w + 63) / 64, strips_y = (h + ROWS - 1) / ROWS;
+    const int blocks_per_img = (strips_x * strips_y + WAVES - 1) / WAVES;
+    const size_t table = (sizeof(double) * slots * kp * 5 + 15) / 16 * 16;
+    const size_t lds = table + sizeof(float) * WAVES * 64 * ld;
+    static_assert((sizeof(double) * 254 * MAXKP * 5 + 15) / 16 * 16 + sizeof(float) * WAVES * 64 * 64 <= (size_t)LS_MAX_LDS, "254 slots beside ld = 64 fit");
+    if (!sigmoid_weights && is_record36(ld, dir_off, conf_off)) {
+        if (lds > 64 * 1024)   // (the limit counts the kernel's static LDS too: ask for what this launch needs, not for the whole 160 KB)
+            CP_REQUIRE(hipFuncSetAttribute(reinterpret_cast<const void*>(&ls_accumulate36_slots_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                           (int)lds) == hipSuccess, "cp_ls_vote_slots_f32: cannot raise the kernel's LDS limit to %zu bytes", lds);
+        CP_LAUNCH(ls_accumulate36_slots_kernel, dim3(batch * blocks_per_img), dim3(256), lds, st, field, slot_map, batch, h, w, slots, sums_ws, strips_x,
+                  strips_y);
+    } else {
+        if (lds > 64 * 1024)
+            CP_REQUIRE(hipFuncSetAttribute(reinterpret_cast<const void*>(&ls_accumulate_kernel<MAXKP>), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                           (int)lds) == hipSuccess, "cp_ls_vote_slots_f32: cannot raise the kernel's LDS limit to %zu bytes", lds);
+        // the generic kernel with given labels: its table has `objects` rows, and the logits (seg_off) are read only without labels
+        CP_LAUNCH((ls_accumulate_kernel<MAXKP>), dim3(batch * blocks_per_img), dim3(256), lds, st, field, ld, 0, dir_off, conf_off, slot_map, batch, h, w,
+                  slots, sums_ws, strips_x, strips_y, sigmoid_weights ? 1 : 0);
+    }
+    const int total = batch * slots * kp;
+    CP_LAUNCH(ls_solve_kernel, dim3((total + 255) / 256), dim3(256), 0, st, sums_ws, total, h, keypoints);
+    return cp::check_launch("cp_ls_vote_slots_f32");
+}

@@ -137,3 +137,35 @@ def ls_vote(field: torch.Tensor, seg_off: int, dir_off: int, conf_off: int, obje
     check(lib.cp_ls_vote_w_f32(field.data_ptr(), ld, seg_off, dir_off, conf_off, labels.data_ptr() if labels is not None else None,
                                b, h, w, objects, kp, 1 if sigmoid_weights else 0, sums.data_ptr(), out.data_ptr(), _stream(field)), "cp_ls_vote_w_f32")
     return (out, sums) if return_sums else out
+
+
+def ccl_instance_labels(labels: torch.Tensor, objects: int, max_instances: int, min_size: int):
+    """cp_ccl_instance_labels on a uint8 label map [B,H,W]: the `max_instances` largest components of each object as separate slots.
+    Returns (slot_map uint8 [B,H,W], inst int32 [B,objects,max_instances,2] = (size, image-local root), (0, -1) for an empty slot).
+    Instance r of object o (1-based) has the slot id (o-1)*max_instances + r + 1 (include/casapose_hip.h states the rule)."""
+    _need_cuda(labels)
+    b, h, w = labels.shape
+    lib = _lib.load()
+    # sizes the library refuses give 0 bytes here; the call below then says what is wrong
+    ws = torch.empty(max(int(lib.cp_ccl_instance_workspace_bytes(b, h, w, objects, max_instances)), 1), dtype=torch.uint8, device=labels.device)
+    slot_map = torch.empty_like(labels)
+    inst = torch.empty(b, max(objects, 0), max(max_instances, 0), 2, dtype=torch.int32, device=labels.device)
+    check(lib.cp_ccl_instance_labels(labels.data_ptr(), b, h, w, objects, max_instances, min_size, ws.data_ptr(), slot_map.data_ptr(), inst.data_ptr(),
+                                     _stream(labels)), "cp_ccl_instance_labels")
+    return slot_map, inst
+
+
+def ls_vote_slots(rec: torch.Tensor, do: int, co: int, slots: int, kp: int, slot_map: torch.Tensor, sigmoid_weights: bool = False,
+                  return_sums: bool = False):
+    """cp_ls_vote_slots_f32 on a [B,H,W,ld] record tensor with directions at `do` and confidences at `co`: one vote per slot of `slot_map`
+    (uint8 [B,H,W], values 0..slots: as with ls_vote's labels, a larger value is the caller's error and undefined outside the production record --
+    ccl_instance_labels never makes one, and nothing here reads the map back to check).  Returns keypoints [B,slots,kp,2] (y,x)."""
+    _need_cuda(rec, slot_map)
+    b, h, w, ld = rec.shape
+    if tuple(slot_map.shape) != (b, h, w) or slot_map.dtype != torch.uint8 or not slot_map.is_contiguous():
+        raise ValueError("ls_vote_slots: slot_map must be a contiguous uint8 [%d, %d, %d] tensor" % (b, h, w))
+    sums = torch.empty(b, max(slots, 0), kp, 5, dtype=torch.float64, device=rec.device)
+    out = torch.empty(b, max(slots, 0), kp, 2, dtype=torch.float32, device=rec.device)
+    check(_lib.load().cp_ls_vote_slots_f32(rec.data_ptr(), ld, do, co, slot_map.data_ptr(), b, h, w, slots, kp, 1 if sigmoid_weights else 0,
+                                           sums.data_ptr(), out.data_ptr(), _stream(rec)), "cp_ls_vote_slots_f32")
+    return (out, sums) if return_sums else out

@@ -1,0 +1,132 @@
+"""Several instances of one object per image (opt-in, CASAPOSE_MAX_INSTANCES=R): the least-squares voter of voting_layers_2d.py:43-122 keyed by
+(object, instance) instead of by object, and a PnP over that axis.
+
+CASAPose's vector field is shared by all classes and the label map tells the voter which pixel votes for what, so the network is used as it is:
+cp_ccl_instance_labels turns the arg-max map into a slot map (the R largest components of each object as separate slots; the rule stands in
+include/casapose_hip.h), cp_ls_vote_slots_f32 votes one keypoint set per slot, and poses_pnp_instances solves every (image, object, instance)
+triple.  Instance r (0-based) of object o (1-based) has the slot id (o-1)*R + r + 1."""
+from __future__ import annotations
+
+import os
+from typing import Optional, Sequence
+
+import numpy as np
+import torch
+
+from .. import _lib, ops
+from . import pnp as _pnp
+from .pose_evaluation import _np, _solved_poses
+from .voting_layers_2d import _as_record
+
+ENV = "CASAPOSE_MAX_INSTANCES"
+MAX_INSTANCES = 16     # cp_ccl_instance_labels' bound on R
+MAX_SLOTS = 254        # slot ids are bytes
+
+
+def max_instances_from_environment() -> Optional[int]:
+    """CASAPOSE_MAX_INSTANCES: unset or 1 -> None (one instance per object, the existing path); an integer in 2..16 -> that many instances per
+    object; anything else is an error."""
+    raw = os.environ.get(ENV)
+    if raw is None or raw.strip() == "1":
+        return None
+    try:
+        r = int(raw.strip())
+    except ValueError:
+        r = None
+    if r is None or not 2 <= r <= MAX_INSTANCES:
+        raise ValueError("%s must be unset, 1 (one instance per object) or an integer in 2..%d (got %r)" % (ENV, MAX_INSTANCES, raw))
+    return r
+
+
+class InstanceLSVoting:
+    """CoordLSVotingWeighted(filter_estimates=True) with up to `max_instances` instances per object: __call__([seg, dirs, conf]) returns the
+    keypoints [b, oc, R, kp, 2] in (y, x).  After a call `last_counts` is int32 [b, oc, R] on the device (the pixels of each instance, in
+    descending order per object, 0 for an empty slot) and `last_labels` the uint8 slot map [b, h, w] that voted."""
+
+    def __init__(self, name, num_classes, num_points=9, max_instances=4, sigmoid_weights=False, min_component=50):
+        oc = int(num_classes) - 1
+        if not 1 <= int(max_instances) <= MAX_INSTANCES or oc < 1 or oc * int(max_instances) > MAX_SLOTS:
+            raise ValueError("InstanceLSVoting: max_instances must be in 1..%d and objects * max_instances at most %d (got %d objects, %d instances)"
+                             % (MAX_INSTANCES, MAX_SLOTS, oc, int(max_instances)))
+        self.name = name
+        self.num_classes = int(num_classes)
+        self.num_points = int(num_points)
+        self.max_instances = int(max_instances)
+        self.sigmoid_weights = bool(sigmoid_weights)
+        self.min_component = int(min_component)   # voting_layers_2d.py:66 has 50
+        self.last_counts: Optional[torch.Tensor] = None
+        self.last_labels: Optional[torch.Tensor] = None
+        self.last_instances: Optional[torch.Tensor] = None   # int32 [b, oc, R, 2]: (size, image-local root) as cp_ccl_instance_labels wrote them
+
+    def slot_of(self, o: int, r: int) -> int:
+        """the slot id of instance r (0-based) of object o (1-based)"""
+        if not (1 <= o < self.num_classes and 0 <= r < self.max_instances):
+            raise ValueError("slot_of: object %d instance %d outside 1..%d / 0..%d" % (o, r, self.num_classes - 1, self.max_instances - 1))
+        return (o - 1) * self.max_instances + r + 1
+
+    def __call__(self, inp: Sequence[torch.Tensor], **kwargs) -> torch.Tensor:
+        seg, direct, conf = inp
+        if not seg.is_cuda:
+            raise _lib.CasaposeHipError("InstanceLSVoting needs CUDA (ROCm) tensors; there is no CPU fallback")
+        if seg.shape[3] != self.num_classes:
+            raise ValueError("InstanceLSVoting: the segmentation has %d classes, the voter was built for %d" % (seg.shape[3], self.num_classes))
+        rec, (so, do, co) = _as_record(seg, direct, conf)
+        objects, R = self.num_classes - 1, self.max_instances
+        b, h, w, _ = rec.shape
+        from ..engine import cached_labels
+
+        lab0 = None
+        if so == 0 and rec.storage_offset() == 0:
+            lab0 = cached_labels(rec.untyped_storage().data_ptr(), (b, h, w), seg._version)  # the forward's own arg-max map
+        if lab0 is None:
+            lab0 = ops.argmax_labels(rec, classes=objects + 1, offset=so)
+        slot_map, inst = ops.ccl_instance_labels(lab0, objects, R, self.min_component)
+        out = ops.ls_vote_slots(rec, do, co, objects * R, self.num_points, slot_map, sigmoid_weights=self.sigmoid_weights)
+        self.last_labels, self.last_instances, self.last_counts = slot_map, inst, inst[..., 0]
+        return out.view(b, objects, R, self.num_points, 2)
+
+
+def poses_pnp_instances(coords, counts, object_points_3d, camera_data, min_num: int = 20, rng=None, solver=None) -> np.ndarray:
+    """Voted keypoints [b, oc, R, kp, 2] in (y, x) and pixel counts [b, oc, R] (InstanceLSVoting's result and last_counts) -> poses float32
+    [b, oc, R, 3, 4].  A slot with count <= min_num gets the zero pose; a pose with t_z < 0 is negated (pose_evaluation._poses_pnp's rules).
+    object_points_3d: the objects' 3-D keypoints, [b, oc, (1,) kp, 3] or [oc, kp, 3].  solver: a DevicePnP solves all (image, object, instance)
+    triples in one call, as oc * R pseudo-objects that share their object's 3-D keypoints; None asks device_pnp.solver_from_environment
+    (CASAPOSE_DEVICE_PNP=1, keypoints on a GPU), and without one the host loop over pnp.pnp_rvec_t runs."""
+    if solver is None and hasattr(coords, "detach") and coords.is_cuda:
+        from .device_pnp import solver_from_environment
+
+        solver = solver_from_environment(int(coords.shape[3]), coords.device)
+    pts = _np(coords)[..., ::-1]     # (y, x) -> (x, y)
+    if pts.ndim != 5 or pts.shape[4] != 2:
+        raise ValueError("poses_pnp_instances: coords must be [b, oc, R, kp, 2] (got %s)" % (tuple(pts.shape),))
+    b, oc, R, kp, _ = pts.shape
+    cnt = _np(counts, np.int64)
+    if tuple(cnt.shape) != (b, oc, R):
+        raise ValueError("poses_pnp_instances: counts must be [%d, %d, %d] (got %s)" % (b, oc, R, tuple(cnt.shape)))
+    kp3 = _np(object_points_3d)
+    lead = kp3.shape[0] if kp3.ndim >= 4 else 1
+    if kp3.size % (lead * kp * 3) or kp3.size // (lead * kp * 3) < oc or lead not in (1, b):
+        raise ValueError("poses_pnp_instances: object_points_3d %s does not hold %d keypoints for %d objects" % (tuple(kp3.shape), kp, oc))
+    kp3 = np.broadcast_to(kp3.reshape(lead, -1, kp, 3)[:, :oc], (b, oc, kp, 3))
+    cam = _np(camera_data)
+    cam = cam[0] if cam.ndim == 3 else cam
+    mask = cnt > int(min_num)
+    if solver is not None:
+        xy = np.ascontiguousarray(pts.reshape(b, oc * R, kp, 2))
+        x3 = np.ascontiguousarray(np.repeat(kp3, R, axis=1))                     # pseudo-object o * R + r has object o's keypoints
+        m = np.ascontiguousarray(mask.reshape(b, oc * R).astype(np.int32))
+        poses = _solved_poses(solver, xy, x3, cam, m, None)
+        bad = np.argwhere((m != 0) & np.isin(np.asarray(solver.last_info)[..., 0], (2, 4)))   # a degenerate keypoint set (3) is the zero pose
+        if len(bad):
+            raise FloatingPointError("poses_pnp_instances: non-finite pose for image %d object %d instance %d"
+                                     % (bad[0][0], bad[0][1] // R, bad[0][1] % R))
+        return poses.reshape(b, oc, R, 3, 4)
+    out = np.zeros((b, oc, R, 3, 4), np.float32)
+    for n, o, r in np.argwhere(mask):
+        p6 = _pnp.pnp_rvec_t(kp3[n, o], pts[n, o, r], cam, rng=rng)
+        if not np.all(np.isfinite(p6)):
+            raise FloatingPointError("poses_pnp_instances: non-finite pose for image %d object %d instance %d" % (n, o, r))
+        Rm, t = _pnp.rodrigues(p6[:3]), p6[3:].astype(np.float64)
+        P = np.concatenate([Rm, t.reshape(3, 1)], axis=1)
+        out[n, o, r] = -P if t[2] < 0 else P
+    return out

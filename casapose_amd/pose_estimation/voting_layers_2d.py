@@ -4,6 +4,8 @@
 """
 from __future__ import annotations
 
+import os
+import warnings
 import weakref
 from typing import Optional, Sequence
 
@@ -52,6 +54,9 @@ class CoordLSVotingWeighted:
         self.min_component = 50  # voting_layers_2d.py:66
         self._voted = None   # the last call's filtered label map, or (record, objects, seg offset) of an unfiltered call
         self.last_field: Optional[torch.Tensor] = None   # with CASAPOSE_UNCERTAINTY_PNP=1: the last call's merged field [b,h,w,2*kp] (dy,dx), a view
+        if os.environ.get("CASAPOSE_MAX_INSTANCES", "1").strip() != "1":   # this voter does not read the switch: say so instead of ignoring it in silence
+            warnings.warn("CASAPOSE_MAX_INSTANCES is set, but CoordLSVotingWeighted finds one instance per object: several instances are voted by "
+                          "instance_voting.InstanceLSVoting (util_scripts/minimal_instances.py)")
 
     @property
     def last_labels(self) -> Optional[torch.Tensor]:

@@ -1192,6 +1192,44 @@ int cp_model_prep_host_f32(const float* verts, long long total, const long long*
                            double* diameter_sq, float* box, float* keypoints, int32_t* indices, int32_t* status, void* workspace,
                            size_t workspace_bytes);
 
+/* ---- several instances of one object per image (csrc/ccl.hip, csrc/ls_vote.hip) -----------------------------------------------------------
+ * The reference's voter (casapose/pose_estimation/voting_layers_2d.py:43-122) keeps ONE component per (image, object) and has one row of sums
+ * per object.  These entry points extend both to R = max_instances instances: the vector field is shared by all classes and the label map
+ * says which pixel votes for what, so a label map whose values name (object, instance) pairs -- a slot map -- is all the voter needs.
+ *
+ * THE RULE of cp_ccl_instance_labels:
+ *   - a component is a 4-connected set of pixels with equal labels in 1..objects (a label above `objects` is background, as in
+ *     cp_ccl_filter_labels);
+ *   - a component is eligible when it has at least min_size pixels;
+ *   - the eligible components of an object are ordered by size descending, then by root ascending, the root being the raster index of the
+ *     component's first pixel;
+ *   - instance r (0-based) of object o (1-based) gets the slot id (o-1)*R + r + 1;
+ *   - a pixel of an ineligible component, or of an eligible one ranked R or later, gets slot 0.
+ * Two deliberate differences from the reference's histogram rule (:64-76), which cp_ccl_filter_labels restates with its quirks: there is no
+ * "bin 0", so an object larger than the rest of the image is kept (the reference drops it); and an object whose components are all below
+ * min_size keeps nothing (the reference keeps the first one in raster order).
+ *   labels_in  uint8 [n,h,w]                    slots_out  uint8 [n,h,w]  the slot map
+ *   inst_out   int32 [n][objects][R][2]         (size, image-local root y*w + x) of every slot, (0, -1) for an empty one; every word is written
+ *   ws         cp_ccl_instance_workspace_bytes(n, h, w, objects, R) bytes; needs no initialisation
+ * 1 <= R <= 16 and objects * R <= 254 (slot ids are bytes); anything else is refused before any launch, and
+ * cp_ccl_instance_workspace_bytes returns 0 for it.  Integer atomics only: two calls with the same input give the same bytes.
+ *
+ * cp_ls_vote_slots_f32 is cp_ls_vote_w_f32 with given labels, except that the table has `slots` rows (1..254) whatever the record's class
+ * count, slot_map is required (values 0..slots, 0 = no vote), and no logits are read: there is no seg_off.  A value above `slots` is the
+ * caller's error, exactly as a label above `objects` is for cp_ls_vote_w_f32: the production record's kernel reads it as 0, on every other
+ * layout (the generic kernel, which cp_ls_vote_w_f32 shares and which uses the byte as its table row) the result is undefined.
+ * cp_ccl_instance_labels never writes such a value.  sums_ws: fp64 [n][slots][kp][5] of
+ * cp_ls_vote_workspace_bytes(n, slots, kp) bytes (zeroed by the call); keypoints: fp32 [n][slots][kp][2] in (y,x) pixels, (0, 0) for a slot
+ * without pixels.  The production record (ld 36, dir_off 9, conf_off 27, softplus weights) has a kernel of its own for any slot count; every
+ * other layout takes the generic kernel.  The LDS table of slots * kp * 5 doubles lies beside the staging buffer of 1024 * ld bytes; the
+ * largest combination (254 slots beside ld = 64) takes 156 976 of the 160 KB a workgroup may have.
+ * Added in ABI 302 without changing any earlier entry point. */
+int cp_ccl_instance_labels(const uint8_t* labels_in, int batch, int h, int w, int objects, int max_instances, int min_size, void* ws,
+                           uint8_t* slots_out, int32_t* inst_out, void* stream);
+size_t cp_ccl_instance_workspace_bytes(int batch, int h, int w, int objects, int max_instances);
+int cp_ls_vote_slots_f32(const float* field, int ld, int dir_off, int conf_off, const uint8_t* slot_map, int batch, int h, int w, int slots,
+                         int kp, int sigmoid_weights, double* sums_ws, float* keypoints, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
