@@ -169,3 +169,37 @@ def ls_vote_slots(rec: torch.Tensor, do: int, co: int, slots: int, kp: int, slot
     check(_lib.load().cp_ls_vote_slots_f32(rec.data_ptr(), ld, do, co, slot_map.data_ptr(), b, h, w, slots, kp, 1 if sigmoid_weights else 0,
                                            sums.data_ptr(), out.data_ptr(), _stream(rec)), "cp_ls_vote_slots_f32")
     return (out, sums) if return_sums else out
+
+
+VOTE_SPLIT_DEFAULTS = dict(kp_index=0, cell=4, vote_stride=2, min_votes=12, rel_percent=25, nms_radius=2, gate=4.0, min_size=50)
+
+
+def vote_split_labels(labels: torch.Tensor, field_record: torch.Tensor, dir_off: int, objects: int, max_instances: int, return_workspace: bool = False,
+                      **params):
+    """cp_vote_split_labels on a uint8 label map [B,H,W] and a [B,H,W,ld] record tensor with directions at `dir_off`: touching instances of one
+    object split by their votes for the object's centre (keypoint `kp_index`, 0 by default).  params: VOTE_SPLIT_DEFAULTS' keys; include/casapose_hip.h
+    states the rule.  Returns (slot_map uint8 [B,H,W], inst int32 [B,objects,max_instances,4] = (pixels, votes, peak cy, peak cx), peaks float32
+    [B,objects,max_instances,2] in (y,x)); slot ids are ccl_instance_labels'.  return_workspace adds the workspace (a uint8 tensor; its parts lie
+    where cp_vote_split_workspace_layout says)."""
+    unknown = set(params) - set(VOTE_SPLIT_DEFAULTS)
+    if unknown:
+        raise TypeError("vote_split_labels: unknown parameter(s) %s (known: %s)" % (sorted(unknown), sorted(VOTE_SPLIT_DEFAULTS)))
+    p = dict(VOTE_SPLIT_DEFAULTS, **params)
+    _need_cuda(labels, field_record)
+    b, h, w = labels.shape
+    if (tuple(field_record.shape[:3]) != (b, h, w) or field_record.dim() != 4 or field_record.dtype != torch.float32 or not field_record.is_contiguous()
+            or labels.dtype != torch.uint8 or not labels.is_contiguous()):
+        raise ValueError("vote_split_labels: labels must be a contiguous uint8 [B,H,W] tensor and field_record a contiguous float32 [B,H,W,ld] one")
+    ld = field_record.shape[3]
+    lib = _lib.load()
+    # sizes the library refuses give 0 bytes here; the call below then says what is wrong
+    ws = torch.empty(max(int(lib.cp_vote_split_workspace_bytes(b, h, w, objects, max_instances, int(p["cell"]))), 16), dtype=torch.uint8,
+                     device=labels.device)
+    slot_map = torch.empty_like(labels)
+    inst = torch.empty(b, max(objects, 0), max(max_instances, 0), 4, dtype=torch.int32, device=labels.device)
+    peaks = torch.empty(b, max(objects, 0), max(max_instances, 0), 2, dtype=torch.float32, device=labels.device)
+    check(lib.cp_vote_split_labels(labels.data_ptr(), field_record.data_ptr(), ld, dir_off, int(p["kp_index"]), b, h, w, objects, max_instances,
+                                   int(p["cell"]), int(p["vote_stride"]), int(p["min_votes"]), int(p["rel_percent"]), int(p["nms_radius"]),
+                                   float(p["gate"]), int(p["min_size"]), ws.data_ptr(), slot_map.data_ptr(), inst.data_ptr(), peaks.data_ptr(),
+                                   _stream(labels)), "cp_vote_split_labels")
+    return (slot_map, inst, peaks, ws) if return_workspace else (slot_map, inst, peaks)

@@ -4,7 +4,11 @@
 CASAPose's vector field is shared by all classes and the label map tells the voter which pixel votes for what, so the network is used as it is:
 cp_ccl_instance_labels turns the arg-max map into a slot map (the R largest components of each object as separate slots; the rule stands in
 include/casapose_hip.h), cp_ls_vote_slots_f32 votes one keypoint set per slot, and poses_pnp_instances solves every (image, object, instance)
-triple.  Instance r (0-based) of object o (1-based) has the slot id (o-1)*R + r + 1."""
+triple.  Instance r (0-based) of object o (1-based) has the slot id (o-1)*R + r + 1.
+
+Components cannot separate instances that touch.  With split="votes" (CASAPOSE_INSTANCE_SPLIT=votes) cp_vote_split_labels builds the slot map
+instead: the pixels vote for their own instance's centre (keypoint 0) and every pixel goes to the peak its direction points at; the voter and
+the PnP are the same."""
 from __future__ import annotations
 
 import os
@@ -21,6 +25,8 @@ from .voting_layers_2d import _as_record
 ENV = "CASAPOSE_MAX_INSTANCES"
 MAX_INSTANCES = 16     # cp_ccl_instance_labels' bound on R
 MAX_SLOTS = 254        # slot ids are bytes
+ENV_SPLIT = "CASAPOSE_INSTANCE_SPLIT"
+SPLITS = ("components", "votes")
 
 
 def max_instances_from_environment() -> Optional[int]:
@@ -38,12 +44,31 @@ def max_instances_from_environment() -> Optional[int]:
     return r
 
 
+def instance_split_from_environment() -> str:
+    """CASAPOSE_INSTANCE_SPLIT: unset or `components` -> "components" (cp_ccl_instance_labels, the existing rule); `votes` -> "votes"
+    (cp_vote_split_labels), which needs CASAPOSE_MAX_INSTANCES; anything else is an error."""
+    raw = os.environ.get(ENV_SPLIT)
+    if raw is None or raw.strip() == "components":
+        return "components"
+    if raw.strip() != "votes":
+        raise ValueError("%s must be unset, `components` or `votes` (got %r)" % (ENV_SPLIT, raw))
+    if max_instances_from_environment() is None:
+        raise ValueError("%s=votes needs %s set to an integer in 2..%d: without it one instance per object is voted" % (ENV_SPLIT, ENV, MAX_INSTANCES))
+    return "votes"
+
+
 class InstanceLSVoting:
     """CoordLSVotingWeighted(filter_estimates=True) with up to `max_instances` instances per object: __call__([seg, dirs, conf]) returns the
     keypoints [b, oc, R, kp, 2] in (y, x).  After a call `last_counts` is int32 [b, oc, R] on the device (the pixels of each instance, in
-    descending order per object, 0 for an empty slot) and `last_labels` the uint8 slot map [b, h, w] that voted."""
+    descending order per object, 0 for an empty slot) and `last_labels` the uint8 slot map [b, h, w] that voted.
 
-    def __init__(self, name, num_classes, num_points=9, max_instances=4, sigmoid_weights=False, min_component=50):
+    split="votes" builds the slot map with cp_vote_split_labels instead (touching instances are separated by their votes for the object's
+    centre; cell, vote_stride, min_votes, rel_percent, nms_radius and gate are its parameters, min_component its min_size).  Then
+    `last_instances` is its int32 table [b, oc, R, 4] = (pixels, votes, peak cy, peak cx), `last_counts` the table's first column (in the order of
+    the peaks' votes) and `last_peaks` the peaks' positions, float32 [b, oc, R, 2] in (y, x)."""
+
+    def __init__(self, name, num_classes, num_points=9, max_instances=4, sigmoid_weights=False, min_component=50, split="components", cell=4,
+                 vote_stride=2, min_votes=12, rel_percent=25, nms_radius=2, gate=4.0):
         oc = int(num_classes) - 1
         if not 1 <= int(max_instances) <= MAX_INSTANCES or oc < 1 or oc * int(max_instances) > MAX_SLOTS:
             raise ValueError("InstanceLSVoting: max_instances must be in 1..%d and objects * max_instances at most %d (got %d objects, %d instances)"
@@ -57,6 +82,12 @@ class InstanceLSVoting:
         self.last_counts: Optional[torch.Tensor] = None
         self.last_labels: Optional[torch.Tensor] = None
         self.last_instances: Optional[torch.Tensor] = None   # int32 [b, oc, R, 2]: (size, image-local root) as cp_ccl_instance_labels wrote them
+        if split not in SPLITS:
+            raise ValueError("InstanceLSVoting: split must be one of %s (got %r)" % (SPLITS, split))
+        self.split = split
+        self.split_params = dict(cell=int(cell), vote_stride=int(vote_stride), min_votes=int(min_votes), rel_percent=int(rel_percent),
+                                 nms_radius=int(nms_radius), gate=float(gate))
+        self.last_peaks: Optional[torch.Tensor] = None       # split="votes": float32 [b, oc, R, 2]
 
     def slot_of(self, o: int, r: int) -> int:
         """the slot id of instance r (0-based) of object o (1-based)"""
@@ -80,7 +111,10 @@ class InstanceLSVoting:
             lab0 = cached_labels(rec.untyped_storage().data_ptr(), (b, h, w), seg._version)  # the forward's own arg-max map
         if lab0 is None:
             lab0 = ops.argmax_labels(rec, classes=objects + 1, offset=so)
-        slot_map, inst = ops.ccl_instance_labels(lab0, objects, R, self.min_component)
+        if self.split == "votes":
+            slot_map, inst, self.last_peaks = ops.vote_split_labels(lab0, rec, do, objects, R, min_size=self.min_component, **self.split_params)
+        else:
+            slot_map, inst = ops.ccl_instance_labels(lab0, objects, R, self.min_component)
         out = ops.ls_vote_slots(rec, do, co, objects * R, self.num_points, slot_map, sigmoid_weights=self.sigmoid_weights)
         self.last_labels, self.last_instances, self.last_counts = slot_map, inst, inst[..., 0]
         return out.view(b, objects, R, self.num_points, 2)

@@ -1230,6 +1230,51 @@ size_t cp_ccl_instance_workspace_bytes(int batch, int h, int w, int objects, int
 int cp_ls_vote_slots_f32(const float* field, int ld, int dir_off, int conf_off, const uint8_t* slot_map, int batch, int h, int w, int slots,
                          int kp, int sigmoid_weights, double* sums_ws, float* keypoints, void* stream);
 
+/* ---- touching instances of one object, split by their centre votes (csrc/vote_split.hip, csrc/vote_split_math.h) ---------------------------
+ * cp_ccl_instance_labels cannot separate two instances of one object that touch: they are one component.  Keypoint 0 of every object is its
+ * box centre, so every pixel carries a direction to its OWN instance's centre; cp_vote_split_labels lets the pixels vote for that centre on a
+ * coarse grid (a Hough step), takes up to R peaks per object and gives every pixel to the peak its direction points at.  The slot map and the
+ * slot ids are cp_ccl_instance_labels'; cp_ls_vote_slots_f32 consumes them unchanged.
+ *
+ * THE RULE of cp_vote_split_labels.  All fp32 arithmetic is one rounding per operation, without contraction; division is correctly rounded;
+ * every integer result is independent of the order of summation.
+ *   inputs   labels uint8 [n,h,w] (a label above `objects` is background); field fp32 [n,h,w,ld]; the direction d = (dy, dx) of a pixel are
+ *            the floats dir_off + 2*kp_index and the next one of its record (kp_index 0 = the centre); R = max_instances in 1..16 with
+ *            objects * R <= 254; cell in {2, 4, 8}; vote_stride 1..4; min_votes >= 1; rel_percent 0..100; nms_radius 1..4 cells; gate > 0 in
+ *            pixels (fp32); min_size >= 1.
+ *   1. accumulate   acc is int32 [n][objects][gh][gw], gh = ceil(h/cell), gw = ceil(w/cell), zeroed by the call.  A pixel (y, x) votes when
+ *            y % vote_stride == 0, x % vote_stride == 0, its label l is in 1..objects, both components of d are finite and d != (0, 0).  The
+ *            major axis is y when |dy| >= |dx|, else x; m = d_minor / d_major; s = +1 when d_major > 0, else -1; a0 = major + 0.5,
+ *            b0 = minor + 0.5.  For k = 0, 1, 2, ...: t = s * float(cell*k), a = a0 + t, b = b0 + t*m (the product rounded, then the sum).
+ *            The ray stops at the first k with (a, b) outside [0, extent_major) x [0, extent_minor); before that
+ *            acc[l-1][floor(a/cell), floor(b/cell)] += 1, the pair mapped back to (cy, cx).  Step 0 is the pixel's own cell.
+ *   2. peaks, per (image, object)   the key of a cell is (votes << 32) | (0xFFFFFFFF - (cy*gw + cx)).  A cell is a candidate when
+ *            votes >= min_votes and its key is the largest in its (2*nms_radius+1)^2 window clipped to the grid.  The R candidates with the
+ *            largest keys are ranked in that order, rank r = the position; every one with votes*100 < rel_percent*top_votes (top_votes: rank
+ *            0's) is dropped.  The peak position is taken in fp64 over the clipped 3 x 3 cells around the peak:
+ *            py = (double)sum(v*(2*cy_i+1)) / (double)sum(v) * (0.5*cell), rounded to fp32, the sums being integers; px likewise.
+ *   3. assign   a pixel of label l (EVERY pixel, whatever vote_stride) compares the peaks of object l in rank order, in fp32 and in this order:
+ *            e = peak - pixel centre; e2 = ey*ey + ex*ex; n2 = dy*dy + dx*dx; dot = ey*dy + ex*dx; cr = ey*dx - ex*dy;
+ *            dist2 = cr*cr / n2 when n2 is finite, n2 > 0 and dot > 0, otherwise dist2 = e2.  The pixel takes the peak with the smallest
+ *            dist2 among those with dist2 <= gate*gate, the lower rank on a tie, and the slot id (l-1)*R + r + 1; with none it takes slot 0.
+ *   4. size gate   a slot with fewer than min_size assigned pixels is emptied: its pixels become 0.  Slots are not renumbered.
+ *   outputs  slots_out uint8 [n,h,w]; inst_out int32 [n][objects][R][4] = (pixels, votes, peak cy, peak cx): (0, 0, -1, -1) for a rank
+ *            without a peak, (0, votes, cy, cx) for one emptied by step 4, every word written; peaks_out fp32 [n][objects][R][2] = (y, x),
+ *            (0, 0) where there is no peak.
+ *   ws       cp_vote_split_workspace_bytes(n, h, w, objects, R, cell) bytes, 16-byte aligned; needs no initialisation.  After the call it holds
+ *            acc and, as uint64 [n][objects][gh][gw], every candidate's key (0 for a cell that is none) at the byte offsets
+ *            cp_vote_split_workspace_layout writes to offsets[0] and offsets[1]; offsets[2] is where the slots' pixel counts before step 4
+ *            lie, int32 [n][objects*R].  The layout function runs on the host and launches nothing.
+ * Further limits: h, w <= 16384; one object's grid has at most 36864 cells (it lies in a workgroup's LDS: 480 x 640 needs cell >= 4);
+ * n*h*w < 2^31.  Every size outside the limits is refused by name before any launch, and cp_vote_split_workspace_bytes returns 0 for it.
+ * Integer atomics only, no floating-point atomics: two calls on equal inputs give equal bytes.  There is no host twin: the arithmetic's host
+ * coverage is csrc/vote_split_selftest.cpp.  Added in ABI 302 without changing any earlier entry point. */
+int cp_vote_split_labels(const uint8_t* labels, const float* field, int ld, int dir_off, int kp_index, int batch, int h, int w, int objects,
+                         int max_instances, int cell, int vote_stride, int min_votes, int rel_percent, int nms_radius, float gate, int min_size,
+                         void* ws, uint8_t* slots_out, int32_t* inst_out, float* peaks_out, void* stream);
+size_t cp_vote_split_workspace_bytes(int batch, int h, int w, int objects, int max_instances, int cell);
+int cp_vote_split_workspace_layout(int batch, int h, int w, int objects, int max_instances, int cell, size_t* offsets /*[3]*/);
+
 #ifdef __cplusplus
 }
 #endif

@@ -11,6 +11,11 @@ object without any gets one zero row with instance 0 and pixels 0 -- and main() 
 speed_eval.csv and `average speed:` are test_minimal.py's.  The switch does not combine with CASAPOSE_UNCERTAINTY_PNP=1 or
 CASAPOSE_MASK_REFINE=1 (keypoint covariances and the mask refinement are per object): refused by name before any device work.
 test_minimal.py itself does not read the switch.
+
+CASAPOSE_INSTANCE_SPLIT=votes (with CASAPOSE_MAX_INSTANCES set; refused by name without it) separates the instances by their votes for the
+object's centre instead of by connected components (InstanceLSVoting(split="votes"), cp_vote_split_labels): the script then also says
+`instances: split by centre votes` once, and poses_est.csv has one more trailing column `votes` after `instance,pixels`, the votes of the
+instance's peak.  Unset or `components`: nothing changes.
 """
 import os
 import sys
@@ -26,7 +31,8 @@ sys.path.insert(0, os.path.join(ROOT, "util_scripts"))
 import test_minimal  # noqa: E402
 from casapose_amd.data_handler.image_only_dataset import ImageOnlyDataset  # noqa: E402
 from casapose_amd.data_handler.vectorfield_dataset import VectorfieldDataset  # noqa: E402
-from casapose_amd.pose_estimation.instance_voting import ENV, InstanceLSVoting, max_instances_from_environment, poses_pnp_instances  # noqa: E402
+from casapose_amd.pose_estimation.instance_voting import (ENV, InstanceLSVoting, instance_split_from_environment,  # noqa: E402
+                                                          max_instances_from_environment, poses_pnp_instances)
 from casapose_amd.pose_models.tfkeras import Classifiers  # noqa: E402
 from casapose_amd.utils.config_parser import parse_config  # noqa: E402
 from casapose_amd.utils.io_utils import latest_checkpoint  # noqa: E402
@@ -34,6 +40,7 @@ from casapose_amd.utils.io_utils import latest_checkpoint  # noqa: E402
 
 def main(argv=None):
     instances = max_instances_from_environment()
+    by_votes = instance_split_from_environment() == "votes"
     if instances is None:
         return test_minimal.main(argv)
     for other in ("CASAPOSE_UNCERTAINTY_PNP", "CASAPOSE_MASK_REFINE"):
@@ -94,11 +101,15 @@ def main(argv=None):
         f.write("batchid,speed \n")
     if opt.write_poses:
         with open(opt.evalf + "/poses_est.csv", "w") as f:
-            f.write("name,object," + ",".join("r%d%d" % (i, j) for i in range(1, 4) for j in range(1, 4)) + ",t1,t2,t3,instance,pixels\n")
+            f.write("name,object," + ",".join("r%d%d" % (i, j) for i in range(1, 4) for j in range(1, 4)) + ",t1,t2,t3,instance,pixels" +
+                    (",votes" if by_votes else "") + "\n")
 
     K, kp = 1 + no_objects, opt.no_points
-    voter = InstanceLSVoting(name="coords_ls_voting", num_classes=K, num_points=kp, max_instances=instances)
+    voter = InstanceLSVoting(name="coords_ls_voting", num_classes=K, num_points=kp, max_instances=instances,
+                             split="votes" if by_votes else "components")
     print("instances: up to {} per object".format(instances))
+    if by_votes:
+        print("instances: split by centre votes")
     rng = np.random.default_rng(opt.manualseed)
     speed, poses_by_name = [], {}
     for batch_idx in range(int(image_batches)):
@@ -109,6 +120,7 @@ def main(argv=None):
         seg, dirs, conf = torch.split(out, [K, 2 * kp, out.shape[3] - K - 2 * kp], dim=3)
         coords = voter([seg, dirs, conf])
         pixels = voter.last_counts.cpu().numpy()
+        votes = voter.last_instances[..., 1].cpu().numpy() if by_votes else None
         poses = poses_pnp_instances(coords, pixels, keypoints, camera_matrix, min_num=opt.min_object_size_test, rng=rng)
         seconds = time.perf_counter() - start
         speed.append(seconds)
@@ -123,7 +135,8 @@ def main(argv=None):
                     for r in found or [0]:
                         P = poses_by_name[name][o, r]
                         f.write("{},{},".format(name, obj) + ",".join("{:.9g}".format(v) for v in np.concatenate([P[:, :3].reshape(-1), P[:, 3]])) +
-                                ",{},{}\n".format(r, int(pixels[0, o, r]) if found else 0))
+                                ",{},{}".format(r, int(pixels[0, o, r]) if found else 0) +
+                                (",{}".format(int(votes[0, o, r]) if found else 0) if by_votes else "") + "\n")
     print("average speed: {}".format(float(np.mean(speed[10:])) if len(speed) > 10 else float("nan")))
     return {"speed": speed, "poses": poses_by_name}
 
