@@ -16,6 +16,8 @@
 // only flushes (LDS fp64 atomics) when its label changes or the strip ends; the block then
 // adds its LDS table to the global fp64 sums with one atomic per entry.
 #include "common.h"
+#include "ls_robust_math.h"
+#include <cmath>
 #include <cstdlib>
 
 namespace {
@@ -113,6 +115,35 @@ __device__ __forceinline__ void ls_add_terms(double (&a)[5], float ny, float nx,
     a[4] += (double)q1;
 }
 
+// A reweighted pass of the robust voter (cp_ls_vote_slots_robust_f32; ls_robust_math.h has the weight and why it is what it is) walks the pixels
+// as the plain pass does and hands ls_add_terms w * rho in place of w.  ROBUST is a template parameter of the two kernels that walk a slot map:
+// the plain instantiation carries none of what follows.
+//
+// The estimates of the keypoints of a lane's current slot, in the voter's normalised coordinates (pixels / H): 18 registers, reloaded from the
+// keypoints of the pass before when the lane's label changes -- as rarely as its accumulators are flushed.  A table of estimates in LDS would
+// not fit beside 254 slots' sums and the staging buffer of ld = 64.
+template <bool ROBUST, int KP>
+struct LsEst {
+    float p[ROBUST ? KP : 1][2];
+    // est_img: fp32 [slots][KP][2] in (y, x) pixels, the image's rows of the keypoints buffer
+    __device__ __forceinline__ void load(const float* __restrict__ est_img, int lab, int H) {
+        const float2* e = reinterpret_cast<const float2*>(est_img + (size_t)(lab - 1) * KP * 2);
+#pragma unroll
+        for (int j = 0; j < (ROBUST ? KP : 0); ++j) {
+            const float2 v = e[j];
+            p[j][0] = v.x / (float)H;
+            p[j][1] = v.y / (float)H;
+        }
+    }
+};
+
+// one keypoint of one labelled pixel, plain or reweighted
+template <bool ROBUST>
+__device__ __forceinline__ void ls_add_pixel(double (&a)[5], float2 n, float w, float cy, float cx, const float (&p)[2], float rscale) {
+    if (ROBUST) w *= cp_lsr::rho(p[0], p[1], cy, cx, n.x, n.y, rscale);
+    ls_add_terms(a, n.x, n.y, w, cy, cx);
+}
+
 // The two arithmetic choices.  Exact (generic kernel): libm weights and d / sqrt(d.d).  Fast (36-float kernel): softplus_fast and
 // d * rsqrt(d.d), one reciprocal square root for both components -- the libm calls cost as much as the whole memory stream.
 __device__ __forceinline__ float ls_weight_exact(float cf, int sigmoid) {
@@ -131,11 +162,13 @@ __device__ __forceinline__ float2 ls_normal_fast(float dy, float dx) {
     return make_float2(dy * inv, dx * inv);
 }
 
-template <int KP>
+// ROBUST (given labels only): est is the keypoints buffer of the pass before, fp32 [B][objects][KP][2], rscale = H / cutoff
+template <int KP, bool ROBUST = false>
 __global__ __launch_bounds__(256) void ls_accumulate_kernel(const float* __restrict__ field, int ld, int seg_off,
                                                             int dir_off, int conf_off, const uint8_t* __restrict__ labels,
                                                             int B, int H, int W, int objects, double* __restrict__ sums,
-                                                            int strips_x, int strips_y, int sigmoid) {
+                                                            int strips_x, int strips_y, int sigmoid, const float* __restrict__ est,
+                                                            float rscale) {
     extern __shared__ __attribute__((aligned(16))) char smem_raw[];
     double* acc_lds = reinterpret_cast<double*>(smem_raw);                         // [objects][KP][5]
     float* stage = reinterpret_cast<float*>(smem_raw + sizeof(double) * objects * KP * 5);  // [WAVES][64*ld]
@@ -153,6 +186,7 @@ __global__ __launch_bounds__(256) void ls_accumulate_kernel(const float* __restr
         const float cx = s.cx(H);
         const int classes = objects + 1;
         LsAcc<KP> acc(acc_lds);
+        LsEst<ROBUST, KP> pe;
 
         const int y_end = min(y0 + ROWS, H);
         // with given labels a row segment without a non-zero label contributes nothing: its records are not read.  The strip's labels are
@@ -180,6 +214,7 @@ __global__ __launch_bounds__(256) void ls_accumulate_kernel(const float* __restr
             if (rd && lane < ncols) {
                 if (labels) {
                     lab = labels[((size_t)img * H + y) * W + x];
+                    if (ROBUST && lab > objects) lab = 0;   // no row of estimates to read
                 } else {
                     float best = px[seg_off];
                     for (int k = 1; k < classes; ++k) {
@@ -188,15 +223,17 @@ __global__ __launch_bounds__(256) void ls_accumulate_kernel(const float* __restr
                     }
                 }
             }
+            const bool moved = lab != acc.cur;
             acc.enter(lab);
             if (lab > 0) {
+                if (ROBUST && moved) pe.load(est + (size_t)img * objects * KP * 2, lab, H);
                 const float cy = ((float)y + 0.5f) / (float)H;
 #pragma unroll
                 for (int j = 0; j < KP; ++j) {
                     const float dy = px[dir_off + 2 * j], dx = px[dir_off + 2 * j + 1];
                     const float w = ls_weight_exact(px[conf_off + j], sigmoid);
                     const float2 n = ls_normal_exact(dy, dx);
-                    ls_add_terms(acc.a[j], n.x, n.y, w, cy, cx);
+                    ls_add_pixel<ROBUST>(acc.a[j], n, w, cy, cx, pe.p[ROBUST ? j : 0], rscale);
                 }
             }
             __builtin_amdgcn_wave_barrier();  // all lanes done reading before the next row overwrites
@@ -670,7 +707,7 @@ extern "C" int cp_ls_vote_w_f32(const float* field, int ld, int seg_off, int dir
             CP_LAUNCH(ls_accumulate36_kernel<false>, dim3(batch * blocks_per_img), dim3(256), lds, st, field, labels, batch, h, w, sums_ws, strips_x, strips_y);
     } else {
         CP_LAUNCH((ls_accumulate_kernel<MAXKP>), dim3(batch * blocks_per_img), dim3(256), lds, st, field, ld, seg_off,
-                  dir_off, conf_off, labels, batch, h, w, objects, sums_ws, strips_x, strips_y, sigmoid_weights ? 1 : 0);
+                  dir_off, conf_off, labels, batch, h, w, objects, sums_ws, strips_x, strips_y, sigmoid_weights ? 1 : 0, (const float*)nullptr, 0.f);
     }
     int total = batch * objects * kp;
     CP_LAUNCH(ls_solve_kernel, dim3((total + 255) / 256), dim3(256), 0, st, sums_ws, total, h, keypoints);
@@ -737,8 +774,11 @@ namespace {
 // one row segment prefetched ahead, nine 16-byte LDS reads per pixel) over the production record, the LDS table [slots][9][5] in front of the
 // staging buffer.  A table of 254 slots is 91 KB, so what a block pays per table entry is kept away from the blocks that have nothing to add:
 // the labels are read BEFORE the table is zeroed, and a block whose four strips hold no label ends there (no zeroing, no commit scan).
+// ROBUST: a reweighted pass; est is the keypoints buffer of the pass before, fp32 [B][slots][9][2], rscale = H / cutoff.
+template <bool ROBUST>
 __global__ __launch_bounds__(256) void ls_accumulate36_slots_kernel(const float* __restrict__ field, const uint8_t* __restrict__ labels, int B, int H,
-                                                                    int W, int slots, double* __restrict__ sums, int strips_x, int strips_y) {
+                                                                    int W, int slots, double* __restrict__ sums, int strips_x, int strips_y,
+                                                                    const float* __restrict__ est, float rscale) {
     constexpr int KP = 9, LD = 36, NV = LD / 4;
     extern __shared__ __attribute__((aligned(16))) char smem_raw[];
     const int nacc = slots * KP * 5;
@@ -791,6 +831,7 @@ __global__ __launch_bounds__(256) void ls_accumulate36_slots_kernel(const float*
     if (rowmask) {   // wave-uniform
         const int img = s.img, x0 = s.x0, y0 = s.y0;
         LsAcc<KP> acc(acc_lds);
+        LsEst<ROBUST, KP> pe;
         float4 pre[NV];
         auto issue = [&](int ry) {
             const float4* g = reinterpret_cast<const float4*>(field + (((size_t)img * H + y0 + ry) * W + x0) * LD);
@@ -833,14 +874,16 @@ __global__ __launch_bounds__(256) void ls_accumulate36_slots_kernel(const float*
             }
             if (ry != prev + 1) acc.enter(0);  // rows in between were skipped: every lane's label was 0 there, which ends its run
             const int lab = label_of(ry);
+            const bool moved = lab != acc.cur;
             acc.enter(lab);
             if (lab > 0) {
+                if (ROBUST && moved) pe.load(est + (size_t)img * slots * KP * 2, lab, H);
                 const float cy = ((float)(y0 + ry) + 0.5f) / (float)H;
 #pragma unroll
                 for (int j = 0; j < KP; ++j) {
                     const float w = softplus_fast(r[27 + j]);  // softplus (:35)
                     const float2 n = ls_normal_fast(r[9 + 2 * j], r[9 + 2 * j + 1]);
-                    ls_add_terms(acc.a[j], n.x, n.y, w, cy, cx);
+                    ls_add_pixel<ROBUST>(acc.a[j], n, w, cy, cx, pe.p[ROBUST ? j : 0], rscale);
                 }
             }
             __builtin_amdgcn_wave_barrier();  // all lanes done reading before the next row overwrites
@@ -852,42 +895,113 @@ __global__ __launch_bounds__(256) void ls_accumulate36_slots_kernel(const float*
     ls_table_commit(acc_lds, nacc, sums + (size_t)s.img * nacc);
 }
 
+// the solve of a reweighted pass: ls_solve_kernel's value where cp_lsr::solve accepts the reweighted system, otherwise the keypoint is left as
+// the pass before wrote it
+__global__ void ls_robust_solve_kernel(const double* __restrict__ plain, const double* __restrict__ sums, int total, int H, float* __restrict__ out) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= total) return;
+    double p0, p1;
+    if (cp_lsr::solve(sums + (size_t)i * 5, plain[(size_t)i * 5] + plain[(size_t)i * 5 + 2], p0, p1)) {
+        out[2 * i] = (float)p0 * (float)H;
+        out[2 * i + 1] = (float)p1 * (float)H;
+    }
+}
+
 constexpr int LS_MAX_LDS = 160 * 1024;   // per workgroup on gfx950
 
-}  // namespace
+// what cp_ls_vote_slots_f32 refuses, under the name `fn` of the entry point that was called
+int ls_slots_check(const char* fn, const float* field, int ld, int dir_off, int conf_off, const uint8_t* slot_map, int batch, int h, int w, int slots,
+                   int kp, const void* sums_ws, const float* keypoints) {
+    CP_REQUIRE(field && slot_map && sums_ws && keypoints, "%s: null pointer (the slot map is required)", fn);
+    CP_REQUIRE(batch > 0 && h > 0 && w > 0 && slots > 0 && slots < 255, "%s: bad sizes (slots must be in 1..254)", fn);
+    CP_REQUIRE(kp == MAXKP, "%s: built for %d keypoints (got %d)", fn, MAXKP, kp);
+    CP_REQUIRE(ld % 4 == 0 && ld > 0 && ld <= 64 && ((uintptr_t)field & 15) == 0, "%s: ld must be a multiple of 4 (<= 64) and field 16-byte aligned", fn);
+    CP_REQUIRE(dir_off >= 0 && dir_off + 2 * kp <= ld && conf_off >= 0 && conf_off + kp <= ld, "%s: channel offsets outside the pixel record", fn);
+    return CP_OK;
+}
 
-extern "C" int cp_ls_vote_slots_f32(const float* field, int ld, int dir_off, int conf_off, const uint8_t* slot_map, int batch, int h, int w,
-                                    int slots, int kp, int sigmoid_weights, double* sums_ws, float* keypoints, void* stream) {
-    CP_REQUIRE(field && slot_map && sums_ws && keypoints, "cp_ls_vote_slots_f32: null pointer (the slot map is required)");
-    CP_REQUIRE(batch > 0 && h > 0 && w > 0 && slots > 0 && slots < 255, "cp_ls_vote_slots_f32: bad sizes (slots must be in 1..254)");
-    CP_REQUIRE(kp == MAXKP, "cp_ls_vote_slots_f32: built for %d keypoints (got %d)", MAXKP, kp);
-    CP_REQUIRE(ld % 4 == 0 && ld > 0 && ld <= 64 && ((uintptr_t)field & 15) == 0,
-               "cp_ls_vote_slots_f32: ld must be a multiple of 4 (<= 64) and field 16-byte aligned");
-    CP_REQUIRE(dir_off >= 0 && dir_off + 2 * kp <= ld && conf_off >= 0 && conf_off + kp <= ld,
-               "cp_ls_vote_slots_f32: channel offsets outside the pixel record");
-    hipStream_t st = (hipStream_t)stream;
-    const size_t nbytes = cp_ls_vote_workspace_bytes(batch, slots, kp);
-    if (hipMemsetAsync(sums_ws, 0, nbytes, st) != hipSuccess) return cp::check_launch("cp_ls_vote_slots_f32 memset");
+template <class Kernel>
+int ls_raise_lds(const char* fn, Kernel kernel, size_t lds) {
+    if (lds > 64 * 1024)   // (the limit counts the kernel's static LDS too: ask for what this launch needs, not for the whole 160 KB)
+        CP_REQUIRE(hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) == hipSuccess,
+                   "%s: cannot raise the kernel's LDS limit to %zu bytes", fn, lds);
+    return CP_OK;
+}
+
+// zeroes `sums` and accumulates one pass over the slot map into it: the plain pass with est == nullptr, otherwise a reweighted pass against the
+// estimates `est` (the keypoints buffer).  The production record has a kernel of its own, every other layout takes the generic kernel's walk.
+int ls_slots_accumulate(const char* fn, const float* field, int ld, int dir_off, int conf_off, const uint8_t* slot_map, int batch, int h, int w,
+                        int slots, int kp, int sigmoid_weights, double* sums, const float* est, float rscale, hipStream_t st) {
+    if (hipMemsetAsync(sums, 0, cp_ls_vote_workspace_bytes(batch, slots, kp), st) != hipSuccess) return cp::check_launch(fn);
     const int strips_x = (w + 63) / 64, strips_y = (h + ROWS - 1) / ROWS;
     const int blocks_per_img = (strips_x * strips_y + WAVES - 1) / WAVES;
     const size_t table = (sizeof(double) * slots * kp * 5 + 15) / 16 * 16;
     const size_t lds = table + sizeof(float) * WAVES * 64 * ld;
     static_assert((sizeof(double) * 254 * MAXKP * 5 + 15) / 16 * 16 + sizeof(float) * WAVES * 64 * 64 <= (size_t)LS_MAX_LDS, "254 slots beside ld = 64 fit");
+    const dim3 grid(batch * blocks_per_img), block(256);
+    const int sig = sigmoid_weights ? 1 : 0;
     if (!sigmoid_weights && is_record36(ld, dir_off, conf_off)) {
-        if (lds > 64 * 1024)   // (the limit counts the kernel's static LDS too: ask for what this launch needs, not for the whole 160 KB)
-            CP_REQUIRE(hipFuncSetAttribute(reinterpret_cast<const void*>(&ls_accumulate36_slots_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                           (int)lds) == hipSuccess, "cp_ls_vote_slots_f32: cannot raise the kernel's LDS limit to %zu bytes", lds);
-        CP_LAUNCH(ls_accumulate36_slots_kernel, dim3(batch * blocks_per_img), dim3(256), lds, st, field, slot_map, batch, h, w, slots, sums_ws, strips_x,
-                  strips_y);
+        if (est) {
+            if (ls_raise_lds(fn, &ls_accumulate36_slots_kernel<true>, lds) != CP_OK) return CP_ERR_INVALID;
+            CP_LAUNCH(ls_accumulate36_slots_kernel<true>, grid, block, lds, st, field, slot_map, batch, h, w, slots, sums, strips_x, strips_y, est, rscale);
+        } else {
+            if (ls_raise_lds(fn, &ls_accumulate36_slots_kernel<false>, lds) != CP_OK) return CP_ERR_INVALID;
+            CP_LAUNCH(ls_accumulate36_slots_kernel<false>, grid, block, lds, st, field, slot_map, batch, h, w, slots, sums, strips_x, strips_y, est, rscale);
+        }
+    } else if (est) {
+        if (ls_raise_lds(fn, &ls_accumulate_kernel<MAXKP, true>, lds) != CP_OK) return CP_ERR_INVALID;
+        CP_LAUNCH((ls_accumulate_kernel<MAXKP, true>), grid, block, lds, st, field, ld, 0, dir_off, conf_off, slot_map, batch, h, w, slots, sums, strips_x,
+                  strips_y, sig, est, rscale);
     } else {
-        if (lds > 64 * 1024)
-            CP_REQUIRE(hipFuncSetAttribute(reinterpret_cast<const void*>(&ls_accumulate_kernel<MAXKP>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                           (int)lds) == hipSuccess, "cp_ls_vote_slots_f32: cannot raise the kernel's LDS limit to %zu bytes", lds);
+        if (ls_raise_lds(fn, &ls_accumulate_kernel<MAXKP, false>, lds) != CP_OK) return CP_ERR_INVALID;
         // the generic kernel with given labels: its table has `objects` rows, and the logits (seg_off) are read only without labels
-        CP_LAUNCH((ls_accumulate_kernel<MAXKP>), dim3(batch * blocks_per_img), dim3(256), lds, st, field, ld, 0, dir_off, conf_off, slot_map, batch, h, w,
-                  slots, sums_ws, strips_x, strips_y, sigmoid_weights ? 1 : 0);
+        CP_LAUNCH((ls_accumulate_kernel<MAXKP, false>), grid, block, lds, st, field, ld, 0, dir_off, conf_off, slot_map, batch, h, w, slots, sums, strips_x,
+                  strips_y, sig, est, rscale);
     }
+    return cp::check_launch(fn);
+}
+
+}  // namespace
+
+extern "C" int cp_ls_vote_slots_f32(const float* field, int ld, int dir_off, int conf_off, const uint8_t* slot_map, int batch, int h, int w,
+                                    int slots, int kp, int sigmoid_weights, double* sums_ws, float* keypoints, void* stream) {
+    const char* fn = "cp_ls_vote_slots_f32";
+    if (ls_slots_check(fn, field, ld, dir_off, conf_off, slot_map, batch, h, w, slots, kp, sums_ws, keypoints) != CP_OK) return CP_ERR_INVALID;
+    hipStream_t st = (hipStream_t)stream;
+    const int rc = ls_slots_accumulate(fn, field, ld, dir_off, conf_off, slot_map, batch, h, w, slots, kp, sigmoid_weights, sums_ws, nullptr, 0.f, st);
+    if (rc != CP_OK) return rc;
     const int total = batch * slots * kp;
     CP_LAUNCH(ls_solve_kernel, dim3((total + 255) / 256), dim3(256), 0, st, sums_ws, total, h, keypoints);
-    return cp::check_launch("cp_ls_vote_slots_f32");
+    return cp::check_launch(fn);
 }
+
+extern "C" size_t cp_ls_vote_robust_workspace_bytes(int batch, int slots, int kp) { return 2 * cp_ls_vote_workspace_bytes(batch, slots, kp); }
+
+// The robust voter per slot: pass 0 is cp_ls_vote_slots_f32's accumulate and solve into block 0 of the workspace; every further pass zeroes
+// block 1, accumulates the sums reweighted against the keypoints of the pass before, and solves by the rule of cp_lsr::solve.
+extern "C" int cp_ls_vote_slots_robust_f32(const float* field, int ld, int dir_off, int conf_off, const uint8_t* slot_map, int batch, int h, int w,
+                                           int slots, int kp, int sigmoid_weights, float cutoff_px, int passes, void* workspace, float* keypoints,
+                                           void* stream) {
+    const char* fn = "cp_ls_vote_slots_robust_f32";
+    if (ls_slots_check(fn, field, ld, dir_off, conf_off, slot_map, batch, h, w, slots, kp, workspace, keypoints) != CP_OK) return CP_ERR_INVALID;
+    CP_REQUIRE(std::isfinite(cutoff_px) && cutoff_px > 0.f, "%s: cutoff_px must be finite and > 0 (got %g)", fn, (double)cutoff_px);
+    CP_REQUIRE(passes >= 0 && passes <= cp_lsr::CP_LS_ROBUST_MAX_PASSES, "%s: passes must be in 0..%d (got %d)", fn, cp_lsr::CP_LS_ROBUST_MAX_PASSES, passes);
+    CP_REQUIRE((((uintptr_t)workspace | (uintptr_t)keypoints) & 7) == 0, "%s: the workspace and the keypoints must be 8-byte aligned", fn);
+    hipStream_t st = (hipStream_t)stream;
+    const int total = batch * slots * kp;
+    double* plain = static_cast<double*>(workspace);
+    double* again = plain + (size_t)total * 5;
+    int rc = ls_slots_accumulate(fn, field, ld, dir_off, conf_off, slot_map, batch, h, w, slots, kp, sigmoid_weights, plain, nullptr, 0.f, st);
+    if (rc != CP_OK) return rc;
+    CP_LAUNCH(ls_solve_kernel, dim3((total + 255) / 256), dim3(256), 0, st, plain, total, h, keypoints);
+    if ((rc = cp::check_launch(fn)) != CP_OK) return rc;
+    const float rscale = cp_lsr::rho_scale(h, cutoff_px);
+    for (int k = 1; k <= passes; ++k) {
+        rc = ls_slots_accumulate(fn, field, ld, dir_off, conf_off, slot_map, batch, h, w, slots, kp, sigmoid_weights, again, keypoints, rscale, st);
+        if (rc != CP_OK) return rc;
+        CP_LAUNCH(ls_robust_solve_kernel, dim3((total + 255) / 256), dim3(256), 0, st, plain, again, total, h, keypoints);
+        if ((rc = cp::check_launch(fn)) != CP_OK) return rc;
+    }
+    return CP_OK;
+}
+

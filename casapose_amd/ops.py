@@ -171,6 +171,24 @@ def ls_vote_slots(rec: torch.Tensor, do: int, co: int, slots: int, kp: int, slot
     return (out, sums) if return_sums else out
 
 
+def ls_vote_slots_robust(rec: torch.Tensor, do: int, co: int, slots: int, kp: int, slot_map: torch.Tensor, cutoff: float = 4.0, passes: int = 2,
+                         sigmoid_weights: bool = False, return_sums: bool = False):
+    """cp_ls_vote_slots_robust_f32: ls_vote_slots followed by `passes` reweighted passes, every term weighted by Tukey's biweight (cut-off
+    `cutoff` pixels) of the distance of the current estimate from the pixel's line; include/casapose_hip.h states the rule.  Returns keypoints
+    [B,slots,kp,2] (y,x); with return_sums also the plain sums and the last pass's reweighted sums, fp64 [B,slots,kp,5] each (views of one
+    workspace; the second is not written with passes = 0)."""
+    _need_cuda(rec, slot_map)
+    b, h, w, ld = rec.shape
+    if tuple(slot_map.shape) != (b, h, w) or slot_map.dtype != torch.uint8 or not slot_map.is_contiguous():
+        raise ValueError("ls_vote_slots_robust: slot_map must be a contiguous uint8 [%d, %d, %d] tensor" % (b, h, w))
+    ws = torch.empty(2, b, max(slots, 0), kp, 5, dtype=torch.float64, device=rec.device)
+    out = torch.empty(b, max(slots, 0), kp, 2, dtype=torch.float32, device=rec.device)
+    check(_lib.load().cp_ls_vote_slots_robust_f32(rec.data_ptr(), ld, do, co, slot_map.data_ptr(), b, h, w, slots, kp, 1 if sigmoid_weights else 0,
+                                                  float(cutoff), int(passes), ws.data_ptr(), out.data_ptr(), _stream(rec)),
+          "cp_ls_vote_slots_robust_f32")
+    return (out, ws[0], ws[1]) if return_sums else out
+
+
 VOTE_SPLIT_DEFAULTS = dict(kp_index=0, cell=4, vote_stride=2, min_votes=12, rel_percent=25, nms_radius=2, gate=4.0, min_size=50)
 
 

@@ -8,7 +8,11 @@ triple.  Instance r (0-based) of object o (1-based) has the slot id (o-1)*R + r 
 
 Components cannot separate instances that touch.  With split="votes" (CASAPOSE_INSTANCE_SPLIT=votes) cp_vote_split_labels builds the slot map
 instead: the pixels vote for their own instance's centre (keypoint 0) and every pixel goes to the peak its direction points at; the voter and
-the PnP are the same."""
+the PnP are the same.
+
+The split gives a few pixels beside a contact to the neighbouring instance, and the least-squares voter counts them in full.  With
+voter="robust" (CASAPOSE_INSTANCE_VOTER=robust) cp_ls_vote_slots_robust_f32 votes instead: after the plain vote, `passes` further passes weight
+every term by Tukey's biweight (cut-off `cutoff` pixels) of the distance of the current estimate from the pixel's line."""
 from __future__ import annotations
 
 import os
@@ -27,6 +31,9 @@ MAX_INSTANCES = 16     # cp_ccl_instance_labels' bound on R
 MAX_SLOTS = 254        # slot ids are bytes
 ENV_SPLIT = "CASAPOSE_INSTANCE_SPLIT"
 SPLITS = ("components", "votes")
+ENV_VOTER = "CASAPOSE_INSTANCE_VOTER"
+VOTERS = ("ls", "robust")
+ROBUST_CUTOFF, ROBUST_PASSES = 4.0, 2     # the defaults of voter="robust": pixels, reweighted passes
 
 
 def max_instances_from_environment() -> Optional[int]:
@@ -57,6 +64,19 @@ def instance_split_from_environment() -> str:
     return "votes"
 
 
+def instance_voter_from_environment() -> str:
+    """CASAPOSE_INSTANCE_VOTER: unset or `ls` -> "ls" (cp_ls_vote_slots_f32, the existing voter); `robust` -> "robust"
+    (cp_ls_vote_slots_robust_f32), which needs CASAPOSE_MAX_INSTANCES; anything else is an error."""
+    raw = os.environ.get(ENV_VOTER)
+    if raw is None or raw.strip() == "ls":
+        return "ls"
+    if raw.strip() != "robust":
+        raise ValueError("%s must be unset, `ls` or `robust` (got %r)" % (ENV_VOTER, raw))
+    if max_instances_from_environment() is None:
+        raise ValueError("%s=robust needs %s set to an integer in 2..%d: without it one instance per object is voted" % (ENV_VOTER, ENV, MAX_INSTANCES))
+    return "robust"
+
+
 class InstanceLSVoting:
     """CoordLSVotingWeighted(filter_estimates=True) with up to `max_instances` instances per object: __call__([seg, dirs, conf]) returns the
     keypoints [b, oc, R, kp, 2] in (y, x).  After a call `last_counts` is int32 [b, oc, R] on the device (the pixels of each instance, in
@@ -65,10 +85,14 @@ class InstanceLSVoting:
     split="votes" builds the slot map with cp_vote_split_labels instead (touching instances are separated by their votes for the object's
     centre; cell, vote_stride, min_votes, rel_percent, nms_radius and gate are its parameters, min_component its min_size).  Then
     `last_instances` is its int32 table [b, oc, R, 4] = (pixels, votes, peak cy, peak cx), `last_counts` the table's first column (in the order of
-    the peaks' votes) and `last_peaks` the peaks' positions, float32 [b, oc, R, 2] in (y, x)."""
+    the peaks' votes) and `last_peaks` the peaks' positions, float32 [b, oc, R, 2] in (y, x).
+
+    voter="robust" votes with cp_ls_vote_slots_robust_f32 (`cutoff` in pixels, `passes` reweighted passes in 0..8) over the same slot map.  Then
+    `last_kept` is float32 [b, oc, R, kp] on the device: the share of the plain weight that the last pass kept, the trace of the reweighted
+    system over the trace of the plain one (0 for an empty slot; with passes = 0 nothing was reweighted and it is 1 wherever there are pixels).  voter="ls" is the plain voter, call for call."""
 
     def __init__(self, name, num_classes, num_points=9, max_instances=4, sigmoid_weights=False, min_component=50, split="components", cell=4,
-                 vote_stride=2, min_votes=12, rel_percent=25, nms_radius=2, gate=4.0):
+                 vote_stride=2, min_votes=12, rel_percent=25, nms_radius=2, gate=4.0, voter="ls", cutoff=ROBUST_CUTOFF, passes=ROBUST_PASSES):
         oc = int(num_classes) - 1
         if not 1 <= int(max_instances) <= MAX_INSTANCES or oc < 1 or oc * int(max_instances) > MAX_SLOTS:
             raise ValueError("InstanceLSVoting: max_instances must be in 1..%d and objects * max_instances at most %d (got %d objects, %d instances)"
@@ -88,6 +112,12 @@ class InstanceLSVoting:
         self.split_params = dict(cell=int(cell), vote_stride=int(vote_stride), min_votes=int(min_votes), rel_percent=int(rel_percent),
                                  nms_radius=int(nms_radius), gate=float(gate))
         self.last_peaks: Optional[torch.Tensor] = None       # split="votes": float32 [b, oc, R, 2]
+        if voter not in VOTERS:
+            raise ValueError("InstanceLSVoting: voter must be one of %s (got %r)" % (VOTERS, voter))
+        if not (float(cutoff) > 0.0 and float(cutoff) < float("inf")) or int(passes) != passes or not 0 <= int(passes) <= 8:
+            raise ValueError("InstanceLSVoting: cutoff must be finite and > 0 and passes an integer in 0..8 (got %r, %r)" % (cutoff, passes))
+        self.voter, self.cutoff, self.passes = voter, float(cutoff), int(passes)
+        self.last_kept: Optional[torch.Tensor] = None        # voter="robust": float32 [b, oc, R, kp]
 
     def slot_of(self, o: int, r: int) -> int:
         """the slot id of instance r (0-based) of object o (1-based)"""
@@ -115,7 +145,14 @@ class InstanceLSVoting:
             slot_map, inst, self.last_peaks = ops.vote_split_labels(lab0, rec, do, objects, R, min_size=self.min_component, **self.split_params)
         else:
             slot_map, inst = ops.ccl_instance_labels(lab0, objects, R, self.min_component)
-        out = ops.ls_vote_slots(rec, do, co, objects * R, self.num_points, slot_map, sigmoid_weights=self.sigmoid_weights)
+        if self.voter == "robust":
+            out, plain, again = ops.ls_vote_slots_robust(rec, do, co, objects * R, self.num_points, slot_map, cutoff=self.cutoff, passes=self.passes,
+                                                         sigmoid_weights=self.sigmoid_weights, return_sums=True)
+            again = again if self.passes else plain                                                # no pass: block 1 is not written
+            weight, kept = plain[..., 0] + plain[..., 2], again[..., 0] + again[..., 2]           # the two traces, on the device
+            self.last_kept = torch.where(weight > 0, kept / weight, torch.zeros_like(weight)).to(torch.float32).view(b, objects, R, self.num_points)
+        else:
+            out = ops.ls_vote_slots(rec, do, co, objects * R, self.num_points, slot_map, sigmoid_weights=self.sigmoid_weights)
         self.last_labels, self.last_instances, self.last_counts = slot_map, inst, inst[..., 0]
         return out.view(b, objects, R, self.num_points, 2)
 

@@ -1275,6 +1275,31 @@ int cp_vote_split_labels(const uint8_t* labels, const float* field, int ld, int 
 size_t cp_vote_split_workspace_bytes(int batch, int h, int w, int objects, int max_instances, int cell);
 int cp_vote_split_workspace_layout(int batch, int h, int w, int objects, int max_instances, int cell, size_t* offsets /*[3]*/);
 
+/* ---- the robust LS voter per slot: reweighted passes reject stray pixels (csrc/ls_vote.hip, csrc/ls_robust_math.h) ---------------------------
+ * A slot map hands a few pixels to the wrong slot (beside the contact of two touching instances, or where the segmentation is wrong); they
+ * carry another instance's directions and the least-squares voter counts them in full.  cp_ls_vote_slots_robust_f32 votes as
+ * cp_ls_vote_slots_f32 does (same arguments, same refusals, same kernels for pass 0) and then repeats the vote `passes` times with every
+ * (pixel, keypoint) term multiplied by rho, Tukey's biweight of the perpendicular distance of the CURRENT estimate from the pixel's line:
+ *     c = ((y + .5) / h, (x + .5) / h);  n = the pixel's unit direction;  p = the keypoint of the pass before / h (fp32);  e = p - c;
+ *     t = (e_y n_x - e_x n_y) * (h / cutoff_px);  u = t * t;  rho = u < 1 ? (1 - u)^2 : 0          (fp32, in this order)
+ * and the term is ls_add_terms' with w * rho in place of w.  A pixel whose direction is (0, 0) has no line: rho = 0 (the plain pass counts it
+ * as w I, as before).  There is no "behind the ray" rule.
+ *   workspace  cp_ls_vote_robust_workspace_bytes(n, slots, kp) bytes, 8-byte aligned, no initialisation needed: two blocks fp64
+ *              [n][slots][kp][5].  After the call block 0 holds the plain sums (cp_ls_vote_slots_f32's sums_ws), block 1 the reweighted sums
+ *              of the last pass (not written with passes = 0: that call launches exactly what cp_ls_vote_slots_f32 launches).
+ *   keypoints  fp32 [n][slots][kp][2] in (y,x) pixels, 8-byte aligned: the last pass's values; (0, 0) for a slot without pixels.
+ *   passes     0..8; 0 gives cp_ls_vote_slots_f32's keypoints (the same kernels on the same input).   cutoff_px  finite and > 0, in pixels.
+ * The solve of a reweighted pass, per (image, slot, keypoint): the new value is taken when the reweighted 2 x 2 system passes the plain solve's
+ * rank rule, its condition number is below 1e6, and its trace S00 + S11 is at least CP_LS_ROBUST_MIN_KEPT = 1/8 of the plain system's trace
+ * (ny^2 + nx^2 = 1, so the trace of a system is the weight it holds); otherwise the keypoint keeps the value of the pass before.  No state is
+ * kept: the next pass starts from the same estimate and decides the same.  trace(block 1) / trace(block 0) is the share of the plain weight
+ * the last pass kept.  Every (slots, ld) cp_ls_vote_slots_f32 accepts is accepted: the estimates of a lane's current slot live in registers.
+ * A slot value above `slots` is the caller's error as it is for cp_ls_vote_slots_f32.  Added in ABI 302 without changing any earlier entry
+ * point. */
+size_t cp_ls_vote_robust_workspace_bytes(int batch, int slots, int kp);
+int cp_ls_vote_slots_robust_f32(const float* field, int ld, int dir_off, int conf_off, const uint8_t* slot_map, int batch, int h, int w, int slots,
+                                int kp, int sigmoid_weights, float cutoff_px, int passes, void* workspace, float* keypoints, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

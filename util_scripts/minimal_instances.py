@@ -16,6 +16,12 @@ CASAPOSE_INSTANCE_SPLIT=votes (with CASAPOSE_MAX_INSTANCES set; refused by name 
 object's centre instead of by connected components (InstanceLSVoting(split="votes"), cp_vote_split_labels): the script then also says
 `instances: split by centre votes` once, and poses_est.csv has one more trailing column `votes` after `instance,pixels`, the votes of the
 instance's peak.  Unset or `components`: nothing changes.
+
+CASAPOSE_INSTANCE_VOTER=robust (with CASAPOSE_MAX_INSTANCES set; refused by name without it) votes with the robust voter per slot
+(InstanceLSVoting(voter="robust"), cp_ls_vote_slots_robust_f32: two reweighted passes at a cut-off of 4 px reject the pixels a split hands to
+the wrong instance): the script then also says `instances: robust voter (cutoff 4 px, 2 passes)` once, and poses_est.csv has one more trailing
+column `kept` after whatever columns are there, the share of the plain weight the last pass kept, averaged over the instance's keypoints.  Unset
+or `ls`: nothing changes.
 """
 import os
 import sys
@@ -31,7 +37,8 @@ sys.path.insert(0, os.path.join(ROOT, "util_scripts"))
 import test_minimal  # noqa: E402
 from casapose_amd.data_handler.image_only_dataset import ImageOnlyDataset  # noqa: E402
 from casapose_amd.data_handler.vectorfield_dataset import VectorfieldDataset  # noqa: E402
-from casapose_amd.pose_estimation.instance_voting import (ENV, InstanceLSVoting, instance_split_from_environment,  # noqa: E402
+from casapose_amd.pose_estimation.instance_voting import (ENV, ROBUST_CUTOFF, ROBUST_PASSES, InstanceLSVoting,  # noqa: E402
+                                                          instance_split_from_environment, instance_voter_from_environment,
                                                           max_instances_from_environment, poses_pnp_instances)
 from casapose_amd.pose_models.tfkeras import Classifiers  # noqa: E402
 from casapose_amd.utils.config_parser import parse_config  # noqa: E402
@@ -41,6 +48,7 @@ from casapose_amd.utils.io_utils import latest_checkpoint  # noqa: E402
 def main(argv=None):
     instances = max_instances_from_environment()
     by_votes = instance_split_from_environment() == "votes"
+    robust = instance_voter_from_environment() == "robust"
     if instances is None:
         return test_minimal.main(argv)
     for other in ("CASAPOSE_UNCERTAINTY_PNP", "CASAPOSE_MASK_REFINE"):
@@ -102,14 +110,16 @@ def main(argv=None):
     if opt.write_poses:
         with open(opt.evalf + "/poses_est.csv", "w") as f:
             f.write("name,object," + ",".join("r%d%d" % (i, j) for i in range(1, 4) for j in range(1, 4)) + ",t1,t2,t3,instance,pixels" +
-                    (",votes" if by_votes else "") + "\n")
+                    (",votes" if by_votes else "") + (",kept" if robust else "") + "\n")
 
     K, kp = 1 + no_objects, opt.no_points
     voter = InstanceLSVoting(name="coords_ls_voting", num_classes=K, num_points=kp, max_instances=instances,
-                             split="votes" if by_votes else "components")
+                             split="votes" if by_votes else "components", **(dict(voter="robust") if robust else {}))
     print("instances: up to {} per object".format(instances))
     if by_votes:
         print("instances: split by centre votes")
+    if robust:
+        print("instances: robust voter (cutoff {:g} px, {} passes)".format(ROBUST_CUTOFF, ROBUST_PASSES))
     rng = np.random.default_rng(opt.manualseed)
     speed, poses_by_name = [], {}
     for batch_idx in range(int(image_batches)):
@@ -121,6 +131,7 @@ def main(argv=None):
         coords = voter([seg, dirs, conf])
         pixels = voter.last_counts.cpu().numpy()
         votes = voter.last_instances[..., 1].cpu().numpy() if by_votes else None
+        kept = voter.last_kept.mean(dim=-1).cpu().numpy() if robust else None
         poses = poses_pnp_instances(coords, pixels, keypoints, camera_matrix, min_num=opt.min_object_size_test, rng=rng)
         seconds = time.perf_counter() - start
         speed.append(seconds)
@@ -136,7 +147,8 @@ def main(argv=None):
                         P = poses_by_name[name][o, r]
                         f.write("{},{},".format(name, obj) + ",".join("{:.9g}".format(v) for v in np.concatenate([P[:, :3].reshape(-1), P[:, 3]])) +
                                 ",{},{}".format(r, int(pixels[0, o, r]) if found else 0) +
-                                (",{}".format(int(votes[0, o, r]) if found else 0) if by_votes else "") + "\n")
+                                (",{}".format(int(votes[0, o, r]) if found else 0) if by_votes else "") +
+                                (",{:.6g}".format(float(kept[0, o, r]) if found else 0.0) if robust else "") + "\n")
     print("average speed: {}".format(float(np.mean(speed[10:])) if len(speed) > 10 else float("nan")))
     return {"speed": speed, "poses": poses_by_name}
 
