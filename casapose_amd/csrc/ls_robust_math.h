@@ -48,8 +48,9 @@ LSR_HD float rho(float py, float px, float cy, float cx, float ny, float nx, flo
 //   - trace(s) >= CP_LS_ROBUST_MIN_KEPT * plain_trace;
 // otherwise false is returned and p is not written: the keypoint keeps the value of the pass before.  The rule keeps no state, so the next
 // pass starts from the same estimate, sums the same terms and decides the same.
-LSR_HD bool solve(const double* s, double plain_trace, double& p0, double& p1) {
-    const double a = s[0], b = s[1], c = s[2], t0 = s[3], t1 = s[4];
+//
+// well_posed is the first two conditions on the matrix [[a, b], [b, c]] alone; the covariance of ls_cov_math.h asks it of its normal matrix.
+LSR_HD bool well_posed(double a, double b, double c) {
     const double half_tr = 0.5 * (a + c), half_df = 0.5 * (a - c);
     const double rad = sqrt(half_df * half_df + b * b);
     const double l1 = half_tr + rad, l2 = half_tr - rad;   // l1 >= l2 (PSD up to rounding)
@@ -57,7 +58,12 @@ LSR_HD bool solve(const double* s, double plain_trace, double& p0, double& p1) {
     const double smax = fmax(fabs(l1), fabs(l2));
     if (!(smax > 0.0)) return false;                                       // empty (or NaN)
     if (!(fabs(l2) > rcond * smax && fabs(l1) > rcond * smax)) return false;   // rank one
-    if (!(l2 > 0.0 && l1 < CP_LS_ROBUST_MAX_COND * l2)) return false;
+    return l2 > 0.0 && l1 < CP_LS_ROBUST_MAX_COND * l2;
+}
+
+LSR_HD bool solve(const double* s, double plain_trace, double& p0, double& p1) {
+    const double a = s[0], b = s[1], c = s[2], t0 = s[3], t1 = s[4];
+    if (!well_posed(a, b, c)) return false;
     if (!(a + c >= CP_LS_ROBUST_MIN_KEPT * plain_trace)) return false;
     const double det = a * c - b * b;
     p0 = (c * t0 - b * t1) / det;

@@ -16,6 +16,7 @@
 // only flushes (LDS fp64 atomics) when its label changes or the strip ends; the block then
 // adds its LDS table to the global fp64 sums with one atomic per entry.
 #include "common.h"
+#include "ls_cov_math.h"
 #include "ls_robust_math.h"
 #include <cmath>
 #include <cstdlib>
@@ -116,20 +117,23 @@ __device__ __forceinline__ void ls_add_terms(double (&a)[5], float ny, float nx,
 }
 
 // A reweighted pass of the robust voter (cp_ls_vote_slots_robust_f32; ls_robust_math.h has the weight and why it is what it is) walks the pixels
-// as the plain pass does and hands ls_add_terms w * rho in place of w.  ROBUST is a template parameter of the two kernels that walk a slot map:
-// the plain instantiation carries none of what follows.
+// as the plain pass does and hands ls_add_terms w * rho in place of w.  The moments pass of cp_ls_slot_covariance_f32 (ls_cov_math.h) makes the
+// same walk against estimates handed in and sums (A00, A01, A11, Q, Wall) in place of (S00, S01, S11, T0, T1).  The mode is a template parameter
+// of the two kernels that walk a slot map: the plain instantiation carries none of what follows, the reweighted one none of the moments' work.
+enum LsMode { LS_PLAIN = 0, LS_REWEIGHTED = 1, LS_MOMENTS = 2 };
 //
 // The estimates of the keypoints of a lane's current slot, in the voter's normalised coordinates (pixels / H): 18 registers, reloaded from the
 // keypoints of the pass before when the lane's label changes -- as rarely as its accumulators are flushed.  A table of estimates in LDS would
 // not fit beside 254 slots' sums and the staging buffer of ld = 64.
-template <bool ROBUST, int KP>
+template <int MODE, int KP>
 struct LsEst {
-    float p[ROBUST ? KP : 1][2];
+    static constexpr bool USED = MODE != LS_PLAIN;
+    float p[USED ? KP : 1][2];
     // est_img: fp32 [slots][KP][2] in (y, x) pixels, the image's rows of the keypoints buffer
     __device__ __forceinline__ void load(const float* __restrict__ est_img, int lab, int H) {
         const float2* e = reinterpret_cast<const float2*>(est_img + (size_t)(lab - 1) * KP * 2);
 #pragma unroll
-        for (int j = 0; j < (ROBUST ? KP : 0); ++j) {
+        for (int j = 0; j < (USED ? KP : 0); ++j) {
             const float2 v = e[j];
             p[j][0] = v.x / (float)H;
             p[j][1] = v.y / (float)H;
@@ -137,10 +141,19 @@ struct LsEst {
     }
 };
 
-// one keypoint of one labelled pixel, plain or reweighted
-template <bool ROBUST>
+// one keypoint of one labelled pixel: plain, reweighted, or the moments (rscale = 0 there: no cut-off)
+template <int MODE>
 __device__ __forceinline__ void ls_add_pixel(double (&a)[5], float2 n, float w, float cy, float cx, const float (&p)[2], float rscale) {
-    if (ROBUST) w *= cp_lsr::rho(p[0], p[1], cy, cx, n.x, n.y, rscale);
+    if (MODE == LS_MOMENTS) {
+        const cp_lsc::Moment m = cp_lsc::moment(p[0], p[1], cy, cx, n.x, n.y, w, rscale);
+        a[0] += (double)((1.0f - n.x * n.x) * m.omega);   // as ls_add_terms forms them, omega in place of w
+        a[1] += (double)((0.0f - n.x * n.y) * m.omega);
+        a[2] += (double)((1.0f - n.y * n.y) * m.omega);
+        a[3] += (double)m.q;
+        a[4] += (double)m.wall;
+        return;
+    }
+    if (MODE == LS_REWEIGHTED) w *= cp_lsr::rho(p[0], p[1], cy, cx, n.x, n.y, rscale);
     ls_add_terms(a, n.x, n.y, w, cy, cx);
 }
 
@@ -162,8 +175,9 @@ __device__ __forceinline__ float2 ls_normal_fast(float dy, float dx) {
     return make_float2(dy * inv, dx * inv);
 }
 
-// ROBUST (given labels only): est is the keypoints buffer of the pass before, fp32 [B][objects][KP][2], rscale = H / cutoff
-template <int KP, bool ROBUST = false>
+// MODE other than LS_PLAIN (given labels only): est is the keypoints buffer of the pass before (the moments: the keypoints handed in), fp32
+// [B][objects][KP][2], rscale = H / cutoff
+template <int KP, int MODE = LS_PLAIN>
 __global__ __launch_bounds__(256) void ls_accumulate_kernel(const float* __restrict__ field, int ld, int seg_off,
                                                             int dir_off, int conf_off, const uint8_t* __restrict__ labels,
                                                             int B, int H, int W, int objects, double* __restrict__ sums,
@@ -186,7 +200,7 @@ __global__ __launch_bounds__(256) void ls_accumulate_kernel(const float* __restr
         const float cx = s.cx(H);
         const int classes = objects + 1;
         LsAcc<KP> acc(acc_lds);
-        LsEst<ROBUST, KP> pe;
+        LsEst<MODE, KP> pe;
 
         const int y_end = min(y0 + ROWS, H);
         // with given labels a row segment without a non-zero label contributes nothing: its records are not read.  The strip's labels are
@@ -214,7 +228,7 @@ __global__ __launch_bounds__(256) void ls_accumulate_kernel(const float* __restr
             if (rd && lane < ncols) {
                 if (labels) {
                     lab = labels[((size_t)img * H + y) * W + x];
-                    if (ROBUST && lab > objects) lab = 0;   // no row of estimates to read
+                    if (MODE != LS_PLAIN && lab > objects) lab = 0;   // no row of estimates to read
                 } else {
                     float best = px[seg_off];
                     for (int k = 1; k < classes; ++k) {
@@ -226,14 +240,14 @@ __global__ __launch_bounds__(256) void ls_accumulate_kernel(const float* __restr
             const bool moved = lab != acc.cur;
             acc.enter(lab);
             if (lab > 0) {
-                if (ROBUST && moved) pe.load(est + (size_t)img * objects * KP * 2, lab, H);
+                if (MODE != LS_PLAIN && moved) pe.load(est + (size_t)img * objects * KP * 2, lab, H);
                 const float cy = ((float)y + 0.5f) / (float)H;
 #pragma unroll
                 for (int j = 0; j < KP; ++j) {
                     const float dy = px[dir_off + 2 * j], dx = px[dir_off + 2 * j + 1];
                     const float w = ls_weight_exact(px[conf_off + j], sigmoid);
                     const float2 n = ls_normal_exact(dy, dx);
-                    ls_add_pixel<ROBUST>(acc.a[j], n, w, cy, cx, pe.p[ROBUST ? j : 0], rscale);
+                    ls_add_pixel<MODE>(acc.a[j], n, w, cy, cx, pe.p[MODE != LS_PLAIN ? j : 0], rscale);
                 }
             }
             __builtin_amdgcn_wave_barrier();  // all lanes done reading before the next row overwrites
@@ -774,8 +788,9 @@ namespace {
 // one row segment prefetched ahead, nine 16-byte LDS reads per pixel) over the production record, the LDS table [slots][9][5] in front of the
 // staging buffer.  A table of 254 slots is 91 KB, so what a block pays per table entry is kept away from the blocks that have nothing to add:
 // the labels are read BEFORE the table is zeroed, and a block whose four strips hold no label ends there (no zeroing, no commit scan).
-// ROBUST: a reweighted pass; est is the keypoints buffer of the pass before, fp32 [B][slots][9][2], rscale = H / cutoff.
-template <bool ROBUST>
+// LS_REWEIGHTED: a reweighted pass; est is the keypoints buffer of the pass before, fp32 [B][slots][9][2], rscale = H / cutoff.
+// LS_MOMENTS: the covariance's pass against the keypoints handed in; rscale = 0 without a cut-off.
+template <int MODE>
 __global__ __launch_bounds__(256) void ls_accumulate36_slots_kernel(const float* __restrict__ field, const uint8_t* __restrict__ labels, int B, int H,
                                                                     int W, int slots, double* __restrict__ sums, int strips_x, int strips_y,
                                                                     const float* __restrict__ est, float rscale) {
@@ -831,7 +846,7 @@ __global__ __launch_bounds__(256) void ls_accumulate36_slots_kernel(const float*
     if (rowmask) {   // wave-uniform
         const int img = s.img, x0 = s.x0, y0 = s.y0;
         LsAcc<KP> acc(acc_lds);
-        LsEst<ROBUST, KP> pe;
+        LsEst<MODE, KP> pe;
         float4 pre[NV];
         auto issue = [&](int ry) {
             const float4* g = reinterpret_cast<const float4*>(field + (((size_t)img * H + y0 + ry) * W + x0) * LD);
@@ -877,13 +892,13 @@ __global__ __launch_bounds__(256) void ls_accumulate36_slots_kernel(const float*
             const bool moved = lab != acc.cur;
             acc.enter(lab);
             if (lab > 0) {
-                if (ROBUST && moved) pe.load(est + (size_t)img * slots * KP * 2, lab, H);
+                if (MODE != LS_PLAIN && moved) pe.load(est + (size_t)img * slots * KP * 2, lab, H);
                 const float cy = ((float)(y0 + ry) + 0.5f) / (float)H;
 #pragma unroll
                 for (int j = 0; j < KP; ++j) {
                     const float w = softplus_fast(r[27 + j]);  // softplus (:35)
                     const float2 n = ls_normal_fast(r[9 + 2 * j], r[9 + 2 * j + 1]);
-                    ls_add_pixel<ROBUST>(acc.a[j], n, w, cy, cx, pe.p[ROBUST ? j : 0], rscale);
+                    ls_add_pixel<MODE>(acc.a[j], n, w, cy, cx, pe.p[MODE != LS_PLAIN ? j : 0], rscale);
                 }
             }
             __builtin_amdgcn_wave_barrier();  // all lanes done reading before the next row overwrites
@@ -907,6 +922,15 @@ __global__ void ls_robust_solve_kernel(const double* __restrict__ plain, const d
     }
 }
 
+// the finish of the moments pass, one thread per (image, slot, keypoint): cp_lsc::finish of the five sums; the keypoints are only read
+__global__ void ls_cov_finish_kernel(const double* __restrict__ sums, const float* __restrict__ keypoints, int total, int H, float* __restrict__ cov,
+                                     float* __restrict__ stat) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= total) return;
+    const float py = keypoints[2 * i], px = keypoints[2 * i + 1];
+    cp_lsc::finish(sums + (size_t)i * 5, isfinite(py) && isfinite(px), H, cov + (size_t)i * 3, stat + (size_t)i * 2);
+}
+
 constexpr int LS_MAX_LDS = 160 * 1024;   // per workgroup on gfx950
 
 // what cp_ls_vote_slots_f32 refuses, under the name `fn` of the entry point that was called
@@ -928,10 +952,10 @@ int ls_raise_lds(const char* fn, Kernel kernel, size_t lds) {
     return CP_OK;
 }
 
-// zeroes `sums` and accumulates one pass over the slot map into it: the plain pass with est == nullptr, otherwise a reweighted pass against the
-// estimates `est` (the keypoints buffer).  The production record has a kernel of its own, every other layout takes the generic kernel's walk.
+// zeroes `sums` and accumulates one pass over the slot map into it: the plain pass with est == nullptr, otherwise a reweighted pass (or, with
+// moments, the covariance's pass) against the estimates `est` (the keypoints buffer).  The production record has a kernel of its own, every other layout takes the generic kernel's walk.
 int ls_slots_accumulate(const char* fn, const float* field, int ld, int dir_off, int conf_off, const uint8_t* slot_map, int batch, int h, int w,
-                        int slots, int kp, int sigmoid_weights, double* sums, const float* est, float rscale, hipStream_t st) {
+                        int slots, int kp, int sigmoid_weights, double* sums, const float* est, float rscale, hipStream_t st, bool moments = false) {
     if (hipMemsetAsync(sums, 0, cp_ls_vote_workspace_bytes(batch, slots, kp), st) != hipSuccess) return cp::check_launch(fn);
     const int strips_x = (w + 63) / 64, strips_y = (h + ROWS - 1) / ROWS;
     const int blocks_per_img = (strips_x * strips_y + WAVES - 1) / WAVES;
@@ -941,21 +965,28 @@ int ls_slots_accumulate(const char* fn, const float* field, int ld, int dir_off,
     const dim3 grid(batch * blocks_per_img), block(256);
     const int sig = sigmoid_weights ? 1 : 0;
     if (!sigmoid_weights && is_record36(ld, dir_off, conf_off)) {
-        if (est) {
-            if (ls_raise_lds(fn, &ls_accumulate36_slots_kernel<true>, lds) != CP_OK) return CP_ERR_INVALID;
-            CP_LAUNCH(ls_accumulate36_slots_kernel<true>, grid, block, lds, st, field, slot_map, batch, h, w, slots, sums, strips_x, strips_y, est, rscale);
+        if (est && moments) {
+            if (ls_raise_lds(fn, &ls_accumulate36_slots_kernel<LS_MOMENTS>, lds) != CP_OK) return CP_ERR_INVALID;
+            CP_LAUNCH(ls_accumulate36_slots_kernel<LS_MOMENTS>, grid, block, lds, st, field, slot_map, batch, h, w, slots, sums, strips_x, strips_y, est, rscale);
+        } else if (est) {
+            if (ls_raise_lds(fn, &ls_accumulate36_slots_kernel<LS_REWEIGHTED>, lds) != CP_OK) return CP_ERR_INVALID;
+            CP_LAUNCH(ls_accumulate36_slots_kernel<LS_REWEIGHTED>, grid, block, lds, st, field, slot_map, batch, h, w, slots, sums, strips_x, strips_y, est, rscale);
         } else {
-            if (ls_raise_lds(fn, &ls_accumulate36_slots_kernel<false>, lds) != CP_OK) return CP_ERR_INVALID;
-            CP_LAUNCH(ls_accumulate36_slots_kernel<false>, grid, block, lds, st, field, slot_map, batch, h, w, slots, sums, strips_x, strips_y, est, rscale);
+            if (ls_raise_lds(fn, &ls_accumulate36_slots_kernel<LS_PLAIN>, lds) != CP_OK) return CP_ERR_INVALID;
+            CP_LAUNCH(ls_accumulate36_slots_kernel<LS_PLAIN>, grid, block, lds, st, field, slot_map, batch, h, w, slots, sums, strips_x, strips_y, est, rscale);
         }
+    } else if (est && moments) {
+        if (ls_raise_lds(fn, &ls_accumulate_kernel<MAXKP, LS_MOMENTS>, lds) != CP_OK) return CP_ERR_INVALID;
+        CP_LAUNCH((ls_accumulate_kernel<MAXKP, LS_MOMENTS>), grid, block, lds, st, field, ld, 0, dir_off, conf_off, slot_map, batch, h, w, slots, sums, strips_x,
+                  strips_y, sig, est, rscale);
     } else if (est) {
-        if (ls_raise_lds(fn, &ls_accumulate_kernel<MAXKP, true>, lds) != CP_OK) return CP_ERR_INVALID;
-        CP_LAUNCH((ls_accumulate_kernel<MAXKP, true>), grid, block, lds, st, field, ld, 0, dir_off, conf_off, slot_map, batch, h, w, slots, sums, strips_x,
+        if (ls_raise_lds(fn, &ls_accumulate_kernel<MAXKP, LS_REWEIGHTED>, lds) != CP_OK) return CP_ERR_INVALID;
+        CP_LAUNCH((ls_accumulate_kernel<MAXKP, LS_REWEIGHTED>), grid, block, lds, st, field, ld, 0, dir_off, conf_off, slot_map, batch, h, w, slots, sums, strips_x,
                   strips_y, sig, est, rscale);
     } else {
-        if (ls_raise_lds(fn, &ls_accumulate_kernel<MAXKP, false>, lds) != CP_OK) return CP_ERR_INVALID;
+        if (ls_raise_lds(fn, &ls_accumulate_kernel<MAXKP, LS_PLAIN>, lds) != CP_OK) return CP_ERR_INVALID;
         // the generic kernel with given labels: its table has `objects` rows, and the logits (seg_off) are read only without labels
-        CP_LAUNCH((ls_accumulate_kernel<MAXKP, false>), grid, block, lds, st, field, ld, 0, dir_off, conf_off, slot_map, batch, h, w, slots, sums, strips_x,
+        CP_LAUNCH((ls_accumulate_kernel<MAXKP, LS_PLAIN>), grid, block, lds, st, field, ld, 0, dir_off, conf_off, slot_map, batch, h, w, slots, sums, strips_x,
                   strips_y, sig, est, rscale);
     }
     return cp::check_launch(fn);
@@ -1005,3 +1036,21 @@ extern "C" int cp_ls_vote_slots_robust_f32(const float* field, int ld, int dir_o
     return CP_OK;
 }
 
+// A covariance per (image, slot, keypoint) for keypoints handed in: one moments pass over the slot map (the reweighted pass's stream) and a
+// finish per keypoint; ls_cov_math.h has the definition, include/casapose_hip.h the rule.
+extern "C" int cp_ls_slot_covariance_f32(const float* field, int ld, int dir_off, int conf_off, const uint8_t* slot_map, int batch, int h, int w,
+                                         int slots, int kp, int sigmoid_weights, float cutoff_px, const float* keypoints, double* sums_ws, float* cov,
+                                         float* stat, void* stream) {
+    const char* fn = "cp_ls_slot_covariance_f32";
+    if (ls_slots_check(fn, field, ld, dir_off, conf_off, slot_map, batch, h, w, slots, kp, sums_ws, keypoints) != CP_OK) return CP_ERR_INVALID;
+    CP_REQUIRE(cov && stat, "%s: null pointer (cov and stat are required)", fn);
+    CP_REQUIRE(std::isfinite(cutoff_px) && cutoff_px >= 0.f, "%s: cutoff_px must be finite and >= 0, 0 for no reweighting (got %g)", fn, (double)cutoff_px);
+    CP_REQUIRE((((uintptr_t)sums_ws | (uintptr_t)keypoints) & 7) == 0, "%s: the workspace and the keypoints must be 8-byte aligned", fn);
+    hipStream_t st = (hipStream_t)stream;
+    const float rscale = cutoff_px > 0.f ? cp_lsr::rho_scale(h, cutoff_px) : 0.f;
+    const int rc = ls_slots_accumulate(fn, field, ld, dir_off, conf_off, slot_map, batch, h, w, slots, kp, sigmoid_weights, sums_ws, keypoints, rscale, st, true);
+    if (rc != CP_OK) return rc;
+    const int total = batch * slots * kp;
+    CP_LAUNCH(ls_cov_finish_kernel, dim3((total + 255) / 256), dim3(256), 0, st, sums_ws, keypoints, total, h, cov, stat);
+    return cp::check_launch(fn);
+}

@@ -189,6 +189,28 @@ def ls_vote_slots_robust(rec: torch.Tensor, do: int, co: int, slots: int, kp: in
     return (out, ws[0], ws[1]) if return_sums else out
 
 
+def ls_slot_covariance(rec: torch.Tensor, do: int, co: int, slots: int, kp: int, slot_map: torch.Tensor, keypoints: torch.Tensor, cutoff=None,
+                       sigmoid_weights: bool = False, return_sums: bool = False):
+    """cp_ls_slot_covariance_f32: a covariance per (image, slot, keypoint) of `keypoints` (fp32 [B,slots,kp,2] in (y,x), either slot voter's
+    result; only read) from one more pass over the slot map; include/casapose_hip.h states the rule.  cutoff: pixels of Tukey's biweight, None
+    (or 0) for no reweighting.  Returns (cov fp32 [B,slots,kp,3] = (sxx, sxy, syy) in (x,y) pixels, three NaNs where there is none,
+    stat fp32 [B,slots,kp,2] = (sigma2, kept)); with return_sums also the five sums (A00, A01, A11, Q, Wall), fp64 [B,slots,kp,5]."""
+    _need_cuda(rec, slot_map, keypoints)
+    b, h, w, ld = rec.shape
+    if tuple(slot_map.shape) != (b, h, w) or slot_map.dtype != torch.uint8 or not slot_map.is_contiguous():
+        raise ValueError("ls_slot_covariance: slot_map must be a contiguous uint8 [%d, %d, %d] tensor" % (b, h, w))
+    n = max(slots, 0)
+    if keypoints.dtype != torch.float32 or keypoints.numel() != b * n * kp * 2 or not keypoints.is_contiguous():
+        raise ValueError("ls_slot_covariance: keypoints must be a contiguous float32 tensor of [%d, %d, %d, 2] values" % (b, n, kp))
+    sums = torch.empty(b, n, kp, 5, dtype=torch.float64, device=rec.device)
+    cov = torch.empty(b, n, kp, 3, dtype=torch.float32, device=rec.device)
+    stat = torch.empty(b, n, kp, 2, dtype=torch.float32, device=rec.device)
+    check(_lib.load().cp_ls_slot_covariance_f32(rec.data_ptr(), ld, do, co, slot_map.data_ptr(), b, h, w, slots, kp, 1 if sigmoid_weights else 0,
+                                                0.0 if cutoff is None else float(cutoff), keypoints.data_ptr(), sums.data_ptr(), cov.data_ptr(),
+                                                stat.data_ptr(), _stream(rec)), "cp_ls_slot_covariance_f32")
+    return (cov, stat, sums) if return_sums else (cov, stat)
+
+
 VOTE_SPLIT_DEFAULTS = dict(kp_index=0, cell=4, vote_stride=2, min_votes=12, rel_percent=25, nms_radius=2, gate=4.0, min_size=50)
 
 

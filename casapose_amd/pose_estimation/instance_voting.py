@@ -12,7 +12,11 @@ the PnP are the same.
 
 The split gives a few pixels beside a contact to the neighbouring instance, and the least-squares voter counts them in full.  With
 voter="robust" (CASAPOSE_INSTANCE_VOTER=robust) cp_ls_vote_slots_robust_f32 votes instead: after the plain vote, `passes` further passes weight
-every term by Tukey's biweight (cut-off `cutoff` pixels) of the distance of the current estimate from the pixel's line."""
+every term by Tukey's biweight (cut-off `cutoff` pixels) of the distance of the current estimate from the pixel's line.
+
+Neither voter says how far a keypoint can be trusted, and an instance beside another one is occluded or truncated: some of its keypoints lie
+far outside its pixels.  With covariance=True (CASAPOSE_INSTANCE_PNP=weighted) cp_ls_slot_covariance_f32 makes one more pass over the slot map
+for the voter's own keypoints and gives a 2 x 2 covariance per (slot, keypoint); poses_pnp_instances(cov=) weights the PnP by it."""
 from __future__ import annotations
 
 import os
@@ -34,6 +38,7 @@ SPLITS = ("components", "votes")
 ENV_VOTER = "CASAPOSE_INSTANCE_VOTER"
 VOTERS = ("ls", "robust")
 ROBUST_CUTOFF, ROBUST_PASSES = 4.0, 2     # the defaults of voter="robust": pixels, reweighted passes
+ENV_PNP = "CASAPOSE_INSTANCE_PNP"
 
 
 def max_instances_from_environment() -> Optional[int]:
@@ -77,6 +82,20 @@ def instance_voter_from_environment() -> str:
     return "robust"
 
 
+def instance_pnp_from_environment() -> str:
+    """CASAPOSE_INSTANCE_PNP: unset or `plain` -> "plain" (the keypoints of a slot count alike, the existing path); `weighted` -> "weighted"
+    (a covariance per slot and keypoint from cp_ls_slot_covariance_f32 weights the PnP), which needs CASAPOSE_MAX_INSTANCES; anything else is
+    an error."""
+    raw = os.environ.get(ENV_PNP)
+    if raw is None or raw.strip() == "plain":
+        return "plain"
+    if raw.strip() != "weighted":
+        raise ValueError("%s must be unset, `plain` or `weighted` (got %r)" % (ENV_PNP, raw))
+    if max_instances_from_environment() is None:
+        raise ValueError("%s=weighted needs %s set to an integer in 2..%d: without it one instance per object is voted" % (ENV_PNP, ENV, MAX_INSTANCES))
+    return "weighted"
+
+
 class InstanceLSVoting:
     """CoordLSVotingWeighted(filter_estimates=True) with up to `max_instances` instances per object: __call__([seg, dirs, conf]) returns the
     keypoints [b, oc, R, kp, 2] in (y, x).  After a call `last_counts` is int32 [b, oc, R] on the device (the pixels of each instance, in
@@ -89,10 +108,15 @@ class InstanceLSVoting:
 
     voter="robust" votes with cp_ls_vote_slots_robust_f32 (`cutoff` in pixels, `passes` reweighted passes in 0..8) over the same slot map.  Then
     `last_kept` is float32 [b, oc, R, kp] on the device: the share of the plain weight that the last pass kept, the trace of the reweighted
-    system over the trace of the plain one (0 for an empty slot; with passes = 0 nothing was reweighted and it is 1 wherever there are pixels).  voter="ls" is the plain voter, call for call."""
+    system over the trace of the plain one (0 for an empty slot; with passes = 0 nothing was reweighted and it is 1 wherever there are pixels).  voter="ls" is the plain voter, call for call.
+
+    covariance=True adds one call of cp_ls_slot_covariance_f32 after the vote, for the voter's own keypoints (cut-off: the voter's when
+    voter="robust" and passes > 0, otherwise none).  Then `last_cov` is float32 [b, oc, R, kp, 3] = (sxx, sxy, syy) in (x, y) pixels on the
+    device, three NaNs where a keypoint has no covariance (an empty slot among them), and `last_cov_stat` float32 [b, oc, R, kp, 2] =
+    (sigma2 in px^2, the share of the weight kept).  covariance=False makes the calls the voter made before, with the arguments they had."""
 
     def __init__(self, name, num_classes, num_points=9, max_instances=4, sigmoid_weights=False, min_component=50, split="components", cell=4,
-                 vote_stride=2, min_votes=12, rel_percent=25, nms_radius=2, gate=4.0, voter="ls", cutoff=ROBUST_CUTOFF, passes=ROBUST_PASSES):
+                 vote_stride=2, min_votes=12, rel_percent=25, nms_radius=2, gate=4.0, voter="ls", cutoff=ROBUST_CUTOFF, passes=ROBUST_PASSES, covariance=False):
         oc = int(num_classes) - 1
         if not 1 <= int(max_instances) <= MAX_INSTANCES or oc < 1 or oc * int(max_instances) > MAX_SLOTS:
             raise ValueError("InstanceLSVoting: max_instances must be in 1..%d and objects * max_instances at most %d (got %d objects, %d instances)"
@@ -118,6 +142,9 @@ class InstanceLSVoting:
             raise ValueError("InstanceLSVoting: cutoff must be finite and > 0 and passes an integer in 0..8 (got %r, %r)" % (cutoff, passes))
         self.voter, self.cutoff, self.passes = voter, float(cutoff), int(passes)
         self.last_kept: Optional[torch.Tensor] = None        # voter="robust": float32 [b, oc, R, kp]
+        self.covariance = bool(covariance)
+        self.last_cov: Optional[torch.Tensor] = None         # covariance=True: float32 [b, oc, R, kp, 3]
+        self.last_cov_stat: Optional[torch.Tensor] = None    # covariance=True: float32 [b, oc, R, kp, 2]
 
     def slot_of(self, o: int, r: int) -> int:
         """the slot id of instance r (0-based) of object o (1-based)"""
@@ -153,16 +180,24 @@ class InstanceLSVoting:
             self.last_kept = torch.where(weight > 0, kept / weight, torch.zeros_like(weight)).to(torch.float32).view(b, objects, R, self.num_points)
         else:
             out = ops.ls_vote_slots(rec, do, co, objects * R, self.num_points, slot_map, sigmoid_weights=self.sigmoid_weights)
+        if self.covariance:
+            cutoff = self.cutoff if self.voter == "robust" and self.passes > 0 else None
+            cov, stat = ops.ls_slot_covariance(rec, do, co, objects * R, self.num_points, slot_map, out, cutoff=cutoff, sigmoid_weights=self.sigmoid_weights)
+            self.last_cov, self.last_cov_stat = cov.view(b, objects, R, self.num_points, 3), stat.view(b, objects, R, self.num_points, 2)
         self.last_labels, self.last_instances, self.last_counts = slot_map, inst, inst[..., 0]
         return out.view(b, objects, R, self.num_points, 2)
 
 
-def poses_pnp_instances(coords, counts, object_points_3d, camera_data, min_num: int = 20, rng=None, solver=None) -> np.ndarray:
+def poses_pnp_instances(coords, counts, object_points_3d, camera_data, min_num: int = 20, rng=None, solver=None, cov=None, return_weighted: bool = False):
     """Voted keypoints [b, oc, R, kp, 2] in (y, x) and pixel counts [b, oc, R] (InstanceLSVoting's result and last_counts) -> poses float32
     [b, oc, R, 3, 4].  A slot with count <= min_num gets the zero pose; a pose with t_z < 0 is negated (pose_evaluation._poses_pnp's rules).
     object_points_3d: the objects' 3-D keypoints, [b, oc, (1,) kp, 3] or [oc, kp, 3].  solver: a DevicePnP solves all (image, object, instance)
     triples in one call, as oc * R pseudo-objects that share their object's 3-D keypoints; None asks device_pnp.solver_from_environment
-    (CASAPOSE_DEVICE_PNP=1, keypoints on a GPU), and without one the host loop over pnp.pnp_rvec_t runs."""
+    (CASAPOSE_DEVICE_PNP=1, keypoints on a GPU), and without one the host loop over pnp.pnp_rvec_t runs.
+    cov: keypoint covariances [b, oc, R, kp, 3] = (sxx, sxy, syy) in (x, y) pixels (InstanceLSVoting(covariance=True).last_cov) weight the final
+    LM of whichever PnP runs, with the floor and the fall-back poses_pnp applies: 1/12 px^2 is added to sxx and syy, and a slot with a
+    covariance that is not finite and positive definite is solved unweighted.  A device tensor goes to the solver where it lies.  With
+    return_weighted the result is (poses, weighted), weighted an int array [b, oc, R]: 1 where the solve was weighted (all 0 without cov)."""
     if solver is None and hasattr(coords, "detach") and coords.is_cuda:
         from .device_pnp import solver_from_environment
 
@@ -182,22 +217,34 @@ def poses_pnp_instances(coords, counts, object_points_3d, camera_data, min_num: 
     cam = _np(camera_data)
     cam = cam[0] if cam.ndim == 3 else cam
     mask = cnt > int(min_num)
+    if cov is not None and (tuple(cov.shape) != (b, oc, R, kp, 3)):
+        raise ValueError("poses_pnp_instances: cov must be [%d, %d, %d, %d, 3] (got %s)" % (b, oc, R, kp, tuple(cov.shape)))
     if solver is not None:
         xy = np.ascontiguousarray(pts.reshape(b, oc * R, kp, 2))
         x3 = np.ascontiguousarray(np.repeat(kp3, R, axis=1))                     # pseudo-object o * R + r has object o's keypoints
         m = np.ascontiguousarray(mask.reshape(b, oc * R).astype(np.int32))
-        poses = _solved_poses(solver, xy, x3, cam, m, None)
+        if cov is not None:
+            cov = cov.reshape(b, oc * R, kp, 3).contiguous() if hasattr(cov, "detach") else np.ascontiguousarray(_np(cov).reshape(b, oc * R, kp, 3))
+        poses = _solved_poses(solver, xy, x3, cam, m, None, cov)
         bad = np.argwhere((m != 0) & np.isin(np.asarray(solver.last_info)[..., 0], (2, 4)))   # a degenerate keypoint set (3) is the zero pose
         if len(bad):
             raise FloatingPointError("poses_pnp_instances: non-finite pose for image %d object %d instance %d"
                                      % (bad[0][0], bad[0][1] // R, bad[0][1] % R))
-        return poses.reshape(b, oc, R, 3, 4)
+        poses = poses.reshape(b, oc, R, 3, 4)
+        if not return_weighted:
+            return poses
+        weighted = np.zeros((b, oc, R), np.int32) if cov is None else np.asarray(solver.last_weighted).reshape(b, oc, R).astype(np.int32)
+        return poses, weighted
     out = np.zeros((b, oc, R, 3, 4), np.float32)
+    weighted = np.zeros((b, oc, R), np.int32)
+    cov = None if cov is None else _np(cov) + np.array([_pnp.COV_FLOOR, 0.0, _pnp.COV_FLOOR])
     for n, o, r in np.argwhere(mask):
-        p6 = _pnp.pnp_rvec_t(kp3[n, o], pts[n, o, r], cam, rng=rng)
+        c = None if cov is None else cov[n, o, r]
+        weighted[n, o, r] = int(c is not None and _pnp.whitening_factors(c, kp) is not None)
+        p6 = _pnp.pnp_rvec_t(kp3[n, o], pts[n, o, r], cam, rng=rng, cov=c)
         if not np.all(np.isfinite(p6)):
             raise FloatingPointError("poses_pnp_instances: non-finite pose for image %d object %d instance %d" % (n, o, r))
         Rm, t = _pnp.rodrigues(p6[:3]), p6[3:].astype(np.float64)
         P = np.concatenate([Rm, t.reshape(3, 1)], axis=1)
         out[n, o, r] = -P if t[2] < 0 else P
-    return out
+    return (out, weighted) if return_weighted else out

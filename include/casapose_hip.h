@@ -1300,6 +1300,33 @@ size_t cp_ls_vote_robust_workspace_bytes(int batch, int slots, int kp);
 int cp_ls_vote_slots_robust_f32(const float* field, int ld, int dir_off, int conf_off, const uint8_t* slot_map, int batch, int h, int w, int slots,
                                 int kp, int sigmoid_weights, float cutoff_px, int passes, void* workspace, float* keypoints, void* stream);
 
+/* ---- a covariance per slot and keypoint from the LS objective itself (csrc/ls_vote.hip, csrc/ls_cov_math.h) ---------------------------------
+ * cp_ls_slot_covariance_f32 says how far each keypoint of each slot can be trusted, for keypoints HANDED IN (either slot voter's, or any
+ * other): one more stream over the labelled pixels (the walk of a reweighted pass) and a finish per keypoint.  Nothing an earlier call summed
+ * is read, no state is kept.  The arguments up to sigmoid_weights are cp_ls_vote_slots_f32's, with the same refusals.
+ * THE RULE, per (image, slot, keypoint) with the estimate p = keypoint / h (fp32).  For every pixel of the slot whose direction is not (0, 0),
+ * in fp32 and in this order:
+ *     c = ((y + .5) / h, (x + .5) / h);  n = the pixel's unit direction;  e = p - c;  d = e_y n_x - e_x n_y;
+ *     rho = Tukey's biweight of d * (h / cutoff_px) as cp_ls_vote_slots_robust_f32 forms it when cutoff_px > 0, otherwise 1;
+ *     omega = w * rho;   the matrix terms (1 - ny^2) omega, (0 - ny nx) omega, (1 - nx^2) omega;   q = omega * (d * d)
+ * summed in fp64 into sums_ws = (A00, A01, A11, Q, Wall), Wall the sum of w before reweighting.  A pixel with direction (0, 0) takes no part in
+ * any of the five, with or without a cut-off (the plain vote counts it as w I).  The finish, in fp64:
+ *     W = A00 + A11;   sigma2 = h^2 Q / W;   kept = W / Wall;   Sigma = sigma2 (A / W)^-1 = h^2 Q A^-1
+ * Sigma is the covariance of ONE vote of average weight, in pixels^2: the scale of a hypothesis scatter, long along the rays of a keypoint far
+ * from the slot's pixels.  It is not the standard error of the estimate.  A truncated Tukey residual underestimates sigma2; not corrected.
+ *   cutoff_px  finite and >= 0, in pixels; 0 means no reweighting.
+ *   keypoints  in, fp32 [n][slots][kp][2] in (y,x) pixels, 8-byte aligned; not written.
+ *   sums_ws    cp_ls_vote_workspace_bytes(n, slots, kp) bytes, 8-byte aligned, no initialisation needed; holds the five sums afterwards.
+ *   cov        out, fp32 [n][slots][kp][3] = (sxx, sxy, syy) in the (x,y) pixels cp_pnp_weighted_f64 reads: (Sigma[1][1], Sigma[0][1],
+ *              Sigma[0][0]) of the (y,x) matrix.  Three NaNs (which the weighted PnP refuses: the pair is solved unweighted and says so) where
+ *              A fails the rank rule or the condition bound 1e6 of the robust voter's solve, kept < CP_LS_ROBUST_MIN_KEPT = 1/8, the keypoint
+ *              is not finite, or W is not > 0 (a slot without pixels).
+ *   stat       out, fp32 [n][slots][kp][2] = (sigma2, kept); (0, 0) where W is not > 0 or the keypoint is not finite.
+ * A slot value above `slots` is background.  Added in ABI 302 without changing any earlier entry point. */
+int cp_ls_slot_covariance_f32(const float* field, int ld, int dir_off, int conf_off, const uint8_t* slot_map, int batch, int h, int w, int slots,
+                              int kp, int sigmoid_weights, float cutoff_px, const float* keypoints, double* sums_ws, float* cov, float* stat,
+                              void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -22,6 +22,13 @@ CASAPOSE_INSTANCE_VOTER=robust (with CASAPOSE_MAX_INSTANCES set; refused by name
 the wrong instance): the script then also says `instances: robust voter (cutoff 4 px, 2 passes)` once, and poses_est.csv has one more trailing
 column `kept` after whatever columns are there, the share of the plain weight the last pass kept, averaged over the instance's keypoints.  Unset
 or `ls`: nothing changes.
+
+CASAPOSE_INSTANCE_PNP=weighted (with CASAPOSE_MAX_INSTANCES set; refused by name without it) weights the PnP of every instance by a covariance
+per keypoint (InstanceLSVoting(covariance=True), cp_ls_slot_covariance_f32: one more pass over the slot map; poses_pnp_instances(cov=), on the
+host PnP and under CASAPOSE_DEVICE_PNP=1; either split, either voter): the script then also says `instances: covariance-weighted PnP` once,
+and poses_est.csv has one more trailing column `weighted` after whatever columns are there, 1 where the instance's solve was weighted and 0
+where it fell back to the unweighted one.  Unset or `plain`: nothing changes.  CASAPOSE_UNCERTAINTY_PNP=1 stays refused: that covariance is
+the per-object RANSAC one.
 """
 import os
 import sys
@@ -38,7 +45,8 @@ import test_minimal  # noqa: E402
 from casapose_amd.data_handler.image_only_dataset import ImageOnlyDataset  # noqa: E402
 from casapose_amd.data_handler.vectorfield_dataset import VectorfieldDataset  # noqa: E402
 from casapose_amd.pose_estimation.instance_voting import (ENV, ROBUST_CUTOFF, ROBUST_PASSES, InstanceLSVoting,  # noqa: E402
-                                                          instance_split_from_environment, instance_voter_from_environment,
+                                                          instance_pnp_from_environment, instance_split_from_environment,
+                                                          instance_voter_from_environment,
                                                           max_instances_from_environment, poses_pnp_instances)
 from casapose_amd.pose_models.tfkeras import Classifiers  # noqa: E402
 from casapose_amd.utils.config_parser import parse_config  # noqa: E402
@@ -49,6 +57,7 @@ def main(argv=None):
     instances = max_instances_from_environment()
     by_votes = instance_split_from_environment() == "votes"
     robust = instance_voter_from_environment() == "robust"
+    weighted_pnp = instance_pnp_from_environment() == "weighted"
     if instances is None:
         return test_minimal.main(argv)
     for other in ("CASAPOSE_UNCERTAINTY_PNP", "CASAPOSE_MASK_REFINE"):
@@ -110,16 +119,19 @@ def main(argv=None):
     if opt.write_poses:
         with open(opt.evalf + "/poses_est.csv", "w") as f:
             f.write("name,object," + ",".join("r%d%d" % (i, j) for i in range(1, 4) for j in range(1, 4)) + ",t1,t2,t3,instance,pixels" +
-                    (",votes" if by_votes else "") + (",kept" if robust else "") + "\n")
+                    (",votes" if by_votes else "") + (",kept" if robust else "") + (",weighted" if weighted_pnp else "") + "\n")
 
     K, kp = 1 + no_objects, opt.no_points
     voter = InstanceLSVoting(name="coords_ls_voting", num_classes=K, num_points=kp, max_instances=instances,
-                             split="votes" if by_votes else "components", **(dict(voter="robust") if robust else {}))
+                             split="votes" if by_votes else "components", **(dict(voter="robust") if robust else {}),
+                             **(dict(covariance=True) if weighted_pnp else {}))
     print("instances: up to {} per object".format(instances))
     if by_votes:
         print("instances: split by centre votes")
     if robust:
         print("instances: robust voter (cutoff {:g} px, {} passes)".format(ROBUST_CUTOFF, ROBUST_PASSES))
+    if weighted_pnp:
+        print("instances: covariance-weighted PnP")
     rng = np.random.default_rng(opt.manualseed)
     speed, poses_by_name = [], {}
     for batch_idx in range(int(image_batches)):
@@ -132,7 +144,12 @@ def main(argv=None):
         pixels = voter.last_counts.cpu().numpy()
         votes = voter.last_instances[..., 1].cpu().numpy() if by_votes else None
         kept = voter.last_kept.mean(dim=-1).cpu().numpy() if robust else None
-        poses = poses_pnp_instances(coords, pixels, keypoints, camera_matrix, min_num=opt.min_object_size_test, rng=rng)
+        weighted = None
+        if weighted_pnp:
+            poses, weighted = poses_pnp_instances(coords, pixels, keypoints, camera_matrix, min_num=opt.min_object_size_test, rng=rng,
+                                                  cov=voter.last_cov, return_weighted=True)
+        else:
+            poses = poses_pnp_instances(coords, pixels, keypoints, camera_matrix, min_num=opt.min_object_size_test, rng=rng)
         seconds = time.perf_counter() - start
         speed.append(seconds)
         with open(opt.evalf + "/speed_eval.csv", "a") as f:
@@ -148,7 +165,8 @@ def main(argv=None):
                         f.write("{},{},".format(name, obj) + ",".join("{:.9g}".format(v) for v in np.concatenate([P[:, :3].reshape(-1), P[:, 3]])) +
                                 ",{},{}".format(r, int(pixels[0, o, r]) if found else 0) +
                                 (",{}".format(int(votes[0, o, r]) if found else 0) if by_votes else "") +
-                                (",{:.6g}".format(float(kept[0, o, r]) if found else 0.0) if robust else "") + "\n")
+                                (",{:.6g}".format(float(kept[0, o, r]) if found else 0.0) if robust else "") +
+                                (",{}".format(int(weighted[0, o, r]) if found else 0) if weighted_pnp else "") + "\n")
     print("average speed: {}".format(float(np.mean(speed[10:])) if len(speed) > 10 else float("nan")))
     return {"speed": speed, "poses": poses_by_name}
 
