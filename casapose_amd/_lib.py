@@ -171,7 +171,7 @@ def parse_header(text: str):
     """Every function prototype of a header in the style of include/casapose_hip.h -> (symbols, pointees, return_pointees, twins):
     symbols [(name, restype, argtypes)] in declaration order; pointees {name: per argument, what a pointer points to ("float", "void",
     "uint8_t*", ...) or None for a scalar}; return_pointees {name: the same for the return value}; twins {X_T: X_host_T} for T in f32 / f64 /
-    u8 / u16 where both are declared -- X_host_T then must take X_T's parameters minus a trailing `void* stream`.  A statement that is no struct, enum
+    u8 / u16 / i32 where both are declared -- X_host_T then must take X_T's parameters minus a trailing `void* stream`.  A statement that is no struct, enum
     or readable prototype raises CasaposeHipError: nothing is skipped."""
     text = re.sub(r"/\*.*?\*/", " ", text, flags=re.S)
     text = re.sub(r"//[^\n]*|^[ \t]*#[^\n]*", " ", text, flags=re.M)
@@ -194,7 +194,7 @@ def parse_header(text: str):
         pointees[name] = tuple(p for _, p in parsed)
     twins, argtypes = {}, {n: a for n, _, a in symbols}
     for host in pointees:
-        m = re.fullmatch(r"(\w+)_host_(f32|f64|u8|u16)", host)
+        m = re.fullmatch(r"(\w+)_host_(f32|f64|u8|u16|i32)", host)
         device = m and "%s_%s" % m.groups()
         if device in pointees:
             if argtypes[device] != argtypes[host] + [C.c_void_p] or pointees[device] != pointees[host] + ("void",):
@@ -218,12 +218,14 @@ TWIN_VARIANTS = {d: _PAIRS[d] for d in ("cp_pnp_weighted_f64",)}
 # pair is listed as a step on that kernel's output.  cp_contour_step_f64 is the same kind of step, and cp_mask_edt_u16 is one on the label map
 # cp_ccl_filter_labels leaves behind.
 TWIN_STEPS = {d: _PAIRS[d] for d in ("cp_depth_icp_step_f64", "cp_contour_step_f64", "cp_mask_edt_u16")}
-TWINS = {d: h for d, h in _PAIRS.items() if d not in TWIN_VARIANTS and d not in TWIN_STEPS}
+# cp_pose_verify_i32 reads another kernel's output (the renderer's planes and records) and rewrites nothing: a reader.
+TWIN_READERS = {d: _PAIRS[d] for d in ("cp_pose_verify_i32",)}
+TWINS = {d: h for d, h in _PAIRS.items() if d not in TWIN_VARIANTS and d not in TWIN_STEPS and d not in TWIN_READERS}
 
 
 def host_twin(name: str) -> Optional[str]:
-    """the host twin of the device entry point `name` (a kernel's, a weighted variant's or a follow-up step's), or None"""
-    return TWINS.get(name) or TWIN_VARIANTS.get(name) or TWIN_STEPS.get(name)
+    """the host twin of the device entry point `name` (a kernel's, a weighted variant's, a follow-up step's or a reader's), or None"""
+    return TWINS.get(name) or TWIN_VARIANTS.get(name) or TWIN_STEPS.get(name) or TWIN_READERS.get(name)
 
 
 _lib: Optional[C.CDLL] = None

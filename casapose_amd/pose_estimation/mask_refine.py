@@ -188,14 +188,15 @@ class DeviceMaskRefiner(ChunkedRefiner):
 
 
 # ---- the inference scripts (test_casapose.py, util_scripts/test_minimal.py) under CASAPOSE_MASK_REFINE=1 ----------------------------------------
-def require_image_frame(offsets) -> None:
-    """The label map is in the network's frame and the camera matrix in the image's: the refinement needs them to be one frame.  offsets [b, 10]
-    or [10] (h_crop, w_crop, -, -, dx, dy, angle, scale, W, H) of a batch; anything but the identity raises before any device work."""
+def require_image_frame(offsets, what: str = "CASAPOSE_MASK_REFINE=1") -> None:
+    """The label map is in the network's frame and the camera matrix in the image's: the refinement (and the verification, pose_verify.py) needs
+    them to be one frame.  offsets [b, 10] or [10] (h_crop, w_crop, -, -, dx, dy, angle, scale, W, H) of a batch; anything but the identity raises
+    before any device work, naming `what` -- the switch that asked."""
     o = _np(offsets, np.float64).reshape(-1, 10)
     if not (np.all(o[:, [0, 1, 4, 5, 6]] == 0.0) and np.all(o[:, 7] == 1.0)):
-        raise ValueError("CASAPOSE_MASK_REFINE=1 needs frames that reach the network as they are: the batch's offsets hold a crop, shift, rotation or scale "
+        raise ValueError("%s needs frames that reach the network as they are: the batch's offsets hold a crop, shift, rotation or scale "
                          "(h_crop, w_crop, dx, dy, angle, scale = %s), so the label map and the camera matrix do not share a frame"
-                         % (o[0, [0, 1, 4, 5, 6, 7]].tolist(),))
+                         % (what, o[0, [0, 1, 4, 5, 6, 7]].tolist()))
 
 
 def mesh_file(path_meshes: str, name: str) -> Optional[str]:
@@ -207,27 +208,33 @@ def mesh_file(path_meshes: str, name: str) -> Optional[str]:
     return None
 
 
-def refiner_for_meshes(verts, counts, path_meshes: str, objects: Sequence[str], device) -> "DeviceMaskRefiner":
-    """A refiner over the objects of an inference script: verts [oc, Vmax, 3] with counts [oc, 1], the vertices the scripts evaluate with (in the
-    keypoints' frame; VectorfieldDataset.generate_object_vertex_array), and the faces of the same mesh files under `path_meshes`.  Missing files
-    or meshes without faces raise before any device work."""
+def gather_meshes(verts, counts, path_meshes: str, objects: Sequence[str], what: str = "CASAPOSE_MASK_REFINE=1"):
+    """What a renderer over the objects of an inference script needs: verts [oc, Vmax, 3] with counts [oc, 1], the vertices the scripts evaluate
+    with (in the keypoints' frame; VectorfieldDataset.generate_object_vertex_array), and the faces of the same mesh files under `path_meshes`
+    -> (one [V, 3] array per object, one [T, 3] array per object, the largest coordinate).  Missing files or meshes without faces raise before
+    any device work, naming `what` -- the switch that asked."""
     from ..data_handler.vectorfield_dataset import read_faces
 
     if not path_meshes or not os.path.isdir(str(path_meshes)) or verts is None or counts is None:
-        raise ValueError("CASAPOSE_MASK_REFINE=1 needs the objects' mesh files under --datameshes (got %r)" % (path_meshes,))
+        raise ValueError("%s needs the objects' mesh files under --datameshes (got %r)" % (what, path_meshes))
     verts, counts = _np(verts, np.float32), _np(counts, np.int64).reshape(-1)
     faces = []
     for i, name in enumerate(objects):
         model = mesh_file(path_meshes, name)
         if model is None or i >= len(counts) or int(counts[i]) == 0:
-            raise ValueError("CASAPOSE_MASK_REFINE=1 needs a mesh for every object: %s has none under %s" % (name, path_meshes))
+            raise ValueError("%s needs a mesh for every object: %s has none under %s" % (what, name, path_meshes))
         f = read_faces(model)
         if len(f) == 0:
-            raise ValueError("CASAPOSE_MASK_REFINE=1 needs meshes with faces to render: %s holds vertices only" % model)
+            raise ValueError("%s needs meshes with faces to render: %s holds vertices only" % (what, model))
         faces.append(f)
     vs = [np.asarray(verts[i, :int(counts[i])], np.float32) for i in range(len(objects))]
-    reach = max(float(np.abs(v).max()) for v in vs)          # the depth range in the meshes' own unit, whatever it is
-    return DeviceMaskRefiner(vs, faces, device, near=1e-2 * reach, far=1e4 * reach)
+    return vs, faces, max(float(np.abs(v).max()) for v in vs)
+
+
+def refiner_for_meshes(verts, counts, path_meshes: str, objects: Sequence[str], device) -> "DeviceMaskRefiner":
+    """A refiner over the objects of an inference script (gather_meshes says what it takes)."""
+    vs, faces, reach = gather_meshes(verts, counts, path_meshes, objects)
+    return DeviceMaskRefiner(vs, faces, device, near=1e-2 * reach, far=1e4 * reach)          # the depth range in the meshes' own unit, whatever it is
 
 
 def refiner_for_dataset(dataset, path_meshes: str, objects: Sequence[str], device) -> "DeviceMaskRefiner":
@@ -297,5 +304,5 @@ def refine_estimates(refiner: "DeviceMaskRefiner", poses, labels, camera_matrix,
     return out.reshape(given.shape)
 
 
-__all__ = ["DEFAULT_GATE", "DEFAULT_MIN_PIXELS", "DeviceMaskRefiner", "mask_refine_enabled", "require_image_frame", "refiner_for_meshes", "refiner_for_dataset",
+__all__ = ["DEFAULT_GATE", "DEFAULT_MIN_PIXELS", "DeviceMaskRefiner", "mask_refine_enabled", "require_image_frame", "gather_meshes", "refiner_for_meshes", "refiner_for_dataset",
            "refiner_from_environment", "refine_voted_poses", "refine_estimates"]

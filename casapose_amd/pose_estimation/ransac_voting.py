@@ -37,7 +37,12 @@ def _device_generator_seed(generator: torch.Generator) -> int:
     return (seed0 * 0x9E3779B97F4A7C15 + ent[1]) % (2**62)
 
 
-def ransac_voting_layer_all_masks(mask: torch.Tensor, vertex: torch.Tensor, round_hyp_num: int, inlier_thresh: float = 0.99,
+# the smallest cosine between a pixel's direction and its ray to a hypothesis that makes the pixel an inlier (the reference's default); the pose
+# verifier (pose_verify.py) counts its agreeing pixels with the same threshold
+INLIER_THRESH = 0.99
+
+
+def ransac_voting_layer_all_masks(mask: torch.Tensor, vertex: torch.Tensor, round_hyp_num: int, inlier_thresh: float = INLIER_THRESH,
                                   confidence: float = 0.99, max_iter: int = 20, min_num: int = 5, max_num: int = 30000,
                                   draws: Optional[torch.Tensor] = None, generator: Optional[torch.Generator] = None,
                                   return_rounds: bool = False, return_covariance: bool = False):

@@ -269,7 +269,7 @@ def poses_from_coords(coords_yx, objects_available, batch, rng=None, solver=None
     return poses, pts
 
 
-def test_step(net, batch, opt, loss_factors, evaluation_points=None, object_points_3d_count=None, evaluator=None, refiner=None):
+def test_step(net, batch, opt, loss_factors, evaluation_points=None, object_points_3d_count=None, evaluator=None, refiner=None, verifier=None):
     """One evaluation step of test_casapose.py (:268-384): inference forward, (component-filtered) LS keypoint voting or
     RANSAC voting, PnP (on the host, or with CASAPOSE_DEVICE_PNP=1 on the GPU: device_pnp.solver_from_environment; with CASAPOSE_UNCERTAINTY_PNP=1
     weighted by the keypoint covariances of keypoint_covariance.py), losses and the eight per-object pose statistics (computed on the GPU with a DevicePoseEvaluator as `evaluator`, or,
@@ -277,6 +277,9 @@ def test_step(net, batch, opt, loss_factors, evaluation_points=None, object_poin
     With a mask_refine.DeviceMaskRefiner as `refiner`, or under CASAPOSE_MASK_REFINE=1 with the one mask_refine.refiner_from_environment keeps for
     `opt.datameshes` and the evaluation meshes, the PnP poses are aligned with the voter's label map before they are evaluated, inside the
     measured time; a batch whose offsets are not the identity is refused first.
+    With a pose_verify.DevicePoseVerifier as `verifier`, or under CASAPOSE_POSE_SCORE=1 with the one pose_verify.verifier_from_environment keeps,
+    the final poses (after the mask refinement, if that is on) are verified against the voter's label map and the direction channels, inside
+    the measured time; `verifier.last_scores` [B, oc] keeps the scores (io_utils.write_poses takes them as `scores=`).
     Returns (losses [5 floats], pose_stats [8 arrays of oc], poses [B,oc,3,4], points, seconds)."""
     import time
 
@@ -294,6 +297,15 @@ def test_step(net, batch, opt, loss_factors, evaluation_points=None, object_poin
             raise ValueError("CASAPOSE_MASK_REFINE=1 needs estimate_coords = 1: the label map is the LS voter's")
         if refiner is None:
             refiner = refiner_from_environment(opt, evaluation_points, object_points_3d_count, dev)
+    if verifier is not None or os.environ.get("CASAPOSE_POSE_SCORE", "0") == "1":
+        from .pose_estimation import pose_verify
+
+        pose_verify.require_image_frame(batch["offsets"], what=pose_verify.WHAT)
+        if not getattr(opt, "estimate_coords", False):
+            raise ValueError("CASAPOSE_POSE_SCORE=1 needs estimate_coords = 1: the label map is the LS voter's")
+        if verifier is None:
+            verifier = pose_verify.verifier_from_environment(opt, evaluation_points, object_points_3d_count, dev)
+        verifier.last_scores = verifier.last_counts = None
     if evaluator is None:
         from .pose_estimation.device_evaluation import evaluator_from_environment
 
@@ -320,7 +332,8 @@ def test_step(net, batch, opt, loss_factors, evaluation_points=None, object_poin
         coords = voter([seg if with_gt else o_seg, o_dirs, conf])
     from .pose_estimation.keypoint_covariance import keypoint_covariance, uncertainty_pnp_enabled
 
-    labels = voter.last_labels if refiner is not None else None   # asked for now: train_step below reuses the network's output buffer
+    labels = voter.last_labels if refiner is not None or verifier is not None else None   # asked for now: train_step below reuses the network's output buffer
+    directions = o_dirs.clone(memory_format=torch.contiguous_format) if verifier is not None else None   # one copy, for the same reason
     cov = None
     if coords is not None and uncertainty_pnp_enabled():   # CASAPOSE_UNCERTAINTY_PNP=1: the covariance about the LS-voted keypoints, over the pixels that voted
         cov = keypoint_covariance(voter.last_labels, o_dirs, coords.flip(-1))
@@ -331,6 +344,8 @@ def test_step(net, batch, opt, loss_factors, evaluation_points=None, object_poin
         poses, pts = poses_from_coords(coords, plan.objects_available, batch, solver=solver, cov=cov)
         if refiner is not None:
             poses = refine_estimates(refiner, poses, labels, batch["cam_mat"])
+        if verifier is not None:
+            pose_verify.verify_estimates(verifier, poses, labels, directions, batch["keypoints3d"], batch["cam_mat"])
         stats, poses, pts = evaluate_pose_estimates(pts, poses, batch["poses_gt"], seg, batch["keypoints3d"], batch["cam_mat"], batch["diameters"],
                                                     evaluation_points=evaluation_points, object_points_3d_count=object_points_3d_count, min_num=1,
                                                     evaluator=evaluator)

@@ -79,16 +79,21 @@ def _append(path: str, header: str, line: str):
         f.write(line)
 
 
-def write_poses(gt_poses, estimated_poses, names: Sequence[str], image_id, path_out: str, time_needed: Optional[float] = None):
+def write_poses(gt_poses, estimated_poses, names: Sequence[str], image_id, path_out: str, time_needed: Optional[float] = None, scores=None):
     """gt_poses [objects,1,3,4] (or [objects,3,4]), estimated_poses [objects,3,4], names = `objectsofinterest`, image_id =
     the batch tuple's entry 12 (`<dir>_<dir>_<file stem>`: its first number is the scene, its second the image).
-    score = 1 for a non-zero estimate, 0 for "not found" (all-zero pose); time = -1 when not measured."""
+    score = 1 for a non-zero estimate, 0 for "not found" (all-zero pose); time = -1 when not measured.  scores [objects] (the verified
+    scores of pose_estimation/pose_verify.py): a non-zero estimate's score is that value, written as repr(float); "not found" stays 0."""
     gt = np.asarray(gt_poses.detach().cpu() if hasattr(gt_poses, "detach") else gt_poses, np.float32)
     if gt.ndim == 4:
         gt = gt[:, 0]
     found = _NUMBER.findall(_text(image_id))
     scene_id, img_id = int(found[0]), int(found[1])
     time = -1.0 if time_needed is None else float(time_needed)
+    if scores is not None:
+        scores = np.asarray(scores.detach().cpu() if hasattr(scores, "detach") else scores, np.float64).reshape(-1)
+        if len(scores) != len(names):
+            raise ValueError("write_poses: scores holds one value per object (got %d for %d objects)" % (len(scores), len(names)))
     all_dir, filtered_dir = path_out + "all_poses/", path_out + "filtered_poses/"
     for d in (path_out, all_dir, filtered_dir):
         os.makedirs(d, exist_ok=True)
@@ -101,8 +106,8 @@ def write_poses(gt_poses, estimated_poses, names: Sequence[str], image_id, path_
         obj_id = int(_NUMBER.findall(name)[0])
         est = _pose(estimated_poses[idx])
         if abs(float(gt[idx].sum())) > 0.0001:
-            score = 1.0 if abs(float(est.sum())) > 0 else 0.0
-            row = "%d,%d,%d,%s,%s,%s,%s\n" % (scene_id, img_id, obj_id, str(score), _numbers(est[:, :3].reshape(-1)),
+            score = (1.0 if scores is None else float(scores[idx])) if abs(float(est.sum())) > 0 else 0.0
+            row = "%d,%d,%d,%s,%s,%s,%s\n" % (scene_id, img_id, obj_id, repr(score), _numbers(est[:, :3].reshape(-1)),
                                                _numbers(est[:, 3].reshape(-1)), str(time))
             _append(path_out + "bop_evaluation.csv", BOP_HEADER, row)
             _append(filtered_dir + "poses_gt_" + name + ".txt", POSE_HEADER, pose_line(_pose(gt[idx])))
@@ -111,6 +116,26 @@ def write_poses(gt_poses, estimated_poses, names: Sequence[str], image_id, path_
             _append(filtered_dir + "poses_gt_" + name + ".txt", POSE_HEADER, pose_line(zeros))
             _append(filtered_dir + "poses_init_" + name + ".txt", POSE_HEADER, pose_line(zeros))
         _append(all_dir + "poses_init_" + name + ".txt", POSE_HEADER, pose_line(est))
+
+
+def write_bop_instances(path: str, frame_name, names: Sequence[str], poses, scores, time_needed: Optional[float] = None):
+    """One row of BOP's result format per found instance of a frame, appended to `path` (util_scripts/bop_score.py reads the file as it is):
+    poses [objects, R, 3, 4] (the zero pose = an empty slot: no row), scores [objects, R], names = `objectsofinterest` (the first number of a
+    name is the obj_id).  scene_id, im_id: the first two numbers of the frame name, as write_poses takes them; with a single number the scene
+    is 0.  time = -1 when not measured."""
+    found = _NUMBER.findall(_text(frame_name))
+    if not found:
+        raise ValueError("write_bop_instances: the frame name %r holds no number to take the image id from" % (_text(frame_name),))
+    scene_id, img_id = (int(found[0]), int(found[1])) if len(found) > 1 else (0, int(found[0]))
+    time = -1.0 if time_needed is None else float(time_needed)
+    poses, scores = np.asarray(poses, np.float32), np.asarray(scores, np.float64)
+    for idx, name in enumerate(names):
+        obj_id = int(_NUMBER.findall(name)[0])
+        for r in range(poses.shape[1]):
+            est = poses[idx, r]
+            if est.any():
+                _append(path, BOP_HEADER, "%d,%d,%d,%s,%s,%s,%s\n" % (scene_id, img_id, obj_id, repr(float(scores[idx, r])), _numbers(est[:, :3].reshape(-1)),
+                                                                     _numbers(est[:, 3].reshape(-1)), str(time)))
 
 
 def latest_checkpoint(checkpoint_path: str):

@@ -1162,6 +1162,53 @@ int cp_contour_step_host_f64(const uint32_t* planes, const int32_t* records, int
                              const double* cams, int images, const int32_t* jobs, int njobs, double sample_offset, double damping, int min_pixels,
                              int update, int split, double* poses, double* stats, int32_t* status, void* workspace, size_t workspace_bytes);
 
+/* ---- pose verification: a rendered estimate against the label map and the vector field (csrc/pose_verify.hip, csrc/verify_math.h) ---------
+ * Per job = (image, rendered plane, label) the integers a score is made of.  Nothing but `counts` and the workspace is written: the entry
+ * point reads another kernel's output and rewrites none of it.  Everything is device memory.
+ *   planes       uint32 [nplanes][H][W]   the workspace of cp_render_masks_u8 after the call
+ *   records      int32 [nplanes][11]      its records; words 2-5 (bbox_obj: x, y, w, h) bound the pixels a plane is read at
+ *   inst_counts  int32 [frames]           the renderer's own, read as clamped to [0, instances_max].  Plane p is slot p % instances_max of
+ *                                         frame p / instances_max; the planes that may hide it are the first inst_counts[frame] of that frame
+ *   labels       uint8 [images][H][W]     the filtered label map or the slot map, 0 = background
+ *   field        fp32 [images][H][W][ld]  keypoint k's direction is (dy, dx) at words dir_off + 2k, dir_off + 2k + 1 of a pixel's record, as
+ *                                         in csrc/ls_vote.hip: the production record is ld 36 / dir_off 9 / kp 9; 1 <= kp <= 32,
+ *                                         2 <= ld <= 4096, 0 <= dir_off, dir_off + 2 kp <= ld
+ *   kp2d         fp64 [njobs][kp][2]      the job's keypoints projected by its pose, (y, x) in pixels of the label map's frame
+ *   jobs         int32 [njobs][4]         (image, plane, label 1..255, unused); several jobs may name one plane
+ *   sample_offset  0 .. 1: pixel (i, j) has its centre at (i + sample_offset, j + sample_offset)
+ *   cos_min      0 .. 1: the smallest cosine between a direction and the ray to the keypoint that makes an inlier
+ *   split        blocks per job, 1 .. 64: a speed setting, the counts do not depend on it
+ *   counts       int32 [njobs][8], zeroed inside the call.  Words 0-4 walk the job's bbox_obj clipped to the image:
+ *                  0 rendered       pixels where the job's own plane is hit (its word is not 0xffffffff)
+ *                  1 hidden         of those, pixels where another plane q of the frame has a smaller word, or an equal word and q < p (depths
+ *                                   are positive fp32: comparing the words compares the depths); q is read inside its own bbox_obj only
+ *                  2 on_label       visible pixels (rendered, not hidden) whose label is the job's
+ *                  3 on_background  visible pixels with label 0
+ *                  4 on_other       visible pixels with any other label: reported, and neutral in pose_estimation/pose_verify.py's score
+ *                  5 label_pixels   pixels of the whole image whose label is the job's
+ *                  6 pairs          over on_label pixels, the (pixel, keypoint) pairs whose direction d has d.d > 0 and finite and whose
+ *                                   e = kp2d - centre has e.e > 0 and finite
+ *                  7 inliers        of those, the pairs with d.e >= 0 and (d.e)^2 >= cos_min^2 (d.d) (e.e)
+ *   workspace    cp_pose_verify_workspace_bytes(images) bytes, 4-byte aligned: the label histogram int32 [images][256] of the same call;
+ *                needs no initialisation
+ * Words 6-7 are fp64 from the fp32 inputs, one rounding per operation, without contraction, square root or division (the rules are listed in
+ * csrc/verify_math.h).  A job whose image, plane or label is out of range, or whose frame is not below `frames`, leaves zeros.  Integer
+ * atomics only: two calls with the same inputs, any split and any workspace contents give the same bytes.  No pixel outside a clipped box is
+ * addressed but by the histogram.  H, W <= 16384, H x W x kp < 2^31, instances_max <= 256, images <= 2^22, njobs * split < 2^31;
+ * cp_pose_verify_workspace_bytes returns 0 outside its limit.  cp_pose_verify_tile(): the pixels a block takes per step (tests place their
+ * sizes by it).  cp_pose_verify_host_i32 runs the same code serially on host pointers and launches nothing: it works without a GPU and gives
+ * the device's bytes.  Added in ABI 302 without changing any earlier entry point. */
+int cp_pose_verify_tile(void);
+size_t cp_pose_verify_workspace_bytes(int images);
+int cp_pose_verify_i32(const uint32_t* planes, const int32_t* records, int nplanes, int H, int W, const int32_t* inst_counts, int frames,
+                       int instances_max, const uint8_t* labels, const float* field, int images, int ld, int dir_off, int kp, const double* kp2d,
+                       const int32_t* jobs, int njobs, double sample_offset, double cos_min, int split, int32_t* counts, void* workspace,
+                       size_t workspace_bytes, void* stream);
+int cp_pose_verify_host_i32(const uint32_t* planes, const int32_t* records, int nplanes, int H, int W, const int32_t* inst_counts, int frames,
+                            int instances_max, const uint8_t* labels, const float* field, int images, int ld, int dir_off, int kp,
+                            const double* kp2d, const int32_t* jobs, int njobs, double sample_offset, double cos_min, int split, int32_t* counts,
+                            void* workspace, size_t workspace_bytes);
+
 /* ---- keypoints and models_info of a mesh set (csrc/models.hip, csrc/model_math.h) --------------------------------------------------------
  * What the dataset converter needs per object and BOP archives do not hold (data_handler/model_prep.py): the axis-aligned box, the squared
  * diameter (the largest squared distance over all vertex pairs) and no_points keypoints, the box centre followed by farthest-point samples of

@@ -29,6 +29,14 @@ host PnP and under CASAPOSE_DEVICE_PNP=1; either split, either voter): the scrip
 and poses_est.csv has one more trailing column `weighted` after whatever columns are there, 1 where the instance's solve was weighted and 0
 where it fell back to the unweighted one.  Unset or `plain`: nothing changes.  CASAPOSE_UNCERTAINTY_PNP=1 stays refused: that covariance is
 the per-object RANSAC one.
+
+CASAPOSE_INSTANCE_SCORE=verify (with CASAPOSE_MAX_INSTANCES set; refused by name without it) scores every found instance against the slot map
+and the vector field (pose_estimation/pose_verify.py: the instance's mesh rendered at its pose, cp_pose_verify_i32; it needs the objects' mesh
+files under --datameshes; either split, either voter, either PnP), inside the frame's measured time: the script then also says
+`instances: verified scores` once, poses_est.csv has one more trailing column `score` after whatever columns are there, and with
+--write_poses 1 <evalf>/bop_instances.csv holds one row of BOP's result format per found instance (scene_id and im_id from the first two
+numbers of the frame name, scene 0 with a single number; obj_id from the object's name; the verified score; the frame's seconds), which
+util_scripts/bop_score.py reads as it is.  Unset or `none`: nothing changes.
 """
 import os
 import sys
@@ -48,9 +56,10 @@ from casapose_amd.pose_estimation.instance_voting import (ENV, ROBUST_CUTOFF, RO
                                                           instance_pnp_from_environment, instance_split_from_environment,
                                                           instance_voter_from_environment,
                                                           max_instances_from_environment, poses_pnp_instances)
+from casapose_amd.pose_estimation.pose_verify import instance_score_from_environment  # noqa: E402
 from casapose_amd.pose_models.tfkeras import Classifiers  # noqa: E402
 from casapose_amd.utils.config_parser import parse_config  # noqa: E402
-from casapose_amd.utils.io_utils import latest_checkpoint  # noqa: E402
+from casapose_amd.utils.io_utils import latest_checkpoint, write_bop_instances  # noqa: E402
 
 
 def main(argv=None):
@@ -58,6 +67,7 @@ def main(argv=None):
     by_votes = instance_split_from_environment() == "votes"
     robust = instance_voter_from_environment() == "robust"
     weighted_pnp = instance_pnp_from_environment() == "weighted"
+    verified = instance_score_from_environment() == "verify"
     if instances is None:
         return test_minimal.main(argv)
     for other in ("CASAPOSE_UNCERTAINTY_PNP", "CASAPOSE_MASK_REFINE"):
@@ -119,7 +129,9 @@ def main(argv=None):
     if opt.write_poses:
         with open(opt.evalf + "/poses_est.csv", "w") as f:
             f.write("name,object," + ",".join("r%d%d" % (i, j) for i in range(1, 4) for j in range(1, 4)) + ",t1,t2,t3,instance,pixels" +
-                    (",votes" if by_votes else "") + (",kept" if robust else "") + (",weighted" if weighted_pnp else "") + "\n")
+                    (",votes" if by_votes else "") + (",kept" if robust else "") + (",weighted" if weighted_pnp else "") + (",score" if verified else "") + "\n")
+        if verified and os.path.exists(opt.evalf + "/bop_instances.csv"):
+            os.remove(opt.evalf + "/bop_instances.csv")
 
     K, kp = 1 + no_objects, opt.no_points
     voter = InstanceLSVoting(name="coords_ls_voting", num_classes=K, num_points=kp, max_instances=instances,
@@ -132,6 +144,17 @@ def main(argv=None):
         print("instances: robust voter (cutoff {:g} px, {} passes)".format(ROBUST_CUTOFF, ROBUST_PASSES))
     if weighted_pnp:
         print("instances: covariance-weighted PnP")
+    verifier = None
+    if verified:
+        from casapose_amd.pose_estimation.pose_verify import require_image_frame, verifier_for_dataset, verify_instance_estimates
+
+        # The frames themselves reach the network as they are (their size was checked above; nothing resizes or crops them), so every slot map is
+        # in the image's frame.  The camera matrix is the first annotated frame's: its offsets say whether it is the image's, too.
+        if first.get("offsets") is None:
+            raise ValueError("CASAPOSE_INSTANCE_SCORE=verify needs the offsets of the annotated frame the camera matrix came from: the dataset gave none")
+        require_image_frame(first["offsets"], what="CASAPOSE_INSTANCE_SCORE=verify")
+        verifier = verifier_for_dataset(annotated, opt.datameshes, objectsofinterest, device)
+        print("instances: verified scores")
     rng = np.random.default_rng(opt.manualseed)
     speed, poses_by_name = [], {}
     for batch_idx in range(int(image_batches)):
@@ -150,6 +173,9 @@ def main(argv=None):
                                                   cov=voter.last_cov, return_weighted=True)
         else:
             poses = poses_pnp_instances(coords, pixels, keypoints, camera_matrix, min_num=opt.min_object_size_test, rng=rng)
+        scores = None
+        if verified:     # the network's output is the field: its directions start behind the K segmentation channels
+            scores = verify_instance_estimates(verifier, np.asarray(poses), voter.last_labels, out, keypoints, camera_matrix, dir_off=K)
         seconds = time.perf_counter() - start
         speed.append(seconds)
         with open(opt.evalf + "/speed_eval.csv", "a") as f:
@@ -166,7 +192,10 @@ def main(argv=None):
                                 ",{},{}".format(r, int(pixels[0, o, r]) if found else 0) +
                                 (",{}".format(int(votes[0, o, r]) if found else 0) if by_votes else "") +
                                 (",{:.6g}".format(float(kept[0, o, r]) if found else 0.0) if robust else "") +
-                                (",{}".format(int(weighted[0, o, r]) if found else 0) if weighted_pnp else "") + "\n")
+                                (",{}".format(int(weighted[0, o, r]) if found else 0) if weighted_pnp else "") +
+                                (",{!r}".format(float(scores[0, o, r]) if found else 0.0) if verified else "") + "\n")
+            if verified:
+                write_bop_instances(opt.evalf + "/bop_instances.csv", name, objectsofinterest, poses_by_name[name], scores[0], seconds)
     print("average speed: {}".format(float(np.mean(speed[10:])) if len(speed) > 10 else float("nan")))
     return {"speed": speed, "poses": poses_by_name}
 
