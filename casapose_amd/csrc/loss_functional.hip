@@ -6,6 +6,7 @@
 //   cp_pose_loss_sep_f32   compute_loss with separated vector fields (oc * 2kp channels)   (train_casapose.py:57,97-125), value + gradient
 // All HBM-bound streaming passes, one pixel per lane, fp64 reductions (wave shuffle -> one atomic per wave).
 #include "common.h"
+#include "instance_rule.h"   // nearest_instance(): the centre rule, shared with the fused training loss
 
 namespace {
 
@@ -21,19 +22,6 @@ __device__ __forceinline__ float sl1(float a) { return a < 1.f ? 0.5f * a * a : 
 __device__ __forceinline__ double wave_sum(double v) {
     for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o);
     return v;
-}
-
-// keypoints [b][objects][instances][kp][2] (y,x).  Instance of object `obj` whose centre (keypoint 0) is nearest to the pixel centre; first
-// minimum wins (tf.argmin).
-__device__ __forceinline__ int nearest_instance(const float* __restrict__ kobj, int instances, int kp, float cy, float cx) {
-    int best = 0;
-    float bd = 3.4e38f;
-    for (int i = 0; i < instances; ++i) {
-        const float dy = cy - kobj[(size_t)i * kp * 2], dx = cx - kobj[(size_t)i * kp * 2 + 1];
-        const float d = sqrtf(dy * dy + dx * dx);
-        if (d < bd) { bd = d; best = i; }
-    }
-    return best;
 }
 
 __global__ __launch_bounds__(THREADS) void vector_field_kernel(const uint8_t* __restrict__ labels, const float* __restrict__ keypoints, int H, int W,

@@ -11,6 +11,12 @@ A side stream copies the records and runs the kernel; an event recorded there is
 max(prefetch, 1) batches in flight, the convention of device_pipeline.DeviceBatches.  The host half of a batch (0.1 ms per image) runs in the
 consumer's thread: a background thread for it changed nothing measurable in a training loop.  The batch dict has the keys, shapes and dtypes of the host
 path; img / target_seg / filtered_seg are device tensors, pixel_gt_count comes from the kernel's counts, the rest stays on the host as before.
+
+A dataset with an instance axis (SyntheticSceneDataset(instances=I), I > 1) gives the unchanged ray-caster oc * I slots per image, slot o * I + r
+being instance r of object o with the object's semi-axes and colour; an absent instance's record is placed behind the camera, where the
+ray-caster's `s > 0` never hits it.  The label map that comes back is the slot map (o * I + r + 1: the id convention of instance_voting.py), and
+one small pass (cp_slot_labels_u8, csrc/slot_labels.hip) turns it into the class labels, instance_seg, the (oc + 1)-channel one-hot and the
+per-object counts.  filtered_seg, instance_seg, instance_count and the small arrays are the host path's byte for byte.
 """
 from __future__ import annotations
 
@@ -33,16 +39,20 @@ class DeviceScenes:
         self.depth = max(int(prefetch), 1)
         self.stream = None   # created by the first launch: the host half needs no GPU
         self.lib = _lib.load()
-        self.words = HEADER + OBJECT * ds.oc
-        if self.lib.cp_render_scenes_record_words(ds.oc) != self.words:
+        self.instances = int(getattr(ds, "instances", 1))
+        self.slots = ds.oc * self.instances          # what the ray-caster sees as objects
+        self.words = HEADER + OBJECT * self.slots
+        if self.lib.cp_render_scenes_record_words(self.slots) != self.words:
             raise _lib.CasaposeHipError("%d objects: the library's scene record has %d words, this binding packs %d"
-                                        % (ds.oc, self.lib.cp_render_scenes_record_words(ds.oc), self.words))
+                                        % (self.slots, self.lib.cp_render_scenes_record_words(self.slots), self.words))
 
     # ---- host half ----------------------------------------------------------------------------------------------------------------
     def record(self, image: int) -> Tuple[np.ndarray, dict]:
         """(the fp64 record of image `image` of the stream, its small per-image arrays)"""
         ds = self.ds
         rng = np.random.default_rng([ds.seed, int(image)])
+        if self.instances > 1:
+            return self._record_instances(rng)
         hc, wc, poses = ds._draw(rng)
         seed = int(rng.integers(0, 1 << 63, dtype=np.int64))   # after the pose draws: they stay the host path's
         kp2, offsets = ds._keypoints(hc, wc, poses)
@@ -57,6 +67,24 @@ class DeviceScenes:
         obj[:, 15:18] = ds.colors
         return rec, dict(poses=poses, kp2=kp2, offsets=offsets)
 
+    def _record_instances(self, rng) -> Tuple[np.ndarray, dict]:
+        """record() with an instance axis: oc * I slots; an absent one sits behind the camera (identity rotation, t_z < 0)"""
+        ds, I = self.ds, self.instances
+        hc, wc, inst, poses = ds._draw_instances(rng)
+        seed = int(rng.integers(0, 1 << 63, dtype=np.int64))   # after the pose draws, as in record()
+        kp2, offsets = ds._keypoints_instances(hc, wc, inst, poses)
+        rec = np.zeros(self.words, np.float64)
+        rec[0:6] = hc, wc, CAMERA[0, 0], CAMERA[1, 1], CAMERA[0, 2], CAMERA[1, 2]
+        rec[6:7].view(np.uint64)[0] = seed
+        rec[7] = self.slots
+        obj = rec[HEADER:].reshape(ds.oc, I, OBJECT)
+        there = np.arange(I)[None, :] < inst[:, None]
+        obj[..., 0:9] = np.where(there[..., None], poses[..., :3].reshape(ds.oc, I, 9), np.eye(3).reshape(9))
+        obj[..., 9:12] = np.where(there[..., None], poses[..., 3], (0.0, 0.0, -1000.0))
+        obj[..., 12:15] = (1.0 / ds.axes)[:, None]
+        obj[..., 15:18] = ds.colors[:, None]
+        return rec, dict(poses=poses, kp2=kp2, offsets=offsets, instance_count=inst)
+
     def host_half(self, images: Iterable[int]) -> dict:
         """The records [b, words] of these stream images (pinned when a GPU is present) and the host tensors of their batch."""
         parts = [self.record(i) for i in images]
@@ -68,11 +96,31 @@ class DeviceScenes:
     def _render(self, records, noise: bool, device, stream) -> dict:
         """cp_render_scenes_f32 on `stream` over device records, or (device None) its host twin over NumPy records: img, label, target_seg, counts"""
         b, oc, (H, W) = records.shape[0], self.ds.oc, self.ds.size
+        if self.instances > 1:
+            return self._render_instances(records, noise, device, stream)
         out = _twin.alloc(dict(img=((b, H, W, 3), np.float32), label=((b, H, W), np.uint8), target_seg=((b, H, W, oc + 1), np.float32),
                                counts=((b, oc), np.int32)), device)
         _twin.call("cp_render_scenes_f32", records, b, oc, H, W, int(noise), out["img"], out["label"], out["target_seg"], out["counts"],
                    host=device is None, stream=stream)
         return out
+
+    def _render_instances(self, records, noise: bool, device, stream) -> dict:
+        """_render with an instance axis: the ray-caster over the slots, then the slot map split into class labels, instance_seg, one-hot and counts
+        (cp_slot_labels_u8 on the device; the same integer arithmetic in NumPy for the host twin)"""
+        b, oc, S, (H, W) = records.shape[0], self.ds.oc, self.slots, self.ds.size
+        raw = _twin.alloc(dict(img=((b, H, W, 3), np.float32), label=((b, H, W), np.uint8), target_seg=((b, H, W, S + 1), np.float32),
+                               counts=((b, S), np.int32)), device)
+        _twin.call("cp_render_scenes_f32", records, b, S, H, W, int(noise), raw["img"], raw["label"], raw["target_seg"], raw["counts"],
+                   host=device is None, stream=stream)
+        if device is None:
+            label, iseg = self.ds.split_slots(raw["label"])
+            counts = np.stack([(label == o + 1).reshape(b, -1).sum(1) for o in range(oc)], 1).astype(np.int32)
+            return dict(img=raw["img"], label=label, instance_seg=iseg, target_seg=np.eye(oc + 1, dtype=np.float32)[label], counts=counts, slots=raw["label"])
+        out = _twin.alloc(dict(label=((b, H, W), np.uint8), instance_seg=((b, H, W), np.uint8), target_seg=((b, H, W, oc + 1), np.float32),
+                               counts=((b, oc), np.int32)), device)
+        _lib.check(self.lib.cp_slot_labels_u8(raw["label"].data_ptr(), b, oc, self.instances, H * W, out["label"].data_ptr(), out["instance_seg"].data_ptr(),
+                                              out["target_seg"].data_ptr(), out["counts"].data_ptr(), stream), "cp_slot_labels_u8")
+        return dict(out, img=raw["img"], slots=raw["label"])
 
     def twin(self, records: np.ndarray, noise: bool = True) -> Dict[str, np.ndarray]:
         """Host records [b, words] through cp_render_scenes_host_f32, the kernel's host twin (no GPU): img, label, target_seg, counts as NumPy arrays."""
@@ -98,6 +146,8 @@ class DeviceScenes:
     def _launch(self, host: dict, noise: bool = True) -> Tuple[dict, torch.cuda.Event]:
         out, done = self.launch_records(host["records"], noise)
         batch = dict(host["small"], img=out["img"], target_seg=out["target_seg"], filtered_seg=out["filtered_seg"])
+        if self.instances > 1:
+            batch["instance_seg"] = out["instance_seg"]
         return dict(batch=batch, counts_host=out["counts_host"]), done
 
     def _finish(self, flight: dict, done: torch.cuda.Event) -> Dict[str, torch.Tensor]:
@@ -110,6 +160,9 @@ class DeviceScenes:
         done.synchronize()   # the counts are host data of the batch
         count = flight["counts_host"].to(torch.float32)[:, :, None, None].clone()
         order = ("img", "target_seg", "keypoints3d", "target_vert", "cam_mat", "diameters", "offsets", "filtered_seg", "poses_gt")
+        if self.instances > 1:     # the host path's two extra fields, in its order
+            batch["instance_seg"].record_stream(consumer)
+            return dict([(k, batch[k]) for k in order], pixel_gt_count=count, instance_count=batch["instance_count"], instance_seg=batch["instance_seg"])
         return dict([(k, batch[k]) for k in order], pixel_gt_count=count)
 
     def render(self, images: Iterable[int], noise: bool = True) -> Dict[str, torch.Tensor]:

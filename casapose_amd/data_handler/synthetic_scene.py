@@ -18,6 +18,15 @@ follow the reference's offsets convention [h_crop, w_crop, -, -, dx, dy, angle, 
 
 The pictures are ray-cast here in NumPy fp64, one image at a time; `batch(..., device=)` / `generate_dataset(..., device=)` hand the per-pixel part
 to the GPU instead (device_scenes.py, csrc/scenes.hip): the same draws, labels, poses and keypoints, other noise samples of the same distribution.
+
+Several instances of one object (`instances=I`, 2..16; the reference's max_instance_count, vectorfield_dataset.py:378-410,452-479): per image and
+object a count n in 1..I is drawn and n ellipsoids of that object -- the same semi-axes and colour -- are posed and rendered; the nearest hit
+wins, as between objects.  The draws of one image, in order: the crop origin; then per object its count n, then per present instance z, u, v and
+the rotation (a stream of its own: it does not relate to the stream of instances=1).  The batch then carries the reference's instance axis:
+target_vert [B,oc,I,kp,2], keypoints3d [B,oc,I,kp,3], poses_gt [B,oc,I,3,4], diameters [B,oc,I], absent instances padded as the reference's reader
+pads them (keypoints -1000, pose 0, diameter -1; :458-470), and two fields more: instance_count int32 [B,oc] and instance_seg uint8 [B,H,W], the
+instance index of the visible hit (0 on background).  target_seg / filtered_seg stay CLASS labels, pixel_gt_count is per object, summed over its
+instances.  With instances=1 every draw and every byte of every batch is what it was.
 """
 from __future__ import annotations
 
@@ -48,9 +57,12 @@ def _fibonacci_sphere(n: int) -> np.ndarray:
 
 class SyntheticSceneDataset:
     def __init__(self, no_objects: int, image_size: Tuple[int, int] = (448, 448), no_points: int = 9, length: int = 64, seed: int = 0,
-                 mesh_vertices: int = 642, random_crop: bool = True):
+                 mesh_vertices: int = 642, random_crop: bool = True, instances: int = 1):
         if no_points != 9:
             raise ValueError("the synthetic scene defines 9 keypoints per object (centre + bounding-box corners)")
+        if not 1 <= int(instances) <= 16 or no_objects * int(instances) > 254:
+            raise ValueError("instances must lie in 1..16 with no_objects * instances <= 254 (got %d objects, %r instances)" % (no_objects, instances))
+        self.instances = int(instances)
         self.oc, self.size, self.kp, self.length, self.seed = no_objects, tuple(image_size), no_points, length, seed
         self.random_crop = random_crop
         rng = np.random.default_rng(seed)
@@ -89,10 +101,39 @@ class SyntheticSceneDataset:
             poses[o, :, 3] = [(u - K[0, 2]) * z / K[0, 0], (v - K[1, 2]) * z / K[1, 1], z]
         return hc, wc, poses
 
+    def _draw_instances(self, rng) -> Tuple[int, int, np.ndarray, np.ndarray]:
+        """The draws of one image with an instance axis, in this order: the crop origin, then per object the count n in 1..I and, per present
+        instance, z, u, v and the rotation -> (hc, wc, counts [oc] int32, poses [oc,I,3,4]; absent instances zero)."""
+        oc, I = self.oc, self.instances
+        H, W = self.size
+        if (H, W) == (FULL_H, FULL_W):
+            hc, wc = 0, 0
+        elif self.random_crop:
+            hc, wc = int(rng.integers(0, FULL_H - H + 1)), int(rng.integers(0, FULL_W - W + 1))
+        else:
+            hc, wc = (FULL_H - H) // 2, (FULL_W - W) // 2
+        K = CAMERA
+        counts = np.zeros(oc, np.int32)
+        poses = np.zeros((oc, I, 3, 4))
+        for o in range(oc):
+            counts[o] = int(rng.integers(1, I + 1))
+            for r in range(counts[o]):
+                z = rng.uniform(650.0, 1100.0)
+                u = rng.uniform(wc + 0.12 * W, wc + 0.88 * W)
+                v = rng.uniform(hc + 0.12 * H, hc + 0.88 * H)
+                poses[o, r, :, :3] = _rot(rng)
+                poses[o, r, :, 3] = [(u - K[0, 2]) * z / K[0, 0], (v - K[1, 2]) * z / K[1, 1], z]
+        return hc, wc, counts, poses
+
     def _pixels(self, rng, hc: int, wc: int, poses: np.ndarray, noise: bool = True) -> Tuple[np.ndarray, np.ndarray]:
         """The per-pixel part of one image -> (img [H,W,3] float64 in [-1,1], label [H,W] uint8).  With noise it draws N(0, 0.02) for the background
         and then N(0, 0.01) for every pixel from `rng`; without, it draws nothing.  csrc/scene_math.h restates this function."""
-        oc = self.oc
+        return self._cast(rng, hc, wc, poses, self.axes, self.colors, None, noise)
+
+    def _cast(self, rng, hc: int, wc: int, poses: np.ndarray, axes: np.ndarray, colors: np.ndarray, present, noise: bool) -> Tuple[np.ndarray, np.ndarray]:
+        """_pixels over a list of ellipsoids (poses [S,3,4], axes / colors [S,3]; present [S] bool or None = all): the label is the 1-based index of the
+        nearest hit in that list.  One object per entry is _pixels; with an instance axis entry (o * I + r) is instance r of object o."""
+        oc = poses.shape[0]
         H, W = self.size
         K = CAMERA
         # ray casting on the crop
@@ -102,8 +143,10 @@ class SyntheticSceneDataset:
         label = np.zeros((H, W), np.uint8)
         shade = np.zeros((H, W))
         for o in range(oc):
+            if present is not None and not present[o]:
+                continue
             R, t = poses[o, :, :3], poses[o, :, 3]
-            inv = 1.0 / self.axes[o]
+            inv = 1.0 / axes[o]
             d = (rays @ R) * inv           # ray direction in the unit-sphere frame (R^T r, scaled)
             c = (-(R.T @ t)) * inv         # camera centre in that frame
             a = (d * d).sum(-1)
@@ -121,7 +164,7 @@ class SyntheticSceneDataset:
         bg = 0.35 + 0.1 * np.sin(xs / 37.0)[..., None] * np.cos(ys / 53.0)[..., None]
         if noise:
             bg = bg + rng.normal(0, 0.02, (H, W, 3))
-        col = np.concatenate([np.zeros((1, 3)), self.colors])[label]
+        col = np.concatenate([np.zeros((1, 3)), colors])[label]
         img[:] = np.where(label[..., None] > 0, col * shade[..., None], bg)
         if noise:
             img = img + rng.normal(0, 0.01, img.shape)
@@ -140,7 +183,37 @@ class SyntheticSceneDataset:
             kp2[o, :, 0], kp2[o, :, 1] = uv[:, 1] - hc, uv[:, 0] - wc
         return kp2, np.array([hc, wc, 0, 0, 0, 0, 0, 1, FULL_W, FULL_H], np.float32)
 
+    def _keypoints_instances(self, hc: int, wc: int, counts: np.ndarray, poses: np.ndarray) -> Tuple[np.ndarray, np.ndarray]:
+        """(kp2 [oc,I,kp,2]: the 2-D keypoints in crop pixels (y,x), -1000 for absent instances; offsets [10])"""
+        K = CAMERA
+        kp2 = np.full((self.oc, self.instances, self.kp, 2), -1000.0)
+        for o in range(self.oc):
+            for r in range(counts[o]):
+                cam = self.keypoints3d[o] @ poses[o, r, :, :3].T + poses[o, r, :, 3]
+                uv = (cam @ K.T)
+                uv = uv[:, :2] / uv[:, 2:]
+                kp2[o, r, :, 0], kp2[o, r, :, 1] = uv[:, 1] - hc, uv[:, 0] - wc
+        return kp2, np.array([hc, wc, 0, 0, 0, 0, 0, 1, FULL_W, FULL_H], np.float32)
+
+    def split_slots(self, slots: np.ndarray) -> Tuple[np.ndarray, np.ndarray]:
+        """slot map (o * I + r + 1, 0 = background: the id convention of pose_estimation/instance_voting.py) -> (class labels, instance_seg), uint8"""
+        s = slots.astype(np.int64)
+        on = s > 0
+        return np.where(on, (s - 1) // self.instances + 1, 0).astype(np.uint8), np.where(on, (s - 1) % self.instances, 0).astype(np.uint8)
+
+    def _render_instances(self, rng, noise: bool = True) -> Dict[str, np.ndarray]:
+        oc, I = self.oc, self.instances
+        hc, wc, inst, poses = self._draw_instances(rng)
+        present = (np.arange(I)[None, :] < inst[:, None]).reshape(-1)
+        img, slots = self._cast(rng, hc, wc, poses.reshape(oc * I, 3, 4), np.repeat(self.axes, I, axis=0), np.repeat(self.colors, I, axis=0), present, noise)
+        label, iseg = self.split_slots(slots)
+        kp2, offsets = self._keypoints_instances(hc, wc, inst, poses)
+        counts = np.array([(label == o + 1).sum() for o in range(oc)], np.int32)
+        return dict(img=img.astype(np.float32), label=label, instance_seg=iseg, instance_count=inst, poses=poses, kp2=kp2, counts=counts, offsets=offsets)
+
     def _render(self, rng, noise: bool = True) -> Dict[str, np.ndarray]:
+        if self.instances > 1:
+            return self._render_instances(rng, noise)
         oc = self.oc
         hc, wc, poses = self._draw(rng)
         img, label = self._pixels(rng, hc, wc, poses, noise)
@@ -151,6 +224,19 @@ class SyntheticSceneDataset:
     def _small_arrays(self, items) -> Dict[str, torch.Tensor]:
         """The batch entries that do not depend on pixels, from per-image dicts with "kp2", "offsets" and "poses"."""
         b = len(items)
+        if self.instances > 1:       # the instance axis; absent instances padded as the reference's reader pads them
+            inst = np.stack([it["instance_count"] for it in items]).astype(np.int32)                       # [b,oc]
+            there = np.arange(self.instances)[None, None, :] < inst[:, :, None]                            # [b,oc,I]
+            k3 = np.where(there[..., None, None], self.keypoints3d[None, :, None], -1000.0)
+            return dict(
+                keypoints3d=torch.from_numpy(k3.astype(np.float32)),
+                target_vert=torch.from_numpy(np.stack([it["kp2"] for it in items]).astype(np.float32)),
+                cam_mat=torch.from_numpy(np.tile(CAMERA[None], (b, 1, 1)).astype(np.float32)),
+                diameters=torch.from_numpy(np.where(there, self.diameters[None, :, None], -1.0).astype(np.float32)),
+                offsets=torch.from_numpy(np.stack([it["offsets"] for it in items])),
+                poses_gt=torch.from_numpy(np.stack([it["poses"] for it in items]).astype(np.float32)),
+                instance_count=torch.from_numpy(inst),
+            )
         return dict(
             keypoints3d=torch.from_numpy(np.tile(self.keypoints3d[None, :, None], (b, 1, 1, 1, 1)).astype(np.float32)),
             target_vert=torch.from_numpy(np.stack([it["kp2"] for it in items])[:, :, None].astype(np.float32)),
@@ -184,6 +270,9 @@ class SyntheticSceneDataset:
         lab = np.stack([it["label"] for it in items])
         seg = np.eye(K1, dtype=np.float32)[lab]
         small = self._small_arrays(items)
+        extra = {}
+        if self.instances > 1:
+            extra = dict(instance_count=small["instance_count"], instance_seg=torch.from_numpy(np.stack([it["instance_seg"] for it in items])))
         return dict(
             img=torch.from_numpy(np.stack([it["img"] for it in items])),
             target_seg=torch.from_numpy(seg),
@@ -195,6 +284,7 @@ class SyntheticSceneDataset:
             filtered_seg=torch.from_numpy(lab[..., None].astype(np.int32)),
             poses_gt=small["poses_gt"],
             pixel_gt_count=torch.from_numpy(np.stack([it["counts"] for it in items]).astype(np.float32)[:, :, None, None]),
+            **extra,
         )
 
     def generate_object_vertex_array(self):

@@ -1185,7 +1185,8 @@ class TrainPlan:
         self.sel_zero = [torch.zeros(B, hs[l], ws[l], **u8) for l in range(3)]  # plain nearest x2
         self.gmask = [torch.empty(B, hs[l], ws[l], **u8) if any(arch.bilinear) else None for l in range(3)]
         self.loss_sums = torch.zeros(3, dtype=torch.float64, device=dev)
-        self.loss_ws = torch.empty(max(lib.cp_pose_loss_workspace_bytes(B, h, w), lib.cp_pose_loss_sep_workspace_bytes(B, h, w, K)), **u8)
+        self.loss_ws = torch.empty(max(lib.cp_pose_loss_workspace_bytes(B, h, w), lib.cp_pose_loss_inst_workspace_bytes(B, h, w),
+                                       lib.cp_pose_loss_sep_workspace_bytes(B, h, w, K)), **u8)
         self.object_loss_values = torch.zeros(B, K - 1, **f32)  # per-object proxy distances (proxy_voting_dist)
         # keypoint-reprojection loss (LS voter forward/backward)
         oc, kp = K - 1, 9
@@ -1643,8 +1644,12 @@ class TrainPlan:
                           "from now on: %s" % (len(out), lo, hi, "; ".join(out)))
 
     def loss_and_grad(self, labels_ce: torch.Tensor, labels_fg: torch.Tensor, keypoints_yx: torch.Tensor, mask_w=1.0, vertex_w=1.0, proxy_w=1.0,
-                      filter_with_segmentation=True, kp: int = 9, filter_high_proxy_errors: bool = False) -> torch.Tensor:
-        """Losses of compute_loss on the last forward's output and d loss / d output into self.dout. Returns fp64 [mask, vertex, proxy]."""
+                      filter_with_segmentation=True, kp: int = 9, filter_high_proxy_errors: bool = False,
+                      inst_counts: Optional[torch.Tensor] = None, inst_map: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """Losses of compute_loss on the last forward's output and d loss / d output into self.dout. Returns fp64 [mask, vertex, proxy].
+        keypoints_yx [B,oc,kp,2]: one keypoint set per object (cp_pose_loss_f32).  keypoints_yx [B,oc,I,kp,2] with inst_counts (int32 [B,oc],
+        every entry in 0..I: the instances of the object present in the image) and optionally inst_map (uint8 [B,h,w], the instance that owns
+        each pixel; without it a pixel follows the instance whose centre is nearest): several instances per object (cp_pose_loss_inst_f32)."""
         lib = _lib.load()
         B, h, w = self.batch, self.h, self.w
         stream = torch.cuda.current_stream(self.out.device).cuda_stream
@@ -1652,8 +1657,13 @@ class TrainPlan:
         # the power of two on the loss (train_bwd_f16x2): on the GRADIENT only -- the kernels' loss sums do not contain the weights
         self._dout_scale = S = 2.0 ** self.loss_exp
         mask_w, vertex_w, proxy_w = mask_w * S, vertex_w * S, proxy_w * S
-        assert tuple(keypoints_yx.shape) == (B, self.seg_dim - 1, kp, 2) and keypoints_yx.is_contiguous()
         oc = self.seg_dim - 1
+        if keypoints_yx.dim() == 5:
+            return self._loss_and_grad_instances(labels_ce, labels_fg, keypoints_yx, mask_w, vertex_w, proxy_w, filter_with_segmentation, kp,
+                                                 filter_high_proxy_errors, inst_counts, inst_map, stream)
+        if inst_counts is not None or inst_map is not None:
+            raise ValueError("inst_counts / inst_map go with keypoints_yx of shape (B, oc, I, kp, 2); got %s" % (tuple(keypoints_yx.shape),))
+        assert tuple(keypoints_yx.shape) == (B, self.seg_dim - 1, kp, 2) and keypoints_yx.is_contiguous()
         if self.pvnet and oc > 1 and self.ver_dim == oc * 2 * kp:   # separated vector fields: per-object slices (compute_loss, train_casapose.py:57,97-125)
             if filter_high_proxy_errors:
                 raise NotImplementedError("filter_high_proxy_errors with separated vector fields is not built")
@@ -1667,6 +1677,35 @@ class TrainPlan:
                                    self.seg_dim - 1, B, h, w, 1 if filter_with_segmentation else 0, 1 if filter_high_proxy_errors else 0, mask_w, vertex_w,
                                    proxy_w, self.loss_ws.data_ptr(), self.dout.data_ptr(), self.GRAD_LD, self.VERT_OFF, self.loss_sums.data_ptr(),
                                    self.object_loss_values.data_ptr(), stream), "cp_pose_loss_f32")
+        return self.loss_sums
+
+    def _loss_and_grad_instances(self, labels_ce, labels_fg, keypoints_yx, mask_w, vertex_w, proxy_w, filter_with_segmentation, kp,
+                                 filter_high_proxy_errors, inst_counts, inst_map, stream) -> torch.Tensor:
+        """loss_and_grad's second form (the weights already carry the plan's 2^loss_exp)"""
+        B, h, w, oc = self.batch, self.h, self.w, self.seg_dim - 1
+        I = int(keypoints_yx.shape[2])
+        if tuple(keypoints_yx.shape) != (B, oc, I, kp, 2) or not keypoints_yx.is_contiguous():
+            raise ValueError("keypoints_yx must be contiguous (B, oc, I, kp, 2) = (%d, %d, I, %d, 2); got %s" % (B, oc, kp, tuple(keypoints_yx.shape)))
+        if self.pvnet and oc > 1 and self.ver_dim == oc * 2 * kp:
+            raise NotImplementedError("several instances per object with the separated vector fields of `pvnet` are not built")
+        if 2 * kp > self.ver_dim:
+            raise ValueError("the output holds %d vertex channels, fewer than 2 * %d keypoints" % (self.ver_dim, kp))
+        if inst_counts is None:
+            raise ValueError("keypoints_yx with an instance axis needs inst_counts (int32 [B, oc])")
+        counts_host = inst_counts.detach().cpu() if isinstance(inst_counts, torch.Tensor) else torch.as_tensor(inst_counts)
+        if tuple(counts_host.shape) != (B, oc) or counts_host.dtype != torch.int32:
+            raise ValueError("inst_counts must be int32 (B, oc) = (%d, %d); got %s %s" % (B, oc, counts_host.dtype, tuple(counts_host.shape)))
+        if int(counts_host.min()) < 0 or int(counts_host.max()) > I:      # the small array, on the host, before it is uploaded
+            raise ValueError("inst_counts holds %d..%d; every count must be in 0..%d, the instances of keypoints_yx"
+                             % (int(counts_host.min()), int(counts_host.max()), I))
+        counts_dev = counts_host.to(self.out.device).contiguous() if not (isinstance(inst_counts, torch.Tensor) and inst_counts.is_cuda) else inst_counts.contiguous()
+        if inst_map is not None and (inst_map.dtype != torch.uint8 or tuple(inst_map.shape) != (B, h, w) or not inst_map.is_contiguous()):
+            raise ValueError("inst_map must be contiguous uint8 (B, h, w) = (%d, %d, %d); got %s %s" % (B, h, w, inst_map.dtype, tuple(inst_map.shape)))
+        check(_lib.load().cp_pose_loss_inst_f32(self.out.data_ptr(), self.out_ld, self.seg_dim, kp, labels_ce.data_ptr(), labels_fg.data_ptr(),
+                                                keypoints_yx.data_ptr(), oc, I, counts_dev.data_ptr(), inst_map.data_ptr() if inst_map is not None else None,
+                                                B, h, w, 1 if filter_with_segmentation else 0, 1 if filter_high_proxy_errors else 0, mask_w, vertex_w,
+                                                proxy_w, self.loss_ws.data_ptr(), self.dout.data_ptr(), self.GRAD_LD, self.VERT_OFF,
+                                                self.loss_sums.data_ptr(), self.object_loss_values.data_ptr(), stream), "cp_pose_loss_inst_f32")
         return self.loss_sums
 
     def kp_loss_and_grad(self, labels_gt: torch.Tensor, gt_xy: torch.Tensor, affine: torch.Tensor, kp_w: float, max_pixel_error: float = 25.0,

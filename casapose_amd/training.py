@@ -146,6 +146,37 @@ def device_bpnp_from_environment(plan, n_points: int, device):
     return kept[int(n_points)]
 
 
+TRAIN_INSTANCE_RULE_ENV = "CASAPOSE_TRAIN_INSTANCE_RULE"
+
+
+def _instance_targets(net, batch, opt, kpts, fg, dev) -> Dict[str, Optional[torch.Tensor]]:
+    """train_step with target_vert [B,oc,I,kp,2], I > 1 (several instances of one object per image): the keywords of the plan's loss_and_grad.
+    batch["instance_count"] (int32 [B,oc]) is required; batch["instance_seg"] (uint8 [B,H,W], the instance that owns each pixel), when present, is
+    the rule -- unless CASAPOSE_TRAIN_INSTANCE_RULE=nearest asks for the reference's (the instance whose centre is nearest).  What is per object in
+    the other losses is refused by name."""
+    I = int(kpts.shape[2])
+    rule = os.environ.get(TRAIN_INSTANCE_RULE_ENV, "map")
+    if rule not in ("map", "nearest"):
+        raise ValueError("%s=%r: the allowed values are unset or `map`, and `nearest`" % (TRAIN_INSTANCE_RULE_ENV, rule))
+    if getattr(opt, "estimate_coords", False):
+        raise NotImplementedError("estimate_coords (the keypoint / BPnP loss) with %d instances per object: the voter and its targets are per object" % I)
+    if net.arch.pvnet and net.seg_dim > 2 and net.ver_dim == (net.seg_dim - 1) * 2 * int(kpts.shape[3]):
+        raise NotImplementedError("the separated-field `pvnet` loss with %d instances per object is not built" % I)
+    if batch.get("instance_count") is None:
+        raise ValueError("target_vert holds %d instances per object: the batch needs instance_count (int32 [B, oc])" % I)
+    counts = torch.as_tensor(batch["instance_count"]).to(torch.int32)
+    imap = None
+    if rule == "map" and batch.get("instance_seg") is not None:
+        imap = torch.as_tensor(batch["instance_seg"]).to(device=dev, dtype=torch.uint8).contiguous()
+        n = torch.cat([torch.zeros((counts.shape[0], 1), dtype=torch.int64, device=dev), counts.to(device=dev, dtype=torch.int64).clamp(min=0)], 1)
+        per_px = torch.gather(n, 1, fg.reshape(fg.shape[0], -1).long()).reshape(fg.shape)
+        orphans = int(((fg != 0) & (imap.long() >= per_px)).sum())
+        if orphans:
+            raise ValueError("filtered_seg disagrees with instance_seg: %d foreground pixel(s) name an instance their object does not have in that "
+                             "image (instance_count)" % orphans)
+    return {"inst_counts": counts, "inst_map": imap}
+
+
 def train_step(net, batch: Dict[str, torch.Tensor], loss_factors, optimizer: Optional[Adam], opt, group=None, world_size: int = 1,
                train: bool = True, coords: Optional[torch.Tensor] = None, min_num: int = 50, min_num_gt: Optional[int] = None,
                filter_with_gt: bool = True):
@@ -166,7 +197,8 @@ def train_step(net, batch: Dict[str, torch.Tensor], loss_factors, optimizer: Opt
     fg = labels_from_onehot(batch["filtered_seg"].to(dev)) if (train and batch.get("filtered_seg") is not None) else labels
     kpts = batch["target_vert"].to(device=dev, dtype=torch.float32)
     B, oc = kpts.shape[0], kpts.shape[1]
-    kpts = kpts.reshape(B, oc, -1, 2).contiguous()
+    inst = _instance_targets(net, batch, opt, kpts, fg, dev) if kpts.dim() == 5 and kpts.shape[2] > 1 else None
+    kpts = kpts.contiguous() if inst is not None else kpts.reshape(B, oc, -1, 2).contiguous()
     with_gt = bool(getattr(opt, "train_vectors_with_ground_truth", False))
     if train:
         plan.update_moving = True
@@ -178,7 +210,8 @@ def train_step(net, batch: Dict[str, torch.Tensor], loss_factors, optimizer: Opt
         plan.out_view.copy_(out)
     wts = (float(loss_factors.mask_loss_weight), float(loss_factors.vertex_loss_weight), float(loss_factors.proxy_loss_weight))
     sums = plan.loss_and_grad(labels, fg, kpts, *wts, filter_with_segmentation=bool(loss_factors.filter_vertex_with_segmentation),
-                              filter_high_proxy_errors=bool(getattr(loss_factors, "filter_high_proxy_errors", False)) and train and batch.get("pixel_gt_count") is not None)
+                              filter_high_proxy_errors=bool(getattr(loss_factors, "filter_high_proxy_errors", False)) and train and batch.get("pixel_gt_count") is not None,
+                              **(inst or {}))
     kp_w = float(getattr(loss_factors, "kp_loss_weight", 0.0))
     kp_loss = None
     if getattr(opt, "estimate_coords", False):

@@ -717,6 +717,31 @@ int cp_pose_loss_f32(const float* out, int ld, int seg_dim, int kp, const uint8_
  * shape cp_pose_loss_f32 refuses. */
 int cp_pose_loss_workspace_layout(int batch, int h, int w, size_t* offsets /*[5]*/);
 
+/* cp_pose_loss_f32 for SEVERAL INSTANCES of one object per image (the reference's max_count > 1: compute_vertex_hcoords_batch_v3,
+ * image_utils.py:17-63; the instance axis of proxy_voting_loss_v2 / proxy_voting_dist, loss_functions.py:47-203).  Everything as
+ * cp_pose_loss_f32 -- the cross-entropy, the two filters, the normalisations, the gradient row, loss_sums, object_loss_values, the workspace
+ * and its five products -- except:
+ *   keypoints_yx  fp32 [batch][objects][instances][kp][2], instances in 1..16
+ *   inst_counts   int32 [batch][objects], required; entry n in 0..instances (the caller checks the range): only instances r < n of the object
+ *                 exist, entries at r >= n are never read into a result (they may hold anything, NaN included)
+ *   inst_map      uint8 [batch][h][w] or null: the 0-based instance of its object that owns the pixel
+ * A foreground pixel of an object with n == 0, or with inst_map[p] >= n, leaves the foreground before anything is counted: fg = 0, not in
+ * count, not in the object sums, no vertex or proxy term.
+ * inst_map == null, the reference's rule: the vertex target is the unit vector to the keypoints of the instance whose keypoint 0 is nearest
+ * to the pixel centre (first minimum over r < n); the proxy distance of keypoint j is the minimum over r < n of |v_y a_x - v_x a_y| / |v|
+ * (first minimum, independently per keypoint), its gradient goes through that instance, and the per-object sums use the same minimum.
+ * inst_map given, the exact rule: both terms use instance inst_map[p].
+ * With instances == 1, every count 1 and no map the maps, counts, object products and dout are cp_pose_loss_f32's byte for byte.
+ * Refused before any launch: a null inst_counts, instances outside 1..16, and whatever cp_pose_loss_f32 refuses.
+ * cp_pose_loss_inst_workspace_bytes / _layout: the size and the five offsets of cp_pose_loss_workspace_bytes / _layout. */
+size_t cp_pose_loss_inst_workspace_bytes(int batch, int h, int w);
+int cp_pose_loss_inst_workspace_layout(int batch, int h, int w, size_t* offsets /*[5]*/);
+int cp_pose_loss_inst_f32(const float* out, int ld, int seg_dim, int kp, const uint8_t* labels_ce, const uint8_t* labels_fg,
+                          const float* keypoints_yx, int objects, int instances, const int32_t* inst_counts, const uint8_t* inst_map,
+                          int batch, int h, int w, int filter_with_segmentation, int filter_high_proxy_errors, float mask_w, float vertex_w,
+                          float proxy_w, void* ws, float* dout, int dld, int vert_off, double* loss_sums, float* object_loss_values,
+                          void* stream);
+
 /* compute_loss for the `pvnet` model with SEPARATED vector fields (train_casapose.py:57,97-125): the output holds seg_dim logits followed by
  * objects*2*kp direction channels, object o in [seg_dim + o*2kp, seg_dim + (o+1)*2kp).  vertex = sum over objects of smooth_l1_loss(slice,
  * target slice, one-hot of the object), proxy = sum over objects of proxy_voting_loss_v2(slice, the object's keypoints, one-hot of the object):
@@ -1020,6 +1045,15 @@ int cp_render_scenes_f32(const double* records, int b, int oc, int H, int W, int
                          int32_t* counts, void* stream);
 int cp_render_scenes_host_f32(const double* records, int b, int oc, int H, int W, int noise, float* img, uint8_t* label, float* target_seg,
                               int32_t* counts);
+
+/* Scenes with several instances of one object (csrc/slot_labels.hip): cp_render_scenes_f32 is given objects * instances slots, slot
+ * o * instances + r being instance r of object o (an absent instance's record placed behind the camera), so its label map is the slot map
+ * `o * instances + r + 1`, 0 on background.  This pass turns slots uint8 [batch][pixels_per_image] into label uint8 (the class
+ * (slot - 1) / instances + 1), instance_seg uint8 ((slot - 1) % instances; both 0 on background and for a slot above objects * instances),
+ * target_seg fp32 [batch][pixels_per_image][objects + 1] (the one-hot of the class) and counts int32 [batch][objects] (pixels of each class).
+ * instances in 1..16, objects * instances <= 254.  Integer atomics only: the same bits on every run. */
+int cp_slot_labels_u8(const uint8_t* slots, int batch, int objects, int instances, long long pixels_per_image, uint8_t* label,
+                      uint8_t* instance_seg, float* target_seg, int32_t* counts, void* stream);
 
 /* ---- segmentation masks of BOP frames (csrc/masks.hip, csrc/mask_math.h) ----------------------------------------------------------------
  * The compute step of the dataset converter (data_handler/bop_converter.py, the reference's create_ndds_mask): every instance's mesh

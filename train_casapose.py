@@ -40,9 +40,31 @@ def create_dir(path):
     os.makedirs(path, exist_ok=True)
 
 
+TRAIN_INSTANCES_ENV = "CASAPOSE_TRAIN_INSTANCES"
+
+
+def train_instances_from_environment(spec):
+    """CASAPOSE_TRAIN_INSTANCES=I (2..16): the synthetic training source (`--data synthetic[:N]`) draws up to I instances of every object per
+    image (SyntheticSceneDataset(instances=I)) and the step trains on them.  Unset: one instance, as ever.  It applies to --data alone; --datatest
+    keeps one instance per object, so every evaluation path stays as it is."""
+    raw = os.environ.get(TRAIN_INSTANCES_ENV)
+    if raw is None:
+        return 1
+    try:
+        n = int(raw)
+    except ValueError:
+        n = 0
+    if not 2 <= n <= 16:
+        raise SystemExit("%s=%r: the allowed values are 2..16 (unset it for one instance per object)" % (TRAIN_INSTANCES_ENV, raw))
+    if not spec.startswith("synthetic"):
+        raise SystemExit("%s applies to `--data synthetic[:N]` only: the folder reader keeps one instance per object (got --data %s)" % (TRAIN_INSTANCES_ENV, spec))
+    return n
+
+
 def open_dataset(spec, opt, no_objects, image_size, random_crop, seed):
     if spec == "":
         return None
+    instances = train_instances_from_environment(spec) if random_crop else 1      # random_crop marks the training source, --data
     if not spec.startswith("synthetic"):  # an NDDS / converted-BOP folder tree (the reference's format)
         from casapose_amd.data_handler.vectorfield_dataset import VectorfieldDataset
 
@@ -58,6 +80,9 @@ def open_dataset(spec, opt, no_objects, image_size, random_crop, seed):
                                   random_translation=(0, 0), random_rotation=0, random_crop=False, use_validation_split=(opt.data == opt.datatest),
                                   train_validation_split=opt.train_validation_split, wxyz_quaterion_input=opt.datatest_wxyz_quaterion, seed=seed)
     n = int(spec.split(":")[1]) if ":" in spec else 64
+    if instances > 1:
+        print("training input: synthetic scenes with up to %d instances per object (%s)" % (instances, TRAIN_INSTANCES_ENV))
+        return SyntheticSceneDataset(no_objects, image_size, opt.no_points, length=n, seed=seed, random_crop=random_crop, instances=instances)
     return SyntheticSceneDataset(no_objects, image_size, opt.no_points, length=n, seed=seed, random_crop=random_crop)
 
 
