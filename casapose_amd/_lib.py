@@ -220,12 +220,16 @@ TWIN_VARIANTS = {d: _PAIRS[d] for d in ("cp_pnp_weighted_f64",)}
 TWIN_STEPS = {d: _PAIRS[d] for d in ("cp_depth_icp_step_f64", "cp_contour_step_f64", "cp_mask_edt_u16")}
 # cp_pose_verify_i32 reads another kernel's output (the renderer's planes and records) and rewrites nothing: a reader.
 TWIN_READERS = {d: _PAIRS[d] for d in ("cp_pose_verify_i32",)}
-TWINS = {d: h for d, h in _PAIRS.items() if d not in TWIN_VARIANTS and d not in TWIN_STEPS and d not in TWIN_READERS}
+# cp_render_shaded_f32 is cp_render_masks_u8's geometry with a colour output: the pair is listed as that kernel's output variant, beside the
+# argument variants above, and TWINS keeps one row per kernel.
+TWIN_OUTPUT_VARIANTS = {d: _PAIRS[d] for d in ("cp_render_shaded_f32",)}
+TWINS = {d: h for d, h in _PAIRS.items()
+         if d not in TWIN_VARIANTS and d not in TWIN_OUTPUT_VARIANTS and d not in TWIN_STEPS and d not in TWIN_READERS}
 
 
 def host_twin(name: str) -> Optional[str]:
-    """the host twin of the device entry point `name` (a kernel's, a weighted variant's, a follow-up step's or a reader's), or None"""
-    return TWINS.get(name) or TWIN_VARIANTS.get(name) or TWIN_STEPS.get(name) or TWIN_READERS.get(name)
+    """the host twin of the device entry point `name` (a kernel's, a variant's, a follow-up step's or a reader's), or None"""
+    return TWINS.get(name) or TWIN_VARIANTS.get(name) or TWIN_OUTPUT_VARIANTS.get(name) or TWIN_STEPS.get(name) or TWIN_READERS.get(name)
 
 
 _lib: Optional[C.CDLL] = None

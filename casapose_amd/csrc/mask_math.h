@@ -59,13 +59,20 @@ MASK_HD size_t workspace_bytes(int frames, int instances_max, int H, int W) {
 
 MASK_HD int64_t sample_origin(double sample_offset) { return (int64_t)rint(256.0 * sample_offset); }
 
+// rule 1: the camera point of one vertex (shade_math.h takes its face normals from the same three points)
+MASK_HD void camera_point(const float* v, const double* P, double& X, double& Y, double& Z) {
+#pragma clang fp contract(off)
+    const double x = (double)v[0], y = (double)v[1], z = (double)v[2];
+    X = ((P[0] * x + P[1] * y) + P[2] * z) + P[3];
+    Y = ((P[4] * x + P[5] * y) + P[6] * z) + P[7];
+    Z = ((P[8] * x + P[9] * y) + P[10] * z) + P[11];
+}
+
 // rules 1, 2 and 6 for one vertex; false: the triangle is dropped
 MASK_HD bool camera_vertex(const float* v, const double* P, const Camera& cam, double near, int64_t& U, int64_t& V, double& Z) {
 #pragma clang fp contract(off)
-    const double x = (double)v[0], y = (double)v[1], z = (double)v[2];
-    const double X = ((P[0] * x + P[1] * y) + P[2] * z) + P[3];
-    const double Y = ((P[4] * x + P[5] * y) + P[6] * z) + P[7];
-    Z = ((P[8] * x + P[9] * y) + P[10] * z) + P[11];
+    double X, Y;
+    camera_point(v, P, X, Y, Z);
     if (!(Z >= near)) return false;   // also NaN
     const double su = 256.0 * ((cam.fx * X) / Z + cam.cx);
     const double sv = 256.0 * ((cam.fy * Y) / Z + cam.cy);

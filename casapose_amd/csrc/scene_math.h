@@ -105,6 +105,25 @@ SCENE_HD void pixel_normals(uint64_t seed, uint32_t pixel, float* normals) {
     normals[5] = r2 * sinf(t2);
 }
 
+// the procedural background at frame coordinates (xs, ys) of a pixel centre (shade_math.h draws the same wave behind its meshes)
+SCENE_HD double background_wave(double xs, double ys) {
+#pragma clang fp contract(off)
+    return 0.35 + (0.1 * sin(xs / 37.0)) * cos(ys / 53.0);
+}
+
+// the last steps of one pixel whose channels v are in [0, 1] before noise: N(0, 0.02) when it is a background pixel, N(0, 0.01) on every
+// pixel, clip(., 0, 1) * 2 - 1 and the one rounding to fp32.  noise = false reads no normal.
+SCENE_HD void finish_pixel(const double* v, bool background, bool noise, const float* normals, float* rgb) {
+#pragma clang fp contract(off)
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+        const double b = background && noise ? v[c] + 0.02 * (double)normals[c] : v[c];
+        double w = noise ? b + 0.01 * (double)normals[3 + c] : b;
+        w = w < 0.0 ? 0.0 : (w > 1.0 ? 1.0 : w);
+        rgb[c] = (float)(w * 2.0 - 1.0);
+    }
+}
+
 // the colour of one pixel in [-1, 1]: colours[label - 1] * shade or the background wave, N(0, 0.02) on background pixels, N(0, 0.01)
 // everywhere, clip(., 0, 1) * 2 - 1.  noise = false gives the noise-free image and reads no normal.
 SCENE_HD void shade_pixel(const double* rec, int label, double shade, double xs, double ys, bool noise, const float* normals, float* rgb) {
@@ -115,16 +134,11 @@ SCENE_HD void shade_pixel(const double* rec, int label, double shade, double xs,
 #pragma unroll
         for (int c = 0; c < 3; ++c) v[c] = colour[c] * shade;
     } else {
-        const double bg = 0.35 + (0.1 * sin(xs / 37.0)) * cos(ys / 53.0);
+        const double bg = background_wave(xs, ys);
 #pragma unroll
-        for (int c = 0; c < 3; ++c) v[c] = noise ? bg + 0.02 * (double)normals[c] : bg;
+        for (int c = 0; c < 3; ++c) v[c] = bg;
     }
-#pragma unroll
-    for (int c = 0; c < 3; ++c) {
-        double w = noise ? v[c] + 0.01 * (double)normals[3 + c] : v[c];
-        w = w < 0.0 ? 0.0 : (w > 1.0 ? 1.0 : w);
-        rgb[c] = (float)(w * 2.0 - 1.0);
-    }
+    finish_pixel(v, label == 0, noise, normals, rgb);
 }
 
 // one image, serially: what cp_render_scenes_host_f32 runs per record.  der is caller-provided scratch of DERIVED * oc words.

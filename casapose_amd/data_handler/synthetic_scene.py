@@ -56,6 +56,8 @@ def _fibonacci_sphere(n: int) -> np.ndarray:
 
 
 class SyntheticSceneDataset:
+    distance = (650.0, 1100.0)   # the range an instance's depth is drawn from, mm (MeshSceneDataset sets its own)
+
     def __init__(self, no_objects: int, image_size: Tuple[int, int] = (448, 448), no_points: int = 9, length: int = 64, seed: int = 0,
                  mesh_vertices: int = 642, random_crop: bool = True, instances: int = 1):
         if no_points != 9:
@@ -94,7 +96,7 @@ class SyntheticSceneDataset:
         # poses: centres spread over the crop, in front of the camera
         poses = np.zeros((oc, 3, 4))
         for o in range(oc):
-            z = rng.uniform(650.0, 1100.0)
+            z = rng.uniform(*self.distance)
             u = rng.uniform(wc + 0.12 * W, wc + 0.88 * W)
             v = rng.uniform(hc + 0.12 * H, hc + 0.88 * H)
             poses[o, :, :3] = _rot(rng)
@@ -118,7 +120,7 @@ class SyntheticSceneDataset:
         for o in range(oc):
             counts[o] = int(rng.integers(1, I + 1))
             for r in range(counts[o]):
-                z = rng.uniform(650.0, 1100.0)
+                z = rng.uniform(*self.distance)
                 u = rng.uniform(wc + 0.12 * W, wc + 0.88 * W)
                 v = rng.uniform(hc + 0.12 * H, hc + 0.88 * H)
                 poses[o, r, :, :3] = _rot(rng)

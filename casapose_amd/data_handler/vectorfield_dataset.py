@@ -130,6 +130,49 @@ _PLY_TYPES = {"float": "<f4", "float32": "<f4", "double": "<f8", "float64": "<f8
               "short": "<i2", "int16": "<i2", "ushort": "<u2", "uint16": "<u2", "int": "<i4", "int32": "<i4", "uint": "<u4", "uint32": "<u4"}
 
 
+def read_vertex_colors(path: str):
+    """Per-vertex colours uint8 [V, 3] of a .ply whose vertex element (the first element, as read_vertices expects it) has uchar `red`, `green`
+    and `blue` properties, ascii or binary_little_endian.  A PLY without them, and an .obj file, give None."""
+    if path.lower().endswith(".obj"):
+        return None
+    with open(path, "rb") as f:
+        if f.readline().strip() != b"ply":
+            raise ValueError("%s: not a PLY file" % path)
+        fmt, count, props, in_vertex = None, 0, [], False
+        while True:
+            line = f.readline()
+            if not line:
+                raise ValueError("%s: truncated PLY header" % path)
+            tok = line.decode("ascii", "replace").split()
+            if not tok:
+                continue
+            if tok[0] == "format":
+                fmt = tok[1]
+            elif tok[0] == "element":
+                in_vertex = tok[1] == "vertex"
+                if in_vertex:
+                    count = int(tok[2])
+            elif tok[0] == "property" and in_vertex:
+                props.append((tok[1], tok[-1]))
+            elif tok[0] == "end_header":
+                break
+        names = [p[1] for p in props]
+        if not all(c in names and props[names.index(c)][0] in ("uchar", "uint8") for c in ("red", "green", "blue")):
+            return None
+        if fmt == "ascii":
+            ix = [names.index(c) for c in ("red", "green", "blue")]
+            rows = [f.readline().split() for _ in range(count)]
+            return np.asarray([[int(r[i]) for i in ix] for r in rows], np.uint8).reshape(-1, 3)
+        if fmt != "binary_little_endian":
+            raise ValueError("%s: unsupported PLY format %s" % (path, fmt))
+        for t, _ in props:
+            if t not in _PLY_TYPES:
+                raise ValueError("%s: unsupported PLY property type %s" % (path, t))
+        dt = np.dtype([(n, _PLY_TYPES[t]) for t, n in props])
+        data = np.frombuffer(f.read(count * dt.itemsize), dtype=dt, count=count)
+        return np.stack([data["red"], data["green"], data["blue"]], axis=1).astype(np.uint8)
+
+
 def _fan(poly) -> List[Tuple[int, int, int]]:
     return [(poly[0], poly[k], poly[k + 1]) for k in range(1, len(poly) - 1)]
 
@@ -276,6 +319,15 @@ class VectorfieldDataset:
             raise NotImplementedError("use_imgaug with color_input off (the reference's seq_grayscale) is not part of this build")
         if separated_vectorfields:
             raise NotImplementedError("separated vector fields (modelname pvnet) are not part of this build")
+        # `meshes:<folder>[:N]` in place of a tree: the scenes are rendered from the meshes (mesh_scene.py) and this object only hands the
+        # caller's image size and object count on to a MeshSceneDataset.  test_casapose.py's folder branch builds this class, so the script
+        # takes `--datatest meshes:` as it stands; path_meshes and the augmentation arguments do not apply to such a source.
+        self.mesh_spec = str(root) if str(root).startswith("meshes:") else None
+        self._mesh_scenes = None
+        if self.mesh_spec is not None:
+            self.no_points, self.objectsofinterest, self.random_crop, self.use_imgaug = no_points, list(objectsofinterest), random_crop, False
+            self.seed = int(_shared_random_seed() if seed is None else seed)
+            return
         self.path_meshes, self.no_points, self.color_input, self.normal = path_meshes, no_points, color_input, list(normal)
         self.objectsofinterest = list(objectsofinterest)
         self.noise, self.random_translation, self.random_rotation, self.random_crop = noise, random_translation, random_rotation, random_crop
@@ -303,7 +355,18 @@ class VectorfieldDataset:
             raise FileNotFoundError("no <name>.png + <name>.seg.png + <name>.json triples under %s" % root)
 
     def __len__(self):
-        return len(self.imgs)
+        return len(self.mesh_scenes()) if self.mesh_spec is not None else len(self.imgs)
+
+    def mesh_scenes(self, imagesize=(448, 448), no_objects=None):
+        """the MeshSceneDataset behind a `meshes:<folder>[:N]` root, built on first use with the image size and object count known then (N
+        defaults to 32, test_casapose.py's default for `synthetic`)"""
+        if self._mesh_scenes is None:
+            from .mesh_scene import MeshSceneDataset, parse_spec
+
+            folder, n = parse_spec(self.mesh_spec)
+            self._mesh_scenes = MeshSceneDataset(folder, no_objects or len(self.objectsofinterest), tuple(imagesize), self.no_points,
+                                                 length=32 if n is None else n, seed=self.seed, random_crop=self.random_crop)
+        return self._mesh_scenes
 
     # ---- discovery ---------------------------------------------------------------------------------
     def load_meshes(self, path) -> Dict[str, dict]:
@@ -493,6 +556,8 @@ class VectorfieldDataset:
         GPU, up to max(prefetch, 1) batches in flight), the only path that runs use_imgaug."""
         from ..parallel import shard_range
 
+        if self.mesh_spec is not None:
+            return self.mesh_scenes(imagesize, no_objects).generate_dataset(batchsize, epochs, prefetch, shard=shard, device=device)
         if device is not None:
             from .device_pipeline import device_batches
 
@@ -525,6 +590,8 @@ class VectorfieldDataset:
 
     def generate_object_vertex_array(self):
         """(vertex_array [oc, Vmax, 3] in the fixed-transform frame, vertex_count [oc,1]) for ADD / ADD-S (:1047-1074)."""
+        if self.mesh_spec is not None:
+            return self.mesh_scenes().generate_object_vertex_array()
         oc = len(self.objectsofinterest)
         count = np.zeros((oc, 1), np.int32)
         for i, o in enumerate(self.objectsofinterest):

@@ -1,6 +1,6 @@
 """One call path for a kernel and its host twin.
 
-A host twin (`cp_X_host_T` beside `cp_X_T` in include/casapose_hip.h; `_lib.TWINS` finds the pairs, `_lib.TWIN_VARIANTS` their weighted variants, `_lib.TWIN_STEPS` the steps on another kernel's output, `_lib.TWIN_READERS` the readers of one; `_lib.host_twin` reads all four) runs a kernel's arithmetic serially on
+A host twin (`cp_X_host_T` beside `cp_X_T` in include/casapose_hip.h; `_lib.TWINS` finds the pairs, `_lib.TWIN_VARIANTS` their weighted variants, `_lib.TWIN_OUTPUT_VARIANTS` a kernel's geometry with another output, `_lib.TWIN_STEPS` the steps on another kernel's output, `_lib.TWIN_READERS` the readers of one; `_lib.host_twin` reads all five) runs a kernel's arithmetic serially on
 host pointers and takes the kernel's arguments minus the trailing stream.  A wrapper therefore writes its argument list once and hands it to
 `call`; only where the arrays live differs: `array` converts an input and `alloc` makes a set of outputs, on a device or as NumPy arrays.
 

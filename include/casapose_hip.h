@@ -1089,6 +1089,42 @@ int cp_render_masks_host_u8(const float* verts, const int32_t* vert_counts, int 
                             const double* poses, int frames, int instances_max, int H, int W, double near, double far, double sample_offset,
                             uint8_t* label, int32_t* records, void* workspace, size_t workspace_bytes);
 
+/* ---- shaded pictures of meshes (csrc/shade.hip, csrc/shade_math.h) ---------------------------------------------------------------------
+ * cp_render_masks_u8's geometry with a colour output: the image source of `--data meshes:<folder>` (data_handler/mesh_scene.py).  The meshes,
+ * cameras, instance tables, poses, near / far / sample_offset are that entry point's arguments and follow its rules (csrc/mask_math.h rules
+ * 1-6); what is added:
+ *   colors       uint8 [objects][Vmax][3]  per-vertex colours, or null: every object then takes its flat colour
+ *   flat_colors  fp32 [objects][3]         in [0, 1]
+ *   lights       fp64 [frames][8]          the unit light direction in camera space (3), ambient, diffuse, the noise seed (the bit pattern of
+ *                                          a uint64), crop row and crop column (where the procedural background is taken)
+ *   background   uint8 [frames][H][W][3]   or null: scene_math.h's wave at the frame's crop origin
+ *   noise        0: the noise-free image; otherwise N(0, 0.02) per channel on background pixels, then N(0, 0.01) per channel everywhere, the
+ *                Philox words of cp_render_scenes_f32 keyed by the frame's seed and counted by pixel
+ *   img          fp32 [frames][H][W][3] in [-1, 1]: clip(albedo * (ambient + diffuse * max(0, n . l)), 0, 1) * 2 - 1 with the albedo
+ *                interpolated perspective-correctly from the winning triangle's vertex colours and n its flat two-sided face normal
+ *   label        uint8 [frames][H][W]      inst_label of the winning instance, 0 on background: byte for byte cp_render_masks_u8's label
+ *   depth        fp32 [frames][H][W] or null: the winning fp32 depth, 0 on background
+ *   dropped      int32 [frames]            triangles dropped at the near plane or for an index out of range, over the frame's instances
+ *   workspace    cp_render_shaded_workspace_bytes(frames, H, W) = 8 bytes per pixel and frame, 8-byte aligned; cleared by the call.  After it
+ *                the workspace holds per pixel depth_bits << 32 | instance << 24 | triangle of the winner, all ones where nothing was hit
+ * One key per pixel decides visibility: the smallest depth, then the lowest instance index, then the lowest triangle index, so every output
+ * is independent of the order of arrival.  Integer atomics only: two calls with the same inputs give the same bytes.  1 <= frames <= 65535,
+ * instances_max <= 256, Tmax <= 2^24, H, W <= 16384, 0 < near <= far; cp_render_shaded_workspace_bytes returns 0 outside these limits.  Widths
+ * that are a multiple of 4 with 16-byte aligned img / depth and 4-byte aligned label take 16-byte stores; every other case stores element by
+ * element.  The rules are listed in csrc/shade_math.h.  cp_render_shaded_host_f32 runs the same code serially on host pointers and launches
+ * nothing: it works without a GPU.  Added in ABI 302 without changing any earlier entry point. */
+size_t cp_render_shaded_workspace_bytes(int frames, int H, int W);
+int cp_render_shaded_f32(const float* verts, const int32_t* vert_counts, int Vmax, const int32_t* faces, const int32_t* face_counts, int Tmax,
+                         int objects, const double* cams, const int32_t* inst_counts, const int32_t* inst_obj, const int32_t* inst_label,
+                         const double* poses, int frames, int instances_max, int H, int W, double near, double far, double sample_offset,
+                         const uint8_t* colors, const float* flat_colors, const double* lights, const uint8_t* background, int noise, float* img,
+                         uint8_t* label, float* depth, int32_t* dropped, void* workspace, size_t workspace_bytes, void* stream);
+int cp_render_shaded_host_f32(const float* verts, const int32_t* vert_counts, int Vmax, const int32_t* faces, const int32_t* face_counts, int Tmax,
+                              int objects, const double* cams, const int32_t* inst_counts, const int32_t* inst_obj, const int32_t* inst_label,
+                              const double* poses, int frames, int instances_max, int H, int W, double near, double far, double sample_offset,
+                              const uint8_t* colors, const float* flat_colors, const double* lights, const uint8_t* background, int noise,
+                              float* img, uint8_t* label, float* depth, int32_t* dropped, void* workspace, size_t workspace_bytes);
+
 /* ---- BOP's Visible Surface Discrepancy (csrc/vsd.hip, csrc/vsd_math.h) -------------------------------------------------------------------
  * For every pair of a rendered estimate and a rendered ground-truth instance of one image, the integers BOP's VSD error is made of: the pixels
  * of the visible union, of the visible intersection and, per tau, the intersection pixels whose cost |d_g - d_e| / diameter reaches tau (BOP19

@@ -10,6 +10,7 @@ Differences that are forced by this environment and documented in DESIGN.md:
     semantics of MirroredStrategy) instead of one process driving all GPUs; `--batchsize` stays the GLOBAL batch;
   * `--data <folder>` reads an NDDS / converted-BOP tree like the reference (casapose_amd/data_handler/vectorfield_dataset.py);
     `--data synthetic[:N]` selects the built-in ray-cast scene generator (synthetic_scene.py) -- there is no dataset here;
+    `--data meshes:<folder>[:N]` renders scenes from a folder of meshes prepared by util_scripts/make_keypoints.py (mesh_scene.py);
   * checkpoints (`training_checkpoints/ckpt-<n>`, tf.train.Checkpoint in the reference) are .npz files holding the network only,
     like the reference's Checkpoint(network=net); `frozen_model/result_w.h5` is real HDF5 in Keras' save_weights layout
     (casapose_amd/utils/h5_weights.py).
@@ -26,6 +27,7 @@ ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, ROOT)
 
 from casapose_amd import parallel  # noqa: E402
+from casapose_amd.data_handler import mesh_scene  # noqa: E402
 from casapose_amd.data_handler.synthetic_scene import SyntheticSceneDataset  # noqa: E402
 from casapose_amd.pose_estimation.pose_evaluation import estimate_and_evaluate_poses, evaluate_pose_estimates  # noqa: E402
 from casapose_amd.pose_estimation.voting_layers_2d import CoordLSVotingWeighted  # noqa: E402
@@ -56,8 +58,9 @@ def train_instances_from_environment(spec):
         n = 0
     if not 2 <= n <= 16:
         raise SystemExit("%s=%r: the allowed values are 2..16 (unset it for one instance per object)" % (TRAIN_INSTANCES_ENV, raw))
-    if not spec.startswith("synthetic"):
-        raise SystemExit("%s applies to `--data synthetic[:N]` only: the folder reader keeps one instance per object (got --data %s)" % (TRAIN_INSTANCES_ENV, spec))
+    if not (spec.startswith("synthetic") or mesh_scene.is_spec(spec)):
+        raise SystemExit("%s applies to `--data synthetic[:N]` and `--data meshes:<folder>[:N]` only: the folder reader keeps one instance per object "
+                         "(got --data %s)" % (TRAIN_INSTANCES_ENV, spec))
     return n
 
 
@@ -65,6 +68,12 @@ def open_dataset(spec, opt, no_objects, image_size, random_crop, seed):
     if spec == "":
         return None
     instances = train_instances_from_environment(spec) if random_crop else 1      # random_crop marks the training source, --data
+    if mesh_scene.is_spec(spec):  # a folder of meshes, rendered (data_handler/mesh_scene.py)
+        folder, n = mesh_scene.parse_spec(spec)
+        if instances > 1:
+            print("training input: mesh scenes with up to %d instances per object (%s)" % (instances, TRAIN_INSTANCES_ENV))
+        return mesh_scene.MeshSceneDataset(folder, no_objects, image_size, opt.no_points, length=64 if n is None else n, seed=seed, random_crop=random_crop,
+                                           instances=instances)
     if not spec.startswith("synthetic"):  # an NDDS / converted-BOP folder tree (the reference's format)
         from casapose_amd.data_handler.vectorfield_dataset import VectorfieldDataset
 
@@ -147,7 +156,7 @@ def main(argv=None):
     from casapose_amd.data_handler import device_scenes
 
     train_scenes, test_scenes = (isinstance(d, SyntheticSceneDataset) and device_scenes.from_environment() for d in (train_ds, test_ds))
-    if train_scenes or test_scenes:
+    if any(on and type(d) is SyntheticSceneDataset for on, d in ((train_scenes, train_ds), (test_scenes, test_ds))):   # a mesh source says so itself
         print(device_scenes.describe())
     trainingdata, train_batches = gen(train_ds, **({"device": device} if device_input or train_scenes else {})) if train_ds else (None, 0)
     testingdata, test_batches = gen(test_ds, **({"device": device} if test_scenes else {})) if test_ds else (None, 0)
