@@ -26,6 +26,8 @@ namespace {
 constexpr int ROWS = 16;        // rows per strip
 constexpr int MAXKP = 9;        // compile-time bound for the private accumulators
 constexpr int WAVES = 4;
+// the production record [9 logits | 18 directions | 9 confidences]: 36 floats = nine 16-byte vectors, directions at 9, confidences at 27
+constexpr int REC_LD = 36, REC_NV = REC_LD / 4, REC_DIR = 9, REC_CONF = 27;
 
 // softplus = max(x,0) + log1p(exp(-|x|)) on the hardware exp2 / log2 units: with t = exp(-|x|) in (0,1] and u = fl(1 + t),
 // log1p(t) = log(u) + (t - (u - 1)) / u restores the bits the addition drops (error ~1e-7 of the result)
@@ -257,117 +259,135 @@ __global__ __launch_bounds__(256) void ls_accumulate_kernel(const float* __restr
     ls_table_commit(acc_lds, nacc, sums + (size_t)s.img * nacc);
 }
 
-// Fast path for the production record [9 logits | 18 directions | 9 confidences] (ld = 36, 8 objects, 9 keypoints): same strip
-// decomposition and arithmetic as above, but
-//   * the next row segment (64 pixels = 9216 contiguous bytes = nine 16-byte loads per lane) is fetched into registers while the
-//     current one is processed -- the generic kernel waits for every row's memory latency (measured 3.1 TB/s with the arithmetic
-//     removed);
-//   * a lane reads its pixel back from the staging buffer as nine 16-byte LDS reads (144-byte pixel stride: conflict-free) with
-//     compile-time channel positions, instead of 27 scalar reads with 4-way bank conflicts; and
-//   * with given labels (LAB) the wave first reads the labels of its whole 64 x 16 strip (1 KB: four 4-byte loads per lane) and
-//     forms by ballot the 16-bit mask of the row segments that hold a non-zero label.  Only those rows are requested, staged and
-//     processed (a wave-uniform walk over the set bits, still one row ahead); a label-0 pixel never contributed, so the sums are the
-//     same sums.  The component-filtered label map of CoordLSVotingWeighted(filter_estimates=True) keeps a small share of the image.
+// ---- the strip walk of the kernels for the production record (ld = 36, 9 keypoints): same strip decomposition and arithmetic as above ----
+//
+// With given labels the wave first reads the labels of its whole 64 x 16 strip (1 KB: four 4-byte loads per lane) and forms by ballot the
+// 16-bit mask of the row segments that hold a non-zero label.  Only those rows are requested, staged and processed; a label-0 pixel never
+// contributed, so the sums are the same sums.  The component-filtered label map of CoordLSVotingWeighted(filter_estimates=True) keeps a small
+// share of the image.
+struct LsStripLabels {
+    // lw[k] of lane l holds the four labels of row 4k + (l >> 4), columns 4 (l & 15) .. + 3 (a label outside the image reads as 0)
+    unsigned lw[4] = {0u, 0u, 0u, 0u};
+
+    // reads the strip's labels (s decoded, nrows of its rows inside the image); returns the row mask
+    __device__ __forceinline__ unsigned load(const uint8_t* __restrict__ labels, const LsStrip& s, int lane, int nrows, int H, int W) {
+        const uint8_t* lb = labels + ((size_t)s.img * H + s.y0) * W + s.x0;
+        const int lr = lane >> 4, lc = (lane & 15) * 4;
+        const bool words = ((W & 3) == 0) && (((uintptr_t)labels & 3) == 0);  // every row segment starts on a 4-byte boundary
+        const bool inside = lc < s.ncols;
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            const int ry = 4 * k + lr;
+            if (ry < nrows) {
+                const uint8_t* p = lb + (size_t)ry * W + lc;
+                if (words) {
+                    if (inside) lw[k] = *reinterpret_cast<const unsigned*>(p);  // ncols % 4 == 0 here: the word is inside the row
+                } else {
+#pragma unroll
+                    for (int c = 0; c < 4; ++c)
+                        if (lc + c < s.ncols) lw[k] |= (unsigned)p[c] << (8 * c);
+                }
+            }
+        }
+        unsigned rowmask = 0;
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            const unsigned long long bal = __builtin_amdgcn_ballot_w64(lw[k] != 0u);
+#pragma unroll
+            for (int j = 0; j < 4; ++j)
+                if ((bal >> (16 * j)) & 0xffffull) rowmask |= 1u << (4 * k + j);
+        }
+        return rowmask;
+    }
+    // this lane's label in row ry: byte (lane & 3) of the word that lane 16 (ry & 3) + (lane >> 2) holds in lw[ry >> 2]
+    __device__ __forceinline__ int at(int ry, int lane) const {
+        const int k = ry >> 2;
+        const unsigned wsel = (k == 0) ? lw[0] : (k == 1) ? lw[1] : (k == 2) ? lw[2] : lw[3];
+        const unsigned wv = (unsigned)__shfl((int)wsel, ((ry & 3) << 4) + (lane >> 2));
+        return (int)((wv >> (8 * (lane & 3))) & 0xffu);
+    }
+};
+
+// Walks the rows of the strip at (x0, y0) whose bit is set in the wave-uniform rowmask and calls body(ry, gap, r) for each: r is the lane's
+// record, gap tells that rows were skipped since the row before (every lane's label was 0 there, which ends its run of equal labels).
+//   * The next row segment (64 pixels = 9216 contiguous bytes = nine 16-byte loads per lane, nvec of them inside the image) is fetched into
+//     registers while the current one is processed -- the generic kernel waits for every row's memory latency (measured 3.1 TB/s with the
+//     arithmetic removed).
+//   * A lane reads its pixel back from the wave's staging buffer as nine 16-byte LDS reads (144-byte pixel stride: conflict-free) with
+//     compile-time channel positions, instead of 27 scalar reads with 4-way bank conflicts.
+template <class Body>
+__device__ __forceinline__ void ls_walk36(const float* __restrict__ field, int img, int H, int W, int x0, int y0, int nvec, int lane, float4* wstage,
+                                          unsigned rowmask, Body body) {
+    float4 pre[REC_NV];
+    auto issue = [&](int ry) {
+        const float4* g = reinterpret_cast<const float4*>(field + (((size_t)img * H + y0 + ry) * W + x0) * REC_LD);
+#pragma unroll
+        for (int i = 0; i < REC_NV; ++i) {
+            const int v = lane + 64 * i;
+            pre[i] = (v < nvec) ? g[v] : make_float4(0.f, 0.f, 0.f, 0.f);
+        }
+    };
+    unsigned todo = rowmask;
+    int ry = -1, prev = -1;
+    if (todo) {
+        ry = __builtin_ctz(todo);
+        todo &= todo - 1;
+        issue(ry);
+    }
+    while (ry >= 0) {
+#pragma unroll
+        for (int i = 0; i < REC_NV; ++i) wstage[lane + 64 * i] = pre[i];
+        int nxt = -1;
+        if (todo) {
+            nxt = __builtin_ctz(todo);
+            todo &= todo - 1;
+            issue(nxt);  // in flight while this row is processed
+        }
+        __builtin_amdgcn_wave_barrier();
+        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // this wave's LDS writes have landed (the prefetch stays in flight)
+        float r[REC_LD];
+#pragma unroll
+        for (int i = 0; i < REC_NV; ++i) {
+            const float4 q = wstage[lane * REC_NV + i];
+            r[4 * i] = q.x; r[4 * i + 1] = q.y; r[4 * i + 2] = q.z; r[4 * i + 3] = q.w;
+        }
+        body(ry, ry != prev + 1, r);
+        __builtin_amdgcn_wave_barrier();  // all lanes done reading before the next row overwrites
+        prev = ry;
+        ry = nxt;
+    }
+}
+
+// The production record with 8 objects: labels given (LAB) or the arg-max of the nine logits, every row walked then.
 template <bool LAB>
 __global__ __launch_bounds__(256) void ls_accumulate36_kernel(const float* __restrict__ field, const uint8_t* __restrict__ labels, int B, int H,
                                                               int W, double* __restrict__ sums, int strips_x, int strips_y) {
-    constexpr int KP = 9, LD = 36, OBJ = 8, NV = LD / 4;
+    constexpr int KP = 9, OBJ = 8;
     extern __shared__ __attribute__((aligned(16))) char smem_raw[];
     double* acc_lds = reinterpret_cast<double*>(smem_raw);                                // [OBJ][KP][5]
-    float4* stage = reinterpret_cast<float4*>(smem_raw + sizeof(double) * OBJ * KP * 5);   // [WAVES][64*NV]
+    float4* stage = reinterpret_cast<float4*>(smem_raw + sizeof(double) * OBJ * KP * 5);   // [WAVES][64*REC_NV]
 
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     constexpr int nacc = OBJ * KP * 5;
     ls_table_zero(acc_lds, nacc);
 
-    float4* wstage = stage + (size_t)wave * 64 * NV;
+    float4* wstage = stage + (size_t)wave * 64 * REC_NV;
     LsStrip s;
     if (s.find(wave, strips_x, strips_y)) {
         s.decode(lane, strips_x, W);
-        const int img = s.img, x0 = s.x0, y0 = s.y0, ncols = s.ncols;
-        const int nvec = ncols * NV;
+        const int ncols = s.ncols, y0 = s.y0;
         const int nrows = min(ROWS, H - y0);
         const float cx = s.cx(H);
-
-        // ---- the strip's labels and its row mask, before any record is requested ----
-        // lw[k] of lane l holds the four labels of row 4k + (l >> 4), columns 4 (l & 15) .. + 3 (a label outside the image reads as 0).
-        unsigned lw[4] = {0u, 0u, 0u, 0u};
-        unsigned rowmask = (1u << nrows) - 1u;
-        if (LAB) {
-            const uint8_t* lb = labels + ((size_t)img * H + y0) * W + x0;
-            const int lr = lane >> 4, lc = (lane & 15) * 4;
-            const bool words = ((W & 3) == 0) && (((uintptr_t)labels & 3) == 0);  // every row segment starts on a 4-byte boundary
-            rowmask = 0;
-#pragma unroll
-            for (int k = 0; k < 4; ++k) {
-                const int ry = 4 * k + lr;
-                if (ry < nrows) {
-                    const uint8_t* p = lb + (size_t)ry * W + lc;
-                    if (words) {
-                        if (lc < ncols) lw[k] = *reinterpret_cast<const unsigned*>(p);  // ncols % 4 == 0 here: the word is inside the row
-                    } else {
-#pragma unroll
-                        for (int c = 0; c < 4; ++c)
-                            if (lc + c < ncols) lw[k] |= (unsigned)p[c] << (8 * c);
-                    }
-                }
-            }
-#pragma unroll
-            for (int k = 0; k < 4; ++k) {
-                const unsigned long long bal = __builtin_amdgcn_ballot_w64(lw[k] != 0u);
-#pragma unroll
-                for (int j = 0; j < 4; ++j)
-                    if ((bal >> (16 * j)) & 0xffffull) rowmask |= 1u << (4 * k + j);
-            }
-        }
+        LsStripLabels lbl;
+        const unsigned rowmask = LAB ? lbl.load(labels, s, lane, nrows, H, W) : (1u << nrows) - 1u;
 
         LsAcc<KP> acc(acc_lds);
-        float4 pre[NV];
-        auto issue = [&](int ry) {
-            const float4* g = reinterpret_cast<const float4*>(field + (((size_t)img * H + y0 + ry) * W + x0) * LD);
-#pragma unroll
-            for (int i = 0; i < NV; ++i) {
-                const int v = lane + 64 * i;
-                pre[i] = (v < nvec) ? g[v] : make_float4(0.f, 0.f, 0.f, 0.f);
-            }
-        };
-        // this lane's label in row ry: byte (lane & 3) of the word that lane 16 (ry & 3) + (lane >> 2) holds in lw[ry >> 2]
-        auto label_of = [&](int ry) {
-            const int k = ry >> 2;
-            const unsigned wsel = (k == 0) ? lw[0] : (k == 1) ? lw[1] : (k == 2) ? lw[2] : lw[3];
-            const unsigned wv = (unsigned)__shfl((int)wsel, ((ry & 3) << 4) + (lane >> 2));
-            return (int)((wv >> (8 * (lane & 3))) & 0xffu);
-        };
-
-        unsigned todo = rowmask;  // wave-uniform
-        int ry = -1, prev = -1;
-        if (todo) {
-            ry = __builtin_ctz(todo);
-            todo &= todo - 1;
-            issue(ry);
-        }
-        while (ry >= 0) {
-#pragma unroll
-            for (int i = 0; i < NV; ++i) wstage[lane + 64 * i] = pre[i];
-            int nxt = -1;
-            if (todo) {
-                nxt = __builtin_ctz(todo);
-                todo &= todo - 1;
-                issue(nxt);  // in flight while this row is processed
-            }
-            __builtin_amdgcn_wave_barrier();
-            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // this wave's LDS writes have landed (the prefetch stays in flight)
-            float r[LD];
-#pragma unroll
-            for (int i = 0; i < NV; ++i) {
-                const float4 q = wstage[lane * NV + i];
-                r[4 * i] = q.x; r[4 * i + 1] = q.y; r[4 * i + 2] = q.z; r[4 * i + 3] = q.w;
-            }
+        ls_walk36(field, s.img, H, W, s.x0, y0, ncols * REC_NV, lane, wstage, rowmask, [&](int ry, bool gap, const float (&r)[REC_LD]) {
             int lab = 0;
             if (LAB) {
-                lab = label_of(ry);
-                if (ry != prev + 1) acc.enter(0);  // rows in between were skipped: every lane's label was 0 there, which ends its run as before
+                lab = lbl.at(ry, lane);
+                if (gap) acc.enter(0);
             } else {
                 float best = r[0];
 #pragma unroll
@@ -380,15 +400,71 @@ __global__ __launch_bounds__(256) void ls_accumulate36_kernel(const float* __res
                 const float cy = ((float)(y0 + ry) + 0.5f) / (float)H;
 #pragma unroll
                 for (int j = 0; j < KP; ++j) {
-                    const float w = softplus_fast(r[27 + j]);  // softplus (:35)
-                    const float2 n = ls_normal_fast(r[9 + 2 * j], r[9 + 2 * j + 1]);
+                    const float w = softplus_fast(r[REC_CONF + j]);  // softplus (:35)
+                    const float2 n = ls_normal_fast(r[REC_DIR + 2 * j], r[REC_DIR + 2 * j + 1]);
                     ls_add_terms(acc.a[j], n.x, n.y, w, cy, cx);
                 }
             }
-            __builtin_amdgcn_wave_barrier();  // all lanes done reading before the next row overwrites
-            prev = ry;
-            ry = nxt;
-        }
+        });
+        acc.flush();
+    }
+    ls_table_commit(acc_lds, nacc, sums + (size_t)s.img * nacc);
+}
+
+// ls_accumulate36_kernel<true> keyed by slot: a run-time number of table rows, the LDS table [slots][9][5] in front of the staging buffer, the
+// logits not read.  A table of 254 slots is 91 KB, so what a block pays per table entry is kept away from the blocks that have nothing to add:
+// the labels are read BEFORE the table is zeroed, and a block whose four strips hold no label ends there (no zeroing, no commit scan).
+// LS_REWEIGHTED: a reweighted pass; est is the keypoints buffer of the pass before, fp32 [B][slots][9][2], rscale = H / cutoff.
+// LS_MOMENTS: the covariance's pass against the keypoints handed in; rscale = 0 without a cut-off.
+template <int MODE>
+__global__ __launch_bounds__(256) void ls_accumulate36_slots_kernel(const float* __restrict__ field, const uint8_t* __restrict__ labels, int B, int H,
+                                                                    int W, int slots, double* __restrict__ sums, int strips_x, int strips_y,
+                                                                    const float* __restrict__ est, float rscale) {
+    constexpr int KP = 9;
+    extern __shared__ __attribute__((aligned(16))) char smem_raw[];
+    const int nacc = slots * KP * 5;
+    double* acc_lds = reinterpret_cast<double*>(smem_raw);                                            // [slots][KP][5]
+    float4* stage = reinterpret_cast<float4*>(smem_raw + (sizeof(double) * nacc + 15) / 16 * 16);       // [WAVES][64*REC_NV]
+
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    float4* wstage = stage + (size_t)wave * 64 * REC_NV;
+    LsStrip s;
+    const bool has = s.find(wave, strips_x, strips_y);
+    int nvec = 0;
+    float cx = 0.f;
+    LsStripLabels lbl;
+    unsigned rowmask = 0;
+    if (has) {
+        s.decode(lane, strips_x, W);
+        nvec = s.ncols * REC_NV;
+        cx = s.cx(H);
+        rowmask = lbl.load(labels, s, lane, min(ROWS, H - s.y0), H, W);
+    }
+    if (!__syncthreads_or(rowmask != 0u)) return;   // block-uniform: nothing labelled in any of its strips
+    ls_table_zero(acc_lds, nacc);
+
+    if (rowmask) {   // wave-uniform
+        const int img = s.img, y0 = s.y0;
+        LsAcc<KP> acc(acc_lds);
+        LsEst<MODE, KP> pe;
+        ls_walk36(field, img, H, W, s.x0, y0, nvec, lane, wstage, rowmask, [&](int ry, bool gap, const float (&r)[REC_LD]) {
+            if (gap) acc.enter(0);
+            const int l = lbl.at(ry, lane);
+            const int lab = l > slots ? 0 : l;   // a value above `slots` has no table row and is background
+            const bool moved = lab != acc.cur;
+            acc.enter(lab);
+            if (lab > 0) {
+                if (MODE != LS_PLAIN && moved) pe.load(est + (size_t)img * slots * KP * 2, lab, H);
+                const float cy = ((float)(y0 + ry) + 0.5f) / (float)H;
+#pragma unroll
+                for (int j = 0; j < KP; ++j) {
+                    const float w = softplus_fast(r[REC_CONF + j]);  // softplus (:35)
+                    const float2 n = ls_normal_fast(r[REC_DIR + 2 * j], r[REC_DIR + 2 * j + 1]);
+                    ls_add_pixel<MODE>(acc.a[j], n, w, cy, cx, pe.p[MODE != LS_PLAIN ? j : 0], rscale);
+                }
+            }
+        });
         acc.flush();
     }
     ls_table_commit(acc_lds, nacc, sums + (size_t)s.img * nacc);
@@ -559,10 +635,10 @@ __global__ void ls_bwd36_kernel(const float* __restrict__ field, const uint8_t* 
         const long long t = i / W;
         const int y = (int)(t % H), b = (int)(t / H);
         const float cy = ((float)y + 0.5f) / (float)H, cx = ((float)x + 0.5f) / (float)H;
-        float rec[36];
-        const float4* r4 = reinterpret_cast<const float4*>(field + i * 36);
+        float rec[REC_LD];
+        const float4* r4 = reinterpret_cast<const float4*>(field + i * REC_LD);
 #pragma unroll
-        for (int q = 0; q < 9; ++q) {
+        for (int q = 0; q < REC_NV; ++q) {
             const float4 v = r4[q];
             rec[4 * q] = v.x; rec[4 * q + 1] = v.y; rec[4 * q + 2] = v.z; rec[4 * q + 3] = v.w;
         }
@@ -576,8 +652,8 @@ __global__ void ls_bwd36_kernel(const float* __restrict__ field, const uint8_t* 
         const bool reg = rlab > 0 && conf_coef;
 #pragma unroll
         for (int j = 0; j < KP; ++j) {
-            const LsGrad d = ls_bwd_keypoint(rec[27 + j], lab, reg, cy, cx,
-                                             [&] { return make_float2(rec[9 + 2 * j], rec[9 + 2 * j + 1]); },
+            const LsGrad d = ls_bwd_keypoint(rec[REC_CONF + j], lab, reg, cy, cx,
+                                             [&] { return make_float2(rec[REC_DIR + 2 * j], rec[REC_DIR + 2 * j + 1]); },
                                              [&] { return *reinterpret_cast<const float4*>(tab + 4 * j); },
                                              [&] { return conf_coef[b * KP + j]; });
             out[2 * j] += d.dy;
@@ -684,7 +760,80 @@ __global__ void kp_reproj_loss_kernel(const float* __restrict__ coords_yx, const
 
 // the production record [9 logits | 18 directions | 9 confidences], which has kernels of its own; CP_LS_GENERIC (read on every call)
 // sends it to the generic ones
-bool is_record36(int ld, int dir_off, int conf_off) { return ld == 36 && dir_off == 9 && conf_off == 27 && !getenv("CP_LS_GENERIC"); }
+bool is_record36(int ld, int dir_off, int conf_off) { return ld == REC_LD && dir_off == REC_DIR && conf_off == REC_CONF && !getenv("CP_LS_GENERIC"); }
+
+// the solve of a reweighted pass: ls_solve_kernel's value where cp_lsr::solve accepts the reweighted system, otherwise the keypoint is left as
+// the pass before wrote it
+__global__ void ls_robust_solve_kernel(const double* __restrict__ plain, const double* __restrict__ sums, int total, int H, float* __restrict__ out) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= total) return;
+    double p0, p1;
+    if (cp_lsr::solve(sums + (size_t)i * 5, plain[(size_t)i * 5] + plain[(size_t)i * 5 + 2], p0, p1)) {
+        out[2 * i] = (float)p0 * (float)H;
+        out[2 * i + 1] = (float)p1 * (float)H;
+    }
+}
+
+// the finish of the moments pass, one thread per (image, slot, keypoint): cp_lsc::finish of the five sums; the keypoints are only read
+__global__ void ls_cov_finish_kernel(const double* __restrict__ sums, const float* __restrict__ keypoints, int total, int H, float* __restrict__ cov,
+                                     float* __restrict__ stat) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= total) return;
+    const float py = keypoints[2 * i], px = keypoints[2 * i + 1];
+    cp_lsc::finish(sums + (size_t)i * 5, isfinite(py) && isfinite(px), H, cov + (size_t)i * 3, stat + (size_t)i * 2);
+}
+
+constexpr int LS_MAX_LDS = 160 * 1024;   // per workgroup on gfx950
+
+// what cp_ls_vote_slots_f32 refuses, under the name `fn` of the entry point that was called
+int ls_slots_check(const char* fn, const float* field, int ld, int dir_off, int conf_off, const uint8_t* slot_map, int batch, int h, int w, int slots,
+                   int kp, const void* sums_ws, const float* keypoints) {
+    CP_REQUIRE(field && slot_map && sums_ws && keypoints, "%s: null pointer (the slot map is required)", fn);
+    CP_REQUIRE(batch > 0 && h > 0 && w > 0 && slots > 0 && slots < 255, "%s: bad sizes (slots must be in 1..254)", fn);
+    CP_REQUIRE(kp == MAXKP, "%s: built for %d keypoints (got %d)", fn, MAXKP, kp);
+    CP_REQUIRE(ld % 4 == 0 && ld > 0 && ld <= 64 && ((uintptr_t)field & 15) == 0, "%s: ld must be a multiple of 4 (<= 64) and field 16-byte aligned", fn);
+    CP_REQUIRE(dir_off >= 0 && dir_off + 2 * kp <= ld && conf_off >= 0 && conf_off + kp <= ld, "%s: channel offsets outside the pixel record", fn);
+    return CP_OK;
+}
+
+// launches an accumulate kernel, its LDS limit raised first where the launch needs more than the default 64 KB
+template <class... P, class... A>
+int ls_launch(const char* fn, void (*kernel)(P...), dim3 grid, size_t lds, hipStream_t st, A... args) {
+    if (lds > 64 * 1024)   // (the limit counts the kernel's static LDS too: ask for what this launch needs, not for the whole 160 KB)
+        CP_REQUIRE(hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) == hipSuccess,
+                   "%s: cannot raise the kernel's LDS limit to %zu bytes", fn, lds);
+    CP_LAUNCH(kernel, grid, dim3(256), lds, st, args...);
+    return CP_OK;
+}
+
+// zeroes `sums` and accumulates one pass over the slot map into it: the plain pass, a reweighted pass or the covariance's moments pass, the two
+// latter against the estimates `est` (the keypoints buffer).  The production record has a kernel of its own, every other layout takes the
+// generic kernel's walk.
+int ls_slots_accumulate(const char* fn, const float* field, int ld, int dir_off, int conf_off, const uint8_t* slot_map, int batch, int h, int w,
+                        int slots, int kp, int sigmoid_weights, double* sums, LsMode mode, const float* est, float rscale, hipStream_t st) {
+    if (hipMemsetAsync(sums, 0, cp_ls_vote_workspace_bytes(batch, slots, kp), st) != hipSuccess) return cp::check_launch(fn);
+    const int strips_x = (w + 63) / 64, strips_y = (h + ROWS - 1) / ROWS;
+    const int blocks_per_img = (strips_x * strips_y + WAVES - 1) / WAVES;
+    const size_t table = (sizeof(double) * slots * kp * 5 + 15) / 16 * 16;
+    const size_t lds = table + sizeof(float) * WAVES * 64 * ld;
+    static_assert((sizeof(double) * 254 * MAXKP * 5 + 15) / 16 * 16 + sizeof(float) * WAVES * 64 * 64 <= (size_t)LS_MAX_LDS, "254 slots beside ld = 64 fit");
+    const dim3 grid(batch * blocks_per_img);
+    int rc;
+    if (!sigmoid_weights && is_record36(ld, dir_off, conf_off)) {
+        const auto kernel = mode == LS_MOMENTS      ? &ls_accumulate36_slots_kernel<LS_MOMENTS>
+                            : mode == LS_REWEIGHTED ? &ls_accumulate36_slots_kernel<LS_REWEIGHTED>
+                                                    : &ls_accumulate36_slots_kernel<LS_PLAIN>;
+        rc = ls_launch(fn, kernel, grid, lds, st, field, slot_map, batch, h, w, slots, sums, strips_x, strips_y, est, rscale);
+    } else {
+        // the generic kernel with given labels: its table has `objects` rows, and the logits (seg_off) are read only without labels
+        const auto kernel = mode == LS_MOMENTS      ? &ls_accumulate_kernel<MAXKP, LS_MOMENTS>
+                            : mode == LS_REWEIGHTED ? &ls_accumulate_kernel<MAXKP, LS_REWEIGHTED>
+                                                    : &ls_accumulate_kernel<MAXKP, LS_PLAIN>;
+        rc = ls_launch(fn, kernel, grid, lds, st, field, ld, 0, dir_off, conf_off, slot_map, batch, h, w, slots, sums, strips_x, strips_y,
+                       sigmoid_weights ? 1 : 0, est, rscale);
+    }
+    return rc != CP_OK ? rc : cp::check_launch(fn);
+}
 
 }  // namespace
 
@@ -782,224 +931,12 @@ extern "C" int cp_kp_reproj_loss_f32(const float* coords_yx, const float* gt_xy,
 // ---------------------------------------------------------------------------------------------------------------------------------------------
 // Voting keyed by (object, instance): cp_ls_vote_slots_f32 takes the slot map of cp_ccl_instance_labels as its label map and keeps one row of
 // sums per slot.  The logits are not read.  The per-pixel arithmetic, the accumulators and the solve are the ones above.
-namespace {
-
-// ls_accumulate36_kernel<true> with a run-time number of table rows: the same strip walk (labels of the 64 x 16 strip first, row mask by ballot,
-// one row segment prefetched ahead, nine 16-byte LDS reads per pixel) over the production record, the LDS table [slots][9][5] in front of the
-// staging buffer.  A table of 254 slots is 91 KB, so what a block pays per table entry is kept away from the blocks that have nothing to add:
-// the labels are read BEFORE the table is zeroed, and a block whose four strips hold no label ends there (no zeroing, no commit scan).
-// LS_REWEIGHTED: a reweighted pass; est is the keypoints buffer of the pass before, fp32 [B][slots][9][2], rscale = H / cutoff.
-// LS_MOMENTS: the covariance's pass against the keypoints handed in; rscale = 0 without a cut-off.
-template <int MODE>
-__global__ __launch_bounds__(256) void ls_accumulate36_slots_kernel(const float* __restrict__ field, const uint8_t* __restrict__ labels, int B, int H,
-                                                                    int W, int slots, double* __restrict__ sums, int strips_x, int strips_y,
-                                                                    const float* __restrict__ est, float rscale) {
-    constexpr int KP = 9, LD = 36, NV = LD / 4;
-    extern __shared__ __attribute__((aligned(16))) char smem_raw[];
-    const int nacc = slots * KP * 5;
-    double* acc_lds = reinterpret_cast<double*>(smem_raw);                                            // [slots][KP][5]
-    float4* stage = reinterpret_cast<float4*>(smem_raw + (sizeof(double) * nacc + 15) / 16 * 16);       // [WAVES][64*NV]
-
-    const int tid = threadIdx.x, lane = tid & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    float4* wstage = stage + (size_t)wave * 64 * NV;
-    LsStrip s;
-    const bool has = s.find(wave, strips_x, strips_y);
-    int nvec = 0;
-    float cx = 0.f;
-    // lw[k] of lane l holds the four labels of row 4k + (l >> 4), columns 4 (l & 15) .. + 3 (a label outside the image reads as 0)
-    unsigned lw[4] = {0u, 0u, 0u, 0u};
-    unsigned rowmask = 0;
-    if (has) {
-        s.decode(lane, strips_x, W);
-        const int ncols = s.ncols, nrows = min(ROWS, H - s.y0);
-        nvec = ncols * NV;
-        cx = s.cx(H);
-        const uint8_t* lb = labels + ((size_t)s.img * H + s.y0) * W + s.x0;
-        const int lr = lane >> 4, lc = (lane & 15) * 4;
-        const bool words = ((W & 3) == 0) && (((uintptr_t)labels & 3) == 0);  // every row segment starts on a 4-byte boundary
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-            const int ry = 4 * k + lr;
-            if (ry < nrows) {
-                const uint8_t* p = lb + (size_t)ry * W + lc;
-                if (words) {
-                    if (lc < ncols) lw[k] = *reinterpret_cast<const unsigned*>(p);  // ncols % 4 == 0 here: the word is inside the row
-                } else {
-#pragma unroll
-                    for (int c = 0; c < 4; ++c)
-                        if (lc + c < ncols) lw[k] |= (unsigned)p[c] << (8 * c);
-                }
-            }
-        }
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-            const unsigned long long bal = __builtin_amdgcn_ballot_w64(lw[k] != 0u);
-#pragma unroll
-            for (int j = 0; j < 4; ++j)
-                if ((bal >> (16 * j)) & 0xffffull) rowmask |= 1u << (4 * k + j);
-        }
-    }
-    if (!__syncthreads_or(rowmask != 0u)) return;   // block-uniform: nothing labelled in any of its strips
-    ls_table_zero(acc_lds, nacc);
-
-    if (rowmask) {   // wave-uniform
-        const int img = s.img, x0 = s.x0, y0 = s.y0;
-        LsAcc<KP> acc(acc_lds);
-        LsEst<MODE, KP> pe;
-        float4 pre[NV];
-        auto issue = [&](int ry) {
-            const float4* g = reinterpret_cast<const float4*>(field + (((size_t)img * H + y0 + ry) * W + x0) * LD);
-#pragma unroll
-            for (int i = 0; i < NV; ++i) {
-                const int v = lane + 64 * i;
-                pre[i] = (v < nvec) ? g[v] : make_float4(0.f, 0.f, 0.f, 0.f);
-            }
-        };
-        // this lane's label in row ry: byte (lane & 3) of the word that lane 16 (ry & 3) + (lane >> 2) holds in lw[ry >> 2]; a value above
-        // `slots` has no table row and is background
-        auto label_of = [&](int ry) {
-            const int k = ry >> 2;
-            const unsigned wsel = (k == 0) ? lw[0] : (k == 1) ? lw[1] : (k == 2) ? lw[2] : lw[3];
-            const unsigned wv = (unsigned)__shfl((int)wsel, ((ry & 3) << 4) + (lane >> 2));
-            const int l = (int)((wv >> (8 * (lane & 3))) & 0xffu);
-            return l > slots ? 0 : l;
-        };
-
-        unsigned todo = rowmask;
-        int ry = __builtin_ctz(todo), prev = -1;
-        todo &= todo - 1;
-        issue(ry);
-        while (ry >= 0) {
-#pragma unroll
-            for (int i = 0; i < NV; ++i) wstage[lane + 64 * i] = pre[i];
-            int nxt = -1;
-            if (todo) {
-                nxt = __builtin_ctz(todo);
-                todo &= todo - 1;
-                issue(nxt);  // in flight while this row is processed
-            }
-            __builtin_amdgcn_wave_barrier();
-            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // this wave's LDS writes have landed (the prefetch stays in flight)
-            float r[LD];
-#pragma unroll
-            for (int i = 0; i < NV; ++i) {
-                const float4 q = wstage[lane * NV + i];
-                r[4 * i] = q.x; r[4 * i + 1] = q.y; r[4 * i + 2] = q.z; r[4 * i + 3] = q.w;
-            }
-            if (ry != prev + 1) acc.enter(0);  // rows in between were skipped: every lane's label was 0 there, which ends its run
-            const int lab = label_of(ry);
-            const bool moved = lab != acc.cur;
-            acc.enter(lab);
-            if (lab > 0) {
-                if (MODE != LS_PLAIN && moved) pe.load(est + (size_t)img * slots * KP * 2, lab, H);
-                const float cy = ((float)(y0 + ry) + 0.5f) / (float)H;
-#pragma unroll
-                for (int j = 0; j < KP; ++j) {
-                    const float w = softplus_fast(r[27 + j]);  // softplus (:35)
-                    const float2 n = ls_normal_fast(r[9 + 2 * j], r[9 + 2 * j + 1]);
-                    ls_add_pixel<MODE>(acc.a[j], n, w, cy, cx, pe.p[MODE != LS_PLAIN ? j : 0], rscale);
-                }
-            }
-            __builtin_amdgcn_wave_barrier();  // all lanes done reading before the next row overwrites
-            prev = ry;
-            ry = nxt;
-        }
-        acc.flush();
-    }
-    ls_table_commit(acc_lds, nacc, sums + (size_t)s.img * nacc);
-}
-
-// the solve of a reweighted pass: ls_solve_kernel's value where cp_lsr::solve accepts the reweighted system, otherwise the keypoint is left as
-// the pass before wrote it
-__global__ void ls_robust_solve_kernel(const double* __restrict__ plain, const double* __restrict__ sums, int total, int H, float* __restrict__ out) {
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= total) return;
-    double p0, p1;
-    if (cp_lsr::solve(sums + (size_t)i * 5, plain[(size_t)i * 5] + plain[(size_t)i * 5 + 2], p0, p1)) {
-        out[2 * i] = (float)p0 * (float)H;
-        out[2 * i + 1] = (float)p1 * (float)H;
-    }
-}
-
-// the finish of the moments pass, one thread per (image, slot, keypoint): cp_lsc::finish of the five sums; the keypoints are only read
-__global__ void ls_cov_finish_kernel(const double* __restrict__ sums, const float* __restrict__ keypoints, int total, int H, float* __restrict__ cov,
-                                     float* __restrict__ stat) {
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= total) return;
-    const float py = keypoints[2 * i], px = keypoints[2 * i + 1];
-    cp_lsc::finish(sums + (size_t)i * 5, isfinite(py) && isfinite(px), H, cov + (size_t)i * 3, stat + (size_t)i * 2);
-}
-
-constexpr int LS_MAX_LDS = 160 * 1024;   // per workgroup on gfx950
-
-// what cp_ls_vote_slots_f32 refuses, under the name `fn` of the entry point that was called
-int ls_slots_check(const char* fn, const float* field, int ld, int dir_off, int conf_off, const uint8_t* slot_map, int batch, int h, int w, int slots,
-                   int kp, const void* sums_ws, const float* keypoints) {
-    CP_REQUIRE(field && slot_map && sums_ws && keypoints, "%s: null pointer (the slot map is required)", fn);
-    CP_REQUIRE(batch > 0 && h > 0 && w > 0 && slots > 0 && slots < 255, "%s: bad sizes (slots must be in 1..254)", fn);
-    CP_REQUIRE(kp == MAXKP, "%s: built for %d keypoints (got %d)", fn, MAXKP, kp);
-    CP_REQUIRE(ld % 4 == 0 && ld > 0 && ld <= 64 && ((uintptr_t)field & 15) == 0, "%s: ld must be a multiple of 4 (<= 64) and field 16-byte aligned", fn);
-    CP_REQUIRE(dir_off >= 0 && dir_off + 2 * kp <= ld && conf_off >= 0 && conf_off + kp <= ld, "%s: channel offsets outside the pixel record", fn);
-    return CP_OK;
-}
-
-template <class Kernel>
-int ls_raise_lds(const char* fn, Kernel kernel, size_t lds) {
-    if (lds > 64 * 1024)   // (the limit counts the kernel's static LDS too: ask for what this launch needs, not for the whole 160 KB)
-        CP_REQUIRE(hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) == hipSuccess,
-                   "%s: cannot raise the kernel's LDS limit to %zu bytes", fn, lds);
-    return CP_OK;
-}
-
-// zeroes `sums` and accumulates one pass over the slot map into it: the plain pass with est == nullptr, otherwise a reweighted pass (or, with
-// moments, the covariance's pass) against the estimates `est` (the keypoints buffer).  The production record has a kernel of its own, every other layout takes the generic kernel's walk.
-int ls_slots_accumulate(const char* fn, const float* field, int ld, int dir_off, int conf_off, const uint8_t* slot_map, int batch, int h, int w,
-                        int slots, int kp, int sigmoid_weights, double* sums, const float* est, float rscale, hipStream_t st, bool moments = false) {
-    if (hipMemsetAsync(sums, 0, cp_ls_vote_workspace_bytes(batch, slots, kp), st) != hipSuccess) return cp::check_launch(fn);
-    const int strips_x = (w + 63) / 64, strips_y = (h + ROWS - 1) / ROWS;
-    const int blocks_per_img = (strips_x * strips_y + WAVES - 1) / WAVES;
-    const size_t table = (sizeof(double) * slots * kp * 5 + 15) / 16 * 16;
-    const size_t lds = table + sizeof(float) * WAVES * 64 * ld;
-    static_assert((sizeof(double) * 254 * MAXKP * 5 + 15) / 16 * 16 + sizeof(float) * WAVES * 64 * 64 <= (size_t)LS_MAX_LDS, "254 slots beside ld = 64 fit");
-    const dim3 grid(batch * blocks_per_img), block(256);
-    const int sig = sigmoid_weights ? 1 : 0;
-    if (!sigmoid_weights && is_record36(ld, dir_off, conf_off)) {
-        if (est && moments) {
-            if (ls_raise_lds(fn, &ls_accumulate36_slots_kernel<LS_MOMENTS>, lds) != CP_OK) return CP_ERR_INVALID;
-            CP_LAUNCH(ls_accumulate36_slots_kernel<LS_MOMENTS>, grid, block, lds, st, field, slot_map, batch, h, w, slots, sums, strips_x, strips_y, est, rscale);
-        } else if (est) {
-            if (ls_raise_lds(fn, &ls_accumulate36_slots_kernel<LS_REWEIGHTED>, lds) != CP_OK) return CP_ERR_INVALID;
-            CP_LAUNCH(ls_accumulate36_slots_kernel<LS_REWEIGHTED>, grid, block, lds, st, field, slot_map, batch, h, w, slots, sums, strips_x, strips_y, est, rscale);
-        } else {
-            if (ls_raise_lds(fn, &ls_accumulate36_slots_kernel<LS_PLAIN>, lds) != CP_OK) return CP_ERR_INVALID;
-            CP_LAUNCH(ls_accumulate36_slots_kernel<LS_PLAIN>, grid, block, lds, st, field, slot_map, batch, h, w, slots, sums, strips_x, strips_y, est, rscale);
-        }
-    } else if (est && moments) {
-        if (ls_raise_lds(fn, &ls_accumulate_kernel<MAXKP, LS_MOMENTS>, lds) != CP_OK) return CP_ERR_INVALID;
-        CP_LAUNCH((ls_accumulate_kernel<MAXKP, LS_MOMENTS>), grid, block, lds, st, field, ld, 0, dir_off, conf_off, slot_map, batch, h, w, slots, sums, strips_x,
-                  strips_y, sig, est, rscale);
-    } else if (est) {
-        if (ls_raise_lds(fn, &ls_accumulate_kernel<MAXKP, LS_REWEIGHTED>, lds) != CP_OK) return CP_ERR_INVALID;
-        CP_LAUNCH((ls_accumulate_kernel<MAXKP, LS_REWEIGHTED>), grid, block, lds, st, field, ld, 0, dir_off, conf_off, slot_map, batch, h, w, slots, sums, strips_x,
-                  strips_y, sig, est, rscale);
-    } else {
-        if (ls_raise_lds(fn, &ls_accumulate_kernel<MAXKP, LS_PLAIN>, lds) != CP_OK) return CP_ERR_INVALID;
-        // the generic kernel with given labels: its table has `objects` rows, and the logits (seg_off) are read only without labels
-        CP_LAUNCH((ls_accumulate_kernel<MAXKP, LS_PLAIN>), grid, block, lds, st, field, ld, 0, dir_off, conf_off, slot_map, batch, h, w, slots, sums, strips_x,
-                  strips_y, sig, est, rscale);
-    }
-    return cp::check_launch(fn);
-}
-
-}  // namespace
-
 extern "C" int cp_ls_vote_slots_f32(const float* field, int ld, int dir_off, int conf_off, const uint8_t* slot_map, int batch, int h, int w,
                                     int slots, int kp, int sigmoid_weights, double* sums_ws, float* keypoints, void* stream) {
     const char* fn = "cp_ls_vote_slots_f32";
     if (ls_slots_check(fn, field, ld, dir_off, conf_off, slot_map, batch, h, w, slots, kp, sums_ws, keypoints) != CP_OK) return CP_ERR_INVALID;
     hipStream_t st = (hipStream_t)stream;
-    const int rc = ls_slots_accumulate(fn, field, ld, dir_off, conf_off, slot_map, batch, h, w, slots, kp, sigmoid_weights, sums_ws, nullptr, 0.f, st);
+    const int rc = ls_slots_accumulate(fn, field, ld, dir_off, conf_off, slot_map, batch, h, w, slots, kp, sigmoid_weights, sums_ws, LS_PLAIN, nullptr, 0.f, st);
     if (rc != CP_OK) return rc;
     const int total = batch * slots * kp;
     CP_LAUNCH(ls_solve_kernel, dim3((total + 255) / 256), dim3(256), 0, st, sums_ws, total, h, keypoints);
@@ -1022,13 +959,13 @@ extern "C" int cp_ls_vote_slots_robust_f32(const float* field, int ld, int dir_o
     const int total = batch * slots * kp;
     double* plain = static_cast<double*>(workspace);
     double* again = plain + (size_t)total * 5;
-    int rc = ls_slots_accumulate(fn, field, ld, dir_off, conf_off, slot_map, batch, h, w, slots, kp, sigmoid_weights, plain, nullptr, 0.f, st);
+    int rc = ls_slots_accumulate(fn, field, ld, dir_off, conf_off, slot_map, batch, h, w, slots, kp, sigmoid_weights, plain, LS_PLAIN, nullptr, 0.f, st);
     if (rc != CP_OK) return rc;
     CP_LAUNCH(ls_solve_kernel, dim3((total + 255) / 256), dim3(256), 0, st, plain, total, h, keypoints);
     if ((rc = cp::check_launch(fn)) != CP_OK) return rc;
     const float rscale = cp_lsr::rho_scale(h, cutoff_px);
     for (int k = 1; k <= passes; ++k) {
-        rc = ls_slots_accumulate(fn, field, ld, dir_off, conf_off, slot_map, batch, h, w, slots, kp, sigmoid_weights, again, keypoints, rscale, st);
+        rc = ls_slots_accumulate(fn, field, ld, dir_off, conf_off, slot_map, batch, h, w, slots, kp, sigmoid_weights, again, LS_REWEIGHTED, keypoints, rscale, st);
         if (rc != CP_OK) return rc;
         CP_LAUNCH(ls_robust_solve_kernel, dim3((total + 255) / 256), dim3(256), 0, st, plain, again, total, h, keypoints);
         if ((rc = cp::check_launch(fn)) != CP_OK) return rc;
@@ -1048,7 +985,7 @@ extern "C" int cp_ls_slot_covariance_f32(const float* field, int ld, int dir_off
     CP_REQUIRE((((uintptr_t)sums_ws | (uintptr_t)keypoints) & 7) == 0, "%s: the workspace and the keypoints must be 8-byte aligned", fn);
     hipStream_t st = (hipStream_t)stream;
     const float rscale = cutoff_px > 0.f ? cp_lsr::rho_scale(h, cutoff_px) : 0.f;
-    const int rc = ls_slots_accumulate(fn, field, ld, dir_off, conf_off, slot_map, batch, h, w, slots, kp, sigmoid_weights, sums_ws, keypoints, rscale, st, true);
+    const int rc = ls_slots_accumulate(fn, field, ld, dir_off, conf_off, slot_map, batch, h, w, slots, kp, sigmoid_weights, sums_ws, LS_MOMENTS, keypoints, rscale, st);
     if (rc != CP_OK) return rc;
     const int total = batch * slots * kp;
     CP_LAUNCH(ls_cov_finish_kernel, dim3((total + 255) / 256), dim3(256), 0, st, sums_ws, keypoints, total, h, cov, stat);
