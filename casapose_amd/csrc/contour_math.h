@@ -34,23 +34,11 @@
 
 namespace cp_contour {
 
-using cp_icp::Camera;
-using cp_icp::Job;
-using cp_icp::LANES;
-using cp_icp::MAX_SIDE;
-using cp_icp::MAX_SPLIT;
-using cp_icp::N_A;
-using cp_icp::N_B;
-using cp_icp::ST_FEW;
-using cp_icp::ST_OK;
-using cp_icp::ST_REFUSED;
-using cp_icp::ST_SINGULAR;
-using cp_icp::SUMS;
-using cp_icp::TILE;
-using cp_icp::EMPTY;
+using cp_icp::Camera, cp_icp::EMPTY, cp_icp::Job, cp_icp::LANES, cp_icp::MAX_SIDE, cp_icp::MAX_SPLIT, cp_icp::N_A, cp_icp::N_B, cp_icp::SUMS, cp_icp::TILE;
+using cp_icp::ST_FEW, cp_icp::ST_OK, cp_icp::ST_REFUSED, cp_icp::ST_SINGULAR;
+using cp_icp::add_tiles, cp_icp::PARTIAL, cp_icp::step_serial, cp_icp::workspace_bytes;   // the step, on Contour's terms (part B)
 
 constexpr int MAX_GATE = 255;
-constexpr int PARTIAL = SUMS + 2;   // fp64 words of a tile's record: the sums, the used count, the contour count (exact: <= TILE)
 
 // ---- A. the field ---------------------------------------------------------------------------------------------------------------------------
 ICP_HD int clamp_of(int G) { return G * G + 1; }
@@ -113,8 +101,6 @@ inline void edt_serial(const uint8_t* labels, int images, int H, int W, const in
 }
 
 // ---- B. the step ----------------------------------------------------------------------------------------------------------------------------
-ICP_HD size_t step_workspace_bytes(int njobs, int H, int W) { return (size_t)njobs * (size_t)cp_icp::max_tiles(H, W) * PARTIAL * sizeof(double); }
-
 // rules B1 and B8: false when the job is refused.  job: (image, plane, field, gate).  Reads the plane's record only when it returns true.
 ICP_HD bool job_setup(const int32_t* job, const int32_t* records, int nplanes, int nfields, int images, int H, int W, Job& j, int& field, int& G) {
     field = job[2], G = job[3];
@@ -186,48 +172,6 @@ ICP_HD int job_pixel(const Job& j, int s, const uint32_t* plane, const uint16_t*
     return pixel(bc, bl, br, bu, bd, field[at], field[at - 1], field[at + 1], field[at - W], field[at + W], x, y, cam, G, t);
 }
 
-// rule B6 for one tile on the host: the lanes one after the other, then the tree -> sums [SUMS], used, contour
-inline void tile_serial(const Job& j, int tile, const uint32_t* plane, const uint16_t* field, int W, const Camera& cam, int G, double* sums, int& used,
-                        int& contour) {
-#pragma clang fp contract(off)
-    double lane[LANES][SUMS];
-    int cu[LANES], cc[LANES];
-    for (int l = 0; l < LANES; ++l) {
-        cu[l] = cc[l] = 0;
-        for (int k = 0; k < SUMS; ++k) lane[l][k] = 0.0;
-        for (int s = tile * TILE + l; s < (tile + 1) * TILE && s < j.total; s += LANES) {
-            Terms t;
-            const int kind = job_pixel(j, s, plane, field, W, cam, G, t);
-            if (kind == 0) continue;
-            cc[l] += 1;
-            if (kind != 2) continue;
-            add_terms(t, lane[l]);
-            cu[l] += 1;
-        }
-    }
-    for (int off = LANES / 2; off >= 1; off /= 2)
-        for (int l = 0; l < off; ++l) {
-            for (int k = 0; k < SUMS; ++k) lane[l][k] = lane[l][k] + lane[l + off][k];
-            cu[l] += cu[l + off];
-            cc[l] += cc[l + off];
-        }
-    for (int k = 0; k < SUMS; ++k) sums[k] = lane[0][k];
-    used = cu[0], contour = cc[0];
-}
-
-// a job's tile records (PARTIAL words each) added in index order -> sums [SUMS], used, contour
-ICP_HD void add_tiles(const double* partials, int tiles, double* sums, long long& used, long long& contour) {
-#pragma clang fp contract(off)
-    for (int k = 0; k < SUMS; ++k) sums[k] = 0.0;
-    used = contour = 0;
-    for (int t = 0; t < tiles; ++t) {
-        const double* p = partials + (size_t)t * PARTIAL;
-        for (int k = 0; k < SUMS; ++k) sums[k] = sums[k] + p[k];
-        used += (long long)p[SUMS];
-        contour += (long long)p[SUMS + 1];
-    }
-}
-
 // rules B7-B9: the step of one job from its sums.  pose: row-major [3, 4], rewritten only with ST_OK and update != 0.  -> the status
 ICP_HD int solve_update(const double* sums, long long used, long long contour, double damping, int min_pixels, int update, double* pose, double* stats) {
     const int code = cp_icp::solve_update(sums, used, damping, min_pixels, update, pose, stats);
@@ -235,35 +179,47 @@ ICP_HD int solve_update(const double* sums, long long used, long long contour, d
     return code;
 }
 
-// The serial step (what the host twin runs).  planes uint32 [nplanes][H][W], records int32 [nplanes][RECORD], fields uint16 [nfields][H][W],
-// cams double [images][4], jobs int32 [njobs][4], sample: the sample offset (a multiple of 1 / 256), poses double [nplanes][12], stats double [njobs][4], status int32 [njobs], partials:
-// step_workspace_bytes(njobs, H, W) bytes.
-inline void step_serial(const uint32_t* planes, const int32_t* records, int nplanes, int H, int W, const uint16_t* fields, int nfields, const double* cams,
-                        int images, const int32_t* jobs, int njobs, double sample, double damping, int min_pixels, int update, double* poses, double* stats,
-                        int32_t* status, double* partials) {
-    const size_t hw = (size_t)H * (size_t)W, per_job = (size_t)cp_icp::max_tiles(H, W) * PARTIAL;
-    for (int n = 0; n < njobs; ++n) {
-        Job j;
+// The contour refiner's terms for cp_icp's step (icp_math.h says what each member is).  Args: planes uint32 [nplanes][H][W], records int32
+// [nplanes][RECORD], fields uint16 [nfields][H][W], cams double [images][4], jobs int32 [njobs][4], sample: the sample offset (a multiple of 1 / 256)
+struct Contour {
+    static constexpr int COUNTS = 2;   // used pixels, contour pixels
+    struct Args {
+        const uint32_t* planes;
+        const int32_t* records;
+        int nplanes, H, W;
+        const uint16_t* fields;
+        int nfields;
+        const double* cams;
+        int images;
+        const int32_t* jobs;
+        double sample;
+    };
+    struct Context {
+        const uint32_t* plane;
+        const uint16_t* field;
+        int W;
+        Camera cam;
+        int G;
+    };
+    static ICP_HD bool setup(const Args& a, size_t n, Job& j, Context& c) {
         int field, G;
-        double* st = stats + 4 * (size_t)n;
-        if (!job_setup(jobs + 4 * (size_t)n, records, nplanes, nfields, images, H, W, j, field, G)) {
-            st[0] = st[1] = st[2] = st[3] = 0.0;
-            status[n] = ST_REFUSED;
-            continue;
-        }
-        const Camera cam = job_camera(cams + 4 * (size_t)j.image, sample);
-        double* part = partials + (size_t)n * per_job;
-        for (int t = 0; t < j.tiles; ++t) {
-            int used, contour;
-            tile_serial(j, t, planes + (size_t)j.plane * hw, fields + (size_t)field * hw, W, cam, G, part + (size_t)t * PARTIAL, used, contour);
-            part[(size_t)t * PARTIAL + SUMS] = (double)used;
-            part[(size_t)t * PARTIAL + SUMS + 1] = (double)contour;
-        }
-        double sums[SUMS];
-        long long used, contour;
-        add_tiles(part, j.tiles, sums, used, contour);
-        status[n] = solve_update(sums, used, contour, damping, min_pixels, update, poses + 12 * (size_t)j.plane, st);
+        if (!job_setup(a.jobs + 4 * n, a.records, a.nplanes, a.nfields, a.images, a.H, a.W, j, field, G)) return false;
+        const size_t hw = (size_t)a.H * (size_t)a.W;
+        c = {a.planes + (size_t)j.plane * hw, a.fields + (size_t)field * hw, a.W, job_camera(a.cams + 4 * (size_t)j.image, a.sample), G};
+        return true;
     }
-}
+    static ICP_HD void add(const Job& j, const Context& c, int s, double* sums, int* counts) {
+        Terms t;
+        const int kind = job_pixel(j, s, c.plane, c.field, c.W, c.cam, c.G, t);
+        if (kind == 0) return;
+        counts[1] += 1;
+        if (kind != 2) return;
+        add_terms(t, sums);
+        counts[0] += 1;
+    }
+    static ICP_HD int solve(const double* sums, const long long* counts, double damping, int min_pixels, int update, double* pose, double* stats) {
+        return solve_update(sums, counts[0], counts[1], damping, min_pixels, update, pose, stats);
+    }
+};
 
 }  // namespace cp_contour

@@ -15,7 +15,7 @@
 
 using namespace cp_contour;
 using cp_icp::absd;
-using cp_icp::R_BOX;
+using cp_icp::R_BOX_OBJ;
 using cp_icp::RECORD;
 
 static uint32_t bits_of(float z) {
@@ -53,7 +53,7 @@ struct Scene {
         : H(h), W(w), planes((size_t)h * w, EMPTY), records(RECORD, -1), cams{f, f, cx, cy}, poses{1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 1000} {}
     void box(int x0, int y0, int x1, int y1) {
         const int32_t b[4] = {x0, y0, x1 - x0, y1 - y0};
-        std::memcpy(&records[R_BOX], b, sizeof b);
+        std::memcpy(&records[R_BOX_OBJ], b, sizeof b);
     }
     struct Out {
         int32_t status;
@@ -64,12 +64,12 @@ struct Scene {
         const std::vector<int32_t> job = {image, plane, field, gate};
         Out o;
         o.pose = poses;
-        o.partials.assign(step_workspace_bytes(1, H, W) / sizeof(double), 0.0);
+        o.partials.assign(workspace_bytes<Contour>(1, H, W) / sizeof(double), 0.0);
         std::memset(o.partials.data(), fill, o.partials.size() * sizeof(double));
         o.status = -1;
         for (double& s : o.stats) s = -1.0;
-        step_serial(planes.data(), records.data(), 1, H, W, fields.data(), 1, cams.data(), 1, job.data(), 1, sample, 1e-6, min_pixels, update, o.pose.data(), o.stats,
-                    &o.status, o.partials.data());
+        const Contour::Args a = {planes.data(), records.data(), 1, H, W, fields.data(), 1, cams.data(), 1, job.data(), sample};
+        step_serial<Contour>(a, 1, 1e-6, min_pixels, update, o.pose.data(), o.stats, &o.status, o.partials.data());
         return o;
     }
 };
@@ -219,8 +219,9 @@ int main() {
                 ++used;
             }
         double sums[SUMS];
-        long long got_used, got_contour;
-        add_tiles(o.partials.data(), j.tiles, sums, got_used, got_contour);
+        long long got[2];
+        add_tiles<2>(o.partials.data(), j.tiles, sums, got);
+        const long long got_used = got[0], got_contour = got[1];
         EXPECT(got_used == used && got_contour == contour && used > 60 && contour > used && o.stats[0] == (double)used && o.stats[2] == (double)contour,
                "patch: %lld of %lld pixels, the naive loop has %lld of %lld", got_used, got_contour, used, contour);
         for (int k = 0; k < SUMS; ++k)
@@ -239,7 +240,7 @@ int main() {
         EXPECT(again.pose == o.pose && zero.pose == o.pose && std::memcmp(again.stats, o.stats, sizeof o.stats) == 0 &&
                    std::memcmp(zero.stats, o.stats, sizeof o.stats) == 0,
                "patch: the result depends on what the workspace held");
-        EXPECT(std::memcmp(again.partials.data(), o.partials.data(), (size_t)j.tiles * PARTIAL * sizeof(double)) == 0, "patch: the tile records differ");
+        EXPECT(std::memcmp(again.partials.data(), o.partials.data(), (size_t)j.tiles * PARTIAL<Contour> * sizeof(double)) == 0, "patch: the tile records differ");
         const Scene::Out eval = s.run(0, 0, 0, G, 24, 0);
         EXPECT(eval.status == ST_OK && eval.pose == s.poses && eval.stats[1] == o.stats[1], "patch: update = 0 writes stats and status only");
     }

@@ -24,11 +24,18 @@
 //                      are zeros); ST_FEW: fewer than min_pixels pixels were used; ST_SINGULAR: a pivot was not > 0 (a NaN included).  Every
 //                      status but ST_OK leaves the pose as it is
 //  11. stats           fp64 [4]: the pixels used, sqrt(sum r r / pixels) before the update (0 without pixels), |omega|, |v| (0 unless ST_OK)
+//
+// Rules 7-11 do not depend on what a pixel contributes, and contour_math.h has other terms on the same sums.  So the second half of this
+// header is the step of any such refiner, once: the host's tile and job loop, and for hipcc the two kernels and the argument checks that
+// depth_icp.hip and mask_contour.hip share.  A refiner hands them its terms as a struct (Depth below, cp_contour::Contour).
 #pragma once
 #include <stddef.h>
 #include <stdint.h>
 
+#include "plane_record.h"
+
 #if defined(__HIPCC__)
+#include "common.h"   // CP_REQUIRE, for check_step
 #define ICP_HD __host__ __device__ inline
 #else
 #define ICP_HD inline
@@ -42,16 +49,9 @@ namespace cp_icp {
 constexpr int TILE = 1024;               // pixels of a tile: 16 per lane
 constexpr int LANES = 64;
 constexpr int SUMS = 28, N_A = 21, N_B = 6;
-constexpr int PARTIAL = SUMS + 1;        // fp64 words of a tile's record in the workspace: the sums, then the count (exact: <= TILE)
 constexpr int MAX_SPLIT = 64;            // blocks per job
-constexpr int MAX_SIDE = 16384;          // H, W: cp_mask::MAX_SIDE
-constexpr int RECORD = 11, R_BOX = 2;    // cp_mask::RECORD, R_BOX_OBJ
-constexpr uint32_t EMPTY = 0xffffffffu;  // cp_mask::EMPTY
 constexpr int ST_OK = 0, ST_FEW = 1, ST_SINGULAR = 2, ST_REFUSED = 3;
-
-struct Camera {
-    double fx, fy, cx, cy;
-};
+using cp_plane::Box, cp_plane::Camera, cp_plane::clipped_box, cp_plane::depth_of, cp_plane::EMPTY, cp_plane::MAX_SIDE, cp_plane::R_BOX_OBJ, cp_plane::RECORD;
 
 // the pixel rectangle [y0, y0 + bh) x [x0, x0 + bw) a job walks (total = bh * bw pixels in tiles tiles; all zero for an empty box)
 struct Job {
@@ -66,19 +66,11 @@ struct Terms {
 
 ICP_HD double absd(double a) { return a < 0.0 ? -a : a; }
 
-ICP_HD float depth_of(uint32_t bits) {
-    float z;
-    __builtin_memcpy(&z, &bits, sizeof z);
-    return z;
-}
-
 // the tiles of the largest clipped box of an H x W image: what the workspace holds per job
 ICP_HD long long max_tiles(int H, int W) {
     if (H < 3 || W < 3) return 1;
     return ((long long)(H - 2) * (long long)(W - 2) + TILE - 1) / TILE;
 }
-
-ICP_HD size_t workspace_bytes(int njobs, int H, int W) { return (size_t)njobs * (size_t)max_tiles(H, W) * PARTIAL * sizeof(double); }
 
 // rules 1 and 10: false when the job is refused.  job: (image, plane, unused, unused).  Reads the plane's record only when it returns true.
 ICP_HD bool job_setup(const int32_t* job, double gate, const int32_t* records, int nplanes, int images, int H, int W, Job& j) {
@@ -86,13 +78,9 @@ ICP_HD bool job_setup(const int32_t* job, double gate, const int32_t* records, i
     j.x0 = j.y0 = j.bw = j.bh = j.total = j.tiles = 0;
     if (j.image < 0 || j.image >= images || j.plane < 0 || j.plane >= nplanes) return false;
     if (!(gate > 0.0)) return false;
-    const int32_t* rec = records + (size_t)j.plane * RECORD;
-    const int64_t x = rec[R_BOX], y = rec[R_BOX + 1], w = rec[R_BOX + 2], h = rec[R_BOX + 3];
-    if (w < 0 || h < 0) return true;
-    const int64_t x0 = x < 1 ? 1 : x, y0 = y < 1 ? 1 : y;
-    const int64_t x1 = x + w > W - 2 ? W - 2 : x + w, y1 = y + h > H - 2 ? H - 2 : y + h;
-    if (x0 > x1 || y0 > y1) return true;
-    j.x0 = (int)x0, j.y0 = (int)y0, j.bw = (int)(x1 - x0 + 1), j.bh = (int)(y1 - y0 + 1);   // inside [1, W-2] x [1, H-2]
+    Box b;
+    if (!clipped_box(records + (size_t)j.plane * RECORD, H, W, 1, b)) return true;   // nothing to walk is no refusal
+    j.x0 = b.x0, j.y0 = b.y0, j.bw = b.x1 - b.x0 + 1, j.bh = b.y1 - b.y0 + 1;        // inside [1, W-2] x [1, H-2]
     j.total = j.bw * j.bh;   // < 2^28
     j.tiles = (j.total + TILE - 1) / TILE;
     return true;
@@ -173,43 +161,6 @@ ICP_HD bool job_pixel(const Job& j, int s, const uint32_t* plane, const float* s
     return pixel(bc, plane[at - 1], plane[at + 1], plane[at - W], plane[at + W], sensor[at], x, y, cam, gate, jump, t);
 }
 
-// rule 7 for one tile on the host: the lanes one after the other, then the tree -> sums [SUMS], count
-inline void tile_serial(const Job& j, int tile, const uint32_t* plane, const float* sensor, int W, const Camera& cam, double gate, double jump,
-                        double* sums, int& count) {
-#pragma clang fp contract(off)
-    double lane[LANES][SUMS];
-    int cnt[LANES];
-    for (int l = 0; l < LANES; ++l) {
-        cnt[l] = 0;
-        for (int k = 0; k < SUMS; ++k) lane[l][k] = 0.0;
-        for (int s = tile * TILE + l; s < (tile + 1) * TILE && s < j.total; s += LANES) {
-            Terms t;
-            if (!job_pixel(j, s, plane, sensor, W, cam, gate, jump, t)) continue;
-            add_terms(t, lane[l]);
-            cnt[l] += 1;
-        }
-    }
-    for (int off = LANES / 2; off >= 1; off /= 2)
-        for (int l = 0; l < off; ++l) {
-            for (int k = 0; k < SUMS; ++k) lane[l][k] = lane[l][k] + lane[l + off][k];
-            cnt[l] += cnt[l + off];
-        }
-    for (int k = 0; k < SUMS; ++k) sums[k] = lane[0][k];
-    count = cnt[0];
-}
-
-// rule 7's last step: a job's tile records (PARTIAL words each) added in index order -> sums [SUMS], count
-ICP_HD void add_tiles(const double* partials, int tiles, double* sums, long long& count) {
-#pragma clang fp contract(off)
-    for (int k = 0; k < SUMS; ++k) sums[k] = 0.0;
-    count = 0;
-    for (int t = 0; t < tiles; ++t) {
-        const double* p = partials + (size_t)t * PARTIAL;
-        for (int k = 0; k < SUMS; ++k) sums[k] = sums[k] + p[k];
-        count += (long long)p[SUMS];
-    }
-}
-
 // rules 8-11: the step of one job from its sums.  pose: row-major [3, 4], rewritten only with ST_OK and update != 0.  -> the status
 ICP_HD int solve_update(const double* sums, long long count, double damping, int min_pixels, int update, double* pose, double* stats) {
 #pragma clang fp contract(off)
@@ -265,33 +216,224 @@ ICP_HD int solve_update(const double* sums, long long count, double damping, int
     return ST_OK;
 }
 
-// The serial step: the same rules, one loop nest (what the host twin runs).  planes uint32 [nplanes][H][W], records int32 [nplanes][RECORD],
-// depth float [images][H][W], cams double [images][4], jobs int32 [njobs][4], gates double [njobs], poses double [nplanes][12], stats double
-// [njobs][4], status int32 [njobs], partials: workspace_bytes(njobs, H, W) bytes.
-inline void step_serial(const uint32_t* planes, const int32_t* records, int nplanes, int H, int W, const float* depth, const double* cams,
-                        int images, const int32_t* jobs, const double* gates, int njobs, double jump, double damping, int min_pixels, int update,
-                        double* poses, double* stats, int32_t* status, double* partials) {
-    const size_t hw = (size_t)H * (size_t)W, per_job = (size_t)max_tiles(H, W) * PARTIAL;
+// The depth refiner's terms, as the step below takes them from any refiner:
+//   COUNTS   the integer counts of a tile's record, after its SUMS sums (each exact: <= TILE)
+//   Args     one call's arrays and settings (H and W among them): planes uint32 [nplanes][H][W], records int32 [nplanes][RECORD], depth float
+//            [images][H][W], cams double [images][4], jobs int32 [njobs][4], gates double [njobs]
+//   Context  one job's values, its data pointers resolved: what the walk reads
+//   setup    job n of a call -> false when it is refused (nothing is read for it then, and c is left alone)
+//   add      pixel s of the job's box: its terms onto a lane's sums and counts, or nothing
+//   solve    rules 8-11 from a job's totals
+struct Depth {
+    static constexpr int COUNTS = 1;   // the pixels used
+    struct Args {
+        const uint32_t* planes;
+        const int32_t* records;
+        int nplanes, H, W;
+        const float* depth;
+        const double* cams;
+        int images;
+        const int32_t* jobs;
+        const double* gates;
+        double jump;
+    };
+    struct Context {
+        const uint32_t* plane;
+        const float* sensor;
+        int W;
+        Camera cam;
+        double gate, step;   // step = jump gate (rule 2)
+    };
+    static ICP_HD bool setup(const Args& a, size_t n, Job& j, Context& c) {
+#pragma clang fp contract(off)
+        const double gate = a.gates[n];
+        if (!job_setup(a.jobs + 4 * n, gate, a.records, a.nplanes, a.images, a.H, a.W, j)) return false;
+        const size_t hw = (size_t)a.H * (size_t)a.W;
+        const double* cam = a.cams + 4 * (size_t)j.image;
+        c = {a.planes + (size_t)j.plane * hw, a.depth + (size_t)j.image * hw, a.W, {cam[0], cam[1], cam[2], cam[3]}, gate, a.jump * gate};
+        return true;
+    }
+    static ICP_HD void add(const Job& j, const Context& c, int s, double* sums, int* counts) {
+        Terms t;
+        if (!job_pixel(j, s, c.plane, c.sensor, c.W, c.cam, c.gate, c.step, t)) return;
+        add_terms(t, sums);
+        counts[0] += 1;
+    }
+    static ICP_HD int solve(const double* sums, const long long* counts, double damping, int min_pixels, int update, double* pose, double* stats) {
+        return solve_update(sums, counts[0], damping, min_pixels, update, pose, stats);
+    }
+};
+
+// ---- the step of a refiner P: rule 7's order, once for the host and once for the device -----------------------------------------------------
+template <class P>
+constexpr int PARTIAL = SUMS + P::COUNTS;   // fp64 words of a tile's record in the workspace: the sums, then the counts
+
+template <class P>
+ICP_HD size_t workspace_bytes(int njobs, int H, int W) {
+    return (size_t)njobs * (size_t)max_tiles(H, W) * PARTIAL<P> * sizeof(double);
+}
+
+// rule 7 for one tile on the host: the lanes one after the other, then the tree -> the tile's record
+template <class P>
+inline void tile_serial(const Job& j, const typename P::Context& c, int tile, double* record) {
+#pragma clang fp contract(off)
+    double lane[LANES][SUMS];
+    int cnt[LANES][P::COUNTS];
+    for (int l = 0; l < LANES; ++l) {
+        for (int k = 0; k < SUMS; ++k) lane[l][k] = 0.0;
+        for (int k = 0; k < P::COUNTS; ++k) cnt[l][k] = 0;
+        for (int s = tile * TILE + l; s < (tile + 1) * TILE && s < j.total; s += LANES) P::add(j, c, s, lane[l], cnt[l]);
+    }
+    for (int off = LANES / 2; off >= 1; off /= 2)
+        for (int l = 0; l < off; ++l) {
+            for (int k = 0; k < SUMS; ++k) lane[l][k] = lane[l][k] + lane[l + off][k];
+            for (int k = 0; k < P::COUNTS; ++k) cnt[l][k] += cnt[l + off][k];
+        }
+    for (int k = 0; k < SUMS; ++k) record[k] = lane[0][k];
+    for (int k = 0; k < P::COUNTS; ++k) record[SUMS + k] = (double)cnt[0][k];
+}
+
+// rule 7's last step: a job's tile records (SUMS + NCOUNTS words each) added in index order -> sums [SUMS], counts [NCOUNTS]
+template <int NCOUNTS>
+ICP_HD void add_tiles(const double* partials, int tiles, double* sums, long long* counts) {
+#pragma clang fp contract(off)
+    for (int k = 0; k < SUMS; ++k) sums[k] = 0.0;
+    for (int k = 0; k < NCOUNTS; ++k) counts[k] = 0;
+    for (int t = 0; t < tiles; ++t) {
+        const double* p = partials + (size_t)t * (SUMS + NCOUNTS);
+        for (int k = 0; k < SUMS; ++k) sums[k] = sums[k] + p[k];
+        for (int k = 0; k < NCOUNTS; ++k) counts[k] += (long long)p[SUMS + k];
+    }
+}
+
+// The serial step: the same rules, one loop nest (what the host twins run).  poses double [nplanes][12], stats double [njobs][4], status int32
+// [njobs], partials: workspace_bytes<P>(njobs, H, W) bytes.
+template <class P>
+inline void step_serial(const typename P::Args& a, int njobs, double damping, int min_pixels, int update, double* poses, double* stats, int32_t* status,
+                        double* partials) {
+    const size_t per_job = (size_t)max_tiles(a.H, a.W) * PARTIAL<P>;
     for (int n = 0; n < njobs; ++n) {
         Job j;
+        typename P::Context c;
         double* st = stats + 4 * (size_t)n;
-        if (!job_setup(jobs + 4 * (size_t)n, gates[n], records, nplanes, images, H, W, j)) {
+        if (!P::setup(a, (size_t)n, j, c)) {
             st[0] = st[1] = st[2] = st[3] = 0.0;
             status[n] = ST_REFUSED;
             continue;
         }
-        const Camera cam = {cams[4 * j.image], cams[4 * j.image + 1], cams[4 * j.image + 2], cams[4 * j.image + 3]};
         double* part = partials + (size_t)n * per_job;
-        for (int t = 0; t < j.tiles; ++t) {
-            int count;
-            tile_serial(j, t, planes + (size_t)j.plane * hw, depth + (size_t)j.image * hw, W, cam, gates[n], jump * gates[n], part + (size_t)t * PARTIAL, count);
-            part[(size_t)t * PARTIAL + SUMS] = (double)count;
-        }
+        for (int t = 0; t < j.tiles; ++t) tile_serial<P>(j, c, t, part + (size_t)t * PARTIAL<P>);
         double sums[SUMS];
-        long long count;
-        add_tiles(part, j.tiles, sums, count);
-        status[n] = solve_update(sums, count, damping, min_pixels, update, poses + 12 * (size_t)j.plane, st);
+        long long counts[P::COUNTS];
+        add_tiles<P::COUNTS>(part, j.tiles, sums, counts);
+        status[n] = P::solve(sums, counts, damping, min_pixels, update, poses + 12 * (size_t)j.plane, st);
     }
 }
+
+#if defined(__HIPCC__)
+// The same step on the device, two launches.
+// accumulate_kernel: grid (split * jobs) on x, part-major (block b is part b / jobs of job b % jobs: neighbouring blocks are different jobs, so
+//   the parts that have tiles -- often only part 0 -- spread over the XCDs for every split), 256 threads = 4 waves.  A tile of TILE = 1024 pixels
+//   of the job's clipped box belongs to one wave: wave w of block `part` takes tiles part * 4 + w, + split * 4, ...  Pixel s of the box is row
+//   s / bw, column s % bw, so the lanes of a wave read runs of consecutive words of a row of the plane and of the rows above and below.  Lane l
+//   keeps the 28 fp64 sums and the counts of its 16 pixels of the tile, the 64 lanes combine by an xor butterfly (both partners of a pair add
+//   the same two numbers, so every lane ends with the bits of rule 7's tree), and lane k stores word k of the tile's record.  No LDS, no
+//   atomics, and every tile of a job is written: the workspace needs no initialisation and the bits do not depend on split.
+// solve_kernel: one wave per job.  Lane k adds word k of the job's tile records in index order; lane 0 takes the totals from LDS, solves,
+//   rewrites the pose in place (only with ST_OK and update) and writes stats and status.  A refused job gets zeros and ST_REFUSED.
+// Every index read from device memory is range-checked before it addresses anything (P::setup).
+constexpr int THREADS = 256, WAVES = THREADS / LANES;
+
+template <class P>
+__global__ void __launch_bounds__(THREADS) accumulate_kernel(const typename P::Args a, int njobs, int split, long long per_job, double* __restrict__ partials) {
+    const int lane = threadIdx.x & (LANES - 1), wave = threadIdx.x / LANES;
+    const size_t n = blockIdx.x % (unsigned)njobs;
+    const int part = (int)(blockIdx.x / (unsigned)njobs);
+    Job j;
+    typename P::Context c;
+    if (!P::setup(a, n, j, c)) return;   // block-uniform
+    double* __restrict__ out = partials + n * (size_t)per_job;
+
+    for (int tile = part * WAVES + wave; tile < j.tiles; tile += split * WAVES) {   // wave-uniform
+        double acc[SUMS];
+        int cnt[P::COUNTS];
+#pragma unroll
+        for (int k = 0; k < SUMS; ++k) acc[k] = 0.0;
+#pragma unroll
+        for (int k = 0; k < P::COUNTS; ++k) cnt[k] = 0;
+        for (int s = tile * TILE + lane; s < (tile + 1) * TILE && s < j.total; s += LANES) P::add(j, c, s, acc, cnt);
+#pragma unroll
+        for (int off = LANES / 2; off >= 1; off >>= 1) {
+#pragma unroll
+            for (int k = 0; k < SUMS; ++k) acc[k] = acc[k] + __shfl_xor(acc[k], off);
+#pragma unroll
+            for (int k = 0; k < P::COUNTS; ++k) cnt[k] += __shfl_xor(cnt[k], off);
+        }
+        double mine = (double)cnt[P::COUNTS - 1];   // words SUMS .. of the record are the counts
+#pragma unroll
+        for (int k = 0; k < P::COUNTS - 1; ++k)
+            if (lane == SUMS + k) mine = (double)cnt[k];
+#pragma unroll
+        for (int k = 0; k < SUMS; ++k)
+            if (lane == k) mine = acc[k];
+        if (lane < PARTIAL<P>) out[(size_t)tile * PARTIAL<P> + lane] = mine;
+    }
+}
+
+template <class P>
+__global__ void __launch_bounds__(LANES) solve_kernel(const typename P::Args a, double damping, int min_pixels, int update, long long per_job,
+                                                      const double* __restrict__ partials, double* __restrict__ poses, double* __restrict__ stats,
+                                                      int32_t* __restrict__ status) {
+    __shared__ double s_sums[PARTIAL<P>];
+    const int lane = threadIdx.x;
+    const size_t n = blockIdx.x;
+    Job j;
+    typename P::Context c;
+    if (!P::setup(a, n, j, c)) {   // block-uniform
+        if (lane < 4) stats[4 * n + lane] = 0.0;
+        if (lane == 0) status[n] = ST_REFUSED;
+        return;
+    }
+    if (lane < PARTIAL<P>) {
+        const double* __restrict__ p = partials + n * (size_t)per_job + lane;
+        double sum = 0.0;
+        for (int t = 0; t < j.tiles; ++t) sum = sum + p[(size_t)t * PARTIAL<P>];
+        s_sums[lane] = sum;
+    }
+    __syncthreads();
+    if (lane != 0) return;
+    double sums[SUMS], pose[12], st[4];
+    long long counts[P::COUNTS];
+#pragma unroll
+    for (int k = 0; k < SUMS; ++k) sums[k] = s_sums[k];
+#pragma unroll
+    for (int k = 0; k < P::COUNTS; ++k) counts[k] = (long long)s_sums[SUMS + k];
+    double* __restrict__ pp = poses + 12 * (size_t)j.plane;
+#pragma unroll
+    for (int k = 0; k < 12; ++k) pose[k] = pp[k];
+    const int code = P::solve(sums, counts, damping, min_pixels, update, pose, st);
+    if (code == ST_OK && update) {
+#pragma unroll
+        for (int k = 0; k < 12; ++k) pp[k] = pose[k];
+    }
+#pragma unroll
+    for (int k = 0; k < 4; ++k) stats[4 * n + k] = st[k];
+    status[n] = code;
+}
+
+// what both entry points ask of their arguments, after their own null-pointer and count checks; query: the name of the workspace's size call
+inline int check_step(const char* fn, int nplanes, int H, int W, int njobs, double damping, int min_pixels, int update, int split, size_t workspace_bytes,
+                      const char* query, size_t needed) {
+    CP_REQUIRE(H >= 1 && W >= 1 && H <= MAX_SIDE && W <= MAX_SIDE, "%s: H and W must lie in [1, %d] (got %d x %d)", fn, MAX_SIDE, H, W);
+    CP_REQUIRE((long long)nplanes < (1ll << 31) / 12, "%s: nplanes %d is too large", fn, nplanes);
+    CP_REQUIRE(damping >= 0.0 && damping <= 1.7976931348623157e308, "%s: damping must be finite and not negative (got %g)", fn, damping);
+    CP_REQUIRE(min_pixels >= 1, "%s: min_pixels must be positive (got %d)", fn, min_pixels);
+    CP_REQUIRE(update == 0 || update == 1, "%s: update must be 0 or 1 (got %d)", fn, update);
+    CP_REQUIRE(split >= 1 && split <= MAX_SPLIT, "%s: split must lie in [1, %d] blocks per job (got %d)", fn, MAX_SPLIT, split);
+    CP_REQUIRE((long long)njobs * split <= 0x7fffffffLL, "%s: njobs %d x split %d is above 2^31 - 1 blocks; split the call", fn, njobs, split);
+    CP_REQUIRE(workspace_bytes >= needed, "%s: workspace_bytes %zu is below %s = %zu", fn, workspace_bytes, query, needed);
+    return CP_OK;
+}
+#endif
 
 }  // namespace cp_icp

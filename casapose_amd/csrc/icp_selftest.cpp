@@ -31,7 +31,7 @@ struct Scene {
           poses{1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 1000} {}
     void box(int x0, int y0, int x1, int y1) {
         const int32_t b[4] = {x0, y0, x1 - x0, y1 - y0};
-        std::memcpy(&records[R_BOX], b, sizeof b);
+        std::memcpy(&records[R_BOX_OBJ], b, sizeof b);
     }
     struct Out {
         int32_t status;
@@ -45,12 +45,12 @@ struct Scene {
         const std::vector<double> gates(1, gate);
         Out o;
         o.pose = poses;
-        o.partials.assign(workspace_bytes(1, H, W) / sizeof(double), 0.0);
+        o.partials.assign(workspace_bytes<Depth>(1, H, W) / sizeof(double), 0.0);
         std::memset(o.partials.data(), fill, o.partials.size() * sizeof(double));
         o.status = -1;
         for (double& s : o.stats) s = -1.0;
-        step_serial(planes.data(), records.data(), nplanes, H, W, depth.data(), cams.data(), images, job.data(), gates.data(), 1, 0.75, damping, min_pixels,
-                    update, o.pose.data(), o.stats, &o.status, o.partials.data());
+        const Depth::Args a = {planes.data(), records.data(), nplanes, H, W, depth.data(), cams.data(), images, job.data(), gates.data(), 0.75};
+        step_serial<Depth>(a, 1, damping, min_pixels, update, o.pose.data(), o.stats, &o.status, o.partials.data());
         return o;
     }
 };
@@ -119,7 +119,7 @@ int main() {
             }
         double sums[SUMS];
         long long got;
-        add_tiles(o.partials.data(), j.tiles, sums, got);
+        add_tiles<1>(o.partials.data(), j.tiles, sums, &got);
         EXPECT(got == count && count > 2000 && o.stats[0] == (double)count, "patch: %lld pixels, the naive loop has %lld", got, count);
         for (int k = 0; k < SUMS; ++k)
             EXPECT(absd(sums[k] - naive[k]) <= (double)count * 2.220446049250313e-16 * mag[k], "patch: sum %d is %.17g, serially %.17g", k, sums[k], naive[k]);
@@ -142,7 +142,7 @@ int main() {
         EXPECT(again.pose == o.pose && zero.pose == o.pose && std::memcmp(again.stats, o.stats, sizeof o.stats) == 0 &&
                    std::memcmp(zero.stats, o.stats, sizeof o.stats) == 0,
                "patch: the result depends on what the workspace held");
-        EXPECT(std::memcmp(again.partials.data(), o.partials.data(), (size_t)j.tiles * PARTIAL * sizeof(double)) == 0, "patch: the tile records differ");
+        EXPECT(std::memcmp(again.partials.data(), o.partials.data(), (size_t)j.tiles * PARTIAL<Depth> * sizeof(double)) == 0, "patch: the tile records differ");
         const Scene::Out eval = s.run(0, 0, 40.0, 8, 1e-6, 0);
         EXPECT(eval.status == ST_OK && eval.pose == s.poses && eval.stats[3] == o.stats[3], "patch: update = 0 writes stats and status only");
     }

@@ -9,11 +9,7 @@
 //   a time (a row of the stage is 64 uint16 = 128 bytes, read from global memory by one wave); thread (column, row group) reads each staged
 //   value once and updates its eight output rows' running minima, so a staged row serves all 32 output rows.  The lanes of a wave read
 //   consecutive uint16 of one staged row: no bank conflicts.  Integers only, no atomics, every pixel of the plane is written exactly once.
-// contour_accumulate_kernel / contour_solve_kernel: depth_icp.hip's two launches on contour_math.h's terms.  Grid (split * jobs) on x,
-//   part-major; one wave per tile of TILE pixels keeps 28 fp64 sums and two counts per lane, an xor butterfly combines the 64 lanes and lanes
-//   0..29 store the tile's record.  No LDS, no atomics; every tile of a job is written, so the workspace needs no initialisation and no bit
-//   depends on split.  The solve: one wave per job, lane k < 30 adds word k of the tile records in index order, lane 0 solves and rewrites
-//   the pose in place.
+// The step's two launches and its host loop are icp_math.h's (accumulate_kernel, solve_kernel, step_serial), on cp_contour::Contour's terms.
 // Every index read from device memory (image, label, plane, field, gate, the box corners) is range-checked before it addresses anything.
 #include <cmath>
 #include <vector>
@@ -25,7 +21,7 @@ namespace {
 
 using namespace cp_contour;
 
-constexpr int THREADS = 256, WAVE = LANES, WAVES = THREADS / WAVE;
+constexpr int THREADS = 256;
 constexpr int COL_TX = 64, COL_TY = 32, COL_STAGE = 128, COL_GROUPS = THREADS / COL_TX, COL_OUT = COL_TY / COL_GROUPS;
 
 __global__ void __launch_bounds__(THREADS) edt_rows_kernel(const uint8_t* __restrict__ labels, int images, int H, int W, const int32_t* __restrict__ jobs,
@@ -87,90 +83,6 @@ __global__ void __launch_bounds__(THREADS) edt_cols_kernel(const int32_t* __rest
     }
 }
 
-__global__ void __launch_bounds__(THREADS) contour_accumulate_kernel(const uint32_t* __restrict__ planes, const int32_t* __restrict__ records, int nplanes,
-                                                                    int H, int W, const uint16_t* __restrict__ fields, int nfields,
-                                                                    const double* __restrict__ cams, int images, const int32_t* __restrict__ jobs,
-                                                                    int njobs, double sample, int split, long long per_job,
-                                                                    double* __restrict__ partials) {
-    const int lane = threadIdx.x & (WAVE - 1), wave = threadIdx.x / WAVE;
-    const size_t n = blockIdx.x % (unsigned)njobs;
-    const int part = (int)(blockIdx.x / (unsigned)njobs);
-    Job j;
-    int fieldno, G;
-    if (!job_setup(jobs + 4 * n, records, nplanes, nfields, images, H, W, j, fieldno, G)) return;   // block-uniform
-    const size_t hw = (size_t)H * (size_t)W;
-    const Camera cam = job_camera(cams + 4 * (size_t)j.image, sample);
-    const uint32_t* __restrict__ plane = planes + (size_t)j.plane * hw;
-    const uint16_t* __restrict__ field = fields + (size_t)fieldno * hw;
-    double* __restrict__ out = partials + n * (size_t)per_job;
-
-    for (int tile = part * WAVES + wave; tile < j.tiles; tile += split * WAVES) {   // wave-uniform
-        double acc[SUMS];
-#pragma unroll
-        for (int k = 0; k < SUMS; ++k) acc[k] = 0.0;
-        int used = 0, contour = 0;
-        for (int s = tile * TILE + lane; s < (tile + 1) * TILE && s < j.total; s += WAVE) {
-            Terms t;
-            const int kind = job_pixel(j, s, plane, field, W, cam, G, t);
-            if (kind == 0) continue;
-            contour += 1;
-            if (kind != 2) continue;
-            add_terms(t, acc);
-            used += 1;
-        }
-#pragma unroll
-        for (int off = WAVE / 2; off >= 1; off >>= 1) {
-#pragma unroll
-            for (int k = 0; k < SUMS; ++k) acc[k] = acc[k] + __shfl_xor(acc[k], off);
-            used += __shfl_xor(used, off);
-            contour += __shfl_xor(contour, off);
-        }
-        double mine = lane == SUMS ? (double)used : (double)contour;   // words SUMS and SUMS + 1
-#pragma unroll
-        for (int k = 0; k < SUMS; ++k)
-            if (lane == k) mine = acc[k];
-        if (lane < PARTIAL) out[(size_t)tile * PARTIAL + lane] = mine;
-    }
-}
-
-__global__ void __launch_bounds__(WAVE) contour_solve_kernel(const int32_t* __restrict__ records, int nplanes, int nfields, int H, int W, int images,
-                                                             const int32_t* __restrict__ jobs, double damping, int min_pixels, int update,
-                                                             long long per_job, const double* __restrict__ partials, double* __restrict__ poses,
-                                                             double* __restrict__ stats, int32_t* __restrict__ status) {
-    __shared__ double s_sums[PARTIAL];
-    const int lane = threadIdx.x;
-    const size_t n = blockIdx.x;
-    Job j;
-    int fieldno, G;
-    if (!job_setup(jobs + 4 * n, records, nplanes, nfields, images, H, W, j, fieldno, G)) {   // block-uniform
-        if (lane < 4) stats[4 * n + lane] = 0.0;
-        if (lane == 0) status[n] = ST_REFUSED;
-        return;
-    }
-    if (lane < PARTIAL) {
-        const double* __restrict__ p = partials + n * (size_t)per_job + lane;
-        double sum = 0.0;
-        for (int t = 0; t < j.tiles; ++t) sum = sum + p[(size_t)t * PARTIAL];
-        s_sums[lane] = sum;
-    }
-    __syncthreads();
-    if (lane != 0) return;
-    double sums[SUMS], pose[12], st[4];
-#pragma unroll
-    for (int k = 0; k < SUMS; ++k) sums[k] = s_sums[k];
-    double* __restrict__ P = poses + 12 * (size_t)j.plane;
-#pragma unroll
-    for (int k = 0; k < 12; ++k) pose[k] = P[k];
-    const int code = solve_update(sums, (long long)s_sums[SUMS], (long long)s_sums[SUMS + 1], damping, min_pixels, update, pose, st);
-    if (code == ST_OK && update) {
-#pragma unroll
-        for (int k = 0; k < 12; ++k) P[k] = pose[k];
-    }
-#pragma unroll
-    for (int k = 0; k < 4; ++k) stats[4 * n + k] = st[k];
-    status[n] = code;
-}
-
 // the rasteriser's sample point in whole 256ths of a pixel (cp_mask::sample_origin), as pixels
 double sample_of(double sample_offset) { return rint(256.0 * sample_offset) / 256.0; }
 
@@ -192,26 +104,19 @@ int check_edt(const char* fn, const uint8_t* labels, int images, int H, int W, c
     return CP_OK;
 }
 
-int check_step(const char* fn, const uint32_t* planes, const int32_t* records, int nplanes, int H, int W, const uint16_t* fields, int nfields,
-               const double* cams, int images, const int32_t* jobs, int njobs, double sample_offset, double damping, int min_pixels, int update, int split,
-               double* poses, double* stats, int32_t* status, void* workspace, size_t workspace_bytes) {
-    CP_REQUIRE(planes && records && fields && cams && jobs && poses && stats && status && workspace, "%s: null pointer", fn);
-    CP_REQUIRE(nplanes >= 1 && nfields >= 1 && images >= 1 && njobs >= 1, "%s: nplanes, nfields, images and njobs must be positive (got %d, %d, %d, %d)", fn,
-               nplanes, nfields, images, njobs);
-    CP_REQUIRE(H >= 1 && W >= 1 && H <= MAX_SIDE && W <= MAX_SIDE, "%s: H and W must lie in [1, %d] (got %d x %d)", fn, MAX_SIDE, H, W);
-    CP_REQUIRE((long long)nplanes < (1ll << 31) / 12, "%s: nplanes %d is too large", fn, nplanes);
+int check_step(const char* fn, const Contour::Args& a, int njobs, double sample_offset, double damping, int min_pixels, int update, int split, double* poses,
+               double* stats, int32_t* status, void* workspace, size_t workspace_bytes) {
+    CP_REQUIRE(a.planes && a.records && a.fields && a.cams && a.jobs && poses && stats && status && workspace, "%s: null pointer", fn);
+    CP_REQUIRE(a.nplanes >= 1 && a.nfields >= 1 && a.images >= 1 && njobs >= 1, "%s: nplanes, nfields, images and njobs must be positive (got %d, %d, %d, %d)",
+               fn, a.nplanes, a.nfields, a.images, njobs);
+    if (int rc = cp_icp::check_step(fn, a.nplanes, a.H, a.W, njobs, damping, min_pixels, update, split, workspace_bytes, "cp_contour_step_workspace_bytes",
+                                    cp_contour::workspace_bytes<Contour>(njobs, a.H, a.W)))
+        return rc;
     CP_REQUIRE(sample_offset >= 0.0 && sample_offset <= 1.0, "%s: sample_offset must lie in [0, 1] (got %g)", fn, sample_offset);
-    CP_REQUIRE(damping >= 0.0 && damping <= 1.7976931348623157e308, "%s: damping must be finite and not negative (got %g)", fn, damping);
-    CP_REQUIRE(min_pixels >= 1, "%s: min_pixels must be positive (got %d)", fn, min_pixels);
-    CP_REQUIRE(update == 0 || update == 1, "%s: update must be 0 or 1 (got %d)", fn, update);
-    CP_REQUIRE(split >= 1 && split <= MAX_SPLIT, "%s: split must lie in [1, %d] blocks per job (got %d)", fn, MAX_SPLIT, split);
-    CP_REQUIRE((long long)njobs * split <= 0x7fffffffLL, "%s: njobs %d x split %d is above 2^31 - 1 blocks; split the call", fn, njobs, split);
-    CP_REQUIRE(workspace_bytes >= step_workspace_bytes(njobs, H, W), "%s: workspace_bytes %zu is below cp_contour_step_workspace_bytes = %zu", fn,
-               workspace_bytes, step_workspace_bytes(njobs, H, W));
-    CP_REQUIRE(((uintptr_t)planes & 3) == 0 && ((uintptr_t)records & 3) == 0 && ((uintptr_t)jobs & 3) == 0 && ((uintptr_t)status & 3) == 0,
+    CP_REQUIRE(((uintptr_t)a.planes & 3) == 0 && ((uintptr_t)a.records & 3) == 0 && ((uintptr_t)a.jobs & 3) == 0 && ((uintptr_t)status & 3) == 0,
                "%s: planes, records, jobs and status must be 4-byte aligned", fn);
-    CP_REQUIRE(((uintptr_t)fields & 1) == 0, "%s: fields must be 2-byte aligned", fn);
-    CP_REQUIRE(((uintptr_t)cams & 7) == 0 && ((uintptr_t)poses & 7) == 0 && ((uintptr_t)stats & 7) == 0 && ((uintptr_t)workspace & 7) == 0,
+    CP_REQUIRE(((uintptr_t)a.fields & 1) == 0, "%s: fields must be 2-byte aligned", fn);
+    CP_REQUIRE(((uintptr_t)a.cams & 7) == 0 && ((uintptr_t)poses & 7) == 0 && ((uintptr_t)stats & 7) == 0 && ((uintptr_t)workspace & 7) == 0,
                "%s: cams, poses, stats and workspace must be 8-byte aligned", fn);
     return CP_OK;
 }
@@ -228,7 +133,7 @@ extern "C" size_t cp_mask_edt_workspace_bytes(int njobs, int H, int W) {
 
 extern "C" size_t cp_contour_step_workspace_bytes(int njobs, int H, int W) {
     if (njobs < 1 || H < 1 || W < 1 || H > MAX_SIDE || W > MAX_SIDE) return 0;
-    return step_workspace_bytes(njobs, H, W);
+    return workspace_bytes<Contour>(njobs, H, W);
 }
 
 extern "C" int cp_mask_edt_u16(const uint8_t* labels, int images, int H, int W, const int32_t* jobs, int njobs, int gate, uint16_t* planes,
@@ -254,26 +159,26 @@ extern "C" int cp_mask_edt_host_u16(const uint8_t* labels, int images, int H, in
 extern "C" int cp_contour_step_f64(const uint32_t* planes, const int32_t* records, int nplanes, int H, int W, const uint16_t* fields, int nfields,
                                    const double* cams, int images, const int32_t* jobs, int njobs, double sample_offset, double damping, int min_pixels, int update,
                                    int split, double* poses, double* stats, int32_t* status, void* workspace, size_t workspace_bytes, void* stream) {
-    if (int rc = check_step("cp_contour_step_f64", planes, records, nplanes, H, W, fields, nfields, cams, images, jobs, njobs, sample_offset, damping, min_pixels,
-                            update, split, poses, stats, status, workspace, workspace_bytes))
+    const Contour::Args a = {planes, records, nplanes, H, W, fields, nfields, cams, images, jobs, sample_of(sample_offset)};
+    if (int rc = check_step("cp_contour_step_f64", a, njobs, sample_offset, damping, min_pixels, update, split, poses, stats, status, workspace, workspace_bytes))
         return rc;
     hipStream_t st = (hipStream_t)stream;
-    const long long per_job = cp_icp::max_tiles(H, W) * PARTIAL;
-    CP_LAUNCH(contour_accumulate_kernel, dim3((unsigned)((long long)njobs * split)), dim3(THREADS), 0, st, planes, records, nplanes, H, W, fields, nfields,
-              cams, images, jobs, njobs, sample_of(sample_offset), split, per_job, (double*)workspace);
+    const long long per_job = cp_icp::max_tiles(H, W) * PARTIAL<Contour>;
+    CP_LAUNCH(cp_icp::accumulate_kernel<Contour>, dim3((unsigned)((long long)njobs * split)), dim3(cp_icp::THREADS), 0, st, a, njobs, split, per_job,
+              (double*)workspace);
     if (int rc = cp::check_launch("cp_contour_step_f64 (accumulate)")) return rc;
-    CP_LAUNCH(contour_solve_kernel, dim3((unsigned)njobs), dim3(WAVE), 0, st, records, nplanes, nfields, H, W, images, jobs, damping, min_pixels, update,
-              per_job, (const double*)workspace, poses, stats, status);
+    CP_LAUNCH(cp_icp::solve_kernel<Contour>, dim3((unsigned)njobs), dim3(LANES), 0, st, a, damping, min_pixels, update, per_job, (const double*)workspace, poses,
+              stats, status);
     return cp::check_launch("cp_contour_step_f64 (solve)");
 }
 
 extern "C" int cp_contour_step_host_f64(const uint32_t* planes, const int32_t* records, int nplanes, int H, int W, const uint16_t* fields, int nfields,
                                         const double* cams, int images, const int32_t* jobs, int njobs, double sample_offset, double damping, int min_pixels,
                                         int update, int split, double* poses, double* stats, int32_t* status, void* workspace, size_t workspace_bytes) {
-    if (int rc = check_step("cp_contour_step_host_f64", planes, records, nplanes, H, W, fields, nfields, cams, images, jobs, njobs, sample_offset, damping, min_pixels,
-                            update, split, poses, stats, status, workspace, workspace_bytes))
+    const Contour::Args a = {planes, records, nplanes, H, W, fields, nfields, cams, images, jobs, sample_of(sample_offset)};
+    if (int rc = check_step("cp_contour_step_host_f64", a, njobs, sample_offset, damping, min_pixels, update, split, poses, stats, status, workspace,
+                            workspace_bytes))
         return rc;
-    step_serial(planes, records, nplanes, H, W, fields, nfields, cams, images, jobs, njobs, sample_of(sample_offset), damping, min_pixels, update, poses, stats, status,
-                (double*)workspace);
+    step_serial<Contour>(a, njobs, damping, min_pixels, update, poses, stats, status, (double*)workspace);
     return CP_OK;
 }

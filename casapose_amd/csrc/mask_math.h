@@ -22,6 +22,8 @@
 #include <stddef.h>
 #include <stdint.h>
 
+#include "plane_record.h"
+
 #if defined(__HIPCC__)
 #define MASK_HD __host__ __device__ inline
 #else
@@ -30,19 +32,13 @@
 
 namespace cp_mask {
 
-constexpr int RECORD = 11;
-constexpr int R_ALL = 0, R_VISIB = 1, R_BOX_OBJ = 2, R_BOX_VISIB = 6, R_DROPPED = 10;
+using cp_plane::Camera, cp_plane::EMPTY, cp_plane::MAX_SIDE, cp_plane::R_BOX_OBJ, cp_plane::RECORD;   // what the planes' readers share
+constexpr int R_ALL = 0, R_VISIB = 1, R_BOX_VISIB = 6, R_DROPPED = 10;
 constexpr int MAX_INSTANCES = 256;     // per frame: the resolve kernel keeps ten LDS words per instance
-constexpr int MAX_SIDE = 16384;        // H, W: samples stay below 2^22 + 256
 constexpr int LANE_SAMPLES = 1024;     // a triangle whose clipped bounding box holds more samples is walked by a whole wave
-constexpr uint32_t EMPTY = 0xffffffffu;   // a depth plane's "nothing hit": above the bit pattern of every positive float, +inf included
 constexpr double SNAP_LIMIT = 268435456.0;   // 2^28
 constexpr int TRI_EMPTY = 0, TRI_DRAW = 1, TRI_DROPPED = 2;
 constexpr int32_t BOX_NONE = 0x7fffffff;
-
-struct Camera {
-    double fx, fy, cx, cy;
-};
 
 // a projected triangle: snapped vertices, camera depths, and the pixel rectangle [i0, i1] x [j0, j1] whose samples its bounding box holds
 struct Tri {

@@ -26,6 +26,8 @@
 #include <stddef.h>
 #include <stdint.h>
 
+#include "plane_record.h"
+
 #if defined(__HIPCC__)
 #define VERIFY_HD __host__ __device__ inline
 #else
@@ -38,17 +40,11 @@ constexpr int COUNTS = 8;
 constexpr int C_RENDERED = 0, C_HIDDEN = 1, C_ON_LABEL = 2, C_ON_BACKGROUND = 3, C_ON_OTHER = 4, C_LABEL_PIXELS = 5, C_PAIRS = 6, C_INLIERS = 7;
 constexpr int TILE = 256;                 // pixels a block takes per step
 constexpr int MAX_SPLIT = 64;             // blocks per job
-constexpr int MAX_SIDE = 16384;           // H, W: cp_mask::MAX_SIDE
 constexpr int MAX_INSTANCES = 256;        // planes of a frame: cp_mask's limit
 constexpr int MAX_KP = 32;
 constexpr int BINS = 256;                 // label values
-constexpr int RECORD = 11, R_BOX = 2;     // cp_mask::RECORD, R_BOX_OBJ
-constexpr uint32_t EMPTY = 0xffffffffu;   // cp_mask::EMPTY
 constexpr double LARGEST = 1.7976931348623157e308;
-
-struct Box {
-    int x0, y0, x1, y1;   // closed, inside the image
-};
+using cp_plane::Box, cp_plane::clipped_box, cp_plane::EMPTY, cp_plane::MAX_SIDE, cp_plane::R_BOX_OBJ, cp_plane::RECORD;
 
 // the pixel rectangle a job walks and what it reads there
 struct Job {
@@ -57,17 +53,6 @@ struct Job {
     bool walks;          // false: the box is empty, only label_pixels is counted
     Box box;
 };
-
-// rule 2 for one record: false when the box is empty or lies outside the image
-VERIFY_HD bool clipped_box(const int32_t* rec, int H, int W, Box& b) {
-    const int64_t x = rec[R_BOX], y = rec[R_BOX + 1], w = rec[R_BOX + 2], h = rec[R_BOX + 3];
-    if (w < 0 || h < 0) return false;
-    const int64_t x0 = x < 0 ? 0 : x, y0 = y < 0 ? 0 : y;
-    const int64_t x1 = x + w > W - 1 ? W - 1 : x + w, y1 = y + h > H - 1 ? H - 1 : y + h;
-    if (x0 > x1 || y0 > y1) return false;
-    b.x0 = (int)x0, b.y0 = (int)y0, b.x1 = (int)x1, b.y1 = (int)y1;
-    return true;
-}
 
 VERIFY_HD bool intersect(const Box& a, const Box& b, Box& out) {
     out.x0 = a.x0 > b.x0 ? a.x0 : b.x0, out.y0 = a.y0 > b.y0 ? a.y0 : b.y0;
@@ -86,14 +71,14 @@ VERIFY_HD bool job_setup(const int32_t* job, const int32_t* records, int nplanes
     j.first = frame * instances_max;
     j.hiders = c < 0 ? 0 : (c > instances_max ? instances_max : c);
     if (j.first + j.hiders > nplanes) j.hiders = nplanes - j.first;   // never a plane beyond the array
-    j.walks = clipped_box(records + (size_t)j.plane * RECORD, H, W, j.box);
+    j.walks = clipped_box(records + (size_t)j.plane * RECORD, H, W, 0, j.box);   // rule 2
     return true;
 }
 
 // the part of plane q's box inside the job's: false when q cannot hide anything of the job
 VERIFY_HD bool hider_box(const Job& j, int q, const int32_t* records, int H, int W, Box& out) {
     Box b;
-    if (q == j.plane || !clipped_box(records + (size_t)q * RECORD, H, W, b)) return false;
+    if (q == j.plane || !clipped_box(records + (size_t)q * RECORD, H, W, 0, b)) return false;
     return intersect(j.box, b, out);
 }
 

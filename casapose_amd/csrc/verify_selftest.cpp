@@ -32,7 +32,7 @@ struct Scene {
         for (int i = y0; i <= y1; ++i)
             for (int j = x0; j <= x1; ++j) planes[((size_t)plane * H + i) * W + j] = bits(z);
         const int32_t box[4] = {x0, y0, x1 - x0, y1 - y0};
-        std::memcpy(&records[(size_t)plane * RECORD + R_BOX], box, sizeof box);
+        std::memcpy(&records[(size_t)plane * RECORD + R_BOX_OBJ], box, sizeof box);
     }
     void word(int plane, int i, int j, float z) { planes[((size_t)plane * H + i) * W + j] = bits(z); }
     void direction(int i, int j, float dy, float dx) {
@@ -127,16 +127,16 @@ int main() {
     {
         Scene s = hand();
         const int32_t none[4] = {-1, -1, -1, -1}, across[4] = {-2, -3, 5, 5}, huge[4] = {0x7ffffff0, 0x7ffffff0, 0x7ffffff0, 0x7ffffff0};
-        std::memcpy(&s.records[R_BOX], none, sizeof none);
+        std::memcpy(&s.records[R_BOX_OBJ], none, sizeof none);
         EXPECT_COUNTS(s.run(0, 0, 1, 2.5, 3.5), "an empty box", 0, 0, 0, 0, 0, 10, 0, 0);
-        std::memcpy(&s.records[R_BOX], huge, sizeof huge);
+        std::memcpy(&s.records[R_BOX_OBJ], huge, sizeof huge);
         EXPECT_COUNTS(s.run(0, 0, 1, 2.5, 3.5), "a box near the end of int32", 0, 0, 0, 0, 0, 10, 0, 0);
-        std::memcpy(&s.records[R_BOX], across, sizeof across);   // columns 0-3 x rows 0-2: (1, 1), (1, 2), (1, 3), (2, 1), (2, 2), (2, 3) of the plane
+        std::memcpy(&s.records[R_BOX_OBJ], across, sizeof across);   // columns 0-3 x rows 0-2: (1, 1), (1, 2), (1, 3), (2, 1), (2, 2), (2, 3) of the plane
         EXPECT_COUNTS(s.run(0, 0, 1, 2.5, 3.5), "a box across the top-left corner", 6, 0, 5, 1, 0, 10, 4, 2);
         // plane 1's box shrunk to column 4: it is read there only, so (3, 3) is no longer hidden
         Scene t = hand();
         const int32_t column[4] = {4, 2, 0, 2};
-        std::memcpy(&t.records[RECORD + R_BOX], column, sizeof column);
+        std::memcpy(&t.records[RECORD + R_BOX_OBJ], column, sizeof column);
         EXPECT_COUNTS(t.run(0, 0, 1, 2.5, 3.5), "a hiding plane is read inside its box only", 12, 1, 8, 1, 2, 10, 4, 2);
     }
     SELFTEST_END("verify_selftest", "the 5 x 7 hand case, cos_min 0 and 1, keypoints that are not finite, instance counts, indices out of range, "

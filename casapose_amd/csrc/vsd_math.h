@@ -23,6 +23,8 @@
 #include <stddef.h>
 #include <stdint.h>
 
+#include "plane_record.h"
+
 #if defined(__HIPCC__)
 #define VSD_HD __host__ __device__ inline
 #else
@@ -34,13 +36,7 @@ namespace cp_vsd {
 constexpr int MAX_TAUS = 32;              // one bit per tau in Pixel::reached
 constexpr int TILE = 256;                 // pixels a block takes per step
 constexpr int MAX_SPLIT = 64;             // blocks per pair
-constexpr int MAX_SIDE = 16384;           // H, W: cp_mask::MAX_SIDE
-constexpr int RECORD = 11, R_BOX = 2;     // cp_mask::RECORD, R_BOX_OBJ
-constexpr uint32_t EMPTY = 0xffffffffu;   // cp_mask::EMPTY
-
-struct Camera {
-    double fx, fy, cx, cy;
-};
+using cp_plane::Box, cp_plane::Camera, cp_plane::clipped_box, cp_plane::depth_of, cp_plane::EMPTY, cp_plane::MAX_SIDE, cp_plane::R_BOX_OBJ, cp_plane::RECORD;
 
 // the pixel rectangle [i0, i0 + bh) x [j0, j0 + bw) a pair walks, and what it reads there
 struct Pair {
@@ -53,41 +49,24 @@ struct Pixel {
     uint32_t reached;   // bit k: inter && cost >= tau_k
 };
 
-// rule 5 for one record: false when the box is empty or lies outside the image
-VSD_HD bool clipped_box(const int32_t* rec, int H, int W, int64_t& x0, int64_t& y0, int64_t& x1, int64_t& y1) {
-    const int64_t x = rec[R_BOX], y = rec[R_BOX + 1], w = rec[R_BOX + 2], h = rec[R_BOX + 3];
-    if (w < 0 || h < 0) return false;
-    x0 = x < 0 ? 0 : x;
-    y0 = y < 0 ? 0 : y;
-    x1 = x + w > W - 1 ? W - 1 : x + w;
-    y1 = y + h > H - 1 ? H - 1 : y + h;
-    return x0 <= x1 && y0 <= y1;
-}
-
 // rules 5 and 7: false when the pair leaves zeros.  pair: (image, estimate plane, ground-truth plane, unused)
 VSD_HD bool pair_setup(const int32_t* pair, const int32_t* records, int nplanes, int images, int H, int W, double diameter, Pair& p) {
     p.image = pair[0], p.plane_e = pair[1], p.plane_g = pair[2];
     if (p.image < 0 || p.image >= images || p.plane_e < 0 || p.plane_e >= nplanes || p.plane_g < 0 || p.plane_g >= nplanes) return false;
     if (!(diameter > 0.0)) return false;
-    int64_t ax0, ay0, ax1, ay1, bx0, by0, bx1, by1;
-    const bool a = clipped_box(records + (size_t)p.plane_e * RECORD, H, W, ax0, ay0, ax1, ay1);
-    const bool b = clipped_box(records + (size_t)p.plane_g * RECORD, H, W, bx0, by0, bx1, by1);
-    if (!a && !b) return false;
-    if (!a) ax0 = bx0, ay0 = by0, ax1 = bx1, ay1 = by1;
-    if (a && b) {
-        if (bx0 < ax0) ax0 = bx0;
-        if (by0 < ay0) ay0 = by0;
-        if (bx1 > ax1) ax1 = bx1;
-        if (by1 > ay1) ay1 = by1;
+    Box a, b;
+    const bool has_a = clipped_box(records + (size_t)p.plane_e * RECORD, H, W, 0, a);
+    const bool has_b = clipped_box(records + (size_t)p.plane_g * RECORD, H, W, 0, b);
+    if (!has_a && !has_b) return false;
+    if (!has_a) a = b;
+    if (has_a && has_b) {
+        if (b.x0 < a.x0) a.x0 = b.x0;
+        if (b.y0 < a.y0) a.y0 = b.y0;
+        if (b.x1 > a.x1) a.x1 = b.x1;
+        if (b.y1 > a.y1) a.y1 = b.y1;
     }
-    p.i0 = (int)ay0, p.j0 = (int)ax0, p.bh = (int)(ay1 - ay0 + 1), p.bw = (int)(ax1 - ax0 + 1);   // inside [0, H) x [0, W)
+    p.i0 = a.y0, p.j0 = a.x0, p.bh = a.y1 - a.y0 + 1, p.bw = a.x1 - a.x0 + 1;   // inside [0, H) x [0, W)
     return true;
-}
-
-VSD_HD float depth_of(uint32_t bits) {
-    float z;
-    __builtin_memcpy(&z, &bits, sizeof z);
-    return z;
 }
 
 // rule 3: the distance from the camera centre of a point at depth 1 on the ray of pixel (i, j)

@@ -27,7 +27,7 @@ struct Scene {
         for (int i = y0; i <= y1; ++i)
             for (int j = x0; j <= x1; ++j) planes[((size_t)plane * H + i) * W + j] = bits;
         const int32_t box[4] = {x0, y0, x1 - x0, y1 - y0};
-        std::memcpy(&records[(size_t)plane * RECORD + R_BOX], box, sizeof box);
+        std::memcpy(&records[(size_t)plane * RECORD + R_BOX_OBJ], box, sizeof box);
     }
     void sensor(int x0, int y0, int x1, int y1, float z) {
         for (int i = y0; i <= y1; ++i)
@@ -129,14 +129,14 @@ int main() {
         s.fill(0, 0, 0, 3, 2, 1000.f);
         s.fill(1, 6, 4, 7, 5, 1000.f);
         const int32_t a[4] = {-2, -3, 5, 5}, b[4] = {6, 4, 10, 10}, out[4] = {W, H, 3, 3}, huge[4] = {0x7ffffff0, 0x7ffffff0, 0x7ffffff0, 0x7ffffff0};
-        std::memcpy(&s.records[0 * RECORD + R_BOX], a, sizeof a);
-        std::memcpy(&s.records[1 * RECORD + R_BOX], b, sizeof b);
+        std::memcpy(&s.records[0 * RECORD + R_BOX_OBJ], a, sizeof a);
+        std::memcpy(&s.records[1 * RECORD + R_BOX_OBJ], b, sizeof b);
         EXPECT_COUNTS(s.run(0, 0, 0), 12, 12, 0, 0, "a box across the top-left corner");
         EXPECT_COUNTS(s.run(0, 1, 1), 4, 4, 0, 0, "a box across the bottom-right corner");
         EXPECT_COUNTS(s.run(0, 0, 1), 16, 0, 0, 0, "both: the union is the whole image");
-        std::memcpy(&s.records[2 * RECORD + R_BOX], out, sizeof out);
+        std::memcpy(&s.records[2 * RECORD + R_BOX_OBJ], out, sizeof out);
         EXPECT_COUNTS(s.run(0, 2, 2), 0, 0, 0, 0, "a box outside the image");
-        std::memcpy(&s.records[2 * RECORD + R_BOX], huge, sizeof huge);
+        std::memcpy(&s.records[2 * RECORD + R_BOX_OBJ], huge, sizeof huge);
         EXPECT_COUNTS(s.run(0, 2, 2), 0, 0, 0, 0, "a box near the end of int32");
     }
     SELFTEST_END("vsd_selftest", "estimate == ground truth, an occluder, missing sensor depth, disjoint renders, empty planes, indices out of range, "

@@ -51,6 +51,24 @@ def test_two_calls_in_a_row(hip_lib, device):
     TH.same_bytes(TH.run_step(a, device, split=3, calls=2), TH.run_step(a, calls=2), TH.tiles_of(a, tile), "two calls")
 
 
+def test_a_wave_takes_a_second_tile_beside_an_empty_and_a_refused_job(hip_lib, device):
+    """72 x 96 under a full-frame box: 70 x 94 = 6580 pixels, seven tiles of 1024 with the last one part full -- more than the four waves of
+    split 1, so three waves take a second tile.  In the same call an empty record and a job refused for its gate (its indices are in range):
+    no tiles, so not a word of their records is written, and a word read for them would be the fill's NaN in their stats"""
+    tile = hip_lib.cp_depth_icp_tile()
+    H, W = 72, 96
+    a = IC.crafted_step(H, W, [(0, 0, W - 1, H - 1), (-1, -1, -1, -1), (0, 0, W - 1, H - 1)], 11)
+    a.update(H=H, W=W, gates=np.array([40.0, 40.0, 0.0]))
+    tiles = TH.tiles_of(a, tile)
+    assert tiles == [-(-70 * 94 // tile), 0, -1] and tiles[0] > 4 and 70 * 94 % tile != 0
+    want = TH.run_step(a)
+    assert want["status"].tolist() == [0, 1, 3] and (want["partials"][0, :tiles[0], 28] > 0).all() and not want["stats"][1:].any()
+    for split, fill in ((1, 0xFF), (3, 0xA5)):
+        got = TH.run_step(a, device, split=split, fill=fill)
+        TH.same_bytes(got, want, tiles, "seven tiles, split %d" % split)
+        assert (got["partials"][0, tiles[0]:].view(np.uint8) == fill).all() and (got["partials"][1:].view(np.uint8) == fill).all()
+
+
 # ---- 2. the loop ---------------------------------------------------------------------------------------------------------------------------
 def same_result(got, want, what):
     assert got[0].tobytes() == want[0].tobytes(), "%s: the poses differ" % what

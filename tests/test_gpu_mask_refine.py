@@ -67,6 +67,33 @@ def test_two_calls_in_a_row(hip_lib, device):
     TH.same_bytes(TH.run_step(a, device, split=3, calls=2), TH.run_step(a, calls=2), TH.tiles_of(a, tile), "two calls")
 
 
+def test_a_wave_takes_a_second_tile_beside_an_empty_and_a_refused_job(hip_lib, device):
+    """72 x 96 under a full-frame box: 70 x 94 = 6580 pixels, seven tiles of 1024 with the last one part full -- more than the four waves of
+    split 1, so three waves take a second tile.  The plane and the label both have a lattice of holes, so every tile has contour pixels near
+    seeds.  In the same call an empty record and a job refused for its gate (its indices are in range): no tiles, so not a word of their
+    records is written, and a word read for them would be the fill's NaN in their stats"""
+    tile = hip_lib.cp_contour_tile()
+    H, W, G = 72, 96, 4
+    yy, xx = np.mgrid[0:H, 0:W]
+    z = (1000.0 + 0.4 * xx - 0.3 * yy + 4.0 * np.sin(0.35 * xx) * np.cos(0.3 * yy)).astype(np.float32)
+    planes = np.full((2, H, W), 0xFFFFFFFF, np.uint32)
+    planes[0] = np.where((xx % 5 == 2) & (yy % 4 == 1), np.uint32(0xFFFFFFFF), z.view(np.uint32))
+    records = np.full((2, 11), -1, np.int32)
+    records[0, 2:6] = (0, 0, W - 1, H - 1)
+    labels = np.where((xx % 6 == 3) & (yy % 5 == 2), 0, 1).astype(np.uint8)[None]
+    a = dict(planes=planes, records=records, fields=TH.run_edt(labels, [(0, 1)], G)["planes"], cams=np.array([[400.0, 410.0, W / 2 - 0.3, H / 2 + 0.2]]),
+             poses=np.tile(np.hstack([np.eye(3), [[0.0], [0.0], [1000.0]]]).reshape(12), (2, 1)),
+             jobs=np.array([(0, 0, 0, G), (0, 1, 0, G), (0, 0, 0, 0)], np.int32), H=H, W=W, offset=0.25)
+    tiles = TH.tiles_of(a, tile)
+    assert tiles == [-(-70 * 94 // tile), 0, -1] and tiles[0] > 4 and 70 * 94 % tile != 0
+    want = TH.run_step(a)
+    assert want["status"].tolist()[1:] == [1, 3] and (want["partials"][0, :tiles[0], 28] > 0).all() and not want["stats"][1:].any()
+    for split, fill in ((1, 0xFF), (3, 0xA5)):
+        got = TH.run_step(a, device, split=split, fill=fill)
+        TH.same_bytes(got, want, tiles, "seven tiles, split %d" % split)
+        assert (got["partials"][0, tiles[0]:].view(np.uint8) == fill).all() and (got["partials"][1:].view(np.uint8) == fill).all()
+
+
 # ---- 3. the loop ---------------------------------------------------------------------------------------------------------------------------
 def same_result(got, want, what):
     assert got[0].tobytes() == want[0].tobytes(), "%s: the poses differ" % what
