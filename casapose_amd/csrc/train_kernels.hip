@@ -332,7 +332,7 @@ __global__ void maxpool_bwd_kernel(const float* __restrict__ x, const float* __r
                 if (oy >= Ho || ox >= Wo) continue;
                 // first maximum of the window in raster order, per channel (its taps are patch rows 2wy.., columns 2wx..)
                 float best[4] = {-INFINITY, -INFINITY, -INFINITY, -INFINITY};
-                int bidx[4] = {-1, -1, -1, -1};
+                int bidx[4] = {0, 0, 0, 0};   // a window of -inf alone: tap 0 is its first maximum, as in maxpool_idx_kernel
 #pragma unroll
                 for (int ky = 0; ky < 3; ++ky)
 #pragma unroll

@@ -284,7 +284,9 @@ int cp_mask_to_labels_f32(const float* mask, int batch, int h, int w, int object
 
 /* arg-max over `classes` contiguous values per pixel (pixel stride ld) -> uint8 label.
  * Replaces softmax(1e6*x) as a hard one-hot (pose_models.py:547-554; voting_layers_2d.py:38-41).
- * First maximum wins (ties are undefined behaviour in the reference). */
+ * First maximum wins (ties are undefined behaviour in the reference).
+ * Two routes, one result: 16-byte loads when ld % 4 == 0, `logits` is 16-byte aligned, classes <= 12 and 4 * ceil(classes / 4) <= ld
+ * (the values of the record past `classes` are loaded and ignored); a scalar loop otherwise.  1 <= classes <= 255, ld >= classes. */
 int cp_argmax_labels(const float* logits, int ld, int classes, long long pixels, uint8_t* labels,
                      void* stream);
 
