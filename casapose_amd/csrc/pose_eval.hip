@@ -14,12 +14,11 @@
 //   symmetric LM mesh: VALU-bound, tens of microseconds over 256 CUs.  16 KB of LDS per block leaves the wave limit (8 blocks per CU) binding.
 // pose_record_kernel: one wave per pair sums the chunk partials, divides by the count, classifies and writes the record.
 #include "common.h"
+#include "pose_eval_math.h"
 
 namespace {
 
-constexpr int THREADS = 256;
-constexpr int EST_TILE = 1024;   // points per LDS tile (16 KB); a multiple of TILE_UNROLL
-constexpr int TILE_UNROLL = 8;
+using namespace cp_pose;   // the per-point arithmetic, the tile and the order of the sums: pose_eval_math.h, shared with pose_match.hip
 constexpr int PAIR_FLOATS = 36, RECORD_FLOATS = 6;
 
 struct Pair {
@@ -39,38 +38,8 @@ __device__ __forceinline__ Pair load_pair(const float* __restrict__ rec) {
     return p;
 }
 
-// |sum of the 12 pose entries| (map_estimates :576,:579).  "Zero pose" is decided here and nowhere else: both kernels classify a pair from it.
-__device__ __forceinline__ double pose_abs_sum(const float* pose) {
-    double s = 0.0;
-#pragma unroll
-    for (int i = 0; i < 12; ++i) s += (double)pose[i];
-    return fabs(s);
-}
 // a pair whose record is fixed by its flags alone: not in the ground truth, or in it with the zero pose
 __device__ __forceinline__ bool pair_skipped(const Pair& p) { return p.valid == 0.f || pose_abs_sum(p.est) < 1e-4; }
-
-__device__ __forceinline__ int clamped_count(const int* __restrict__ counts, int o, int vmax) {
-    const int c = counts[o];
-    return c < 0 ? 0 : (c > vmax ? vmax : c);
-}
-
-__device__ __forceinline__ float3 transform(const float* rt, float x, float y, float z) {
-    return make_float3(fmaf(rt[0], x, fmaf(rt[1], y, fmaf(rt[2], z, rt[3]))), fmaf(rt[4], x, fmaf(rt[5], y, fmaf(rt[6], z, rt[7]))),
-                       fmaf(rt[8], x, fmaf(rt[9], y, fmaf(rt[10], z, rt[11]))));
-}
-
-// project_tf (:173-182): pixel = (K cam).xy / (K cam).z, 0 where that z is exactly 0 (divide_no_nan)
-__device__ __forceinline__ float2 project(const float* k, float3 c) {
-    const float u = fmaf(k[0], c.x, fmaf(k[1], c.y, k[2] * c.z)), v = fmaf(k[3], c.x, fmaf(k[4], c.y, k[5] * c.z));
-    const float w = fmaf(k[6], c.x, fmaf(k[7], c.y, k[8] * c.z));
-    return w != 0.f ? make_float2(u / w, v / w) : make_float2(0.f, 0.f);
-}
-
-__device__ __forceinline__ double wave_sum(double v) {
-#pragma unroll
-    for (int m = 32; m >= 1; m >>= 1) v += __shfl_xor(v, m);
-    return v;
-}
 
 __global__ void __launch_bounds__(THREADS) pose_points_kernel(const float* __restrict__ points, const int* __restrict__ counts,
                                                               const int* __restrict__ symmetric, int objects, int vmax,
@@ -99,37 +68,26 @@ __global__ void __launch_bounds__(THREADS) pose_points_kernel(const float* __res
         const float x = obj[3 * (size_t)i], y = obj[3 * (size_t)i + 1], z = obj[3 * (size_t)i + 2];
         const float3 es = transform(p.est, x, y, z);
         tg = transform(p.gt, x, y, z);
-        const float2 pe = project(p.k, es), pt = project(p.k, tg);
-        const float du = pt.x - pe.x, dv = pt.y - pe.y;
-        e2 = sqrtf(fmaf(du, du, dv * dv));
-        const float dx = tg.x - es.x, dy = tg.y - es.y, dz = tg.z - es.z;
-        e3 = sqrtf(fmaf(dx, dx, fmaf(dy, dy, dz * dz)));
+        e2 = pixel_distance(project(p.k, tg), project(p.k, es));
+        e3 = add_distance(tg, es);
     }
     if (symmetric[o] != 0) {
         float best = __builtin_inff();
         for (int t0 = 0; t0 < cnt; t0 += EST_TILE) {
-            const int n = min(EST_TILE, cnt - t0);
-            const int padded = (n + TILE_UNROLL - 1) / TILE_UNROLL * TILE_UNROLL;   // <= EST_TILE
             __syncthreads();   // the previous tile has been read
-            // slots n .. padded-1 repeat the tile's first point: the minimum does not change and the walk below needs no remainder loop
-            for (int j = tid; j < padded; j += THREADS) {
-                const size_t s = (size_t)(t0 + (j < n ? j : 0));
-                const float3 q = transform(p.est, obj[3 * s], obj[3 * s + 1], obj[3 * s + 2]);
-                tile[j] = make_float4(q.x, q.y, q.z, 0.f);
-            }
+            const int padded = fill_tile(tile, obj, p.est, t0, cnt, tid);
             __syncthreads();
             if (active) {
                 for (int j = 0; j < padded; j += TILE_UNROLL) {
 #pragma unroll
                     for (int u = 0; u < TILE_UNROLL; ++u) {
                         const float4 q = tile[j + u];
-                        const float dx = tg.x - q.x, dy = tg.y - q.y, dz = tg.z - q.z;
-                        best = fminf(best, fmaf(dx, dx, fmaf(dy, dy, dz * dz)));
+                        best = fminf(best, squared_distance(tg, q.x, q.y, q.z));
                     }
                 }
             }
         }
-        if (active) e3 = sqrtf(fabsf(best) + 1e-5f);   // :610
+        if (active) e3 = adds_distance(best);
     }
     if (active) {
         if (point_err2) point_err2[(size_t)pair * vmax + i] = e2;
@@ -189,8 +147,6 @@ __global__ void __launch_bounds__(64) pose_record_kernel(const int* __restrict__
 #pragma unroll
     for (int i = 0; i < RECORD_FLOATS; ++i) r[i] = v[i];
 }
-
-inline int chunks_of(int vmax) { return (vmax + THREADS - 1) / THREADS; }
 
 }  // namespace
 

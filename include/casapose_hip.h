@@ -916,6 +916,38 @@ int cp_pose_eval_est_tile(void);
 int cp_pose_eval_f32(const float* points, const int32_t* counts, const int32_t* symmetric, int objects, int vmax, const float* pairs, int batch,
                      float allowed_error_2d, void* workspace, float* records, float* point_err2, float* point_err3, void* stream);
 
+/* ---- pose statistics for several instances per object (csrc/pose_match.hip, csrc/match_math.h, csrc/pose_eval_math.h) ------------------------
+ * For every group = (image b, object o): up to `slots` estimated poses against up to `instances` ground-truth instances.  Every (estimate e,
+ * instance g) pair gets the two mean errors of cp_pose_eval_f32 -- the same per-point arithmetic and the same order of summation
+ * (pose_eval_math.h), so a finite entry of `err` equals records 0 and 1 of cp_pose_eval_f32 on that pair bit for bit -- and the pairs are
+ * matched greedily by the 3-D error: repeatedly the smallest finite cost among the free non-empty estimates and the free instances g < count,
+ * on ties the smaller g, then the smaller e (match_math.h).  No distance gates a match: a far match is simply no true positive.  Everything is
+ * device memory and fp32 unless noted.
+ *   points, counts, symmetric, objects, vmax   the evaluation meshes, exactly as cp_pose_eval_f32 takes them
+ *   est        [batch][objects][slots][12]      estimated poses, row-major 3x4.  A slot whose |sum of the 12 entries| < 1e-4 is empty, as
+ *                                               cp_pose_eval_f32 decides a zero pose
+ *   gt         [batch][objects][instances][12]  ground-truth poses; rows at and beyond the group's count are never read
+ *   gt_counts  int32 [batch][objects]           instances per group, read as clamped to [0, instances]
+ *   cams       [batch][9]                       K per image, row-major
+ *   diameters  [objects]
+ *   err        [batch][objects][slots][instances][2]  (err_2d, err_3d): the mean 2-D reprojection distance and the mean ADD, or ADD-S where
+ *                                               symmetric[o] is set; (+inf, +inf) for an empty estimate and for g >= count
+ *   gt_rec     [batch][objects][instances][5]   (matched slot or -1, err_2d, err_3d, valid_3d = err_3d < 0.1 * diameter, valid_2d = err_2d <
+ *                                               allowed_error_2d) of the match, compared in fp64; (-1, 0, 0, 0, 0) for an instance without a
+ *                                               match and for g >= count
+ *   est_match  int32 [batch][objects][slots]    the matched g; -1 for a non-empty estimate without a match (a false positive); -2 for an
+ *                                               empty slot
+ *   tally      int32 [batch][objects][5]        (ground-truth instances, non-empty estimates, matched, valid_3d matches, valid_2d matches)
+ *   workspace  cp_pose_match_workspace_bytes(batch, objects, vmax, slots, instances) bytes, 8-byte aligned (0 for arguments the call refuses);
+ *              needs no initialisation
+ * A cost that is not finite (an empty mesh gives NaN means) is never matched.  fp64 sums in a fixed order without atomics: two calls on the
+ * same input give the same bytes.  slots and instances in 1..16, batch * objects * slots <= 65535, vmax <= 2^24.  Added in ABI 302 without
+ * changing any earlier entry point. */
+size_t cp_pose_match_workspace_bytes(int batch, int objects, int vmax, int slots, int instances);
+int cp_pose_match_f32(const float* points, const int32_t* counts, const int32_t* symmetric, int objects, int vmax, const float* est, int slots,
+                      const float* gt, int instances, const int32_t* gt_counts, const float* cams, const float* diameters, int batch,
+                      float allowed_error_2d, void* workspace, float* err, float* gt_rec, int32_t* est_match, int32_t* tally, void* stream);
+
 /* ---- BOP pose errors with object symmetries (csrc/bop_errors.hip, csrc/bop_math.h) -------------------------------------------------------
  * For every pair of an estimated pose P^ and a ground-truth pose P_ of one object, over the object's symmetry transforms S and the vertices x of
  * its evaluation mesh:  e_MSSD = min_S max_x |P^ x - P_ S x| (millimetres),  e_MSPD = min_S max_x |proj_K(P^ x) - proj_K(P_ S x)| (pixels), with
